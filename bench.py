@@ -17,12 +17,15 @@ Other configs: --config C2 | C3 | C5.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # the driver's launcher form: used as it is
 
-The JSON line carries
+A plain run sets up, warms up, times the K steps and prints the JSON line; it carries
   roofline      the bound of the dominant kernel (the longest half-step): every candidate limiter of that kernel family is
-                priced and the largest fraction is `frac`
+                priced and the largest fraction is `frac` (PMC `traffic` only with --full)
+--full adds every leg beside the timed region (child runs, CPU work, other sizes and hosts), among them
   cpu_baseline  the CPU oracle (oracle/, test infrastructure) on the host cores, on a bounded sample of the same recipe
   to_ref_objective   iterations / seconds until the GPU's recorded objective is <= J_ref (1 + 1e-5), where J_ref is what the CPU
                 oracle reaches with default ProxGradParams() and its own stop rule on a scaled-down problem of the same recipe
+  to_reference_stop, other_configs, setup_s.create_from_host, inlib_host (N > 1), the PMC traffic of the dominant kernel
+--dump-outputs DIR writes what the last timed step left a caller (objectives, X, Y) as .npy files (dump_outputs below).
 """
 import argparse
 import json
@@ -36,12 +39,41 @@ sys.path.insert(0, ROOT)
 from bench_legs import *  # noqa: E402,F401,F403  (config table, rooflines, CPU / PMC / host legs: bench_legs.py)
 from bench_legs import _oracle_problem, _time_oracle, _pmc_note  # noqa: E402,F401  (underscore names the tests reach for)
 
+DUMP_FACTOR_BYTES = 24 << 20  # per factor (vectors + their indices): the whole dump stays well under 64 MB
+DUMP_SEED = 20261016          # the vectors a sampled factor keeps: the same on every run of the same shape
+
+
+def dump_outputs(path, sf, objs):
+    """--dump-outputs DIR: what the timed path hands a caller after its last step, as float64 .npy files --
+      objective.npy            the recorded objectives: initial, each warm-up iteration, each timed step (the last is the last step's)
+      X.npy, Y.npy             the factors' vectors, one row of k values per row / column vector of the model
+      X_index.npy, Y_index.npy which vectors those rows are: all of them, or a fixed sample (DUMP_SEED, ascending) when a factor
+                               would take more than DUMP_FACTOR_BYTES
+    The inputs depend only on the arguments (counter-based generator, fixed seeds), so two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "objective.npy"), np.asarray(objs, dtype=np.float64))
+    for name, buf, count in (("X", sf.dX, sf.m), ("Y", sf.dY, sf.d)):
+        vecs = buf.view(count, sf.ld)[:, : sf.k]
+        cap = DUMP_FACTOR_BYTES // (8 * (sf.k + 1))
+        idx = np.arange(count, dtype=np.int64)
+        if count > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(count, cap, replace=False))
+            vecs = vecs.index_select(0, torch.from_numpy(idx).to(buf.device))
+        np.save(os.path.join(path, name + ".npy"), vecs.cpu().numpy().astype(np.float64, copy=False))
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the timed region: the reference-stop run, PMC traffic, "
+                    "to_ref_objective, cpu_baseline, other_configs, create_from_host and (N > 1) the in-library host's leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the objectives and the factors of the last "
+                    "step as DIR/<name>.npy (float64; factors beyond 24 MB as a fixed, seeded sample of their vectors)")
     ap.add_argument("--config", default="C4", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="rows of the whole problem (strong scaling) or per rank (--scaling weak); 0 = the config's")
     ap.add_argument("--rows-per-gpu", type=int, default=0, help="alias: rows per rank with --scaling weak")
@@ -85,6 +117,13 @@ def main():
                     "killed and the in-library host (one process, N devices) runs instead")
     ap.add_argument("--cpu-full", action="store_true", help="one warm-up + one timed iteration of the CPU oracle on the FULL lists of the config (minutes, tens of GB of host memory)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.emulate_rank >= 0 or args.cpu_full or args.host == "inlib"):
+        raise SystemExit("--dump-outputs covers the timed path of the one-process-per-GPU host")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line -- every leg beside them is behind --full
+        args.no_convergence_run = args.no_cpu_baseline = args.no_jref = args.no_other_configs = args.no_create_from_host = args.no_inlib_leg = True
+        args.pmc = "off"
     if args.emulate_rank >= 0:
         return emulate_rank(args)
     if args.cpu_full:
@@ -202,6 +241,8 @@ def main():
         tot_r, tot_c = int(tot[0].item()), int(tot[1].item())
     else:
         tot_r, tot_c = nnz_r, nnz_c
+    if args.dump_outputs and rank == 0:  # X and Y are replicated: rank 0's copy is the whole answer
+        dump_outputs(args.dump_outputs, sf, [obj0] + objs)
     st = api.kernel_stats(sf.h)
     # what the exchanges added to the iterations of the timed region (events on the rank's stream around every exchange; with row
     # chunks: the wait for the chunks the pipeline did not hide), and the set-up probe that picked the exchange (N > 2 on RCCL)

@@ -850,7 +850,7 @@ def other_config_line(args, name, extra=(), timeout_s=600):
     # tests/golden/jref_<config>.json, ~1e8 observations, a few seconds of GPU time after the timed region has released its memory)
     jref = [] if name in ("C2", "C5") and not args.no_jref else ["--no-jref"]
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", name, "--steps", str(steps), "--warmup", str(args.warmup), "--seed", str(args.seed),
-           "--no-cpu-baseline", *jref, "--no-convergence-run", "--no-other-configs", "--pmc", args.pmc, "--pmc-timeout", str(args.pmc_timeout), *extra]
+           "--full", "--no-cpu-baseline", *jref, "--no-convergence-run", "--no-other-configs", "--pmc", args.pmc, "--pmc-timeout", str(args.pmc_timeout), *extra]
     t0 = time.time()
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)

@@ -197,3 +197,32 @@ def test_exchange_model_and_signature_combine():
     w = _capi.CSignature.combine([a, b.astuple()])
     assert w.astuple() == (17, 13, 9, 5, 1, 1)
     assert bench.passes_priced("cached") == 1 and bench.passes_priced("blocked") == 2
+
+
+def test_dump_outputs_writes_float64_within_budget_and_samples_the_same_vectors(tmp_path):
+    """--dump-outputs: objectives and both factors as float64 .npy; a factor beyond DUMP_FACTOR_BYTES becomes a fixed sample of its vectors
+    (the same on every run of the same shape), the padding beyond k is never written, and the whole dump stays under 64 MB."""
+    import numpy as np
+    import torch
+
+    class SF:  # the fields of ShardedFit the dump reads: flat (count x ld) factors, k of ld entries used
+        m, d, k, ld = 200_000, 3_000, 20, 24
+        dX = torch.arange(m * ld, dtype=torch.float64)
+        dY = -torch.arange(d * ld, dtype=torch.float64)
+
+    objs = [5.0, 4.0, 3.5]
+    runs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), SF, objs)
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b = runs
+    assert set(a) == {"objective", "X", "X_index", "Y", "Y_index"} and all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 << 20
+    assert list(a["objective"]) == objs
+    cap = bench.DUMP_FACTOR_BYTES // (8 * (SF.k + 1))
+    assert cap < SF.m and a["X"].shape == (cap, SF.k) and np.all(np.diff(a["X_index"]) > 0)   # sampled, ascending
+    rows = a["X_index"].astype(np.int64)
+    assert np.array_equal(a["X"], (rows[:, None] * SF.ld + np.arange(SF.k)).astype(np.float64))
+    assert a["Y"].shape == (SF.d, SF.k) and np.array_equal(a["Y_index"], np.arange(SF.d))              # small enough: whole
+    assert np.array_equal(a["Y"], -(np.arange(SF.d)[:, None] * SF.ld + np.arange(SF.k)).astype(np.float64))

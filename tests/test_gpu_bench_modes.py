@@ -55,3 +55,22 @@ def test_inlib_host_equals_the_single_device_objective():
     assert len(lib["host"]["row_bounds"]) == 5 and lib["host"]["row_bounds"][-1] == 200000
     m = lib["host"]["model_ms"]["X_block"]
     assert m["ring"] == pytest.approx(3 * m["direct"]) and m["link_GBps_one_direction"] == 76.8
+
+
+def test_plain_line_times_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain run (no --full) is set-up, warm-up, the timed steps and the line -- none of the legs beside them -- and --dump-outputs
+    writes what the last timed step left: the same files from two runs of the same arguments, the line's last objective among them."""
+    import numpy as np
+    common = ["--config", "C4", "--rows", "200000", "--cols", "10000", "--steps", "4", "--warmup", "2"]
+    a = run(common + ["--dump-outputs", str(tmp_path / "a")])
+    b = run(common + ["--dump-outputs", str(tmp_path / "b")])
+    assert a["steps"] == 4 and a["ms_per_step"] > 0 and a["value"] > 0 and a["dtype"] == "f64"
+    assert a["to_reference_stop"] is None and "cpu_baseline" not in a and "to_ref_objective" not in a and a["roofline"]["traffic"] is None
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) == ["X.npy", "X_index.npy", "Y.npy", "Y_index.npy", "objective.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y), f
+    obj = np.load(tmp_path / "a" / "objective.npy")
+    assert len(obj) == 1 + 2 + 4 and obj[0] == a["objective"]["initial"] and obj[-1] == a["objective"]["after_warmup_and_steps"]
+    assert np.load(tmp_path / "a" / "X.npy").shape[1] == 64 and np.all(np.load(tmp_path / "a" / "X.npy") >= 0)  # NonNegConstraint

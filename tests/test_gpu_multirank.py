@@ -52,7 +52,7 @@ def test_c4_recipe_strong_scaling_equals_one_rank(nranks):
     columns are cut into `nranks` shards (strong scaling) -- same recorded objectives, bit for bit, as the single-rank run."""
     common = ["--config", "C4", "--rows", "48000", "--cols", "4000", "--obs-per-row", "100", "--steps", "3", "--warmup", "2"] + QUIET
     env = dict(os.environ, GLRM_BENCH_BACKEND="gloo", GLRM_GATHER="allgather", GLRM_BENCH_INLIB="shared")
-    many = run(torchrun(nranks) + common, env)
+    many = run(torchrun(nranks) + common + ["--full"], env)  # --full: rank 0 adds the in-library host's leg
     one = run([sys.executable, "bench.py"] + common, dict(os.environ))
     assert many["n_gpus"] == nranks and many["scaling"] == "strong" and many["config"]["k"] == 64
     # rank 0 ran the in-library host (glrm_hip_multi_fit: what the Julia shim ccalls) on the same problem as a child process and
