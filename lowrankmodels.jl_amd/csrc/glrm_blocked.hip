@@ -39,6 +39,10 @@ using namespace glrm;
 #define GLRM_BLOCKED_NW 1
 #endif
 constexpr int BNW = GLRM_BLOCKED_NW;                                       // waves per workgroup
+// GLRM_HIP_BLOCKED_GATE: phase gate of the passes in rows (tiled_pass, L2 = true), 0 = off.  Off is NOT the kernel of round 6: the gated
+// loop is compiled in either way (134 instead of 118 VGPRs, 3 waves per SIMD), and C4's Y half-step runs 134.1 ms with the gate off
+// against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).
+constexpr int BLOCKED_GATE_DEFAULT = 8192;
 constexpr int LOCK_CTR_WORDS = 8 * 32 + 32;                                // lockstep windows: one 128-byte line per XCD + one for the give-up count
 constexpr int tile_rows_b(int kp) { return ((150 * 1024) / (kp * 8 + 16)) / 16 * 16; } // the LDS tile unit the super-tiles are counted in
 
@@ -170,6 +174,9 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
   int64_t& cap_slot = h->blocked_cap[rows ? 0 : 1][GRAD ? 0 : 1];
   if (cap_slot == 0) cap_slot = slice_capacity(kernel, h->device, SPB);
   const int64_t cap = cap_slot;
+  // phase gate in rows of the opposing factor (tiled_pass, L2 = true): read at every pass, so that one handle can be timed under several
+  // settings.  Changes no sum.
+  a.gate = std::max(0, env_int("GLRM_HIP_BLOCKED_GATE", BLOCKED_GATE_DEFAULT));
   const int64_t nseg = a.npass > 0 ? a.npass : a.nseg;
   // equal slices: ceil(nseg / cap) launches per super-tile, all of the same size (a last slice of a few percent of the others is a launch
   // that cannot fill the chip)

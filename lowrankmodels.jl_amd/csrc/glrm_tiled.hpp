@@ -88,6 +88,8 @@ struct TiledArgs {
   int32_t* actlist_out;       // nullable
   const int32_t* actlist_in;  // col_decide_kernel: nullable; the segments to decide (nact_in of them) instead of all nseg
   int64_t nact_in;
+  int gate;                   // phase-aligned passes (tiled_pass<..., L2 = true>): a lane group whose next observation lies more than `gate` rows
+                              // past the wave's trailing group sits the step out (0 = off; see tiled_pass)
 };
 
 // v from lane (lane ^ X) for X = 4 or 8 (ds_swizzle bit-mask mode: and 0x1F, or 0, xor X; no LDS memory touched)
@@ -343,6 +345,15 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
   double ab;
   load_entry(pos + j, cb, ab, db);
   if (!(active && pos + j < end)) cb = 0x7fffffff;
+  // Phase gate (L2 only; a.gate rows, 0 = off).  The groups of a wave start together but drift apart in rows (a step consumes G
+  // observations, whose row gaps are random), and the band of rows the groups in flight read from grows past what the L2 holds.  With the
+  // gate, a group whose next observation lies more than a.gate rows past the wave's TRAILING group (the least next-observation row among
+  // the groups still walking) sits the step out.  A step is skipped whole -- pos, the batch and every accumulator stay as they are -- so
+  // each accumulator still receives the same terms in the same order: the bits do not depend on the gate.  The trailing group is never
+  // held back, so the walk ends whatever the order of the list inside a tile.
+  // (The same gate as a wave reduction over the lanes still inside a divergent loop -- the gate-off loop's shape, 4 fewer VGPRs -- did not
+  // pay: Y half-step 133.7 ms at any gate width against 129.9 without it, LABNOTES round 7.)
+  const int gate = L2 ? a.gate : 0; // wave-uniform
   if constexpr (LW > 0) __syncthreads(); // B0
   for (int t = tile_begin; t < (L2 ? tile_begin + 1 : tile_end); ++t) {
     const int64_t lo = (int64_t)t * TROWS;
@@ -367,7 +378,28 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
 #else
     bool done = !active;
 #endif
-    while (!done) {
+    for (;;) {
+      if (gate > 0) {
+        // Every lane of the wave runs this loop until all groups are done (with the gate on, no lane leaves it alone), so the minimum
+        // can be formed over all 64 lanes.  Each lane offers its GROUP's next row c0 (its first lane's entry), never its own: the lists
+        // are only ordered by tile, so another lane of the group may hold a smaller row.  A done group offers INT_MAX, a walking one at
+        // most INT_MAX - 1 (c0 is INT_MAX past the end of its list).
+        const int c0 = group_bcast_i32<G>(cb, 0, lane);
+        int trail = done ? 0x7fffffff : min(c0, 0x7ffffffe);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) trail = min(trail, __shfl_xor(trail, o, 64));
+        if (trail == 0x7fffffff) break; // every group of the wave is done (wave-uniform)
+        // The trailing group has c0 - trail <= 0 and steps, and a step either consumes an observation or ends the group's walk: the loop
+        // ends for any list the family admits.  A waiting (or done) lane's iteration changes none of its own values; the volatile asm
+        // keeps the compiler from taking that for an endless loop without side effects (undefined behaviour it may assume away: it then
+        // drops the gate or miscompiles the loop).
+        if (done || (c0 < (int)hi && c0 - trail > gate)) { // 0 <= trail <= c0 < hi: no overflow
+          asm volatile("" ::: "memory");
+          continue;
+        }
+      } else if (done) {
+        break;
+      }
       int cn, dn; // prefetch the next batch while this one is consumed
       double an;
       load_entry(pos + G + j, cn, an, dn);
