@@ -106,7 +106,7 @@ def build_testing(force=False, verbose=True):
 
 def build_variant(tag, defines, verbose=True):
     """libglrm_hip_<tag>.so: the engine compiled with extra -D switches, next to the product library (same-box A/B of kernel variants with
-    tests/perf/ab_lib.py; e.g. tag "libm", defines GLRM_LOGISTIC_LIBM GLRM_ORDINAL_BRANCHY GLRM_POISSON_LIBM = round 2's loss formulas)."""
+    tests/perf/ab_lib.py; e.g. tag "exp", defines GLRM_MY_VARIANT=1 for an `#if GLRM_MY_VARIANT` the experiment adds to the sources)."""
     srcs, _ = TARGETS["libglrm_hip.so"]
     out = os.path.join(PKG, f"libglrm_hip_{tag}.so")
     objs, procs = [], []
@@ -128,7 +128,7 @@ def build_variant(tag, defines, verbose=True):
 
 if __name__ == "__main__":
     import sys
-    if len(sys.argv) > 2 and sys.argv[1] == "--variant":  # python -m lowrankmodels.jl_amd.build --variant libm GLRM_LOGISTIC_LIBM ...
+    if len(sys.argv) > 2 and sys.argv[1] == "--variant":  # python -m lowrankmodels.jl_amd.build --variant exp GLRM_MY_VARIANT=1 ...
         build_variant(sys.argv[2], sys.argv[3:])
     else:
         build_all(force=True)

@@ -26,10 +26,6 @@ using namespace glrm;
 
 namespace {
 
-#ifndef CACHED_U
-#define CACHED_U 4 // observations per lane group in flight per trip of the LDS variant (2: 111.9 ms, 4: 109.6 ms at C4)
-#endif
-
 struct CachedArgs {
   int64_t nseg;
   const int64_t* ptr;
@@ -66,7 +62,7 @@ template <int G, int R, int LOSS, bool GRAD>
 __device__ __forceinline__ double cached_pass(const CachedArgs& a, const char* __restrict__ ybuf, const double* __restrict__ lval,
                                               const int32_t* __restrict__ lidx, const Vec<G, R>& xv, Vec<G, R>& g, int len, int gi, int j,
                                               const LossDesc& segloss) {
-  constexpr int KPB = G * R * 8, NG = 64 / G, LM = loss_mode(LOSS), U = CACHED_U;
+  constexpr int KPB = G * R * 8, NG = 64 / G, LM = loss_mode(LOSS), U = 4; // U: observations per group in flight per trip (2: 111.9 ms, 4: 109.6 ms at C4)
   constexpr bool TRIG = loss_trig(LOSS);
   double J = 0.0;
   if (GRAD) {
@@ -474,14 +470,8 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
     for (int q = 0; q < PF; ++q) {
       int e = q * 128 + tid;
       e = e < len ? e : (len > 0 ? len - 1 : 0);
-#if defined(GLRM_CACHED_NT) // experiment: the streamed lists bypass the caches' retention (the opposing factor is what should stay in them)
-      pi[q] = len > 0 ? __builtin_nontemporal_load(a.idx + beg + e) : 0;
-      const double vd = len > 0 ? __builtin_nontemporal_load(a.vals + beg + e) : 0.0;
-      const int2 v = make_int2(__double2loint(vd), __double2hiint(vd));
-#else
       pi[q] = len > 0 ? a.idx[beg + e] : 0;
       const int2 v = len > 0 ? *reinterpret_cast<const int2*>(a.vals + beg + e) : make_int2(0, 0);
-#endif
       pv[2 * q] = v.x; pv[2 * q + 1] = v.y;
     }
   };
@@ -628,7 +618,7 @@ int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 128, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
       int cus = 256;
       if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-      nb = (int)((int64_t)per_cu * cus * env_int("GLRM_HIP_CACHED_PERSIST_FILL", 100) / 100); // percent of the resident grid
+      nb = per_cu * cus; // the resident grid
       if (nb < 1) nb = 1;
       cache = nb;
     }

@@ -131,8 +131,8 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   if ((rc = alloc_arr(&h->activebuf, nl1))) return rc;
   if ((rc = alloc_arr(&h->ntrialbuf, nl1))) return rc;
   if ((rc = alloc_arr(&h->nactive, 1))) return rc;
-  // glrm_options.quad_gram (GLRM_HIP_DENSE_GRAM overrides): line-search trials from the quadratic form, no pass over A per trial
-  h->dense_gram = env_int("GLRM_HIP_DENSE_GRAM", h->opts.quad_gram ? 1 : 0) != 0;
+  // glrm_options.quad_gram: line-search trials from the quadratic form, no pass over A per trial
+  h->dense_gram = h->opts.quad_gram != 0;
   if (h->dense_gram) {
     if ((rc = alloc_arr(&h->gramH, (int64_t)h->kp * h->kp))) return rc;
     if ((rc = alloc_arr(&h->gram_part, (int64_t)GRAM_BLOCKS * h->kp * h->kp))) return rc;
@@ -171,9 +171,7 @@ static void launch_dense_inst(bool grad, const DenseArgs& a, hipStream_t st) {
 template <int KP>
 static void launch_dense_pass(bool grad, const DenseArgs& a, hipStream_t st) {
   // 16-wave workgroups (256 segments share one staged tile) unless the problem is too small to fill the chip with them
-  int nw = a.nseg * (int64_t)a.nsup >= 256 * 256 ? 16 : 4;
-  nw = env_int("GLRM_HIP_DENSE_NW", nw) == 16 ? 16 : 4; // tuning override
-  if (nw == 16) launch_dense_inst<KP, 16>(grad, a, st);
+  if (a.nseg * (int64_t)a.nsup >= 256 * 256) launch_dense_inst<KP, 16>(grad, a, st);
   else launch_dense_inst<KP, 4>(grad, a, st);
 }
 

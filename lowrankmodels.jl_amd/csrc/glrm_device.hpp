@@ -141,11 +141,7 @@ __device__ __forceinline__ void loss_both(const LossDesc& l, double u, double a,
       break;
     }
     case GLRM_LOSS_POISSON: { // :237-241
-#if defined(GLRM_POISSON_LIBM)
-      const double eu = exp(u);
-#else
       const double eu = fm_exp(u);
-#endif
       L = s * (eu - a * u + (a == 0 ? 0.0 : a * (log(a) - 1)));
       if (NEED_GRAD) dL = s * (eu - a);
       break;
@@ -154,27 +150,6 @@ __device__ __forceinline__ void loss_both(const LossDesc& l, double u, double a,
       // in n and f only: the operands are selected, the expression is evaluated once -- the same operations on the same values as the
       // literal transcription (oracle/glrm_oracle.c), without four divergent code paths.
       const double mn = l.p0, mx = l.p1;
-#if defined(GLRM_ORDINAL_BRANCHY)
-      double n, loss;
-      if (u > mx - 1) {
-        n = fmin(floor(u), mx - 1) - a;
-        loss = n * (n + 1) / 2 + (n + 1) * (u - mx + 1);
-      } else if (u > a) {
-        n = fmin(floor(u), mx) - a;
-        loss = n * (n + 1) / 2 + (n + 1) * (u - floor(u));
-      } else if (u > mn + 1) {
-        n = a - fmax(ceil(u), mn + 1);
-        loss = n * (n + 1) / 2 + (n + 1) * (ceil(u) - u);
-      } else {
-        n = a - fmax(ceil(u), mn + 1);
-        loss = n * (n + 1) / 2 + (n + 1) * (mn + 1 - u);
-      }
-      L = s * loss;
-      if (NEED_GRAD) {
-        const double g = u > a ? fmin(ceil(u), mx) - a : -(a - fmax(floor(u), mn));
-        dL = s * g;
-      }
-#else
       const double fl = floor(u), ce = ceil(u);
       const bool top = u > mx - 1, up = top || u > a, mid = u > mn + 1;
       const double n_up = fmin(fl, top ? mx - 1 : mx) - a, f_up = top ? u - mx + 1 : u - fl;
@@ -185,17 +160,10 @@ __device__ __forceinline__ void loss_both(const LossDesc& l, double u, double a,
         const double g = u > a ? fmin(ce, mx) - a : -(a - fmax(fl, mn));
         dL = s * g;
       }
-#endif
       break;
     }
     case GLRM_LOSS_LOGISTIC: { // :304,306 ; a is 1.0 (true) / 0.0 (false).  One exponential per observation: glrm_fastmath.hpp
-#if defined(GLRM_LOGISTIC_LIBM)
-      const double aa = 2 * a - 1;
-      L = s * log(1 + exp(-aa * u));
-      if (NEED_GRAD) dL = -aa * s / (1 + exp(aa * u));
-#else
       fm_logistic<NEED_GRAD>(s, 2 * a - 1, u, L, dL);
-#endif
       break;
     }
     case GLRM_LOSS_WEIGHTED_HINGE: { // :326-341

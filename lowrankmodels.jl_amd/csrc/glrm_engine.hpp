@@ -18,10 +18,9 @@ enum { LOSS_QUAD_UNIFORM = 0, LOSS_SEGMENT = 1, LOSS_PER_OBS = 2, LOSS_SEGMENT_N
 constexpr int loss_mode(int loss) { return loss >= 3 ? loss - 2 : loss; }
 constexpr bool loss_trig(int loss) { return loss < 3; }
 
-// conflict-free tile reads of the LDS-tiled column passes (glrm_tiled.hpp: tile_rot); also read by glrm_hip_sum_order
-#ifndef GLRM_TILE_ROT
-#define GLRM_TILE_ROT 1
-#endif
+// opposing vectors per LDS tile (rows padded by 16 B, ~150 KB: one 16-wave workgroup per CU): the tile of the LDS-tiled and lane passes,
+// the unit of the tile-order check and of the super-tiles of the phase-aligned passes
+constexpr int glrm_tile_rows(int kp) { return ((150 * 1024) / (kp * 8 + 16)) / 16 * 16; }
 
 extern thread_local char g_err[768];
 
@@ -47,7 +46,6 @@ struct glrm_handle {
   bool own_stream = false;
   int64_t m = 0, n = 0;
   int k = 0, kp = 0, G = 4, R = 2;
-  int unroll_row = 1, unroll_col = 1, unroll_long = 8;
   // LDS-tiled sweeps (glrm_tiled.hpp)
   bool rows_sorted = false, cols_sorted = false;
   double fixed_alpha = 0.0;           // > 0 while a SparseProxGradParams step (no line search) is being launched
@@ -55,21 +53,15 @@ struct glrm_handle {
   int tiled_opt = 0;                  // glrm_options.tiled
   int tiled_row = 0, tiled_col = 0;   // 0 = gather sweep, 1 = tiled
   int tG = 4, tR = 2;                 // lane layout of the tiled kernels (kp = tG*tR)
-  int tile_cfg = 0;                   // 0: 8 waves + ~64 KB tile, 1: 16 waves + ~128 KB tile
-  int tile_lw = 0, tile_lw_sides = 1; // loader waves per workgroup of the double-buffered tiled sweeps; which sides use them
-  bool tile_cfg12 = false;            // GLRM_HIP_TILE_CFG=2: heterogeneous row sweep on 12 waves
   int nsup = 0, tiles_per_sup = 0;
   int blocked_row = 0, blocked_col = 0; // phase-aligned gather passes (glrm_blocked.hip) instead of the one-kernel gather sweep
-  int row_split = 0, tiles_per_sup_r = 0; // row sweep in super-tile passes (nsup_r super-tiles; buffers part_r ... ntrial_r below)
+  int tiles_per_sup_r = 0;            // row passes: tiles per super-tile (nsup_r super-tiles; buffers part_r ... ntrial_r below)
   int tile_rounds = 0;                // LDS-tiled sweeps: line-search rounds over the still-searching segments only (bit0 rows, bit1 columns)
   int32_t* actlist = nullptr;         // two lists of actlist_cap segment ids (glrm_tiled.hpp: TiledArgs::actlist_out / actlist_in)
   int64_t actlist_cap = 0;
   double *part = nullptr, *gsum = nullptr, *trialbuf = nullptr, *joldbuf = nullptr;
   int32_t *activebuf = nullptr, *ntrialbuf = nullptr;
   unsigned int* nactive = nullptr;
-  // lockstep form of the phase-aligned column passes (glrm_blocked.hip: lockstep_col_pass_kernel): 0 off, 1 on; per-XCD window counters
-  int lockstep = 0;
-  unsigned int* lock_ctr = nullptr;
   int* dflag = nullptr;
   uint8_t* rowdescid = nullptr;       // heterogeneous tiled row sweep: id of the loss descriptor of every entry of the row view
   glrm_loss* udesc = nullptr;         // the model's distinct loss descriptors (<= 256), device
@@ -153,7 +145,6 @@ struct glrm_handle {
   int64_t blocked_cap[2][2] = {{0, 0}, {0, 0}}; // phase-aligned passes: segments per launch slice, [row / column view][gradient / trial instantiation]
   int cached_grid[2] = {0, 0};        // persistent cached row sweep: resident workgroups, MAXT = 7 / 4 instantiation
   glrm_signature sig_local{}, sig{};  // this shard's contribution / the whole problem's
-  int order_unit = 0;                 // opposing vectors per unit of the tile-order check (glrm_tiled.hip)
   hipStream_t side_stream = nullptr;  // the launches of the minority classes run beside the main launch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int profile = 0;
@@ -197,7 +188,7 @@ constexpr int glrm_class_waves(int cls) { return cls <= 1 ? 1 : (cls == 2 ? 4 : 
 // rows the register-cached sweep takes: at most 13 trips of the lane layout, 64 / G observations each
 inline int64_t glrm_cached_reg_maxlen(int G) { return (int64_t)13 * (64 / G); }
 
-// LDS-tiled sweeps (glrm_tiled.hip).  prepare: tile configuration + the tile-order check of this shard's lists (create);
+// LDS-tiled sweeps (glrm_tiled.hip).  prepare: lane layout + the tile-order check of this shard's lists (create);
 // setup: family choice from h->sig and buffers (finalize)
 int glrm_prepare_tiled(glrm_handle* h);
 int glrm_setup_tiled(glrm_handle* h);

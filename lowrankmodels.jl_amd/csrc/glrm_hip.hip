@@ -475,7 +475,7 @@ struct DeviceGuard {
 extern "C" int glrm_hip_version(void) { return GLRM_HIP_ABI_VERSION; }
 extern "C" const char* glrm_hip_last_error(void) { return g_err; }
 
-// kp = G*R >= k.  Default layouts; GLRM_HIP_LANES_PER_OBS (tuning knob) selects another G for the same kp.
+// kp = G*R >= k: lanes per observation G and components per lane R
 static int pick_layout(int k, int& G, int& R) {
   int kp;
   if (k <= 8) { kp = 8; G = 4; }
@@ -484,13 +484,6 @@ static int pick_layout(int k, int& G, int& R) {
   else if (k <= 64) { kp = 64; G = 8; }
   else if (k <= 128) { kp = 128; G = 16; }
   else return -1;
-  const int want = env_int("GLRM_HIP_LANES_PER_OBS", 0);
-  if ((want == 4 || want == 8 || want == 16) && kp % want == 0) {
-    const int r = kp / want;
-    const bool have = (want == 4 && (r == 2 || r == 4 || r == 8)) || (want == 8 && (r == 4 || r == 8)) ||
-                      (want == 16 && (r == 2 || r == 4 || r == 8));
-    if (have) G = want;
-  }
   R = kp / G;
   return 0;
 }
@@ -585,7 +578,7 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
                   h->activebuf, h->ntrialbuf, h->nactive, h->dflag, h->Arow, h->Acol, h->part_r, h->gsum_r, h->trial_r,
                   h->jold_r, h->active_r, h->ntrial_r, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
                   h->mobjold, h->mactive, h->mnactive, h->colperm, h->rowperm, h->seglist_r, h->seglist_c, h->rowdescid, h->udesc,
-                  h->gramH, h->gram_part, h->jloss_r, h->jloss_c, h->lock_ctr, h->actlist, h->blk_perm_c, h->blk_long_c,
+                  h->gramH, h->gram_part, h->jloss_r, h->jloss_c, h->actlist, h->blk_perm_c, h->blk_long_c,
                   h->lane_bptr[0], h->lane_bptr[1], h->lane_off[0], h->lane_off[1], h->lane_val[0], h->lane_val[1],
                   h->lane_inv[0], h->lane_inv[1], h->lane_off16[0], h->lane_off16[1], h->lane_vptr[0], h->lane_vptr[1], h->lane_sval[0], h->lane_sval[1], h->lane_gcnt, h->lane_gbase, h->lane_gtotal, h->lane_glist};
   for (void* p : ptrs)
@@ -645,13 +638,6 @@ static int build_class_plan(glrm_handle* h, bool rows) {
   for (int c = 0; c < 4; ++c) populated += ncls[c] > 0;
   for (int c = 2; c < 4; ++c) if (ncls[c] > ncls[best]) best = c;
   (rows ? h->waves_row : h->waves_col) = forced ? glrm_class_waves(forced) : glrm_class_waves(best);
-  if (populated > 1 && !env_int("GLRM_HIP_SPLIT_LONG", 1)) { // experiment switch: ONE launch on the majority wave class (not shard-invariant)
-    const int64_t all = ncls[0] + ncls[1] + ncls[2] + ncls[3];
-    if (cached) h->cached_row = 0;
-    for (int c = 0; c < 4; ++c) ncls[c] = 0;
-    ncls[best] = all;
-    populated = 1;
-  }
   if (populated <= 1) return GLRM_OK;
   std::vector<int64_t> ptr((size_t)nseg + 1);
   HIPCK(hipMemcpyAsync(ptr.data(), rows ? h->rowptr : h->colptr, ((size_t)nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -682,9 +668,6 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
   h->ml = h->re - h->rb; h->nl = h->ce - h->cb;
   pick_layout(p->k, h->G, h->R);
   h->kp = h->G * h->R;
-  h->unroll_row = env_int("GLRM_HIP_UNROLL_ROW", 2) == 2 ? 2 : 1; // 2 observations per group in flight: -20 % on the L2-latency-bound row sweep
-  h->unroll_col = env_int("GLRM_HIP_UNROLL_COL", 1) == 2 ? 2 : 1;
-  h->unroll_long = env_int("GLRM_HIP_UNROLL_LONG", 8) >= 8 ? 8 : 1; // 8-wave segments: observations per lane group in flight (launch_sweep_loss)
   h->profile = o ? o->profile : 0;
   h->tiled_opt = o ? o->tiled : 0;
   h->sum_order_opt = o ? o->sum_order : 0;
@@ -993,8 +976,9 @@ extern "C" int glrm_hip_synchronize(glrm_handle* h) {
 
 // ------------------------------------------------------------------ sweep launch
 
+// Observations per lane group in flight (a group adds its observations in ascending order whatever the count: the bits do not depend on it)
 template <int G, int R, int WAVES>
-static void launch_sweep_loss(int loss, int unroll, const SweepArgs& a, hipStream_t st) {
+static void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)(WAVES == 1 ? (a.nseg + 3) / 4 : a.nseg);
   const dim3 block(WAVES == 1 ? 256 : WAVES * 64);
 #define GLRM_LAUNCH(LOSSV, UV)                                                                                  \
@@ -1002,57 +986,46 @@ static void launch_sweep_loss(int loss, int unroll, const SweepArgs& a, hipStrea
     if (a.eval_only) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSSV, 1, true>), dim3(grid), block, 0, st, a); \
     else hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSSV, UV, false>), dim3(grid), block, 0, st, a);          \
   } while (0)
-  if constexpr (WAVES == 8) {
-    // One 8-wave workgroup per very long segment (the diverted columns of a power-law view: 880 000 observations at the C2-Zipf recipe) is
-    // bound by the latency of its factor gathers: with one observation per lane group in flight the longest column alone took 13.7 ms of a
-    // 15.7 ms Y half-step (profiles/r06_c2_zipf_kernel_stats.csv).  Eight per group in flight (a group still adds its observations
-    // t == gg (mod TG) in ascending order: the bits do not depend on U) -- session r6_26.
-    if (unroll >= 8 && !a.eval_only) {
-      switch (loss) {
-        case LOSS_QUAD_UNIFORM: hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS_QUAD_UNIFORM, 8, false>), dim3(grid), block, 0, st, a); break;
-        case LOSS_SEGMENT: hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS_SEGMENT, 8, false>), dim3(grid), block, 0, st, a); break;
-        case LOSS_SEGMENT_NOTRIG: hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS_SEGMENT_NOTRIG, 8, false>), dim3(grid), block, 0, st, a); break;
-        case LOSS_PER_OBS_NOTRIG: hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS_PER_OBS_NOTRIG, 8, false>), dim3(grid), block, 0, st, a); break;
-        default: hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS_PER_OBS, 8, false>), dim3(grid), block, 0, st, a); break;
-      }
-      return;
-    }
-  }
+  // One 8-wave workgroup per very long segment (the diverted columns of a power-law view: 880 000 observations at the C2-Zipf recipe) is
+  // bound by the latency of its factor gathers: with one observation per lane group in flight the longest column alone took 13.7 ms of a
+  // 15.7 ms Y half-step (profiles/r06_c2_zipf_kernel_stats.csv).  Eight per group in flight -- session r6_26.
+  // G == 4, one wave: four observations per trip, one loss evaluation per lane (C5-family row sweep 169 -> 115 ms); the 4-wave sweeps of
+  // long same-loss segments are bound by the factor gather and keep the leaner one-observation body.
+  constexpr int U_SEG = WAVES == 8 ? 8 : (G == 4 && WAVES == 1 ? 4 : 1), U_OBS = WAVES == 8 ? 8 : (G == 4 ? 4 : 1);
   switch (loss) {
     case LOSS_QUAD_UNIFORM:
-      if (unroll == 2) GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 2);
-      else GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 1);
+      if constexpr (WAVES == 1) { // two observations in flight on the row view: -20 % on the L2-latency-bound row sweep
+        if (rows) GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 2);
+        else GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 1);
+      } else {
+        GLRM_LAUNCH(LOSS_QUAD_UNIFORM, (WAVES == 8 ? 8 : 1));
+      }
       break;
-    // G == 4: four observations per trip, one loss evaluation per lane (C5-family row sweep 169 -> 115 ms); the multi-wave
-    // sweeps of long same-loss segments are bound by the factor gather and keep the leaner one-observation body
-    case LOSS_SEGMENT: GLRM_LAUNCH(LOSS_SEGMENT, (G == 4 && WAVES == 1 ? 4 : 1)); break;
-    case LOSS_SEGMENT_NOTRIG: GLRM_LAUNCH(LOSS_SEGMENT_NOTRIG, (G == 4 && WAVES == 1 ? 4 : 1)); break;
-    case LOSS_PER_OBS_NOTRIG: GLRM_LAUNCH(LOSS_PER_OBS_NOTRIG, (G == 4 ? 4 : 1)); break;
-    default: GLRM_LAUNCH(LOSS_PER_OBS, (G == 4 ? 4 : 1)); break;
+    case LOSS_SEGMENT: GLRM_LAUNCH(LOSS_SEGMENT, U_SEG); break;
+    case LOSS_SEGMENT_NOTRIG: GLRM_LAUNCH(LOSS_SEGMENT_NOTRIG, U_SEG); break;
+    case LOSS_PER_OBS_NOTRIG: GLRM_LAUNCH(LOSS_PER_OBS_NOTRIG, U_OBS); break;
+    default: GLRM_LAUNCH(LOSS_PER_OBS, U_OBS); break;
   }
 #undef GLRM_LAUNCH
 }
 
 template <int G, int R>
-static void launch_sweep_waves(int waves, int loss, int unroll, const SweepArgs& a, hipStream_t st) {
+static void launch_sweep_waves(int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
   switch (waves) {
-    case 1: launch_sweep_loss<G, R, 1>(loss, unroll, a, st); break;
-    case 4: launch_sweep_loss<G, R, 4>(loss, unroll, a, st); break;
-    default: launch_sweep_loss<G, R, 8>(loss, unroll, a, st); break;
+    case 1: launch_sweep_loss<G, R, 1>(loss, rows, a, st); break;
+    case 4: launch_sweep_loss<G, R, 4>(loss, rows, a, st); break;
+    default: launch_sweep_loss<G, R, 8>(loss, rows, a, st); break;
   }
 }
 
-// (lanes per observation G, components per lane R) with G*R == kp
-static void launch_sweep(int G, int R, int waves, int loss, int unroll, const SweepArgs& a, hipStream_t st) {
+// (lanes per observation G, components per lane R) with G*R == kp: the layouts of pick_layout
+static void launch_sweep(int G, int R, int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
   switch (G * 100 + R) {
-    case 402: launch_sweep_waves<4, 2>(waves, loss, unroll, a, st); break;
-    case 404: launch_sweep_waves<4, 4>(waves, loss, unroll, a, st); break;
-    case 408: launch_sweep_waves<4, 8>(waves, loss, unroll, a, st); break;
-    case 804: launch_sweep_waves<8, 4>(waves, loss, unroll, a, st); break;
-    case 1602: launch_sweep_waves<16, 2>(waves, loss, unroll, a, st); break;
-    case 808: launch_sweep_waves<8, 8>(waves, loss, unroll, a, st); break;
-    case 1604: launch_sweep_waves<16, 4>(waves, loss, unroll, a, st); break;
-    default: launch_sweep_waves<16, 8>(waves, loss, unroll, a, st); break;
+    case 402: launch_sweep_waves<4, 2>(waves, loss, rows, a, st); break;
+    case 404: launch_sweep_waves<4, 4>(waves, loss, rows, a, st); break;
+    case 408: launch_sweep_waves<4, 8>(waves, loss, rows, a, st); break;
+    case 808: launch_sweep_waves<8, 8>(waves, loss, rows, a, st); break;
+    default: launch_sweep_waves<16, 8>(waves, loss, rows, a, st); break;
   }
 }
 
@@ -1169,7 +1142,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
       SweepArgs b = a;
       b.seglist = h->blk_long_c;
       b.nseg = h->blk_nlong_c;
-      launch_sweep(h->G, h->R, 8, loss, h->unroll_long, b, h->side_stream);
+      launch_sweep(h->G, h->R, 8, loss, false, b, h->side_stream);
     }
     rc = tiled ? glrm_run_tiled(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only)
                : glrm_run_blocked(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only);
@@ -1185,14 +1158,13 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
     // gather sweeps (and the cached row sweep), class by class -- see build_class_plan
     const int64_t* ncls = rows ? h->ncls_r : h->ncls_c;
     const int32_t* lst = rows ? h->seglist_r : h->seglist_c;
-    const int unroll = rows ? h->unroll_row : h->unroll_col;
     if (!lst) { // one class holds every local segment
       int cls = 1;
       for (int c = 0; c < 4; ++c) if (ncls[c] > 0) cls = c;
       if (cls == 0 && !eval_only) {
         if ((rc = glrm_run_cached(h, loss, min_stepsize, nullptr, 0, h->stream))) return rc;
       } else {
-        launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, cls <= 1 ? unroll : (glrm_class_waves(cls) == 8 ? h->unroll_long : 1), a, h->stream);
+        launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, rows, a, h->stream);
       }
     } else {
       // fork: the minority classes on the side stream, beside the majority class on the main stream; join
@@ -1211,7 +1183,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
           SweepArgs b = a;
           b.seglist = lst + off;
           b.nseg = ncls[c];
-          launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, c <= 1 ? unroll : (glrm_class_waves(c) == 8 ? h->unroll_long : 1), b, st);
+          launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, rows, b, st);
         }
       }
       if (rc_cls) { // join before reporting: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
@@ -1339,7 +1311,7 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
   int rc = GLRM_OK;
   // the pass families of the column view can start on a part of X (the phase-aligned passes super-tile by super-tile in true arrival order,
   // the LDS-tiled / lane passes in runs of super-tiles in the announced order: round 6); everything else needs all of it
-  const bool by_super_tile = ((h->blocked_col && !h->lockstep && !h->tiled_col) || h->tiled_col) && !h->multi && !h->dense && !h->sum_order_opt && env_int("GLRM_HIP_ARRIVAL", 1);
+  const bool by_super_tile = (h->blocked_col || h->tiled_col) && !h->multi && !h->dense && !h->sum_order_opt && env_int("GLRM_HIP_ARRIVAL", 1);
   if (!by_super_tile) rc = glrm_arrival_wait(h, 0, h->m);
   if (!rc) rc = run_sweep(h, 1, min_stepsize, 0);
   if (!rc) rc = glrm_arrival_wait(h, 0, h->m); // (a shard without columns launches nothing: later work on the stream still follows the arrivals)
@@ -1465,18 +1437,16 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
   if (h->sum_order_opt) {
     o.family = GLRM_ORDER_REFERENCE; // glrm_reforder.hip: one lane per segment, list order, one accumulator per sum
     o.lanes = 1; o.comps = h->kp;
-  } else if (h->multi || h->dense || (blocked && !rows && h->lockstep)) {
+  } else if (h->multi || h->dense) {
     o.family = GLRM_ORDER_OTHER;
   } else if (tiled) {
-    const int T = h->order_unit; // vectors per staged tile (half a tile with loader waves)
-    const bool lw = h->tile_lw > 0 && h->tile_cfg && ((h->tile_lw_sides >> (rows && !h->row_split ? 0 : 1)) & 1);
+    const int T = glrm_tile_rows(h->kp); // vectors per staged tile
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->tG; o.comps = h->tR;
-    o.window = lw ? T : (h->tile_lw > 0 ? 2 * T : T);
-    const int64_t tps = rows ? (h->row_split ? h->tiles_per_sup_r : 0) : h->tiles_per_sup; // (row rounds: one super-tile, nothing re-added = 0)
-    o.windows_per_sup = lw ? 2 * tps : tps;
+    o.window = T;
+    o.windows_per_sup = rows ? 0 : h->tiles_per_sup; // (rows: one super-tile, nothing re-added = 0)
     o.batch = (!quad && (h->tG == 4 || h->tG == 8)) ? h->tG : 2;
-    o.rotate = (!(rows && !h->row_split) && !lw && !quad && GLRM_TILE_ROT && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
+    o.rotate = (!rows && !quad && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
     // a private copy in another order: lists the engine tile-sorted, rows regrouped by loss kind inside the tile windows
     const bool sorted_here = rows ? h->sig_local.rows_unordered != 0 : h->sig_local.cols_unordered != 0;
     const bool grouped = rows && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !h->lane[0]; // glrm_tiled.hpp: group_rows_by_kind_kernel (lane rows keep the caller's order)
@@ -1489,10 +1459,9 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
       o.windows_per_sup = rows ? 0 : h->tiles_per_sup;
     }
   } else if (blocked) {
-    const int Tb = ((150 * 1024) / (h->kp * 8 + 16)) / 16 * 16; // glrm_blocked.hip: tile_rows_b
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->G; o.comps = h->R;
-    o.window = (int64_t)Tb * (rows ? h->tiles_per_sup_r : h->tiles_per_sup); // one walk per super-tile: the super-tile is the window
+    o.window = (int64_t)glrm_tile_rows(h->kp) * (rows ? h->tiles_per_sup_r : h->tiles_per_sup); // one walk per super-tile: the super-tile is the window
     o.windows_per_sup = 1;
     o.batch = (!quad && (h->G == 4 || h->G == 8)) ? h->G : 2;
   } else {

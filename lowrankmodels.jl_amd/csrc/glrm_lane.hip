@@ -23,11 +23,10 @@ using namespace glrm;
 namespace {
 
 constexpr int LANE_NW = 8; // 8 waves x 64 segments per workgroup, 256 VGPRs per lane
-constexpr int lane_tile_rows(int kp) { return ((150 * 1024) / (kp * 8 + 16)) / 16 * 16; } // = tile_rows_c(kp, 1): the order unit of the lists
 
 template <int LOSS, bool GRAD, int FORM, bool COMPACT = false>
 int launch_lane_inst(const TiledArgs& a, const LaneArgs& la, int64_t nblocks, hipStream_t st) {
-  constexpr int KP = 32, T = lane_tile_rows(KP);
+  constexpr int KP = 32, T = glrm_tile_rows(KP);
   const int LDSB = T * KP * 8 + (loss_mode(LOSS) == 2 ? a.n_udesc * 32 : 0);
   auto k = lane_pass_kernel<KP, LANE_NW, T, LOSS, GRAD, FORM, COMPACT>;
   HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB)); // (per device: a process may drive several)
@@ -72,7 +71,7 @@ int launch_lane_loss(int loss, const TiledArgs& a, const LaneArgs& la, int64_t n
 // a wave per (segment, super-tile), no tile: the tail rounds (glrm_lane.hpp: lane_tail_kernel)
 constexpr int LANE_TAIL_CAP = 2048; // terms it parks in LDS at a time
 int launch_lane_tail(int loss, const TiledArgs& a, const int32_t* list, int64_t nact, hipStream_t st) {
-  constexpr int KP = 32, T = lane_tile_rows(KP);
+  constexpr int KP = 32, T = glrm_tile_rows(KP);
   nact *= a.nsup; // waves of the round
   const unsigned gx = (unsigned)((nact + 1) / 2);
   switch (loss) {
@@ -117,11 +116,10 @@ bool glrm_lane_few_descriptors(const glrm_handle* h) {
   return true;
 }
 
-// what does not depend on the buffers: padded rank, tile configuration, losses, view size -- all of the WHOLE problem
+// what does not depend on the buffers: padded rank, losses, view size -- all of the WHOLE problem
 bool glrm_lane_wants(const glrm_handle* h, bool rows) {
   const int want = env_int("GLRM_HIP_LANE", 3); // bit0 rows, bit1 columns
-  if (!((want >> (rows ? 0 : 1)) & 1) || h->kp != 32 || !h->tile_cfg || h->tile_lw > 0 || h->multi || h->dense || h->sum_order_opt) return false;
-  if (lane_tile_rows(h->kp) != h->order_unit) return false; // (loader-wave experiments order the lists by half tiles)
+  if (!((want >> (rows ? 0 : 1)) & 1) || h->kp != 32 || h->multi || h->dense || h->sum_order_opt) return false;
   // a loss per column: the row view meets a descriptor per observation -- through one-byte ids, i.e. at most 256 distinct descriptors.
   // Default since session r6_33 (GLRM_HIP_LANE_PER_OBS=0 keeps such rows on the four-lane kernels): with the trial rounds read out of the
   // SELL layout (glrm_run_lane) the C5 recipe's X half-step is 42.5 against 46.6 ms at 1M rows and 194 against 215 ms at its stated size.
@@ -139,12 +137,12 @@ bool glrm_lane_wants(const glrm_handle* h, bool rows) {
 int glrm_setup_lane(glrm_handle* h) {
   h->lane[0] = h->lane[1] = 0;
   int64_t gseg_max = 0;
-  const int T = lane_tile_rows(h->kp);
+  const int T = glrm_tile_rows(h->kp);
   hipStream_t st = h->stream;
   for (int side = 0; side < 2; ++side) {
     const bool rows = side == 0;
     if (!glrm_lane_wants(h, rows)) continue;
-    if (rows ? !(h->tiled_row && !h->row_split && (h->tile_rounds & 1) && h->actlist && h->part_r) : !h->tiled_col) continue;
+    if (rows ? !(h->tiled_row && (h->tile_rounds & 1) && h->actlist && h->part_r) : !h->tiled_col) continue;
     if (rows && h->n_losses > 1 && !(h->rowdescid && h->n_udesc > 0)) continue;
     h->lane[side] = 1;
     const int64_t nseg = rows ? h->ml : h->nl;
@@ -288,7 +286,7 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
     r.npass = 0;
     return launch_lane_loss<true, 1>(loss, r, csr_args(r), (r.nseg + 63) / 64, st);
   };
-  rc = rows ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * lane_tile_rows(h->kp), grad); // (rows read Y: complete)
+  rc = rows ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), grad); // (rows read Y: complete)
   if (rc) return rc;
   launch_small(0, a, st);
   HIPCK(hipGetLastError());

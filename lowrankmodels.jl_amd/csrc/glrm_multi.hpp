@@ -18,10 +18,6 @@
 
 #include "glrm_device.hpp"
 
-#ifndef GLRM_MULTI_PF
-#define GLRM_MULTI_PF 0 // software-pipeline depth of the row sweep with register-resident blocks (multi_pass); measured: 0 is fastest (the extra registers spill)
-#endif
-
 namespace glrm {
 
 struct MultiArgs {
@@ -383,17 +379,10 @@ __device__ inline double obs_loss(const LossDesc& l, double u, double u0, double
   double e_hi = 0.0, e_lo = 0.0, u_hi = 0.0;
   if (__any(ord)) {
     const double TOL = 1e-3;
-#if defined(GLRM_MNLORD_LIBM) // A/B build: the thresholds through LDS, one read per lower threshold
-    if (ord && in) us[sub] = u;
-    wave_sync();
-    double w = -TOL;
-    if (ord && in) for (int i = 0; i <= sub; ++i) { const double wi = us[i] + i * TOL; w = wi < w ? wi : w; }
-#else
     (void)us;
     const double wi = u + sub * TOL;
     const double pm = slot_prefix((ord && in && wi == wi) ? wi : __builtin_inf(), sub, lg, OpMin());
     const double w = (ord && in && pm < -TOL) ? pm : -TOL;
-#endif
     const double up = w - sub * TOL;
     const double ea = ord ? fm_exp(up) : 0.0;
     int hi = a > 0 ? a - 1 : 0, lo = a < dd ? a : dd - 1; // lanes of u'_{a-1}, u'_a
@@ -402,9 +391,6 @@ __device__ inline double obs_loss(const LossDesc& l, double u, double u0, double
     e_hi = __shfl(ea, slot_lane0 + hi, 64); // exp(u'_{a-1})
     e_lo = __shfl(ea, slot_lane0 + lo, 64); // exp(u'_a)
     u_hi = __shfl(up, slot_lane0 + hi, 64);
-#if defined(GLRM_MNLORD_LIBM)
-    wave_sync();
-#endif
   }
   // stage 3: per-kind closing formulas (lane-local)
   cg = 0.0;
@@ -431,21 +417,6 @@ __device__ inline double obs_loss(const LossDesc& l, double u, double u0, double
         break;
       default: { // GLRM_LOSS_MULTINOMIAL_ORDINAL
         if (!mk_has<KM>(GLRM_LOSS_MULTINOMIAL_ORDINAL)) break;
-#if defined(GLRM_MNLORD_LIBM) // A/B build: ocml log and a division per branch (the form before round 3)
-        double g = 0.0;
-        if (a == 0) {
-          L = -s * log(1.0 - e_lo);
-          if (sub == 0) g = -e_lo / (1.0 - e_lo);
-        } else if (a == dd) {
-          L = -s * u_hi;
-          if (sub == a - 1) g = 1.0;
-        } else {
-          const double den = e_hi - e_lo;
-          L = -s * log(den);
-          if (sub == a) g = -e_lo / den;
-          else if (sub == a - 1) g = e_hi / den;
-        }
-#else
         // src/losses.jl:581-609 with the operands selected per level and ONE logarithm, ONE division: level 1: -log(1 - e_1), the top
         // level: -u'_{d}, between: -log(e_{a-1} - e_a); the two lanes of the thresholds next to the level hold the only nonzero gradients
         const bool bot = a == 0, top = a == dd;
@@ -457,7 +428,6 @@ __device__ inline double obs_loss(const LossDesc& l, double u, double u0, double
           const double q = (at_lo ? -e_lo : e_hi) / den;
           g = top ? (at_hi ? 1.0 : 0.0) : (at_lo || at_hi ? q : 0.0);
         }
-#endif
         if (GRAD && in) cg = -s * g;
       }
     }
@@ -517,32 +487,6 @@ __device__ inline double multi_pass(const MultiArgs& a, int64_t b, int64_t e, co
       xr_n = a.other[(int64_t)id_nn * kp + (comp ? sub : 0)];
     }
   }
-  // Rows with register-resident blocks: the chain index -> (loss descriptor, first vector of the column) -> the column's vectors is
-  // software-pipelined as well.  PF = 1: descriptor and ystart of the NEXT observation are requested while this one is worked on, so
-  // the block loads at the top of an iteration wait for one memory round trip instead of two; PF = 2: they run two ahead and the block
-  // itself one ahead (RD more doubles per lane).
-  constexpr int PF = (ROWS && RD > 0) ? GLRM_MULTI_PF : 0;
-  LossDesc l_n = lseg, l_nn = lseg;
-  int d_n = 1, d_nn = 1;
-  int64_t ys_n = 0, ys_nn = 0;
-  double ynx[(PF >= 2) ? RD : 1];
-  auto fetch_desc = [&](int32_t idc, LossDesc& lo, int& dc, int64_t& ysc) {
-    const int64_t li = a.loss_single ? 0 : idc;
-    lo = load_loss(a.losses, li);
-    dc = a.losses[li].dim > 1 ? a.losses[li].dim : 1;
-    ysc = a.ystart[idc];
-  };
-  if constexpr (PF >= 1) {
-    if (e > b) {
-      fetch_desc(id_n, l_n, d_n, ys_n);
-      if constexpr (PF >= 2) {
-        fetch_desc(id_nn, l_nn, d_nn, ys_nn);
-        const double* Yb = a.other + ys_n * kp;
-#pragma unroll
-        for (int j = 0; j < RD; ++j) ynx[j] = (j < d_n && comp) ? Yb[j * kp + sub] : 0.0;
-      }
-    }
-  }
   for (int64_t t0 = b + (int64_t)wave * SL; t0 < e; t0 += stride) { // wave-uniform trip count
     const bool valid = t < e;
     const int32_t id = id_n;
@@ -558,23 +502,7 @@ __device__ inline double multi_pass(const MultiArgs& a, int64_t b, int64_t e, co
     if constexpr (!ROWS) xr_n = a.other[(int64_t)id_nn * kp + (comp ? sub : 0)]; // the row two observations ahead
     LossDesc l = lseg;
     int d = dseg;
-    if constexpr (PF >= 1) { // (id_n is the NEXT observation from here on)
-      l = l_n; d = d_n;
-      if constexpr (PF >= 2) {
-#pragma unroll
-        for (int j = 0; j < RD; ++j) yreg[j] = ynx[j];
-        l_n = l_nn; d_n = d_nn; ys_n = ys_nn;
-        fetch_desc(id_nn, l_nn, d_nn, ys_nn);
-        const double* Yn = a.other + ys_n * kp;
-#pragma unroll
-        for (int j = 0; j < RD; ++j) ynx[j] = (j < d_n && comp) ? Yn[j * kp + sub] : 0.0;
-      } else {
-        const double* Yb = a.other + ys_n * kp;
-#pragma unroll
-        for (int j = 0; j < RD; ++j) yreg[j] = (j < d && comp) ? Yb[j * kp + sub] : 0.0;
-        fetch_desc(id_n, l_n, d_n, ys_n);
-      }
-    } else if constexpr (ROWS) {
+    if constexpr (ROWS) {
       const int64_t li = a.loss_single ? 0 : id;
       l = load_loss(a.losses, li);
       d = a.losses[li].dim > 1 ? a.losses[li].dim : 1;

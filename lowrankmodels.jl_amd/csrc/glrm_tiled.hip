@@ -13,11 +13,7 @@ using namespace glrm;
 
 // ------------------------------------------------------------------ LDS-tiled sweeps: setup and launch
 
-// opposing vectors per LDS tile (rows are padded by 16 B): cfg 0 = 64 KB tile, 8 waves, two workgroups per CU;
-// cfg 1 = 150 KB tile, 16 waves, one workgroup per CU (fewer barriers, fewer factor re-reads)
-constexpr int tile_rows_c(int kp, int cfg) { return ((cfg ? 150 * 1024 : 64 * 1024) / (kp * 8 + 16)) / 16 * 16; }
-static int tile_rows(int kp, int cfg) { return tile_rows_c(kp, cfg); }
-static bool tile_rot_rt(int G, int R) { return GLRM_TILE_ROT && (G == 4 || G == 8) && R == 8; }
+static bool tile_rot_rt(int G, int R) { return (G == 4 || G == 8) && R == 8; }
 
 // slot -> segment permutation of a tiled sweep: segments sorted by (loss kind of the column,) descending length, so that the 16
 // lane groups of a wave meet one loss formula and lists of similar length.  nullptr when the natural order is already that
@@ -95,30 +91,17 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
   return GLRM_OK;
 }
 
-// create phase: the tile configuration and whether this shard's lists are in tile order (glrm_signature::rows_unordered / cols_unordered)
+// create phase: the lane layout of the tiled kernels and whether this shard's lists are in tile order (glrm_signature::rows_unordered /
+// cols_unordered): the entries of staged tile t must precede those of tile t+1
 int glrm_prepare_tiled(glrm_handle* h) {
   hipStream_t st = h->stream;
-  h->tile_cfg = env_int("GLRM_HIP_TILE_CFG", 1);
-  h->tile_cfg12 = h->tile_cfg == 2; // experiment: 12-wave heterogeneous row sweep
-  // Loader waves of the double-buffered tiled sweeps (0 = single tile staged by every wave; glrm_tiled.hpp).  Round 2 ran the ROW sweep of
-  // uniform QuadLoss models on two loader waves (C2 row sweep 8.31 -> 7.41 ms against load / ds_write staging).  Since round 3 the single
-  // tile is staged by LDS-DMA from all waves (dma_tile_all) and wins on the four shapes that default was chosen on (tools/gpu_r3_30.sh,
-  // profiles/r03_tile_dma_all_ab.txt: C2 row sweep 7.50 -> 7.12 ms, 1M x 50k 23.0 -> 20.4, 1M x 2k 1.51 -> 1.48, 300k x 3k 0.73 -> 0.69, same
-  // objective bits): the default is 0 everywhere; GLRM_HIP_TILE_LW = 1 | 2 still selects the loader waves.
-  h->tile_lw = env_int("GLRM_HIP_TILE_LW", 0);
-  if (h->tile_lw < 0 || h->tile_lw > 2 || !((h->G == 4 || h->G == 8) && h->R == 8) || !h->tile_cfg) h->tile_lw = 0;
-  h->tile_lw_sides = env_int("GLRM_HIP_TILE_LW_SIDES", 1); // bit0: row sweep, bit1: column passes
-  h->tile_cfg = h->tile_cfg ? 1 : 0;
   h->tG = h->G;
   h->tR = h->R;
-  // order granularity of the index lists: the entries of staged tile t must precede those of tile t+1; with loader waves the
-  // staged unit is HALF a tile (a list ordered by half tile is ordered by tile as well)
-  const int T0 = h->tile_lw > 0 ? tile_rows(h->kp, h->tile_cfg) / 2 : tile_rows(h->kp, h->tile_cfg);
-  h->order_unit = T0;
+  const int T = glrm_tile_rows(h->kp);
   HIPCK(hipMalloc((void**)&h->dflag, 2 * sizeof(int)));
   HIPCK(hipMemsetAsync(h->dflag, 0, 2 * sizeof(int), st));
-  if (h->ml > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->ml, T0, h->dflag);
-  if (h->nl > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->nl), dim3(256), 0, st, h->colptr, h->rowidx, h->nl, T0, h->dflag + 1);
+  if (h->ml > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->ml, T, h->dflag);
+  if (h->nl > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->nl), dim3(256), 0, st, h->colptr, h->rowidx, h->nl, T, h->dflag + 1);
   HIPCK(hipGetLastError());
   int flags[2] = {0, 0};
   HIPCK(hipMemcpyAsync(flags, h->dflag, sizeof flags, hipMemcpyDeviceToHost, st));
@@ -133,11 +116,10 @@ int glrm_prepare_tiled(glrm_handle* h) {
 int glrm_setup_tiled(glrm_handle* h) {
   hipStream_t st = h->stream;
   int rc0 = GLRM_OK;
-  const int T0 = h->order_unit;
   h->rows_sorted = !h->sig.rows_unordered;
   h->cols_sorted = !h->sig.cols_unordered;
 
-  const int T = tile_rows(h->kp, h->tile_cfg);
+  const int T = glrm_tile_rows(h->kp);
   // expected observations of one segment inside one tile; the tiled sweeps pay off when a staged
   // vector is reused by several of the workgroup's segments
   const double per_tile_r = (double)h->sig.nnz_rows / (double)h->m * T / (double)h->n;
@@ -149,7 +131,7 @@ int glrm_setup_tiled(glrm_handle* h) {
   // Auto choice (measured on MI355X, tests/perf/bench_small.py): the tiled sweeps need enough workgroups to fill 256 CUs and
   // enough observations to amortise their per-tile barriers; below ~2e7 observations per view the gather sweeps win (100k x 5k
   // at 1e7 observations: 1.06 vs 1.23 ms per iteration; 300k x 3k at 4.5e7: 4.6 vs 3.1 ms).
-  const int spb_auto = ((h->tile_cfg ? 16 : 8) - h->tile_lw) * (64 / h->tG);
+  const int spb_auto = 16 * (64 / h->tG);
   const bool big_r = h->sig.nnz_rows >= 20000000 && h->m >= (int64_t)512 * spb_auto;
   const bool big_c = h->sig.nnz_cols >= 20000000 && h->n >= 256;
   bool want_row = want < 0 ? (per_tile_r >= 4.0 && big_r) : (want & 1) != 0;
@@ -164,7 +146,7 @@ int glrm_setup_tiled(glrm_handle* h) {
   const int64_t sort_limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0) > 0 ? env_int("GLRM_HIP_TILE_SORT_BATCH", 0) : 1500000000ll;
   if (want_row && !h->rows_sorted && may_sort && h->sig.max_row_len <= sort_limit) {
     if (h->sig_local.rows_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->rowptr, h->ml, h->nnz_r, T0, h->n, &h->colidx, &h->rowvals, h->own_rowview);
+      const int rc = glrm_tile_sort_view(st, h->rowptr, h->ml, h->nnz_r, T, h->n, &h->colidx, &h->rowvals, h->own_rowview);
       if (rc) return rc;
       h->own_rowview = true;
     }
@@ -172,7 +154,7 @@ int glrm_setup_tiled(glrm_handle* h) {
   }
   if (want_col && !h->cols_sorted && may_sort && h->sig.max_col_len <= sort_limit) {
     if (h->sig_local.cols_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->colptr, h->nl, h->nnz_c, T0, h->m, &h->rowidx, &h->colvals, h->own_colview);
+      const int rc = glrm_tile_sort_view(st, h->colptr, h->nl, h->nnz_c, T, h->m, &h->rowidx, &h->colvals, h->own_colview);
       if (rc) return rc;
       h->own_colview = true;
     }
@@ -182,13 +164,13 @@ int glrm_setup_tiled(glrm_handle* h) {
   h->tiled_col = (h->cols_sorted && want_col) ? 1 : 0;
   // (rows on the lane-per-segment passes -- glrm_lane.hpp -- keep the caller's order: every lane evaluates its own observation's loss, so
   // there is no wave-wide formula to align, and the grouped copy would cost 12 B per observation beside the SELL stream)
-  const bool lane_rows = h->tiled_row && !env_int("GLRM_HIP_ROW_SPLIT", 0) && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && !(h->tile_cfg12) && glrm_lane_wants(h, true);
+  const bool lane_rows = h->tiled_row && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && glrm_lane_wants(h, true);
   if (h->tiled_row && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !lane_rows) {
     int32_t* oidx = nullptr;
     double* ovals = nullptr;
     HIPCK(hipMalloc((void**)&oidx, (size_t)h->nnz_r * 4));
     if (hipMalloc((void**)&ovals, (size_t)h->nnz_r * 8) != hipSuccess) { (void)hipFree(oidx); return fail(GLRM_ERR_OOM, "out of device memory"); }
-    hipLaunchKernelGGL(group_rows_by_kind_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->rowvals, h->ml, T0, h->losses, oidx, ovals);
+    hipLaunchKernelGGL(group_rows_by_kind_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->rowvals, h->ml, T, h->losses, oidx, ovals);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(st));
     if (h->own_rowview) {
@@ -241,7 +223,7 @@ int glrm_setup_tiled(glrm_handle* h) {
     // them: more, shorter super-tiles even the workgroups out -- C2 Y half-step 7.6 -> 7.0 ms at twice the workgroups, session r6_09; the
     // family is a function of the whole problem's signature, so this still is)
     const bool lane_c = h->tiled_col && glrm_lane_wants(h, false);
-    const int spb = lane_c ? 512 : (h->tile_cfg ? 16 : 8) * (64 / h->tG);
+    const int spb = lane_c ? 512 : 16 * (64 / h->tG);
     const int64_t groups = (h->n + spb - 1) / spb;
     const int64_t want_wg = env_int("GLRM_HIP_COL_WORKGROUPS", lane_c ? 2048 : 1024);
     int64_t nsup_target = (want_wg + groups - 1) / groups;
@@ -292,51 +274,24 @@ int glrm_setup_tiled(glrm_handle* h) {
   // first trial; rows: everything after the first trial, which stays fused with the gradient pass in one kernel (GLRM_HIP_TILE_ROUNDS:
   // bit0 rows, bit1 columns, default 3; 0 = the round-3 forms).  Two lists (the decide kernel reads one and writes the next).
   h->tile_rounds = env_int("GLRM_HIP_TILE_ROUNDS", 3);
-  if (h->tile_cfg12) h->tile_rounds &= ~1; // the 12-wave experiment exists for the one-kernel row sweep only
   if ((h->tiled_row && (h->tile_rounds & 1)) || (h->tiled_col && (h->tile_rounds & 2))) {
     const int64_t cap = std::max<int64_t>(1, std::max(h->tiled_row ? h->ml : 0, h->tiled_col ? h->nl : 0));
     HIPCK(hipMalloc((void**)&h->actlist, (size_t)cap * 2 * sizeof(int32_t)));
     h->actlist_cap = cap;
   }
-  // Row sweep in super-tile passes.  The one-kernel row sweep streams the WHOLE opposing factor through LDS per workgroup and pass;
-  // workgroups that started at different times are at different tiles, so once Y no longer fits the 4 MB L2 of an XCD every tile
-  // they stage comes from the Infinity Cache (~8 TB/s for the whole chip, profiles/r02_ubench_gather.txt) -- at 1M x 50k, k = 32
-  // that is 100 GB per half-step and 2/3 of its time.  In pass form (the column machinery: pass over one super-tile per workgroup,
-  // partials, reduce, trial passes, decide) the grid is ordered super-tile major, so the workgroups in flight all stage tiles of
-  // the same L2-sized super-tile.  Super-tile = ~2.5 MB of Y, a function of (n, tile, kp) only.
-  h->row_split = 0;
-  if (h->tiled_row) {
-    const int want_split = env_int("GLRM_HIP_ROW_SPLIT", 0); // measured: no gain (the staged tiles already hit L2 at 88 %); kept as an experiment switch
-    if (!want_split && (h->tile_rounds & 1)) { // the pass buffers of the row rounds: ONE super-tile (nothing is re-added: the bits of the one-kernel sweep)
-      const int64_t nt = (h->n + T - 1) / T;
-      h->tiles_per_sup_r = (int)(nt > 0 ? nt : 1);
-      h->nsup_r = 1;
-      const int64_t ml1 = h->ml > 0 ? h->ml : 1;
-      HIPCK(hipMalloc((void**)&h->part_r, (size_t)ml1 * (h->kp + 2) * 8));
-      HIPCK(hipMalloc((void**)&h->gsum_r, (size_t)ml1 * h->kp * 8));
-      HIPCK(hipMalloc((void**)&h->trial_r, (size_t)ml1 * h->kp * 8));
-      HIPCK(hipMalloc((void**)&h->jold_r, (size_t)ml1 * 8));
-      HIPCK(hipMalloc((void**)&h->active_r, (size_t)ml1 * 4));
-      HIPCK(hipMalloc((void**)&h->ntrial_r, (size_t)ml1 * 4));
-      if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
-    }
-    if (want_split) {
-      h->tile_rounds &= ~1;
-      const int64_t nt = (h->n + T - 1) / T;
-      int64_t tps = ((int64_t)5 * 512 * 1024) / ((int64_t)T * h->kp * 8);
-      tps = env_int("GLRM_HIP_ROW_TPS", (int)(tps < 1 ? 1 : tps));
-      h->tiles_per_sup_r = (int)tps;
-      h->nsup_r = (int)((nt + tps - 1) / tps);
-      const int64_t ml1 = h->ml > 0 ? h->ml : 1;
-      HIPCK(hipMalloc((void**)&h->part_r, (size_t)ml1 * h->nsup_r * (h->kp + 2) * 8));
-      HIPCK(hipMalloc((void**)&h->gsum_r, (size_t)ml1 * h->kp * 8));
-      HIPCK(hipMalloc((void**)&h->trial_r, (size_t)ml1 * h->kp * 8));
-      HIPCK(hipMalloc((void**)&h->jold_r, (size_t)ml1 * 8));
-      HIPCK(hipMalloc((void**)&h->active_r, (size_t)ml1 * 4));
-      HIPCK(hipMalloc((void**)&h->ntrial_r, (size_t)ml1 * 4));
-      if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
-      h->row_split = 1;
-    }
+  // the pass buffers of the row rounds: ONE super-tile (nothing is re-added: the bits of the one-kernel sweep)
+  if (h->tiled_row && (h->tile_rounds & 1)) {
+    const int64_t nt = (h->n + T - 1) / T;
+    h->tiles_per_sup_r = (int)(nt > 0 ? nt : 1);
+    h->nsup_r = 1;
+    const int64_t ml1 = h->ml > 0 ? h->ml : 1;
+    HIPCK(hipMalloc((void**)&h->part_r, (size_t)ml1 * (h->kp + 2) * 8));
+    HIPCK(hipMalloc((void**)&h->gsum_r, (size_t)ml1 * h->kp * 8));
+    HIPCK(hipMalloc((void**)&h->trial_r, (size_t)ml1 * h->kp * 8));
+    HIPCK(hipMalloc((void**)&h->jold_r, (size_t)ml1 * 8));
+    HIPCK(hipMalloc((void**)&h->active_r, (size_t)ml1 * 4));
+    HIPCK(hipMalloc((void**)&h->ntrial_r, (size_t)ml1 * 4));
+    if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
   }
   return glrm_setup_lane(h); // the lane-per-segment form of the passes where it applies (glrm_lane.hip)
 }
@@ -348,80 +303,55 @@ static int set_lds(K kernel, int bytes) {
 }
 
 // kind: 0 = whole sweep (tiled_sweep_kernel), 1 = column pass 1, 2 = column trial pass, 3 = row sweep in rounds form (gradient pass +
-// first trial, the rest handed to the rounds), 4 = trial pass of the row rounds.  LW > 0: double-buffered half tiles, the first LW waves
-// of the workgroup are LDS-DMA loaders (glrm_tiled.hpp)
-template <int G, int R, int NW, int TILE, int LOSS, int LW = 0>
+// first trial, the rest handed to the rounds), 4 = trial pass of the row rounds
+template <int G, int R, int NW, int TILE, int LOSS>
 static int launch_tiled_inst(int kind, const TiledArgs& a, hipStream_t st) {
-  constexpr int SPB = (NW - LW) * (64 / G);
-  const int lds = tile_lds_bytes<G, R, TILE, LW>() + (loss_mode(LOSS) == 2 && a.descid ? a.n_udesc * 32 : 0);
+  constexpr int SPB = NW * (64 / G);
+  const int lds = tile_lds_bytes<G, R, TILE>() + (loss_mode(LOSS) == 2 && a.descid ? a.n_udesc * 32 : 0);
   const unsigned gx = (unsigned)(((a.npass > 0 ? a.npass : a.nseg) + SPB - 1) / SPB);
   int rc = GLRM_OK;
   if (kind == 0 && a.fixed_alpha > 0.0) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, true, LW>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, true, LW>), dim3(gx), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, true>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, true>), dim3(gx), dim3(NW * 64), lds, st, a);
   } else if (kind == 0) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, LW>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, LW>), dim3(gx), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false>), dim3(gx), dim3(NW * 64), lds, st, a);
   } else if (kind == 3) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, LW, true>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, LW, true>), dim3(gx), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, true>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, true>), dim3(gx), dim3(NW * 64), lds, st, a);
   } else if (kind == 4) {
-    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, LW, true>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, LW, true>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, true>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, true>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
   } else if (kind == 1) {
-    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, true, false, LW>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, true, false, LW>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, true, false>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, true, false>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
   } else {
-    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, LW>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, LW>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
+    if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false>, lds))) return rc;
+    hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
   }
   return GLRM_OK;
 }
 
+// 16 waves and one ~150 KB tile per CU
 template <int G, int R>
-static int launch_tiled_layout(int cfg, int loss, int kind, const TiledArgs& a, hipStream_t st) {
-  constexpr int KP = G * R, T0 = tile_rows_c(KP, 0), T1 = tile_rows_c(KP, 1);
-  if constexpr ((G == 4 || G == 8) && R == 8) {
-    // heterogeneous row sweep on 12 waves (3 per SIMD, 168 VGPRs: no spills) instead of 16 (128 VGPRs, ~45 spilled)
-    if (cfg == 2 && kind == 0 && a.fixed_alpha <= 0.0 && (loss == LOSS_PER_OBS || loss == LOSS_PER_OBS_NOTRIG)) // (legacy one-kernel form only)
-      return loss == LOSS_PER_OBS ? launch_tiled_inst<G, R, 12, T1, 2>(kind, a, st) : launch_tiled_inst<G, R, 12, T1, 4>(kind, a, st);
-  }
-  if (cfg == 2) cfg = 1;
-  if constexpr ((G == 4 || G == 8) && R == 8) { // double-buffered half tiles with 1 / 2 loader waves (cfg 11 / 12)
-#define GLRM_TLW(LOSSV) (cfg == 11 ? launch_tiled_inst<G, R, 16, T1, LOSSV, 1>(kind, a, st) : launch_tiled_inst<G, R, 16, T1, LOSSV, 2>(kind, a, st))
-    if (cfg == 11 || cfg == 12) {
-      switch (loss) {
-        case LOSS_QUAD_UNIFORM: return GLRM_TLW(0);
-        case LOSS_SEGMENT: return GLRM_TLW(1);
-        case LOSS_SEGMENT_NOTRIG: return GLRM_TLW(3);
-        case LOSS_PER_OBS_NOTRIG: return GLRM_TLW(4);
-        default: return GLRM_TLW(2);
-      }
-    }
-#undef GLRM_TLW
-  }
-  if (cfg >= 11) cfg = 1;
-#define GLRM_TL(LOSSV)                                                                   \
-  (cfg ? launch_tiled_inst<G, R, 16, T1, LOSSV>(kind, a, st) : launch_tiled_inst<G, R, 8, T0, LOSSV>(kind, a, st))
+static int launch_tiled_layout(int loss, int kind, const TiledArgs& a, hipStream_t st) {
+  constexpr int T = glrm_tile_rows(G * R);
   switch (loss) {
-    case LOSS_QUAD_UNIFORM: return GLRM_TL(0);
-    case LOSS_SEGMENT: return GLRM_TL(1);
-    case LOSS_SEGMENT_NOTRIG: return GLRM_TL(3);
-    case LOSS_PER_OBS_NOTRIG: return GLRM_TL(4);
-    default: return GLRM_TL(2);
+    case LOSS_QUAD_UNIFORM: return launch_tiled_inst<G, R, 16, T, 0>(kind, a, st);
+    case LOSS_SEGMENT: return launch_tiled_inst<G, R, 16, T, 1>(kind, a, st);
+    case LOSS_SEGMENT_NOTRIG: return launch_tiled_inst<G, R, 16, T, 3>(kind, a, st);
+    case LOSS_PER_OBS_NOTRIG: return launch_tiled_inst<G, R, 16, T, 4>(kind, a, st);
+    default: return launch_tiled_inst<G, R, 16, T, 2>(kind, a, st);
   }
-#undef GLRM_TL
 }
 
 static int launch_tiled(glrm_handle* h, int loss, int kind, const TiledArgs& a) {
-  const bool lw_here = h->tile_lw > 0 && h->tile_cfg && ((h->tile_lw_sides >> ((kind == 0 || kind == 3 || kind == 4) ? 0 : 1)) & 1);
-  const int cfg = lw_here ? 10 + h->tile_lw : (h->tile_cfg12 && h->tile_cfg) ? 2 : h->tile_cfg;
   switch (h->tG * 100 + h->tR) {
-    case 402: return launch_tiled_layout<4, 2>(cfg, loss, kind, a, h->stream);
-    case 404: return launch_tiled_layout<4, 4>(cfg, loss, kind, a, h->stream);
-    case 408: return launch_tiled_layout<4, 8>(cfg, loss, kind, a, h->stream);
-    case 808: return launch_tiled_layout<8, 8>(cfg, loss, kind, a, h->stream);
-    case 1608: return launch_tiled_layout<16, 8>(cfg, loss, kind, a, h->stream);
+    case 402: return launch_tiled_layout<4, 2>(loss, kind, a, h->stream);
+    case 404: return launch_tiled_layout<4, 4>(loss, kind, a, h->stream);
+    case 408: return launch_tiled_layout<4, 8>(loss, kind, a, h->stream);
+    case 808: return launch_tiled_layout<8, 8>(loss, kind, a, h->stream);
+    case 1608: return launch_tiled_layout<16, 8>(loss, kind, a, h->stream);
     default: return fail(GLRM_ERR_UNSUPPORTED, "no tiled kernel for lane layout G=%d R=%d", h->tG, h->tR);
   }
 }
@@ -470,7 +400,6 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
   a.eval_only = eval_only;
   a.fixed_alpha = eval_only ? 0.0 : h->fixed_alpha;
   a.descid = rows ? h->rowdescid : nullptr;
-  a.stagger = env_int("GLRM_HIP_TILE_STAGGER", 0);
   a.udesc = h->udesc;
   a.n_udesc = h->n_udesc;
   if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range
@@ -481,14 +410,14 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
     if (!a.reg_single) a.regs += s0;
     a.trials += s0; a.accepts += s0;
   }
-  const bool row_rounds = rows && !h->row_split && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
+  const bool row_rounds = rows && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
   // lane-per-segment passes (glrm_lane.hpp): the ProxGradParams half-steps and the evaluation pass of the sides that run that family
   const bool lane_here = h->lane[rows ? 0 : 1] && glrm_lane_loss_ok(h, loss) && a.fixed_alpha <= 0.0 && (rows ? row_rounds : true);
-  if (rows && !h->row_split && !row_rounds) {
+  if (rows && !row_rounds) {
     a.segperm = h->rng_e >= 0 ? nullptr : h->rowperm; // a sub-range sweep keeps the natural order
     return launch_tiled(h, loss, 0, a);
   }
-  if (rows) { // pass buffers of the rows (row_split: super-tile passes, glrm_setup_tiled; rounds: one super-tile)
+  if (rows) { // pass buffers of the row rounds (one super-tile, glrm_setup_tiled)
     const int64_t s0 = h->rng_e >= 0 ? h->rng_b : 0;
     a.nsup = h->nsup_r;
     a.tiles_per_sup = h->tiles_per_sup_r;
@@ -517,13 +446,11 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
   int cur = 0; // the list the kernels of this stage append to
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   a.actlist_out = list[cur];
-  if (row_rounds) {
+  if (rows) {
     if ((rc = launch_tiled(h, loss, 3, a))) return rc; // gradient pass + first trial; rejected rows are listed
   } else {
     // gradient pass: under glrm_hip_step_y_arrival in runs of super-tiles, each behind the blocks of X it reads (announced order)
-    const int T_ = tile_rows(h->kp, h->tile_cfg);
-    if (rows) rc = launch_tiled(h, loss, 1, a); // (the row view reads Y, which is complete)
-    else rc = glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * T_, [&](int s0, int s1) {
+    rc = glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), [&](int s0, int s1) {
       TiledArgs r = a;
       r.sup0 = s0;
       r.nsup_launch = s1 - s0;
@@ -551,13 +478,13 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
     TiledArgs t = full;
     // the trial pass: over the listed segments when they are the minority (a full grid keeps the length / kind order of segperm, which
     // pays while nearly every segment still takes part: the first trial of the columns)
-    const bool compact = lists && (row_rounds || (int64_t)nact * 4 < full.nseg * 3);
+    const bool compact = lists && (rows || (int64_t)nact * 4 < full.nseg * 3);
     if (compact) {
       t.segperm = list[cur];
       t.nseg = nact;
       t.npass = 0;
     }
-    if ((rc = launch_tiled(h, loss, rows && row_rounds ? 4 : 2, t))) return rc;
+    if ((rc = launch_tiled(h, loss, rows ? 4 : 2, t))) return rc;
     TiledArgs d = full;
     if (lists) {
       d.actlist_in = list[cur];

@@ -84,7 +84,6 @@ struct TiledArgs {
   // least `long_from` observations are swept by the 8-wave gather sweep beside the passes and are skipped by col_reduce / col_decide.
   int64_t npass;              // 0 = every segment
   int64_t long_from;          // 0 = no segment is diverted
-  int stagger;                // > 0: workgroup i of the 32 an XCD holds at a time starts i x stagger x ~0.2 us late (tile_stagger below)
   int32_t* actlist_out;       // nullable
   const int32_t* actlist_in;  // col_decide_kernel: nullable; the segments to decide (nact_in of them) instead of all nseg
   int64_t nact_in;
@@ -134,11 +133,8 @@ __device__ __forceinline__ double pair_bcast_f64(double v, int u0, int lane) {
 // kernel, SQ_WAIT_INST_LDS / 20 -- but the sweeps are not LDS-bound.  Row sweeps: QuadLoss 8.56 vs 8.48 ms, heterogeneous 407 vs 387 ms
 // (three more address XORs per observation, a few more spilled registers).  Column passes: QuadLoss 9.80 vs 9.67 ms, heterogeneous
 // 47.96 vs 50.08 ms.  So only the column passes of models with non-quadratic losses (LOSS != 0) use it.
-#ifndef GLRM_TILE_ROT
-#define GLRM_TILE_ROT 1
-#endif
 template <int G, int R>
-constexpr bool tile_rot() { return GLRM_TILE_ROT && (G == 4 || G == 8) && R == 8; }
+constexpr bool tile_rot() { return (G == 4 || G == 8) && R == 8; }
 __host__ __device__ __forceinline__ int tile_rot_of(int64_t gseg) { return ((int)gseg & 7) >> 1; }
 
 template <int G, int R>
@@ -146,87 +142,15 @@ constexpr int tile_row_bytes() { return G * R * 8 + 16; } // LDS budget per stag
 template <int G, int R, bool ROT>
 constexpr int tile_row_stride() { return ROT ? G * R * 8 : tile_row_bytes<G, R>(); } // ROT: unpadded rows inside the same budget
 
-// Copy opposing vectors [lo, hi) into LDS (coalesced 16-byte loads, padded rows).
-template <int G, int R, int NT, bool ROT = false>
-__device__ __forceinline__ void stage_tile(const double* __restrict__ other, int64_t lo, int64_t hi, char* lds) {
-  constexpr int KPB = G * R * 8, ROWB = tile_row_stride<G, R, ROT>();
-  const char* src = reinterpret_cast<const char*>(other) + lo * KPB;
-  const int total = (int)(hi - lo) * KPB;
-  constexpr int U = 4; // 4 x 16-byte loads in flight per thread before the LDS writes
-  for (int base = 0; base < total; base += NT * 16 * U) {
-    double2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) { // unconditional loads (clamped), predicated writes
-      int off = base + (u * NT + (int)threadIdx.x) * 16;
-      off = off < total ? off : total - 16;
-      v[u] = *reinterpret_cast<const double2*>(src + off);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int off = base + (u * NT + (int)threadIdx.x) * 16;
-      if (off < total) {
-        const int row = off / KPB, col = off - row * KPB;
-        *reinterpret_cast<double2*>(lds + row * ROWB + col) = v[u];
-      }
-    }
-  }
-}
+template <int G, int R, int TILE>
+constexpr int tile_lds_bytes() { return TILE * tile_row_bytes<G, R>(); } // the staged tile; the descriptor table sits behind
 
-// ---- double-buffered tiles (LW > 0 loader waves) ------------------------------------------------------------------------
-// Measured (tools/gpu_r2l.sh): staging is 20 % (C2) to 37 % (1M x 50k) of an LDS-tiled sweep and fully exposed -- every wave loads,
-// waits, writes LDS and meets two barriers per tile before anyone computes.  With LW > 0 the first LW waves of the workgroup are
-// LOADERS: they bring the next HALF tile into the other half of LDS with LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write
-// pass) while the remaining waves consume the current one; one barrier per half tile ("next one landed, everybody done with this
-// one").  Ordinary global loads of the compute waves cannot drain the DMA queue (hipcc waits vmcnt(0) at the first use of any
-// load result while LDS-DMA is in flight) because the DMA is issued by other waves.
-// The padded row layout is kept: the DMA destination is linear (base + lane x 16 B), so the SOURCE address of each 16-byte piece is
-// computed from its position in the padded image (piece c of the image = row c / 17, piece c % 17 of that row for kp = 32; the 17th
-// piece is the pad and re-reads the 16th).
-template <int G, int R, int TILE, int LW>
-constexpr int tile_buf_rows() { return LW > 0 ? TILE / 2 : TILE; }
-template <int G, int R, int TILE, int LW>
-constexpr int tile_buf_bytes() { // one staged buffer; a multiple of 1 KiB in loader mode (a DMA instruction writes a whole KiB)
-  return LW > 0 ? (tile_buf_rows<G, R, TILE, LW>() * tile_row_bytes<G, R>() + 1023) / 1024 * 1024 : TILE * tile_row_bytes<G, R>();
-}
-template <int G, int R, int TILE, int LW>
-constexpr int tile_lds_bytes() { return (LW > 0 ? 2 : 1) * tile_buf_bytes<G, R, TILE, LW>(); } // the descriptor table sits behind
-
-template <int G, int R, int LW>
-__device__ __forceinline__ void dma_tile(const double* __restrict__ other, int64_t lo, int64_t hi, char* buf, int wave, int lane) {
-  constexpr int KPB = G * R * 8, ROWB = tile_row_bytes<G, R>(), CPR = ROWB / 16;
-  const int rows = (int)(hi - lo), total = rows * CPR;
-  const char* src0 = reinterpret_cast<const char*>(other) + lo * KPB;
-  for (int base = wave * 64; base < total; base += LW * 64) { // one KiB of the padded image per instruction
-    int c = base + lane;
-    c = c < total ? c : total - 1;
-    const int row = c / CPR;
-    int cc = c - row * CPR;
-    cc = cc < CPR - 1 ? cc : CPR - 2; // the pad piece
-    const char* src = src0 + row * KPB + cc * 16;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(buf + base * 16), 16, 0, 0);
-  }
-}
-
-// Single-buffer staging by LDS-DMA from ALL waves (round 3; GLRM_TILE_DMA_ALL=0 builds the load / ds_write staging of stage_tile for A/B):
-// every 16-byte piece of the tile image is one lane of a global_load_lds_dwordx4 -- all pieces of the tile in flight at once (nine
-// instructions per wave for the 149 KB tile of k = 32), no VGPRs, no ds_write pass -- where stage_tile keeps four loads per thread in
-// flight and needs three rounds of load -> wait -> write.  Lanes past the end of the image are masked off (an inactive lane writes
-// nothing), so the buffer needs no KiB rounding.  Padded rows: piece c = row c / 17, piece c % 17 of it (the pad piece re-reads the
-// 16th); ROT rows are unpadded and the image is a plain copy.  Measured on one box (profiles/r03_tile_dma_all_ab.txt): C5-family row sweep
-// 63.2 -> 54.0 ms, C2 column passes 9.92 -> 9.00 ms, identical objectives.
-#ifndef GLRM_TILE_DMA_ALL
-#define GLRM_TILE_DMA_ALL 1
-#endif
-#ifndef GLRM_TILE_NT
-#define GLRM_TILE_NT 0
-#endif
-#ifndef GLRM_TILE_CHUNK_MAJOR
-#define GLRM_TILE_CHUNK_MAJOR 1
-#endif
-#ifndef GLRM_TILE_QUAD_FOUR
-#define GLRM_TILE_QUAD_FOUR 0
-#endif
+// Staging by LDS-DMA from all waves (round 3): every 16-byte piece of the tile image is one lane of a global_load_lds_dwordx4 -- all
+// pieces of the tile in flight at once (nine instructions per wave for the 149 KB tile of k = 32), no VGPRs, no ds_write pass -- where the
+// load / ds_write staging of rounds 1-2 kept four loads per thread in flight and needed three rounds of load -> wait -> write.  Lanes past
+// the end of the image are masked off (an inactive lane writes nothing).  Padded rows: piece c = row c / 17, piece c % 17 of it (the pad
+// piece re-reads the 16th); ROT rows are unpadded and the image is a plain copy.  Measured on one box (profiles/r03_tile_dma_all_ab.txt):
+// C5-family row sweep 63.2 -> 54.0 ms, C2 column passes 9.92 -> 9.00 ms, identical objectives.
 template <int G, int R, int NW, bool ROT>
 __device__ __forceinline__ void dma_tile_all(const double* __restrict__ other, int64_t lo, int64_t hi, char* buf, int wave, int lane) {
   constexpr int KPB = G * R * 8, ROWB = tile_row_stride<G, R, ROT>(), CPR = ROWB / 16;
@@ -268,26 +192,20 @@ __device__ __forceinline__ double2 tile_chunk(const char* tile, int ro, int i) {
 // barrier.  It is what the phase-aligned pass kernels below run: when every group in flight walks its sorted list through the same
 // super-tile at the same time, those reads hit the 4 MB L2 of the XCD (~30 TB/s) instead of the Infinity Cache / HBM (6.5-8 TB/s,
 // profiles/r02_ubench_gather.txt).
-template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, int LW = 0, bool ROTK = false, bool ACC = false>
+template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROTK = false>
 __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const Vec<G, R>& xv, Vec<G, R>& g, double& J,
                                            bool active, int64_t& pos, int64_t end, int tile_begin, int tile_end,
                                            const LossDesc& segloss, int lane, int j, int rot = 0) {
-  constexpr bool ROT = ROTK && !L2 && LW == 0 && tile_rot<G, R>(); // register i holds chunk i ^ rot (see tile_rot)
-  constexpr int ROWB = L2 ? G * R * 8 : tile_row_stride<G, R, ROT>(), NT = NW * 64;
+  constexpr bool ROT = ROTK && !L2 && tile_rot<G, R>(); // register i holds chunk i ^ rot (see tile_rot)
+  constexpr int ROWB = L2 ? G * R * 8 : tile_row_stride<G, R, ROT>();
   constexpr int CB = 2 * G * 8;                 // bytes per chunk row of the group
   const int jrot = j * 16 + (ROT ? rot * CB : 0);
-  constexpr int TROWS = tile_buf_rows<G, R, TILE, LW>(), BUFB = tile_buf_bytes<G, R, TILE, LW>(); // staged rows / bytes per buffer
-  if constexpr (LW > 0) { // tiles are counted in half tiles from here on
-    tile_begin *= 2;
-    tile_end *= 2;
-  }
-  // the whole batch of G observations per step (below).  GLRM_TILE_QUAD_FOUR: the uniform QuadLoss kernels too (G = 4 only).  The first
-  // attempt (round 2, trial pass only, observation-major loops) lost to the two-observation step: one long dependent chain per four
-  // observations.  With the chunk-major loops of round 4 the four chains are independent and interleaved.
-  constexpr bool FOUR = (G == 4 || G == 8) && (LOSS != 0 || (GLRM_TILE_QUAD_FOUR && G == 4));
+  // the whole batch of G observations per step (below) for every model but the uniform QuadLoss one: its two-observation step already
+  // keeps eight LDS reads in flight on two interleaved chains (the four-observation step there: C2 15.70 -> 19.05 ms, LABNOTES round 4)
+  constexpr bool FOUR = (G == 4 || G == 8) && LOSS != 0;
   const double two_scale = 2 * segloss.scale;
   J = 0.0;
-  if (GRAD && !ACC) { // ACC: the caller's gradient is carried on (lockstep windows, glrm_blocked.hip)
+  if (GRAD) {
 #pragma unroll
     for (int i = 0; i < R / 2; ++i) g.v[i] = make_double2(0.0, 0.0);
   }
@@ -300,47 +218,16 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
   constexpr bool UDESC = FOUR && loss_mode(LOSS) == 2 && !L2; // descriptor ids travel with the entries (see TiledArgs::descid)
   const uint8_t* __restrict__ descid = a.descid;
   const bool have_ids = UDESC && descid != nullptr;    // uniform
-  const char* udesc_lds = lds + tile_lds_bytes<G, R, TILE, LW>(); // the kernel staged the distinct descriptors there
-  // GLRM_TILE_NT: the (index, value, descriptor id) stream is read ONCE per pass -- 13 bytes per observation, 1.1 MB per tile step and XCD at
-  // the C5 shape -- and with the default policy it pushes the staged tiles, which the other workgroups of the XCD are about to read, out
-  // of the 4 MB L2; non-temporal loads keep it from being retained.
+  const char* udesc_lds = lds + tile_lds_bytes<G, R, TILE>(); // the kernel staged the distinct descriptors there
   auto load_entry = [&](int64_t p, int& c, double& av, int& did) {
     const int64_t q = p < last ? p : last;
-#if GLRM_TILE_NT
-    c = __builtin_nontemporal_load(idx + q);
-    av = __builtin_nontemporal_load(vals + q);
-#else
     c = idx[q];
     av = vals[q];
-#endif
     did = 0;
     if constexpr (UDESC) {
-#if GLRM_TILE_NT
-      if (have_ids) did = __builtin_nontemporal_load(descid + q);
-#else
       if (have_ids) did = descid[q];
-#endif
     }
   };
-  if constexpr (LW > 0) {
-    if ((int)(threadIdx.x >> 6) < LW) { // loader wave: half tile t+1 lands in the other buffer while the compute waves consume t
-      const int lwave = threadIdx.x >> 6;
-      auto dma = [&](int t) {
-        const int64_t lo = (int64_t)t * TROWS;
-        const int64_t hi = lo + TROWS < a.n_other ? lo + TROWS : a.n_other;
-        if (lo < hi) dma_tile<G, R, LW>(a.other, lo, hi, lds + ((t - tile_begin) & 1) * BUFB, lwave, lane);
-      };
-      if (tile_begin < tile_end) dma(tile_begin);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads(); // B0: the first half tile is in LDS
-      for (int t = tile_begin; t < tile_end; ++t) {
-        if (t + 1 < tile_end) dma(t + 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads(); // B(t+1): half tile t+1 has landed and every compute wave is done with half tile t
-      }
-      return;
-    }
-  }
   int cb, db;
   double ab;
   load_entry(pos + j, cb, ab, db);
@@ -354,30 +241,18 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
   // (The same gate as a wave reduction over the lanes still inside a divergent loop -- the gate-off loop's shape, 4 fewer VGPRs -- did not
   // pay: Y half-step 133.7 ms at any gate width against 129.9 without it, LABNOTES round 7.)
   const int gate = L2 ? a.gate : 0; // wave-uniform
-  if constexpr (LW > 0) __syncthreads(); // B0
   for (int t = tile_begin; t < (L2 ? tile_begin + 1 : tile_end); ++t) {
-    const int64_t lo = (int64_t)t * TROWS;
-    const int64_t hi_ = L2 ? (int64_t)tile_end * TROWS : lo + TROWS;
+    const int64_t lo = (int64_t)t * TILE;
+    const int64_t hi_ = L2 ? (int64_t)tile_end * TILE : lo + TILE;
     const int64_t hi = hi_ < a.n_other ? hi_ : a.n_other;
-    const char* const mem = L2 ? reinterpret_cast<const char*>(a.other) : (LW > 0 ? lds + ((t - tile_begin) & 1) * BUFB : lds);
-    if constexpr (!L2 && LW == 0) {
+    const char* const mem = L2 ? reinterpret_cast<const char*>(a.other) : lds;
+    if constexpr (!L2) {
       __syncthreads(); // everybody is done with the previous tile
-#if defined(GLRM_EXP_NOSTAGE) // timing experiment: stage only the first tile of the pass (results are wrong, the control flow stays finite)
-      if (t == tile_begin) stage_tile<G, R, NT, ROT>(a.other, lo, hi, lds);
-#elif GLRM_TILE_DMA_ALL
       dma_tile_all<G, R, NW, ROT>(a.other, lo, hi, lds, (int)(threadIdx.x >> 6), lane);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-      stage_tile<G, R, NT, ROT>(a.other, lo, hi, lds);
-#endif
       __syncthreads();
     }
-#if defined(GLRM_EXP_NOCOMPUTE) // timing experiment: staging and barriers only
-    bool done = true;
-    if (t + 1 == tile_end && active) J = 1.0;
-#else
     bool done = !active;
-#endif
     for (;;) {
       if (gate > 0) {
         // Every lane of the wave runs this loop until all groups are done (with the gate on, no lane leaves it alone), so the minimum
@@ -436,7 +311,6 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
             mine = (j == u) ? ok[u] : mine;
             p[u] = 0.0;
           }
-#if GLRM_TILE_CHUNK_MAJOR
           // chunk-major: the G reads of a chunk are issued together and feed G INDEPENDENT fma chains (round 4: the observation-major
           // order compiled to sixteen serialized LDS round trips per step -- one read in flight, `s_waitcnt lgkmcnt(0)` after each --
           // because the scheduler minimises registers in a kernel at its VGPR cap).  Every p[u] still adds its chunks in ascending order.
@@ -451,17 +325,6 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
               p[u] = fma(xv.v[i].y, yv[u].y, p[u]);
             }
           }
-#else
-#pragma unroll
-          for (int u = 0; u < G; ++u) {
-#pragma unroll
-            for (int i = 0; i < R / 2; ++i) {
-              const double2 y = L2 ? *reinterpret_cast<const double2*>(rp[u] + i * CB) : tile_chunk<ROT, CB>(mem, ro[u], i);
-              p[u] = fma(xv.v[i].x, y.x, p[u]);
-              p[u] = fma(xv.v[i].y, y.y, p[u]);
-            }
-          }
-#endif
           const bool hi2 = (j & 2) != 0;
           double q[G / 2]; // q[i]: observation 2i + odd, summed over lanes {j, j^1}
 #pragma unroll
@@ -502,7 +365,6 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
           J += L; // every observation once
           if (GRAD) {
             asm volatile("" ::: "memory"); // the reads below are real re-reads, not the values of the first ones kept in VGPRs
-#if GLRM_TILE_CHUNK_MAJOR
             double dv[G]; // observations past the tile window carry a zero derivative
 #pragma unroll
             for (int u = 0; u < G; ++u) dv[u] = group_bcast_f64<G>(dL, u, lane);
@@ -517,18 +379,6 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
                 g.v[i].y = fma(dv[u], yv[u].y, g.v[i].y);
               }
             }
-#else
-#pragma unroll
-            for (int u = 0; u < G; ++u) { // list order; observations past the tile window carry a zero derivative
-              const double d = group_bcast_f64<G>(dL, u, lane);
-#pragma unroll
-              for (int i = 0; i < R / 2; ++i) {
-                const double2 y = L2 ? *reinterpret_cast<const double2*>(rp[u] + i * CB) : tile_chunk<ROT, CB>(mem, ro[u], i);
-                g.v[i].x = fma(d, y.x, g.v[i].x);
-                g.v[i].y = fma(d, y.y, g.v[i].y);
-              }
-            }
-#endif
           }
 #pragma unroll
           for (int u = 0; u < G; ++u) nproc += ok[u] ? 1 : 0;
@@ -625,30 +475,18 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
         if (!(pos + j < end)) cb = 0x7fffffff;
       }
     }
-    if constexpr (LW > 0) __syncthreads(); // B(t+1), see the loader loop
   }
   J = group_sum<G>(J) * (FOUR ? 1.0 : 2.0 / G); // two per step: lanes hold parity-partial sums, each observation counted G/2 times
 }
 
-// Experiment (GLRM_HIP_TILE_STAGGER): the workgroups an XCD holds at a time all stage the SAME tile at the same moment -- they start
-// together and do equal work -- and 32 simultaneous requests for a line that is not in L2 yet are 32 misses.  Started a fraction of a
-// tile step apart, the first one misses and the others find the line in L2.  Workgroup b runs on XCD b % 8; its place among the 32 the
-// XCD holds is (b / 8) % 32.  Changes no result.
-__device__ __forceinline__ void tile_stagger(int stagger, unsigned linear_block) {
-  if (stagger > 0) {
-    const int n = (int)((linear_block >> 3) & 31u) * stagger;
-    for (int t = 0; t < n; ++t) __builtin_amdgcn_s_sleep(8); // ~512 clocks each
-  }
-}
-
 // distinct loss descriptors -> LDS behind the tile (read after the first tile barrier of tiled_pass); see TiledArgs::descid
-template <int G, int R, int NW, int TILE, int LOSS, int LW = 0>
+template <int G, int R, int NW, int TILE, int LOSS>
 __device__ __forceinline__ void stage_udesc(const TiledArgs& a, char* lds) {
   if constexpr (loss_mode(LOSS) == 2) {
     if (a.descid) {
       const int words = a.n_udesc * 8; // 32 bytes each
       const int* src = reinterpret_cast<const int*>(a.udesc);
-      int* dst = reinterpret_cast<int*>(lds + tile_lds_bytes<G, R, TILE, LW>());
+      int* dst = reinterpret_cast<int*>(lds + tile_lds_bytes<G, R, TILE>());
       for (int w = threadIdx.x; w < words; w += NW * 64) dst[w] = src[w];
     }
   }
@@ -663,21 +501,20 @@ __device__ __forceinline__ void stage_udesc(const TiledArgs& a, char* lds) {
 // leaves its state -- gradient, J_old, shrunk step size, next trial point -- in the pass buffers (gsum, jold, alpha, trial, ntrial,
 // active) and its id in actlist_out, and the host runs the remaining trials as rounds of (tiled_col_pass_kernel<GRAD = false, ROWS> over
 // the listed segments, col_decide_kernel): only workgroups made of still-searching rows stage tiles again.  Same sums, same bits.
-template <int G, int R, int NW, int TILE, int LOSS, bool FIXED, int LW = 0, bool ROUNDS = false>
-__global__ void __launch_bounds__(NW * 64, NW == 12 ? 3 : 4) tiled_sweep_kernel(const TiledArgs a) {
-  constexpr int KP = G * R, NGW = 64 / G, SPB = (NW - LW) * NGW; // the first LW waves are loaders (double-buffered tiles)
+template <int G, int R, int NW, int TILE, int LOSS, bool FIXED, bool ROUNDS = false>
+__global__ void __launch_bounds__(NW * 64, 4) tiled_sweep_kernel(const TiledArgs a) {
+  constexpr int KP = G * R, NGW = 64 / G, SPB = NW * NGW;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane % G, gi = lane / G;
-  const int64_t slot = (int64_t)blockIdx.x * SPB + (wave - LW) * NGW + gi;
-  const bool have = wave >= LW && slot < a.nseg;
+  const int64_t slot = (int64_t)blockIdx.x * SPB + wave * NGW + gi;
+  const bool have = slot < a.nseg;
   const int64_t seg = (have && a.segperm) ? (int64_t)a.segperm[slot] : slot; // segments of similar length share a wave (skewed data)
   const int64_t beg = have ? a.ptr[seg] : 0, end = have ? a.ptr[seg + 1] : 0;
   const int64_t gseg = a.own_offset + (have ? seg : 0);
   double2* ownp = reinterpret_cast<double2*>(a.own + gseg * KP);
   const int ntiles = (int)((a.n_other + TILE - 1) / TILE);
-  tile_stagger(a.stagger, blockIdx.x);
-  stage_udesc<G, R, NW, TILE, LOSS, LW>(a, lds);
+  stage_udesc<G, R, NW, TILE, LOSS>(a, lds);
 
   Vec<G, R> g, xn;
   const RegDesc rd = load_reg(a.regs, (a.reg_single || !have) ? 0 : seg);
@@ -691,7 +528,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 12 ? 3 : 4) tiled_sweep_kernel(
     Vec<G, R> x;
 #pragma unroll
     for (int i = 0; i < R / 2; ++i) x.v[i] = have ? ownp[i * G + j] : make_double2(0.0, 0.0);
-    tiled_pass<G, R, NW, TILE, LOSS, true, false, LW>(a, lds, x, g, Jold, have, pos, end, 0, ntiles, segloss, lane, j);
+    tiled_pass<G, R, NW, TILE, LOSS, true>(a, lds, x, g, Jold, have, pos, end, 0, ntiles, segloss, lane, j);
     if constexpr (FIXED) { // src/algorithms/sparse_proxgrad.jl:72-78: g *= -alpha/l; x += g; prox!(r, x, alpha/l)
       const double s = a.fixed_alpha / l;
 #pragma unroll
@@ -730,7 +567,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 12 ? 3 : 4) tiled_sweep_kernel(
     double Jn;
     Vec<G, R> dummy;
     pos = beg;
-    tiled_pass<G, R, NW, TILE, LOSS, false, false, LW>(a, lds, xn, dummy, Jn, searching, pos, end, 0, ntiles, segloss, lane, j);
+    tiled_pass<G, R, NW, TILE, LOSS, false>(a, lds, xn, dummy, Jn, searching, pos, end, 0, ntiles, segloss, lane, j);
     Jn += reg_eval<G, R>(rd, xn, j, a.k);
     if (searching) {
       ++ntrials;
@@ -813,22 +650,19 @@ __device__ __forceinline__ int64_t lower_bound_idx(const int32_t* idx, int64_t b
 // L2 = true: the phase-aligned gather pass (no LDS tile, tiled_pass<..., L2>).  One launch covers ONE super-tile (a.sup_fixed) and
 // a slice [a.seg_begin, a.seg_begin + a.nseg_slice) of the segments that is at most what the chip holds at once, so every group of
 // the launch starts its walk through the super-tile at the same moment; the host issues the launches super-tile by super-tile.
-template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, int LW = 0, bool ROWS = false>
+template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROWS = false>
 __global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(const TiledArgs a) {
-  constexpr int KP = G * R, NGW = 64 / G, SPB = (NW - LW) * NGW, PSTRIDE = KP + 2;
+  constexpr int KP = G * R, NGW = 64 / G, SPB = NW * NGW, PSTRIDE = KP + 2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane % G, gi = lane / G;
-  const int64_t slot = (L2 ? a.seg_begin : 0) + (int64_t)blockIdx.x * SPB + (wave - LW) * NGW + gi;
+  const int64_t slot = (L2 ? a.seg_begin : 0) + (int64_t)blockIdx.x * SPB + wave * NGW + gi;
   const int sup = L2 ? a.sup_fixed : a.sup0 + (int)blockIdx.y;
-  bool have = wave >= LW && slot < (L2 ? a.seg_begin + a.nseg_slice : (a.npass > 0 ? a.npass : a.nseg));
+  bool have = slot < (L2 ? a.seg_begin + a.nseg_slice : (a.npass > 0 ? a.npass : a.nseg));
   const int64_t seg = (have && a.segperm) ? (int64_t)a.segperm[slot] : slot; // which column a group works on does not change any sum
   if (!GRAD && have) have = a.active[seg] != 0;
   if (!GRAD && !__syncthreads_or(have ? 1 : 0)) return; // nothing left to evaluate in this column group
-  if constexpr (!L2) {
-    tile_stagger(a.stagger, blockIdx.y * gridDim.x + blockIdx.x);
-    stage_udesc<G, R, NW, TILE, LOSS, LW>(a, lds);
-  }
+  if constexpr (!L2) stage_udesc<G, R, NW, TILE, LOSS>(a, lds);
   const int64_t beg = have ? a.ptr[seg] : 0, end = have ? a.ptr[seg + 1] : 0;
   const int64_t gseg = a.own_offset + (have ? seg : 0);
   const int ntiles = (int)((a.n_other + TILE - 1) / TILE);
@@ -836,7 +670,7 @@ __global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(con
   const int te = tb + a.tiles_per_sup < ntiles ? tb + a.tiles_per_sup : ntiles;
   const double2* xp = reinterpret_cast<const double2*>(GRAD ? a.own + gseg * KP : a.trial + (have ? seg : 0) * (int64_t)KP);
   // ROWS: the trial rounds of the row view (the row sweep's own passes read padded tiles without rotation: the same bits here)
-  constexpr bool ROT = !ROWS && !L2 && LW == 0 && LOSS != 0 && tile_rot<G, R>();
+  constexpr bool ROT = !ROWS && !L2 && LOSS != 0 && tile_rot<G, R>();
   const int rot = ROT ? tile_rot_of(gseg) : 0; // register i <-> chunk i ^ rot (conflict-free tile reads, see tile_rot)
   Vec<G, R> x, g;
 #pragma unroll
@@ -845,7 +679,7 @@ __global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(con
   if constexpr (loss_mode(LOSS) != 2) segloss = load_loss(a.losses, (a.loss_by_segment && have) ? gseg : 0);
   int64_t pos = have ? lower_bound_idx<G>(a.idx, beg, end, (int64_t)tb * TILE) : 0;
   double J;
-  tiled_pass<G, R, NW, TILE, LOSS, GRAD, L2, LW, ROT>(a, lds, x, g, J, have, pos, end, tb, te, segloss, lane, j, rot);
+  tiled_pass<G, R, NW, TILE, LOSS, GRAD, L2, ROT>(a, lds, x, g, J, have, pos, end, tb, te, segloss, lane, j, rot);
   if (have) {
     double* p = a.part + ((int64_t)seg * a.nsup + sup) * PSTRIDE;
     if (GRAD) {

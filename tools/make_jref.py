@@ -39,7 +39,7 @@ NSAMPLE = 512
 
 
 def tile_rows(kp):
-    return ((150 * 1024) // (kp * 8 + 16)) // 16 * 16  # csrc/glrm_tiled.hip: tile_rows_c(kp, 1)
+    return ((150 * 1024) // (kp * 8 + 16)) // 16 * 16  # csrc/glrm_engine.hpp: glrm_tile_rows(kp)
 
 
 def expected_orders(m, n, k, q, mixed=False):
