@@ -27,6 +27,7 @@
 #include <thread>
 
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 #include "glrm_tiled.hpp"
 
 using namespace glrm;
@@ -67,34 +68,22 @@ int glrm_setup_blocked(glrm_handle* h) {
     return reuse >= 2.0;
   };
   const bool br = decide(true), bc = decide(false);
-  auto sups = [&](int64_t nopp, int& tps, int& nsup) {
+  int rc;
+  auto buffers = [&](int side, int64_t nopp) { // super-tile geometry and pass buffers of one side
     const int64_t ntiles = (nopp + T - 1) / T;
     int64_t t = ((int64_t)128 * 1024 * 1024) / ((int64_t)T * h->kp * 8); // ~128 MB of the opposing factor per super-tile
     t = env_int("GLRM_HIP_BLOCKED_TPS", (int)(t < 1 ? 1 : t));
-    tps = (int)t;
-    nsup = (int)((ntiles + t - 1) / t);
+    h->pass[side].tiles_per_sup = (int)t;
+    h->pass[side].nsup = (int)((ntiles + t - 1) / t);
+    return glrm_alloc_pass_buffers(h, side);
   };
   if (br) {
-    sups(h->n, h->tiles_per_sup_r, h->nsup_r);
-    const int64_t ml1 = h->ml > 0 ? h->ml : 1;
-    HIPCK(hipMalloc((void**)&h->part_r, (size_t)ml1 * h->nsup_r * (h->kp + 2) * 8));
-    HIPCK(hipMalloc((void**)&h->gsum_r, (size_t)ml1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->trial_r, (size_t)ml1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->jold_r, (size_t)ml1 * 8));
-    HIPCK(hipMalloc((void**)&h->active_r, (size_t)ml1 * 4));
-    HIPCK(hipMalloc((void**)&h->ntrial_r, (size_t)ml1 * 4));
+    if ((rc = buffers(0, h->n))) return rc;
     h->blocked_row = 1;
   }
   if (bc) {
-    sups(h->m, h->tiles_per_sup, h->nsup);
-    const int64_t nl1 = h->nl > 0 ? h->nl : 1;
-    HIPCK(hipMalloc((void**)&h->part, (size_t)nl1 * h->nsup * (h->kp + 2) * 8));
-    HIPCK(hipMalloc((void**)&h->gsum, (size_t)nl1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->trialbuf, (size_t)nl1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->joldbuf, (size_t)nl1 * 8));
-    HIPCK(hipMalloc((void**)&h->activebuf, (size_t)nl1 * 4));
-    HIPCK(hipMalloc((void**)&h->ntrialbuf, (size_t)nl1 * 4));
-    HIPCK(hipMemsetAsync(h->activebuf, 0, (size_t)nl1 * 4, h->stream)); // diverted columns are never touched by col_reduce: they must read "not searching"
+    if ((rc = buffers(1, h->m))) return rc;
+    HIPCK(hipMemsetAsync(h->pass[1].active, 0, (size_t)(h->nl > 0 ? h->nl : 1) * 4, h->stream)); // diverted columns are never touched by col_reduce: they must read "not searching"
     h->blocked_col = 1;
     // Skewed column lengths (power-law Omega; round 5).  A launch covers one super-tile x a slice of the columns, one lane group per column:
     // a column 100 x the mean keeps its group walking 100 x longer than the others of its launch, alone and latency bound (C4 recipe with
@@ -110,29 +99,15 @@ int glrm_setup_blocked(glrm_handle* h) {
     h->blk_long_from = env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0) > 0 ? env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0)
                                                                      : std::max<int64_t>(4096, 2 * mean_len);
     if (h->nl > 0 && h->blk_long_from > 0) {
-      std::vector<int64_t> ptr((size_t)h->nl + 1);
-      HIPCK(hipMemcpyAsync(ptr.data(), h->colptr, ((size_t)h->nl + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-      HIPCK(hipStreamSynchronize(h->stream));
+      std::vector<int64_t> ptr;
       std::vector<int32_t> shortl, longl;
-      for (int64_t s = 0; s < h->nl; ++s) (ptr[s + 1] - ptr[s] >= h->blk_long_from ? longl : shortl).push_back((int32_t)s);
-      std::stable_sort(shortl.begin(), shortl.end(), [&](int32_t x, int32_t y) { return ptr[x + 1] - ptr[x] > ptr[y + 1] - ptr[y]; });
+      if ((rc = glrm_host_ptr(h, false, ptr))) return rc;
+      glrm_split_by_length(ptr, h->blk_long_from, shortl, longl);
       h->blk_nshort_c = (int64_t)shortl.size();
-      h->blk_nlong_c = (int64_t)longl.size();
-      HIPCK(hipMalloc((void**)&h->blk_perm_c, std::max<size_t>(1, shortl.size()) * 4));
-      HIPCK(hipMemcpyAsync(h->blk_perm_c, shortl.data(), shortl.size() * 4, hipMemcpyHostToDevice, h->stream));
-      if (!longl.empty()) {
-        HIPCK(hipMalloc((void**)&h->blk_long_c, longl.size() * 4));
-        HIPCK(hipMemcpyAsync(h->blk_long_c, longl.data(), longl.size() * 4, hipMemcpyHostToDevice, h->stream));
-        if (!h->side_stream) {
-          HIPCK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-          HIPCK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-          HIPCK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        }
-      }
-      HIPCK(hipStreamSynchronize(h->stream)); // the lists are locals
+      if ((rc = glrm_upload_list(h, shortl, &h->blk_perm_c))) return rc;
+      if ((rc = glrm_set_long_columns(h, longl))) return rc;
     }
   }
-  if ((br || bc) && !h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
   return GLRM_OK;
 }
 
@@ -248,61 +223,25 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
 }
 
 
-template <int G, int R>
-static int launch_blocked_layout(glrm_handle* h, int loss, bool grad, const TiledArgs& a, bool rows) {
-#define GLRM_BL(LOSSV) (grad ? launch_blocked_inst<G, R, LOSSV, true>(h, a, rows) : launch_blocked_inst<G, R, LOSSV, false>(h, a, rows))
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: return GLRM_BL(0);
-    case LOSS_SEGMENT: return GLRM_BL(1);
-    case LOSS_SEGMENT_NOTRIG: return GLRM_BL(3);
-    case LOSS_PER_OBS_NOTRIG: return GLRM_BL(4);
-    default: return GLRM_BL(2);
-  }
-#undef GLRM_BL
-}
-
 static int launch_blocked(glrm_handle* h, int loss, bool grad, const TiledArgs& a, bool rows) {
-  switch (h->G * 100 + h->R) {
-    case 402: return launch_blocked_layout<4, 2>(h, loss, grad, a, rows);
-    case 404: return launch_blocked_layout<4, 4>(h, loss, grad, a, rows);
-    case 408: return launch_blocked_layout<4, 8>(h, loss, grad, a, rows);
-    case 808: return launch_blocked_layout<8, 8>(h, loss, grad, a, rows);
-    case 1608: return launch_blocked_layout<16, 8>(h, loss, grad, a, rows);
-    default: return fail(GLRM_ERR_UNSUPPORTED, "no phase-aligned pass kernel for lane layout G=%d R=%d", h->G, h->R);
-  }
+  auto by_layout = [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    auto by_loss = [&](auto LOSS) {
+      constexpr int L = decltype(LOSS)::value;
+      return grad ? launch_blocked_inst<G, R, L, true>(h, a, rows) : launch_blocked_inst<G, R, L, false>(h, a, rows);
+    };
+    return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
+  };
+  return glrm_dispatch_layout<8, 16, 32, 64, 128>(h->G, h->R, by_layout,
+                                                  [&] { return fail(GLRM_ERR_UNSUPPORTED, "no phase-aligned pass kernel for lane layout G=%d R=%d", h->G, h->R); });
 }
 
 int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
   TiledArgs a{};
-  a.nseg = rows ? h->ml : h->nl;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
-  a.n_other = rows ? h->n : h->m;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.losses = h->losses;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
   a.loss_by_segment = loss_by_segment;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.k = h->k;
-  a.min_stepsize = min_stepsize;
-  a.trials = rows ? h->trials_r : h->trials_c;
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
-  a.eval_only = eval_only;
-  a.fixed_alpha = eval_only ? 0.0 : h->fixed_alpha;
-  a.nsup = rows ? h->nsup_r : h->nsup;
-  a.tiles_per_sup = rows ? h->tiles_per_sup_r : h->tiles_per_sup;
-  a.part = rows ? h->part_r : h->part;
-  a.gsum = rows ? h->gsum_r : h->gsum;
-  a.trial = rows ? h->trial_r : h->trialbuf;
-  a.jold = rows ? h->jold_r : h->joldbuf;
-  a.active = rows ? h->active_r : h->activebuf;
-  a.ntrial = rows ? h->ntrial_r : h->ntrialbuf;
-  a.nactive = h->nactive;
+  const bool range = rows && h->rng_e >= 0; // glrm_hip_step_x_range: local rows [rng_b, rng_e)
+  glrm_bind_pass_buffers(a, h, rows ? 0 : 1, range ? h->rng_b : 0);
   if (!rows && h->blk_perm_c) { // length-sorted slots; the columns at or above long_from run on the gather sweep (run_sweep, glrm_hip.hip)
     a.segperm = h->blk_perm_c;
     a.npass = h->blk_nshort_c;
@@ -312,15 +251,9 @@ int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, d
       return GLRM_OK;
     }
   }
-  if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    const int64_t s0 = h->rng_b;
-    a.nseg = h->rng_e - s0;
+  if (range) {
+    glrm_apply_row_range(a, h->rng_b, h->rng_e);
     if (a.nseg <= 0) return GLRM_OK;
-    a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-    if (!a.reg_single) a.regs += s0;
-    a.trials += s0; a.accepts += s0;
-    a.part += s0 * (int64_t)a.nsup * (h->kp + 2); a.gsum += s0 * (int64_t)h->kp; a.trial += s0 * (int64_t)h->kp;
-    a.jold += s0; a.active += s0; a.ntrial += s0;
   }
   int rc;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
@@ -343,17 +276,8 @@ int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, d
   glrm_launch_col_small(h->kp, 0, a, h->stream);                 // reduce in super-tile order, J_old, first trial point
   HIPCK(hipGetLastError());
   if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
-  constexpr int MAX_ROUNDS = 4096; // see glrm_run_tiled: a guard, never a silent cut
-  for (int round = 0;; ++round) {
-    if (round == MAX_ROUNDS) return fail(GLRM_ERR_INVALID, "line search still running after %d rounds (min_stepsize %g)", MAX_ROUNDS, min_stepsize);
-    unsigned int nact = 0;
-    HIPCK(hipMemcpyAsync(&nact, h->nactive, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    if (nact == 0) break;
-    HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-    if ((rc = launch_blocked(h, loss, false, a, rows))) return rc; // loss partials at the trial points of the searching segments
-    glrm_launch_col_small(h->kp, 1, a, h->stream);               // accept / shrink / give up, next trial point
-    HIPCK(hipGetLastError());
-  }
-  return GLRM_OK;
+  return glrm_run_rounds(
+      h, a, min_stepsize, glrm_act_lists{},
+      [&](int, unsigned int, int32_t*) { return launch_blocked(h, loss, false, a, rows); },  // loss partials at the trial points of the searching segments
+      [&](const TiledArgs& d) { glrm_launch_col_small(h->kp, 1, d, h->stream); });           // accept / shrink / give up, next trial point
 }

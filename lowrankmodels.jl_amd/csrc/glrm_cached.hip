@@ -21,6 +21,7 @@
 
 #include "glrm_device.hpp"
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 
 using namespace glrm;
 
@@ -640,17 +641,6 @@ int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.
   return GLRM_OK;
 }
 
-template <int G, int R>
-int launch_reg_layout(int loss, const CachedArgs& a, hipStream_t st, glrm_handle* h) {
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: return launch_reg_inst<G, R, LOSS_QUAD_UNIFORM>(a, st, h);
-    case LOSS_SEGMENT: return launch_reg_inst<G, R, LOSS_SEGMENT>(a, st, h);
-    case LOSS_SEGMENT_NOTRIG: return launch_reg_inst<G, R, LOSS_SEGMENT_NOTRIG>(a, st, h);
-    case LOSS_PER_OBS_NOTRIG: return launch_reg_inst<G, R, LOSS_PER_OBS_NOTRIG>(a, st, h);
-    default: return launch_reg_inst<G, R, LOSS_PER_OBS>(a, st, h);
-  }
-}
-
 template <int G, int R, int LOSS>
 int launch_inst(const CachedArgs& a, hipStream_t st) {
   const int lds = a.cap * (G * R * 8 + 12);
@@ -658,17 +648,6 @@ int launch_inst(const CachedArgs& a, hipStream_t st) {
     HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(cached_sweep_kernel<G, R, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   hipLaunchKernelGGL((cached_sweep_kernel<G, R, LOSS>), dim3((unsigned)a.nseg), dim3(64), lds, st, a);
   return GLRM_OK;
-}
-
-template <int G, int R>
-int launch_layout(int loss, const CachedArgs& a, hipStream_t st) {
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: return launch_inst<G, R, LOSS_QUAD_UNIFORM>(a, st);
-    case LOSS_SEGMENT: return launch_inst<G, R, LOSS_SEGMENT>(a, st);
-    case LOSS_SEGMENT_NOTRIG: return launch_inst<G, R, LOSS_SEGMENT_NOTRIG>(a, st);
-    case LOSS_PER_OBS_NOTRIG: return launch_inst<G, R, LOSS_PER_OBS_NOTRIG>(a, st);
-    default: return launch_inst<G, R, LOSS_PER_OBS>(a, st);
-  }
 }
 
 } // namespace
@@ -716,22 +695,7 @@ void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen) {
 // seglist == nullptr: every local row (restricted to the range of glrm_hip_step_x_range, if one is set); otherwise the rows listed
 int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st) {
   CachedArgs a{};
-  a.nseg = h->ml;
-  a.ptr = h->rowptr;
-  a.idx = h->colidx;
-  a.vals = h->rowvals;
-  a.own = h->X;
-  a.own_offset = h->rb;
-  a.other = h->Y;
-  a.alpha = h->alpharow;
-  a.losses = h->losses;
-  a.regs = h->rx;
-  a.reg_single = h->n_rx == 1;
-  a.k = h->k;
-  a.fixed_alpha = h->fixed_alpha;
-  a.min_stepsize = min_stepsize;
-  a.trials = h->trials_r;
-  a.accepts = h->accepts_r;
+  glrm_fill_side(a, h, true, min_stepsize, 0);
   a.cap = h->cached_cap;
   a.seg_lo = 0;
   a.seg_hi = h->ml;
@@ -741,16 +705,19 @@ int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t
     if (h->rng_e >= 0) { a.seg_lo = h->rng_b; a.seg_hi = h->rng_e; }
     if (a.nseg <= 0 || a.seg_hi <= a.seg_lo) return GLRM_OK;
   } else if (h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    const int64_t s0 = h->rng_b;
-    a.nseg = h->rng_e - s0;
+    glrm_apply_row_range(a, h->rng_b, h->rng_e);
     if (a.nseg <= 0) return GLRM_OK;
-    a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-    if (!a.reg_single) a.regs += s0;
-    a.trials += s0; a.accepts += s0;
   }
-  int rc;
-  if (h->cached_row == 2) rc = h->G == 4 ? launch_reg_layout<4, 8>(loss, a, st, h) : launch_reg_layout<8, 8>(loss, a, st, h);
-  else rc = h->G == 4 ? launch_layout<4, 8>(loss, a, st) : launch_layout<8, 8>(loss, a, st);
+  // layouts (4, 8) and (8, 8) only (glrm_setup_cached); register variant (cached_row == 2) or LDS variant
+  auto by_layout = [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    auto by_loss = [&](auto LOSS) {
+      constexpr int L = decltype(LOSS)::value;
+      return h->cached_row == 2 ? launch_reg_inst<G, R, L>(a, st, h) : launch_inst<G, R, L>(a, st);
+    };
+    return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
+  };
+  const int rc = glrm_dispatch_layout<32>(h->G, 8, by_layout, [&] { return by_layout(glrm_const<8>{}, glrm_const<8>{}); });
   if (rc) return rc;
   HIPCK(hipGetLastError());
   return GLRM_OK;

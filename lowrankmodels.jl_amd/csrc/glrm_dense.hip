@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 #include "glrm_tiled.hpp"
 #include "glrm_dense.hpp"
 
@@ -114,23 +115,11 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
     }
   }
   if (rc) return rc;
-  pick_sup(h->n, h->nsup_r, h->vps_r);
-  pick_sup(h->m, h->nsup_c, h->vps_c);
+  pick_sup(h->n, h->pass[0].nsup, h->vps_r);
+  pick_sup(h->m, h->pass[1].nsup, h->vps_c);
   const int64_t ml1 = h->ml > 0 ? h->ml : 1, nl1 = h->nl > 0 ? h->nl : 1;
-  const int ps = h->kp + 2;
-  if ((rc = alloc_arr(&h->part_r, ml1 * h->nsup_r * ps))) return rc;
-  if ((rc = alloc_arr(&h->gsum_r, ml1 * h->kp))) return rc;
-  if ((rc = alloc_arr(&h->trial_r, ml1 * h->kp))) return rc;
-  if ((rc = alloc_arr(&h->jold_r, ml1))) return rc;
-  if ((rc = alloc_arr(&h->active_r, ml1))) return rc;
-  if ((rc = alloc_arr(&h->ntrial_r, ml1))) return rc;
-  if ((rc = alloc_arr(&h->part, nl1 * h->nsup_c * ps))) return rc;
-  if ((rc = alloc_arr(&h->gsum, nl1 * h->kp))) return rc;
-  if ((rc = alloc_arr(&h->trialbuf, nl1 * h->kp))) return rc;
-  if ((rc = alloc_arr(&h->joldbuf, nl1))) return rc;
-  if ((rc = alloc_arr(&h->activebuf, nl1))) return rc;
-  if ((rc = alloc_arr(&h->ntrialbuf, nl1))) return rc;
-  if ((rc = alloc_arr(&h->nactive, 1))) return rc;
+  if ((rc = glrm_alloc_pass_buffers(h, 0))) return rc;
+  if ((rc = glrm_alloc_pass_buffers(h, 1))) return rc;
   // glrm_options.quad_gram: line-search trials from the quadratic form, no pass over A per trial
   h->dense_gram = h->opts.quad_gram != 0;
   if (h->dense_gram) {
@@ -142,23 +131,19 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   return GLRM_OK;
 }
 
-template <int KP>
-static void launch_gram_inst(int which, const TiledArgs& a, const double* other, int64_t n_other, double* part, double* H, double scale, hipStream_t st) {
-  if (which == 0) {
-    hipLaunchKernelGGL((dense_gram_partial_kernel<KP>), dim3(GRAM_BLOCKS), dim3(256), 0, st, other, n_other, part);
-    hipLaunchKernelGGL((dense_gram_final_kernel<KP>), dim3((KP * KP + 255) / 256), dim3(256), 0, st, part, H);
-  } else {
-    hipLaunchKernelGGL((dense_gram_trial_kernel<KP>), dim3((unsigned)((a.nseg + 255) / 256)), dim3(256), 0, st, a, H, scale);
-  }
-}
-
 // which = 0: H = other other' (kp x kp); which = 1: the trial objectives of the active segments from the quadratic form
 static void launch_gram(int kp, int which, const TiledArgs& a, const double* other, int64_t n_other, double* part, double* H, double scale, hipStream_t st) {
-  switch (kp) {
-    case 16: launch_gram_inst<16>(which, a, other, n_other, part, H, scale, st); break;
-    case 32: launch_gram_inst<32>(which, a, other, n_other, part, H, scale, st); break;
-    default: launch_gram_inst<64>(which, a, other, n_other, part, H, scale, st); break;
-  }
+  auto by_kp = [&](auto kpc) {
+    constexpr int KP = decltype(kpc)::value;
+    if (which == 0) {
+      hipLaunchKernelGGL((dense_gram_partial_kernel<KP>), dim3(GRAM_BLOCKS), dim3(256), 0, st, other, n_other, part);
+      hipLaunchKernelGGL((dense_gram_final_kernel<KP>), dim3((KP * KP + 255) / 256), dim3(256), 0, st, part, H);
+    } else {
+      hipLaunchKernelGGL((dense_gram_trial_kernel<KP>), dim3((unsigned)((a.nseg + 255) / 256)), dim3(256), 0, st, a, H, scale);
+    }
+    return GLRM_OK;
+  };
+  glrm_dispatch<16, 32>(kp, by_kp, [&] { return by_kp(glrm_const<64>{}); }); // (glrm_setup_dense admits kp 16 / 32 / 64)
 }
 
 template <int KP, int NWD>
@@ -168,19 +153,15 @@ static void launch_dense_inst(bool grad, const DenseArgs& a, hipStream_t st) {
   else hipLaunchKernelGGL((dense_pass_kernel<KP, false, NWD>), grid, dim3(NWD * 64), 0, st, a);
 }
 
-template <int KP>
-static void launch_dense_pass(bool grad, const DenseArgs& a, hipStream_t st) {
-  // 16-wave workgroups (256 segments share one staged tile) unless the problem is too small to fill the chip with them
-  if (a.nseg * (int64_t)a.nsup >= 256 * 256) launch_dense_inst<KP, 16>(grad, a, st);
-  else launch_dense_inst<KP, 4>(grad, a, st);
-}
-
 static void launch_dense_any(int kp, bool grad, const DenseArgs& a, hipStream_t st) {
-  switch (kp) {
-    case 16: launch_dense_pass<16>(grad, a, st); break;
-    case 32: launch_dense_pass<32>(grad, a, st); break;
-    default: launch_dense_pass<64>(grad, a, st); break;
-  }
+  auto by_kp = [&](auto kpc) {
+    constexpr int KP = decltype(kpc)::value;
+    // 16-wave workgroups (256 segments share one staged tile) unless the problem is too small to fill the chip with them
+    if (a.nseg * (int64_t)a.nsup >= 256 * 256) launch_dense_inst<KP, 16>(grad, a, st);
+    else launch_dense_inst<KP, 4>(grad, a, st);
+    return GLRM_OK;
+  };
+  glrm_dispatch<16, 32>(kp, by_kp, [&] { return by_kp(glrm_const<64>{}); });
 }
 
 // One half-step on the dense path: pass 1 (residuals, objective, gradient on the matrix cores) -> per-segment
@@ -197,34 +178,15 @@ int glrm_run_dense(glrm_handle* h, bool rows, double min_stepsize, int eval_only
   d.A = rows ? h->Arow : h->Acol;
   d.lda = rows ? h->lda_r : h->lda_c;
   d.scale = h->dense_scale;
-  d.nsup = rows ? h->nsup_r : h->nsup_c;
   d.vec_per_sup = rows ? h->vps_r : h->vps_c;
-  d.part = rows ? h->part_r : h->part;
-  d.active = rows ? h->active_r : h->activebuf;
   TiledArgs a{};
-  a.nseg = nseg;
-  a.ptr = nullptr;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  a.ptr = nullptr; // no view: every segment has dense_len observations
   a.dense_len = d.n_other;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = d.own_offset;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.k = h->k;
-  a.min_stepsize = min_stepsize;
-  a.trials = rows ? h->trials_r : h->trials_c;
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
-  a.nsup = d.nsup;
-  a.part = d.part;
-  a.gsum = rows ? h->gsum_r : h->gsum;
-  a.trial = rows ? h->trial_r : h->trialbuf;
-  a.jold = rows ? h->jold_r : h->joldbuf;
-  a.active = rows ? h->active_r : h->activebuf;
-  a.ntrial = rows ? h->ntrial_r : h->ntrialbuf;
-  a.nactive = h->nactive;
-  a.eval_only = eval_only;
-  a.fixed_alpha = eval_only ? 0.0 : h->fixed_alpha;
+  glrm_bind_pass_buffers(a, h, rows ? 0 : 1);
+  d.nsup = a.nsup;
+  d.part = a.part;
+  d.active = a.active;
   const bool gram = h->dense_gram && !eval_only && a.fixed_alpha <= 0.0;
   a.jloss = gram ? (rows ? h->jloss_r : h->jloss_c) : nullptr;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
@@ -236,18 +198,12 @@ int glrm_run_dense(glrm_handle* h, bool rows, double min_stepsize, int eval_only
   DenseArgs t = d;
   t.xsrc = a.trial; // trial points are stored per local segment
   t.own_offset = 0;
-  constexpr int MAX_ROUNDS = 4096; // see glrm_run_tiled: a guard against a loop that cannot end, never a silent cut of the search
-  for (int round = 0;; ++round) {
-    if (round == MAX_ROUNDS) return fail(GLRM_ERR_INVALID, "line search still running after %d rounds (min_stepsize %g)", MAX_ROUNDS, min_stepsize);
-    unsigned int nact = 0;
-    HIPCK(hipMemcpyAsync(&nact, h->nactive, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    if (nact == 0) break;
-    HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-    if (gram) launch_gram(h->kp, 1, a, d.other, d.n_other, h->gram_part, h->gramH, d.scale, h->stream);
-    else launch_dense_any(h->kp, false, t, h->stream);
-    glrm_launch_col_small(h->kp, 1, a, h->stream);
-    HIPCK(hipGetLastError());
-  }
-  return GLRM_OK;
+  return glrm_run_rounds(
+      h, a, min_stepsize, glrm_act_lists{},
+      [&](int, unsigned int, int32_t*) {
+        if (gram) launch_gram(h->kp, 1, a, d.other, d.n_other, h->gram_part, h->gramH, d.scale, h->stream);
+        else launch_dense_any(h->kp, false, t, h->stream);
+        return GLRM_OK;
+      },
+      [&](const TiledArgs& dd) { glrm_launch_col_small(h->kp, 1, dd, h->stream); });
 }

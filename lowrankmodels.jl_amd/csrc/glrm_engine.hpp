@@ -1,6 +1,13 @@
-// glrm_engine.hpp -- host-side declarations shared by the translation units of libglrm_hip.so
-// (glrm_hip.hip: C ABI + gather sweeps; glrm_tiled.hip: LDS-tiled sweeps; glrm_dense.hip: MFMA path;
-// glrm_multi.hip: multi-dimensional losses / block regularizers).
+// glrm_engine.hpp -- host-side declarations shared by the translation units of libglrm_hip.so:
+//   glrm_hip.hip        C ABI, gather sweeps, the shared host helpers declared below
+//   glrm_tiled.hip      LDS-tiled sweeps            glrm_lane.hip       lane-per-segment LDS-tiled passes
+//   glrm_blocked.hip    phase-aligned gather passes glrm_cached.hip     cached gather row sweep
+//   glrm_dense.hip      MFMA path                   glrm_multi.hip      multi-dimensional losses / block regularizers
+//   glrm_reforder.hip   reference-order sweeps      glrm_tilesort.hip   segmented sort of a view into tile order
+//   glrm_transpose.hip  row view from column view   glrm_subset.hip     child handles (cross-validation)
+//   glrm_svd.hip        SVD initialisation          glrm_impute.hip     imputation
+//   glrm_multigpu.hip   sharded fits                glrm_testhooks.hip  test hooks (constant in the product library)
+// The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +15,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <vector>
 
 #include "../../include/glrm_hip.h"
@@ -53,15 +61,18 @@ struct glrm_handle {
   int tiled_opt = 0;                  // glrm_options.tiled
   int tiled_row = 0, tiled_col = 0;   // 0 = gather sweep, 1 = tiled
   int tG = 4, tR = 2;                 // lane layout of the tiled kernels (kp = tG*tR)
-  int nsup = 0, tiles_per_sup = 0;
   int blocked_row = 0, blocked_col = 0; // phase-aligned gather passes (glrm_blocked.hip) instead of the one-kernel gather sweep
-  int tiles_per_sup_r = 0;            // row passes: tiles per super-tile (nsup_r super-tiles; buffers part_r ... ntrial_r below)
   int tile_rounds = 0;                // LDS-tiled sweeps: line-search rounds over the still-searching segments only (bit0 rows, bit1 columns)
   int32_t* actlist = nullptr;         // two lists of actlist_cap segment ids (glrm_tiled.hpp: TiledArgs::actlist_out / actlist_in)
   int64_t actlist_cap = 0;
-  double *part = nullptr, *gsum = nullptr, *trialbuf = nullptr, *joldbuf = nullptr;
-  int32_t *activebuf = nullptr, *ntrialbuf = nullptr;
-  unsigned int* nactive = nullptr;
+  // per-segment buffers of the multi-pass families (LDS-tiled, lane, phase-aligned, dense), [0] rows, [1] columns: TiledArgs::part ... ntrial
+  // and the super-tile geometry they were sized for (glrm_alloc_pass_buffers / glrm_bind_pass_buffers)
+  struct PassBuffers {
+    double *part = nullptr, *gsum = nullptr, *trial = nullptr, *jold = nullptr;
+    int32_t *active = nullptr, *ntrial = nullptr;
+    int nsup = 0, tiles_per_sup = 0;
+  } pass[2];
+  unsigned int* nactive = nullptr;    // segments still searching (one counter: a half-step at a time)
   int* dflag = nullptr;
   uint8_t* rowdescid = nullptr;       // heterogeneous tiled row sweep: id of the loss descriptor of every entry of the row view
   glrm_loss* udesc = nullptr;         // the model's distinct loss descriptors (<= 256), device
@@ -99,10 +110,7 @@ struct glrm_handle {
   double *Arow = nullptr, *Acol = nullptr; // packed, zero padded: [ml_pad][lda_r], [nl_pad][lda_c]
   int64_t lda_r = 0, lda_c = 0;
   double dense_scale = 1.0;
-  int nsup_r = 1, nsup_c = 1;
   int64_t vps_r = 0, vps_c = 0;           // opposing vectors per super-tile
-  double *part_r = nullptr, *gsum_r = nullptr, *trial_r = nullptr, *jold_r = nullptr;
-  int32_t *active_r = nullptr, *ntrial_r = nullptr;
   int cached_row = 0, cached_cap = 0; // cached gather row sweep (glrm_cached.hip): 0 off, 1 LDS, 2 registers; trips / vectors a row may have
   int cached_want = 0;                // the whole problem runs its short rows on the cached sweep (decided from glrm_signature, never from the shard)
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
@@ -180,6 +188,8 @@ inline int env_int(const char* name, int dflt) {
   return (v && *v) ? atoi(v) : dflt;
 }
 
+namespace glrm { struct TiledArgs; }
+
 
 // per-segment class of the gather sweeps (see glrm_handle::seglist_r)
 constexpr int64_t GLRM_WAVES4_FROM = 1536, GLRM_WAVES8_FROM = 98304;
@@ -196,7 +206,6 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
 
 // lane-per-segment LDS-tiled passes (glrm_lane.hip): setup decides lane[] from the whole problem's signature and builds the SELL layouts;
 // run takes the TiledArgs glrm_run_tiled prepared (glrm_tiled.hpp)
-namespace glrm { struct TiledArgs; }
 bool glrm_lane_wants(const glrm_handle* h, bool rows);   // the whole problem's shape / losses / options admit the family on that side (given that the side runs the LDS tiles)
 int glrm_setup_lane(glrm_handle* h);
 bool glrm_lane_loss_ok(const glrm_handle* h, int loss);
@@ -213,7 +222,6 @@ int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi);
 // LDS-tiled / lane column passes under glrm_hip_step_y_arrival (round 6): runs of super-tiles in the order their rows of X are announced --
 // launch(sup_lo, sup_hi) is called once per run, behind the in-stream waits for the blocks the run touches; without arrival blocks: one call
 // over all super-tiles.  Partial sums are per (column, super-tile) and are reduced in super-tile order: which run went first changes no bit.
-#include <functional>
 int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch);
 
 // stable segmented sort of a view by tile index (glrm_tilesort.hip)
@@ -245,5 +253,20 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
 int glrm_run_multi_penalty(glrm_handle* h, bool rows);
 
 // per-segment reduce (which = 0) / decide (which = 1) kernels of glrm_tiled.hpp for a kp-wide factor
-namespace glrm { struct TiledArgs; }
 void glrm_launch_col_small(int kp, int which, const glrm::TiledArgs& a, hipStream_t st);
+
+// ---- shared host helpers (glrm_hip.hip)
+// the pass buffers of one side ([0] rows, [1] columns) for the local segments and pass[side].nsup super-tiles, and nactive
+int glrm_alloc_pass_buffers(glrm_handle* h, int side);
+// side stream + fork / join events (created once): launches that run beside the main stream's
+int glrm_ensure_side_stream(glrm_handle* h);
+int glrm_fork_side_stream(glrm_handle* h);        // the side stream continues behind what h->stream holds
+hipError_t glrm_join_side_stream(glrm_handle* h); // h->stream continues behind the side stream; g_err is left as it was (joins also run on error paths)
+// host copy of a view's segment offsets (nseg + 1)
+int glrm_host_ptr(glrm_handle* h, bool rows, std::vector<int64_t>& ptr);
+// a host list as a device array of its own (at least one element is allocated); synchronizes, so the list may be a local
+int glrm_upload_list(glrm_handle* h, const std::vector<int32_t>& list, int32_t** out);
+// segments split at long_from observations (<= 0: none is long): the short ones by descending length (stable), the long ones by id
+void glrm_split_by_length(const std::vector<int64_t>& ptr, int64_t long_from, std::vector<int32_t>& shorts, std::vector<int32_t>& longs);
+// the columns that leave the passes for the 8-wave gather sweep on the side stream (blk_long_c / blk_nlong_c)
+int glrm_set_long_columns(glrm_handle* h, const std::vector<int32_t>& longs);

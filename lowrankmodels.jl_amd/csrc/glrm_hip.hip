@@ -31,6 +31,7 @@
 
 #include "glrm_device.hpp"
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 
 using namespace glrm;
 
@@ -574,9 +575,9 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
   if (!h->own_colview) { h->rowidx = nullptr; h->colvals = nullptr; }
   void* ptrs[] = {h->rowptr, h->colptr, h->colidx, h->rowidx, h->rowvals, h->colvals, h->losses, h->rx, h->ry,
                   h->alpharow, h->alphacol, h->oX, h->oY, h->oobjcol, h->oobjrow, h->partials, h->dscalar, h->dcount,
-                  h->trials_r, h->accepts_r, h->trials_c, h->accepts_c, h->part, h->gsum, h->trialbuf, h->joldbuf,
-                  h->activebuf, h->ntrialbuf, h->nactive, h->dflag, h->Arow, h->Acol, h->part_r, h->gsum_r, h->trial_r,
-                  h->jold_r, h->active_r, h->ntrial_r, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
+                  h->trials_r, h->accepts_r, h->trials_c, h->accepts_c, h->pass[0].part, h->pass[0].gsum, h->pass[0].trial,
+                  h->pass[0].jold, h->pass[0].active, h->pass[0].ntrial, h->pass[1].part, h->pass[1].gsum, h->pass[1].trial, h->pass[1].jold,
+                  h->pass[1].active, h->pass[1].ntrial, h->nactive, h->dflag, h->Arow, h->Acol, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
                   h->mobjold, h->mactive, h->mnactive, h->colperm, h->rowperm, h->seglist_r, h->seglist_c, h->rowdescid, h->udesc,
                   h->gramH, h->gram_part, h->jloss_r, h->jloss_c, h->actlist, h->blk_perm_c, h->blk_long_c,
                   h->lane_bptr[0], h->lane_bptr[1], h->lane_off[0], h->lane_off[1], h->lane_val[0], h->lane_val[1],
@@ -593,6 +594,73 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
   if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
+}
+
+// ------------------------------------------------------------------ host helpers shared by the families (glrm_engine.hpp)
+
+int glrm_alloc_pass_buffers(glrm_handle* h, int side) {
+  glrm_handle::PassBuffers& b = h->pass[side];
+  const size_t nseg1 = (size_t)std::max<int64_t>(1, side == 0 ? h->ml : h->nl);
+  HIPCK(hipMalloc((void**)&b.part, nseg1 * b.nsup * (h->kp + 2) * 8));
+  HIPCK(hipMalloc((void**)&b.gsum, nseg1 * h->kp * 8));
+  HIPCK(hipMalloc((void**)&b.trial, nseg1 * h->kp * 8));
+  HIPCK(hipMalloc((void**)&b.jold, nseg1 * 8));
+  HIPCK(hipMalloc((void**)&b.active, nseg1 * 4));
+  HIPCK(hipMalloc((void**)&b.ntrial, nseg1 * 4));
+  if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
+  return GLRM_OK;
+}
+
+int glrm_ensure_side_stream(glrm_handle* h) {
+  if (h->side_stream) return GLRM_OK;
+  HIPCK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
+  HIPCK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+  HIPCK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+  return GLRM_OK;
+}
+
+int glrm_fork_side_stream(glrm_handle* h) {
+  HIPCK(hipEventRecord(h->ev_fork, h->stream));
+  HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+  return GLRM_OK;
+}
+
+hipError_t glrm_join_side_stream(glrm_handle* h) {
+  char keep[sizeof g_err];
+  memcpy(keep, g_err, sizeof keep);
+  const hipError_t e_rec = hipEventRecord(h->ev_join, h->side_stream);
+  const hipError_t e_wait = hipStreamWaitEvent(h->stream, h->ev_join, 0);
+  memcpy(g_err, keep, sizeof keep);
+  return e_rec != hipSuccess ? e_rec : e_wait;
+}
+
+int glrm_host_ptr(glrm_handle* h, bool rows, std::vector<int64_t>& ptr) {
+  const size_t nseg = (size_t)(rows ? h->ml : h->nl);
+  ptr.resize(nseg + 1);
+  HIPCK(hipMemcpyAsync(ptr.data(), rows ? h->rowptr : h->colptr, (nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return GLRM_OK;
+}
+
+int glrm_upload_list(glrm_handle* h, const std::vector<int32_t>& list, int32_t** out) {
+  HIPCK(hipMalloc((void**)out, std::max<size_t>(1, list.size()) * 4));
+  HIPCK(hipMemcpyAsync(*out, list.data(), list.size() * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return GLRM_OK;
+}
+
+void glrm_split_by_length(const std::vector<int64_t>& ptr, int64_t long_from, std::vector<int32_t>& shorts, std::vector<int32_t>& longs) {
+  const int64_t nseg = (int64_t)ptr.size() - 1;
+  shorts.reserve((size_t)nseg);
+  for (int64_t s = 0; s < nseg; ++s) (long_from > 0 && ptr[s + 1] - ptr[s] >= long_from ? longs : shorts).push_back((int32_t)s);
+  std::stable_sort(shorts.begin(), shorts.end(), [&](int32_t x, int32_t y) { return ptr[x + 1] - ptr[x] > ptr[y + 1] - ptr[y]; });
+}
+
+int glrm_set_long_columns(glrm_handle* h, const std::vector<int32_t>& longs) {
+  h->blk_nlong_c = (int64_t)longs.size();
+  if (longs.empty()) return GLRM_OK;
+  const int rc = glrm_upload_list(h, longs, &h->blk_long_c);
+  return rc ? rc : glrm_ensure_side_stream(h);
 }
 
 static int view_stats(glrm_handle* h, bool rows, int forced_cls, int64_t cache_maxlen, unsigned long long (&st)[6]) {
@@ -639,9 +707,8 @@ static int build_class_plan(glrm_handle* h, bool rows) {
   for (int c = 2; c < 4; ++c) if (ncls[c] > ncls[best]) best = c;
   (rows ? h->waves_row : h->waves_col) = forced ? glrm_class_waves(forced) : glrm_class_waves(best);
   if (populated <= 1) return GLRM_OK;
-  std::vector<int64_t> ptr((size_t)nseg + 1);
-  HIPCK(hipMemcpyAsync(ptr.data(), rows ? h->rowptr : h->colptr, ((size_t)nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCK(hipStreamSynchronize(h->stream));
+  std::vector<int64_t> ptr;
+  if ((rc = glrm_host_ptr(h, rows, ptr))) return rc;
   std::vector<int32_t> lst((size_t)nseg);
   int64_t pos[4] = {0, ncls[0], ncls[0] + ncls[1], ncls[0] + ncls[1] + ncls[2]};
   for (int64_t s = 0; s < nseg; ++s) {
@@ -649,16 +716,8 @@ static int build_class_plan(glrm_handle* h, bool rows) {
     const int c = (cmax >= 0 && len <= cmax) ? 0 : (forced ? forced : glrm_wave_class(len));
     lst[(size_t)pos[c]++] = (int32_t)s;
   }
-  int32_t** dst = rows ? &h->seglist_r : &h->seglist_c;
-  HIPCK(hipMalloc((void**)dst, (size_t)nseg * 4));
-  HIPCK(hipMemcpyAsync(*dst, lst.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipStreamSynchronize(h->stream)); // lst is a local
-  if (!h->side_stream) {
-    HIPCK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-    HIPCK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  }
-  return GLRM_OK;
+  if ((rc = glrm_upload_list(h, lst, rows ? &h->seglist_r : &h->seglist_c))) return rc;
+  return glrm_ensure_side_stream(h);
 }
 
 static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options* o) {
@@ -981,52 +1040,39 @@ template <int G, int R, int WAVES>
 static void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)(WAVES == 1 ? (a.nseg + 3) / 4 : a.nseg);
   const dim3 block(WAVES == 1 ? 256 : WAVES * 64);
-#define GLRM_LAUNCH(LOSSV, UV)                                                                                  \
-  do {                                                                                                          \
-    if (a.eval_only) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSSV, 1, true>), dim3(grid), block, 0, st, a); \
-    else hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSSV, UV, false>), dim3(grid), block, 0, st, a);          \
-  } while (0)
+  auto launch = [&](auto LOSS, auto U) {
+    if (a.eval_only) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, 1, true>), dim3(grid), block, 0, st, a);
+    else hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, U, false>), dim3(grid), block, 0, st, a);
+    return GLRM_OK;
+  };
   // One 8-wave workgroup per very long segment (the diverted columns of a power-law view: 880 000 observations at the C2-Zipf recipe) is
   // bound by the latency of its factor gathers: with one observation per lane group in flight the longest column alone took 13.7 ms of a
   // 15.7 ms Y half-step (profiles/r06_c2_zipf_kernel_stats.csv).  Eight per group in flight -- session r6_26.
   // G == 4, one wave: four observations per trip, one loss evaluation per lane (C5-family row sweep 169 -> 115 ms); the 4-wave sweeps of
   // long same-loss segments are bound by the factor gather and keep the leaner one-observation body.
   constexpr int U_SEG = WAVES == 8 ? 8 : (G == 4 && WAVES == 1 ? 4 : 1), U_OBS = WAVES == 8 ? 8 : (G == 4 ? 4 : 1);
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM:
+  auto by_loss = [&](auto LOSS) {
+    if constexpr (LOSS == LOSS_QUAD_UNIFORM) {
       if constexpr (WAVES == 1) { // two observations in flight on the row view: -20 % on the L2-latency-bound row sweep
-        if (rows) GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 2);
-        else GLRM_LAUNCH(LOSS_QUAD_UNIFORM, 1);
+        return rows ? launch(LOSS, glrm_const<2>{}) : launch(LOSS, glrm_const<1>{});
       } else {
-        GLRM_LAUNCH(LOSS_QUAD_UNIFORM, (WAVES == 8 ? 8 : 1));
+        return launch(LOSS, glrm_const<(WAVES == 8 ? 8 : 1)>{});
       }
-      break;
-    case LOSS_SEGMENT: GLRM_LAUNCH(LOSS_SEGMENT, U_SEG); break;
-    case LOSS_SEGMENT_NOTRIG: GLRM_LAUNCH(LOSS_SEGMENT_NOTRIG, U_SEG); break;
-    case LOSS_PER_OBS_NOTRIG: GLRM_LAUNCH(LOSS_PER_OBS_NOTRIG, U_OBS); break;
-    default: GLRM_LAUNCH(LOSS_PER_OBS, U_OBS); break;
-  }
-#undef GLRM_LAUNCH
-}
-
-template <int G, int R>
-static void launch_sweep_waves(int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
-  switch (waves) {
-    case 1: launch_sweep_loss<G, R, 1>(loss, rows, a, st); break;
-    case 4: launch_sweep_loss<G, R, 4>(loss, rows, a, st); break;
-    default: launch_sweep_loss<G, R, 8>(loss, rows, a, st); break;
-  }
+    } else {
+      return launch(LOSS, glrm_const<(loss_mode(LOSS) == 1 ? U_SEG : U_OBS)>{});
+    }
+  };
+  glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
 }
 
 // (lanes per observation G, components per lane R) with G*R == kp: the layouts of pick_layout
 static void launch_sweep(int G, int R, int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
-  switch (G * 100 + R) {
-    case 402: launch_sweep_waves<4, 2>(waves, loss, rows, a, st); break;
-    case 404: launch_sweep_waves<4, 4>(waves, loss, rows, a, st); break;
-    case 408: launch_sweep_waves<4, 8>(waves, loss, rows, a, st); break;
-    case 808: launch_sweep_waves<8, 8>(waves, loss, rows, a, st); break;
-    default: launch_sweep_waves<16, 8>(waves, loss, rows, a, st); break;
-  }
+  auto by_layout = [&](auto g, auto r) {
+    constexpr int GG = decltype(g)::value, RR = decltype(r)::value;
+    auto by_waves = [&](auto W) { launch_sweep_loss<GG, RR, decltype(W)::value>(loss, rows, a, st); return GLRM_OK; };
+    return glrm_dispatch<1, 4>(waves, by_waves, [&] { return by_waves(glrm_const<8>{}); });
+  };
+  glrm_dispatch_layout<8, 16, 32, 64>(G, R, by_layout, [&] { return by_layout(glrm_const<16>{}, glrm_const<8>{}); });
 }
 
 static int drain_events(glrm_handle* h) {
@@ -1071,39 +1117,18 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
   if (rc) return rc;
   SweepArgs a{};
   const bool rows = which == 0;
-  a.nseg = rows ? h->ml : h->nl;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
   if (a.nseg <= 0) return GLRM_OK;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.losses = h->losses;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.k = h->k;
-  a.eval_only = eval_only;
-  a.fixed_alpha = eval_only ? 0.0 : h->fixed_alpha;
-  a.min_stepsize = min_stepsize;
-  a.trials = eval_only ? nullptr : (rows ? h->trials_r : h->trials_c);
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
+  if (eval_only) a.trials = nullptr;
   a.seg_lo = 0;
   a.seg_hi = a.nseg;
   if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    const int64_t s0 = h->rng_b;
-    if (h->rng_e - s0 <= 0) return GLRM_OK;
+    if (h->rng_e - h->rng_b <= 0) return GLRM_OK;
     if (h->seglist_r) { // several classes: the class launches filter their lists by the range
-      a.seg_lo = s0; a.seg_hi = h->rng_e;
+      a.seg_lo = h->rng_b; a.seg_hi = h->rng_e;
     } else {
-      a.nseg = h->rng_e - s0;
+      glrm_apply_row_range(a, h->rng_b, h->rng_e);
       a.seg_hi = a.nseg;
-      a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-      if (!a.reg_single) a.regs += s0;
-      if (a.trials) a.trials += s0;
-      a.accepts += s0;
     }
   }
   int loss;
@@ -1135,8 +1160,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
     if (divert) {
       // the gather sweep reads all of X: behind the sweeps already queued (fork) and, while X is still arriving
       // (glrm_hip_step_y_arrival), behind every block -- without holding up the passes on the main stream
-      HIPCK(hipEventRecord(h->ev_fork, h->stream));
-      HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+      if ((rc = glrm_fork_side_stream(h))) return rc;
       for (int b = 0; b < h->n_arrival; ++b)
         if (h->arrival[b].event) HIPCK(hipStreamWaitEvent(h->side_stream, (hipEvent_t)h->arrival[b].event, 0));
       SweepArgs b = a;
@@ -1146,13 +1170,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
     }
     rc = tiled ? glrm_run_tiled(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only)
                : glrm_run_blocked(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only);
-    if (divert) { // join before anything else (also before reporting an error: later work on the stream stays ordered)
-      char keep[sizeof g_err];
-      memcpy(keep, g_err, sizeof keep);
-      (void)hipEventRecord(h->ev_join, h->side_stream);
-      (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
-      memcpy(g_err, keep, sizeof keep);
-    }
+    if (divert) (void)glrm_join_side_stream(h); // join before anything else (also before reporting an error: later work on the stream stays ordered)
     if (rc) return rc;
   } else {
     // gather sweeps (and the cached row sweep), class by class -- see build_class_plan
@@ -1170,8 +1188,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
       // fork: the minority classes on the side stream, beside the majority class on the main stream; join
       int main_cls = 0;
       for (int c = 1; c < 4; ++c) if (ncls[c] > ncls[main_cls]) main_cls = c;
-      HIPCK(hipEventRecord(h->ev_fork, h->stream));
-      HIPCK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+      if ((rc = glrm_fork_side_stream(h))) return rc;
       int64_t off = 0;
       int rc_cls = GLRM_OK;
       for (int c = 0; c < 4 && !rc_cls; off += ncls[c], ++c) {
@@ -1186,16 +1203,10 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
           launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, rows, b, st);
         }
       }
-      if (rc_cls) { // join before reporting: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
-        char keep[sizeof g_err];
-        memcpy(keep, g_err, sizeof keep);
-        (void)hipEventRecord(h->ev_join, h->side_stream);
-        (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
-        memcpy(g_err, keep, sizeof keep);
-        return rc_cls;
-      }
-      HIPCK(hipEventRecord(h->ev_join, h->side_stream));
-      HIPCK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+      // join also before reporting an error: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
+      const hipError_t e_join = glrm_join_side_stream(h);
+      if (rc_cls) return rc_cls;
+      HIPCK(e_join);
     }
   }
   HIPCK(hipGetLastError());
@@ -1444,7 +1455,7 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->tG; o.comps = h->tR;
     o.window = T;
-    o.windows_per_sup = rows ? 0 : h->tiles_per_sup; // (rows: one super-tile, nothing re-added = 0)
+    o.windows_per_sup = rows ? 0 : h->pass[1].tiles_per_sup; // (rows: one super-tile, nothing re-added = 0)
     o.batch = (!quad && (h->tG == 4 || h->tG == 8)) ? h->tG : 2;
     o.rotate = (!rows && !quad && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
     // a private copy in another order: lists the engine tile-sorted, rows regrouped by loss kind inside the tile windows
@@ -1456,12 +1467,12 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
       o.batch = 2;
       o.rotate = 2;
       o.window = T;
-      o.windows_per_sup = rows ? 0 : h->tiles_per_sup;
+      o.windows_per_sup = rows ? 0 : h->pass[1].tiles_per_sup;
     }
   } else if (blocked) {
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->G; o.comps = h->R;
-    o.window = (int64_t)glrm_tile_rows(h->kp) * (rows ? h->tiles_per_sup_r : h->tiles_per_sup); // one walk per super-tile: the super-tile is the window
+    o.window = (int64_t)glrm_tile_rows(h->kp) * h->pass[rows ? 0 : 1].tiles_per_sup; // one walk per super-tile: the super-tile is the window
     o.windows_per_sup = 1;
     o.batch = (!quad && (h->G == 4 || h->G == 8)) ? h->G : 2;
   } else {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 #include "glrm_lane.hpp"
 
 using namespace glrm;
@@ -36,36 +37,20 @@ int launch_lane_inst(const TiledArgs& a, const LaneArgs& la, int64_t nblocks, hi
   return GLRM_OK;
 }
 
+// The family instantiates the scalar-loss variants; its compact stream (sides without a descriptor id in the offset word) the per-segment ones.
 template <bool GRAD, int FORM>
 int launch_lane_loss(int loss, const TiledArgs& a, const LaneArgs& la, int64_t nblocks, hipStream_t st) {
-  if constexpr (FORM == 0) {
-    if (la.off16) { // the compact form of the stream (sides without a descriptor id in the offset word)
-      switch (loss) {
-        case LOSS_QUAD_UNIFORM: return launch_lane_inst<0, GRAD, 0, true>(a, la, nblocks, st);
-        case LOSS_SEGMENT: return launch_lane_inst<1, GRAD, 0, true>(a, la, nblocks, st);
-        case LOSS_SEGMENT_NOTRIG: return launch_lane_inst<3, GRAD, 0, true>(a, la, nblocks, st);
-        default: return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes, compact stream: no kernel for loss variant %d", loss);
-      }
-    }
-  } else if constexpr (FORM == 2 && !GRAD) {
+  if constexpr (FORM == 0 || (FORM == 2 && !GRAD)) {
     if (la.off16) {
-      if (!la.sval) return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: the gathered form needs the step bases of the compact stream");
-      switch (loss) {
-        case LOSS_QUAD_UNIFORM: return launch_lane_inst<0, false, 2, true>(a, la, nblocks, st);
-        case LOSS_SEGMENT: return launch_lane_inst<1, false, 2, true>(a, la, nblocks, st);
-        case LOSS_SEGMENT_NOTRIG: return launch_lane_inst<3, false, 2, true>(a, la, nblocks, st);
-        default: return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes, compact stream: no kernel for loss variant %d", loss);
-      }
+      if (FORM == 2 && !la.sval) return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: the gathered form needs the step bases of the compact stream");
+      return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG>(
+          loss, [&](auto LOSS) { return launch_lane_inst<decltype(LOSS)::value, GRAD, FORM, true>(a, la, nblocks, st); },
+          [&] { return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes, compact stream: no kernel for loss variant %d", loss); });
     }
   }
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: return launch_lane_inst<0, GRAD, FORM>(a, la, nblocks, st);
-    case LOSS_SEGMENT: return launch_lane_inst<1, GRAD, FORM>(a, la, nblocks, st);
-    case LOSS_SEGMENT_NOTRIG: return launch_lane_inst<3, GRAD, FORM>(a, la, nblocks, st);
-    case LOSS_PER_OBS: return launch_lane_inst<2, GRAD, FORM>(a, la, nblocks, st);
-    case LOSS_PER_OBS_NOTRIG: return launch_lane_inst<4, GRAD, FORM>(a, la, nblocks, st);
-    default: return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: no kernel for loss variant %d", loss);
-  }
+  return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS, LOSS_PER_OBS_NOTRIG>(
+      loss, [&](auto LOSS) { return launch_lane_inst<decltype(LOSS)::value, GRAD, FORM>(a, la, nblocks, st); },
+      [&] { return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: no kernel for loss variant %d", loss); });
 }
 
 // a wave per (segment, super-tile), no tile: the tail rounds (glrm_lane.hpp: lane_tail_kernel)
@@ -74,15 +59,13 @@ int launch_lane_tail(int loss, const TiledArgs& a, const int32_t* list, int64_t 
   constexpr int KP = 32, T = glrm_tile_rows(KP);
   nact *= a.nsup; // waves of the round
   const unsigned gx = (unsigned)((nact + 1) / 2);
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: hipLaunchKernelGGL((lane_tail_kernel<KP, 0, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T); break;
-    case LOSS_SEGMENT: hipLaunchKernelGGL((lane_tail_kernel<KP, 1, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T); break;
-    case LOSS_SEGMENT_NOTRIG: hipLaunchKernelGGL((lane_tail_kernel<KP, 3, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T); break;
-    case LOSS_PER_OBS: hipLaunchKernelGGL((lane_tail_kernel<KP, 2, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T); break;
-    case LOSS_PER_OBS_NOTRIG: hipLaunchKernelGGL((lane_tail_kernel<KP, 4, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T); break;
-    default: return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: no tail kernel for loss variant %d", loss);
-  }
-  return GLRM_OK;
+  return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS, LOSS_PER_OBS_NOTRIG>(
+      loss,
+      [&](auto LOSS) {
+        hipLaunchKernelGGL((lane_tail_kernel<KP, decltype(LOSS)::value, LANE_TAIL_CAP>), dim3(gx), dim3(128), 0, st, a, list, nact, T);
+        return GLRM_OK;
+      },
+      [&] { return fail(GLRM_ERR_UNSUPPORTED, "lane-per-segment passes: no tail kernel for loss variant %d", loss); });
 }
 
 // the small kernels of the pass machinery in the two-lane layout the family's sums are reported in
@@ -142,7 +125,7 @@ int glrm_setup_lane(glrm_handle* h) {
   for (int side = 0; side < 2; ++side) {
     const bool rows = side == 0;
     if (!glrm_lane_wants(h, rows)) continue;
-    if (rows ? !(h->tiled_row && (h->tile_rounds & 1) && h->actlist && h->part_r) : !h->tiled_col) continue;
+    if (rows ? !(h->tiled_row && (h->tile_rounds & 1) && h->actlist && h->pass[0].part) : !h->tiled_col) continue;
     if (rows && h->n_losses > 1 && !(h->rowdescid && h->n_udesc > 0)) continue;
     h->lane[side] = 1;
     const int64_t nseg = rows ? h->ml : h->nl;
@@ -266,11 +249,9 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
   const int64_t nslots = a.npass > 0 ? a.npass : a.nseg;
   const int64_t blk_lo = la.slot0 / 64, blk_hi = (la.slot0 + nslots + 63) / 64;
   int rc;
-  const bool lists = h->actlist && (rows ? (h->tile_rounds & 1) != 0 : (h->tile_rounds & 2) != 0) && a.nseg <= h->actlist_cap;
-  int32_t* list[2] = {lists ? h->actlist : nullptr, lists ? h->actlist + h->actlist_cap : nullptr};
-  int cur = 0;
+  const glrm_act_lists lists = glrm_active_lists(h, rows, a.nseg);
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, st));
-  a.actlist_out = list[cur];
+  a.actlist_out = lists.list[0];
   auto csr_args = [&](const TiledArgs& t) { // the CSR form numbers its slots from 0 over t.nseg (a compact list or a plain range)
     LaneArgs c = la;
     c.slot0 = 0;
@@ -294,16 +275,9 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
   const TiledArgs full = a;
   const bool gather = env_int("GLRM_HIP_LANE_ROUNDS", 1) != 0 && sell_ok && h->lane_glist && la.bptr && h->lane_steps[side] > 0 &&
                       full.nseg <= h->lane_gchunks * (int64_t)LANE_CC;
-  constexpr int MAX_ROUNDS = 4096; // see glrm_run_tiled
-  for (int round = 0;; ++round) {
-    if (round == MAX_ROUNDS) return fail(GLRM_ERR_INVALID, "line search still running after %d rounds (min_stepsize %g)", MAX_ROUNDS, min_stepsize);
-    unsigned int nact = 0;
+  // the round's trial pass in whichever form fits the fraction of segments that still searches; `list` holds them (nullptr without lists)
+  auto trial = [&](int round, unsigned int nact, int32_t* list) -> int {
     TiledArgs t = full;
-    TiledArgs d = full;
-    HIPCK(hipMemcpyAsync(&nact, h->nactive, 4, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    if (nact == 0) break;
-    HIPCK(hipMemsetAsync(h->nactive, 0, 4, st));
     const int trace = env_int("GLRM_HIP_LANE_TRACE", 0);
     // Three forms of the trial pass, all adding the same terms in the same order (tests/test_gpu_families.py forces each of them on every
     // round).  FORM 0 walks the SELL layout over the full grid (idle segments masked): the cost of a whole pass whatever the fraction that
@@ -317,18 +291,11 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
     const int64_t pct = (int64_t)nact * 100 / (full.nseg > 0 ? full.nseg : 1);
     // Tail rounds: a wave per (segment, super-tile) instead of a lane's serial walk through every tile (rows: 1.5-9 ms per round at C5's stated
     // size, eight to ten of them per X half-step) -- below GLRM_HIP_LANE_TAIL / GLRM_HIP_LANE_TAIL_COLS percent of the segments
-    if (lists && (int64_t)nact * 100 < full.nseg * (int64_t)(full.nsup == 1 ? env_int("GLRM_HIP_LANE_TAIL", 5) : env_int("GLRM_HIP_LANE_TAIL_COLS", 3))) {
+    if (list && (int64_t)nact * 100 < full.nseg * (int64_t)(full.nsup == 1 ? env_int("GLRM_HIP_LANE_TAIL", 5) : env_int("GLRM_HIP_LANE_TAIL_COLS", 3))) {
       if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: a wave per segment\n", rows ? "row" : "column", round, nact, (long long)full.nseg);
-      if ((rc = launch_lane_tail(loss, full, list[cur], (int64_t)nact, st))) return rc;
-      d.actlist_in = list[cur];
-      d.actlist_out = list[cur ^ 1];
-      d.nact_in = nact;
-      cur ^= 1;
-      launch_small(1, d, st);
-      HIPCK(hipGetLastError());
-      continue;
+      return launch_lane_tail(loss, full, list, (int64_t)nact, st);
     }
-    bool packed = lists && (int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_GATHER_PACKED", 4);
+    bool packed = list && (int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_GATHER_PACKED", 4);
     // (sides with permuted slots: chunk lists over the SLOTS, which were dealt out class by class -- make_segperm)
     const int32_t* gperm = la.inv ? full.segperm : nullptr;
     const bool chunks_ok = !la.inv || (h->lane_dealt[side] && gperm && env_int("GLRM_HIP_LANE_GATHER_SLOTS", 1));
@@ -340,7 +307,7 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
         const int spread = env_int("GLRM_HIP_LANE_GATHER_SPREAD", 32768); // searching segments per step of q: ~2 048 waves before a wave takes more per class
         int q = (int)(((int64_t)nact + spread - 1) / spread);
         q = q < 1 ? 1 : (q > 4 ? 4 : q);
-        hipLaunchKernelGGL(lane_compact_list_kernel, dim3(1), dim3(1024), 0, st, list[cur], (int)nact, off16, q, (int)h->lane_gcap, h->lane_glist, h->lane_gtotal);
+        hipLaunchKernelGGL(lane_compact_list_kernel, dim3(1), dim3(1024), 0, st, list, (int)nact, off16, q, (int)h->lane_gcap, h->lane_glist, h->lane_gtotal);
         HIPCK(hipGetLastError());
         HIPCK(hipMemcpyAsync(&gwaves, h->lane_gtotal, 4, hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));
@@ -365,45 +332,24 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
       la.gwaves = gwaves;
       if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: SELL gathered%s, %d waves\n", rows ? "row" : "column", round, nact, (long long)full.nseg, packed ? " (packed)" : "", (int)gwaves);
       t.npass = 0;
-      rc = launch_lane_loss<false, 2>(loss, t, la, (int64_t)gwaves, st);
-      if (rc) return rc;
-      if (lists) {
-        d.actlist_in = list[cur];
-        d.actlist_out = list[cur ^ 1];
-        d.nact_in = nact;
-        cur ^= 1;
-      }
-      launch_small(1, d, st);
-      HIPCK(hipGetLastError());
-      continue;
+      return launch_lane_loss<false, 2>(loss, t, la, (int64_t)gwaves, st);
     }
     // (measured cross-over of the two older forms at about a sixth of the segments, session r6_20)
-    const bool compact = lists && ((int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_CSR_BELOW", 16) || !sell_ok);
+    const bool compact = list && ((int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_CSR_BELOW", 16) || !sell_ok);
     if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: %s\n", rows ? "row" : "column", round, nact, (long long)full.nseg, compact ? "CSR" : "SELL full grid");
     if (compact) {
       // (tried in session r6_45/46 and taken out again: this form over class-aware wave lists -- conflict-free tile reads -- measured the same at
       // full waves and worse spread over the chip; nor did batching its list reads move it.  A CSR round costs 2.8 x the full grid's time
       // per workgroup and tile at C5's stated size: 512 lanes walk 512 lists 1.2 MB apart, which is an address-translation pattern, not a
       // bandwidth or bank pattern.  Cross-over with the full grid stays at a sixth of the segments.)
-      t.segperm = list[cur];
+      t.segperm = list;
       t.nseg = nact;
       t.npass = 0;
-      rc = launch_lane_loss<false, 1>(loss, t, csr_args(t), ((int64_t)nact + 63) / 64, st);
-    } else if (sell_ok) {
-      rc = launch_lane_loss<false, 0>(loss, t, la, blk_hi - blk_lo, st);
-    } else {
-      t.npass = 0;
-      rc = launch_lane_loss<false, 1>(loss, t, csr_args(t), (t.nseg + 63) / 64, st);
+      return launch_lane_loss<false, 1>(loss, t, csr_args(t), ((int64_t)nact + 63) / 64, st);
     }
-    if (rc) return rc;
-    if (lists) {
-      d.actlist_in = list[cur];
-      d.actlist_out = list[cur ^ 1];
-      d.nact_in = nact;
-      cur ^= 1;
-    }
-    launch_small(1, d, st);
-    HIPCK(hipGetLastError());
-  }
-  return GLRM_OK;
+    if (sell_ok) return launch_lane_loss<false, 0>(loss, t, la, blk_hi - blk_lo, st);
+    t.npass = 0;
+    return launch_lane_loss<false, 1>(loss, t, csr_args(t), (t.nseg + 63) / 64, st);
+  };
+  return glrm_run_rounds(h, full, min_stepsize, lists, trial, [&](const TiledArgs& d) { launch_small(1, d, st); });
 }

@@ -3,6 +3,7 @@
 #include "glrm_multi.hpp"
 
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 
 using namespace glrm;
 
@@ -129,36 +130,15 @@ static int run_split_cols(glrm_handle* h, const MultiArgs& a) {
 
 int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only) {
   MultiArgs a{};
-  a.nseg = rows ? h->ml : h->nl;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
   a.ystart = h->ystart;
-  a.losses = h->losses;
   a.loss_single = h->n_losses == 1;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.k = h->k; a.kp = h->kp; a.dmax = h->dmax;
+  a.kp = h->kp; a.dmax = h->dmax;
   a.lgP = 2;
   while ((1 << a.lgP) < h->k || (1 << a.lgP) < h->dmax) ++a.lgP;
   a.mode = eval_only ? 1 : (h->fixed_alpha > 0.0 ? 2 : 0);
-  a.fixed_alpha = h->fixed_alpha;
-  a.min_stepsize = min_stepsize;
-  a.trials = (eval_only || a.mode == 2) ? nullptr : (rows ? h->trials_r : h->trials_c);
-  a.accepts = (eval_only || a.mode == 2) ? nullptr : (rows ? h->accepts_r : h->accepts_c);
-  if (rows && h->rng_e >= 0) {
-    const int64_t s0 = h->rng_b;
-    a.nseg = h->rng_e - s0;
-    a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-    if (!a.reg_single) a.regs += s0;
-    if (a.trials) a.trials += s0;
-    if (a.accepts) a.accepts += s0;
-  }
+  if (a.mode != 0) a.trials = a.accepts = nullptr; // the counters belong to the line-search steps
+  if (rows && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e);
   if (a.nseg <= 0) return GLRM_OK;
   if (rows) {
     const size_t lds = multi_lds_doubles(true, 1, h->kp, h->dmax, a.lgP) * 8;

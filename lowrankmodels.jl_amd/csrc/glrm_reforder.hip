@@ -29,6 +29,7 @@
 
 #include "glrm_device.hpp"
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 
 using namespace glrm;
 
@@ -421,40 +422,14 @@ int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_o
     return fail(GLRM_ERR_UNSUPPORTED, "glrm_options.sum_order = 1 (reference order) restates the ProxGradParams half-steps only, not the fixed-step sweeps of SparseProxGradParams");
   if (rows && eval_only) return fail(GLRM_ERR_INVALID, "no evaluation pass over the row view");
   RefArgs a{};
-  a.nseg = rows ? h->ml : h->nl;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.losses = h->losses;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
   a.n_losses = h->n_losses;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.k = h->k;
-  a.min_stepsize = min_stepsize;
-  a.trials = eval_only ? nullptr : (rows ? h->trials_r : h->trials_c);
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
-  a.eval_only = eval_only;
-  if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    const int64_t s0 = h->rng_b;
-    a.nseg = h->rng_e - s0;
-    a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-    if (!a.reg_single) a.regs += s0;
-    if (a.trials) a.trials += s0;
-    a.accepts += s0;
-  }
+  if (eval_only) a.trials = nullptr;
+  if (rows && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e); // glrm_hip_step_x_range
   if (a.nseg <= 0) return GLRM_OK;
-  switch (h->kp) {
-    case 8: return launch_ref<8>(rows, h->has_trig, a, h->stream);
-    case 16: return launch_ref<16>(rows, h->has_trig, a, h->stream);
-    case 32: return launch_ref<32>(rows, h->has_trig, a, h->stream);
-    case 64: return launch_ref<64>(rows, h->has_trig, a, h->stream);
-    default: return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp);
-  }
+  return glrm_dispatch<8, 16, 32, 64>(
+      h->kp, [&](auto KP) { return launch_ref<decltype(KP)::value>(rows, h->has_trig, a, h->stream); },
+      [&] { return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp); });
 }
 
 // sum(::Vector{Float64}) as Julia adds it (pairwise, blocks of 1024): the recorded objective sum(obj_by_col), proxgrad.jl:205
@@ -489,14 +464,9 @@ int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out) {
     try { host.resize((size_t)chunk); } catch (const std::exception&) { (void)hipFree(dterms); return fail(GLRM_ERR_OOM, "out of host memory"); }
     for (int64_t t0 = 0; t0 < h->nnz_c; t0 += chunk) {
       const int64_t t1 = std::min(h->nnz_c, t0 + chunk);
-      int rc;
-      switch (h->kp) {
-        case 8: rc = launch_ref_terms<8>(h->has_trig, a, t0, t1, dterms, h->stream); break;
-        case 16: rc = launch_ref_terms<16>(h->has_trig, a, t0, t1, dterms, h->stream); break;
-        case 32: rc = launch_ref_terms<32>(h->has_trig, a, t0, t1, dterms, h->stream); break;
-        case 64: rc = launch_ref_terms<64>(h->has_trig, a, t0, t1, dterms, h->stream); break;
-        default: rc = fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp);
-      }
+      const int rc = glrm_dispatch<8, 16, 32, 64>(
+          h->kp, [&](auto KP) { return launch_ref_terms<decltype(KP)::value>(h->has_trig, a, t0, t1, dterms, h->stream); },
+          [&] { return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp); });
       hipError_t e = rc ? hipSuccess : hipMemcpyAsync(host.data(), dterms, (size_t)(t1 - t0) * 8, hipMemcpyDeviceToHost, h->stream);
       if (!rc && e == hipSuccess) e = hipStreamSynchronize(h->stream);
       if (rc || e != hipSuccess) {

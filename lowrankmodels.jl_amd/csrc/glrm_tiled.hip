@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "glrm_engine.hpp"
+#include "glrm_launch.hpp"
 #include "glrm_tiled.hpp"
 
 using namespace glrm;
@@ -25,27 +26,22 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
   const int64_t nseg = rows ? h->ml : h->nl;
   if (nshort) *nshort = nseg;
   if (nseg <= 1 || !env_int("GLRM_HIP_SEGPERM", 1)) return GLRM_OK;
-  std::vector<int64_t> ptr((size_t)nseg + 1);
-  HIPCK(hipMemcpyAsync(ptr.data(), rows ? h->rowptr : h->colptr, ((size_t)nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCK(hipStreamSynchronize(h->stream));
+  std::vector<int64_t> ptr;
+  int rc = glrm_host_ptr(h, rows, ptr);
+  if (rc) return rc;
   int64_t lmin = INT64_MAX, lmax = 0;
   for (int64_t s = 0; s < nseg; ++s) { const int64_t l = ptr[s + 1] - ptr[s]; lmin = l < lmin ? l : lmin; lmax = l > lmax ? l : lmax; }
   const bool kinds = !rows && h->n_losses > 1;
   const bool divert = long_from > 0 && longs && lmax >= long_from;
   if (!kinds && !divert && lmax * 4 <= lmin * 5) return GLRM_OK;
-  std::vector<int32_t> perm;
-  perm.reserve((size_t)nseg);
-  for (int64_t s = 0; s < nseg; ++s) {
-    if (divert && ptr[s + 1] - ptr[s] >= long_from) longs->push_back((int32_t)s);
-    else perm.push_back((int32_t)s);
-  }
+  std::vector<int32_t> perm, none;
+  glrm_split_by_length(ptr, divert ? long_from : 0, perm, divert ? *longs : none); // by descending length
   const int64_t nslots = (int64_t)perm.size();
   if (nshort) *nshort = nslots;
-  const glrm_loss* lt = kinds ? h->losses_h.data() + h->cb : nullptr;
-  std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
-    if (kinds && lt[x].kind != lt[y].kind) return lt[x].kind < lt[y].kind;
-    return ptr[x + 1] - ptr[x] > ptr[y + 1] - ptr[y];
-  });
+  if (kinds) { // loss kind first (stable: by descending length inside a kind)
+    const glrm_loss* lt = h->losses_h.data() + h->cb;
+    std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return lt[x].kind < lt[y].kind; });
+  }
   const bool lane_side = (rows ? h->tiled_row : h->tiled_col) && glrm_lane_wants(h, rows) && env_int("GLRM_HIP_LANE_DEAL", 1);
   if (lane_side) {
     // The lane-per-segment passes (glrm_lane.hpp) read their tiles conflict free when the 16 lanes of an LDS cycle hold 16 different
@@ -85,10 +81,7 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
       perm[(size_t)slot] = q[c][head[c]++];
     }
   }
-  HIPCK(hipMalloc((void**)out, (size_t)(nslots > 0 ? nslots : 1) * 4));
-  HIPCK(hipMemcpyAsync(*out, perm.data(), (size_t)nslots * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipStreamSynchronize(h->stream)); // perm is a local
-  return GLRM_OK;
+  return glrm_upload_list(h, perm, out);
 }
 
 // create phase: the lane layout of the tiled kernels and whether this shard's lists are in tile order (glrm_signature::rows_unordered /
@@ -232,19 +225,12 @@ int glrm_setup_tiled(glrm_handle* h) {
     const int64_t tps_max = 32768 / T > 1 ? 32768 / T : 1; // at most ~32k rows per super-tile (long columns still spread out)
     if (tps > tps_max) tps = tps_max;
     if (tps < 1) tps = 1;
-    h->tiles_per_sup = (int)tps;
+    h->pass[1].tiles_per_sup = (int)tps;
   }
-  h->nsup = (int)((ntiles + h->tiles_per_sup - 1) / h->tiles_per_sup);
+  h->pass[1].nsup = (int)((ntiles + h->pass[1].tiles_per_sup - 1) / h->pass[1].tiles_per_sup);
   if (h->tiled_col) {
-    const int64_t nl1 = h->nl > 0 ? h->nl : 1;
-    HIPCK(hipMalloc((void**)&h->part, (size_t)nl1 * h->nsup * (h->kp + 2) * 8));
-    HIPCK(hipMalloc((void**)&h->gsum, (size_t)nl1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->trialbuf, (size_t)nl1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->joldbuf, (size_t)nl1 * 8));
-    HIPCK(hipMalloc((void**)&h->activebuf, (size_t)nl1 * 4));
-    HIPCK(hipMalloc((void**)&h->ntrialbuf, (size_t)nl1 * 4));
-    HIPCK(hipMalloc((void**)&h->nactive, 4));
-    HIPCK(hipMemsetAsync(h->activebuf, 0, (size_t)nl1 * 4, st)); // diverted columns are never touched by col_reduce: "not searching"
+    if ((rc0 = glrm_alloc_pass_buffers(h, 1))) return rc0;
+    HIPCK(hipMemsetAsync(h->pass[1].active, 0, (size_t)(h->nl > 0 ? h->nl : 1) * 4, st)); // diverted columns are never touched by col_reduce: "not searching"
     // Skewed column lengths (round 5, like the phase-aligned passes: glrm_blocked.hip).  The columns are already handed out sorted by
     // length; a workgroup's 256 columns walk a tile in lockstep (one barrier per tile), so ONE column many times the others keeps its
     // workgroup on every tile for its own entries alone, and the few workgroups of the head of the sorted list are the makespan (C2
@@ -257,17 +243,7 @@ int glrm_setup_tiled(glrm_handle* h) {
     h->blk_long_from = env_int("GLRM_HIP_TILED_LONG_FROM", -1) >= 0 ? env_int("GLRM_HIP_TILED_LONG_FROM", 0) : std::max<int64_t>(4096, 4 * mean_len);
     std::vector<int32_t> longl;
     if ((rc0 = make_segperm(h, false, &h->colperm, h->blk_long_from, &longl, &h->blk_nshort_c))) return rc0;
-    h->blk_nlong_c = (int64_t)longl.size();
-    if (!longl.empty()) {
-      HIPCK(hipMalloc((void**)&h->blk_long_c, longl.size() * 4));
-      HIPCK(hipMemcpyAsync(h->blk_long_c, longl.data(), longl.size() * 4, hipMemcpyHostToDevice, st));
-      if (!h->side_stream) {
-        HIPCK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        HIPCK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-      }
-      HIPCK(hipStreamSynchronize(st)); // longl is a local
-    }
+    if ((rc0 = glrm_set_long_columns(h, longl))) return rc0;
   }
   if (h->tiled_row && (rc0 = make_segperm(h, true, &h->rowperm))) return rc0;
   // Line-search rounds over the still-searching segments only (glrm_tiled.hpp: TiledArgs::actlist_out).  Columns: the passes after the
@@ -282,16 +258,9 @@ int glrm_setup_tiled(glrm_handle* h) {
   // the pass buffers of the row rounds: ONE super-tile (nothing is re-added: the bits of the one-kernel sweep)
   if (h->tiled_row && (h->tile_rounds & 1)) {
     const int64_t nt = (h->n + T - 1) / T;
-    h->tiles_per_sup_r = (int)(nt > 0 ? nt : 1);
-    h->nsup_r = 1;
-    const int64_t ml1 = h->ml > 0 ? h->ml : 1;
-    HIPCK(hipMalloc((void**)&h->part_r, (size_t)ml1 * (h->kp + 2) * 8));
-    HIPCK(hipMalloc((void**)&h->gsum_r, (size_t)ml1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->trial_r, (size_t)ml1 * h->kp * 8));
-    HIPCK(hipMalloc((void**)&h->jold_r, (size_t)ml1 * 8));
-    HIPCK(hipMalloc((void**)&h->active_r, (size_t)ml1 * 4));
-    HIPCK(hipMalloc((void**)&h->ntrial_r, (size_t)ml1 * 4));
-    if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
+    h->pass[0].tiles_per_sup = (int)(nt > 0 ? nt : 1);
+    h->pass[0].nsup = 1;
+    if ((rc0 = glrm_alloc_pass_buffers(h, 0))) return rc0;
   }
   return glrm_setup_lane(h); // the lane-per-segment form of the passes where it applies (glrm_lane.hip)
 }
@@ -333,119 +302,59 @@ static int launch_tiled_inst(int kind, const TiledArgs& a, hipStream_t st) {
 }
 
 // 16 waves and one ~150 KB tile per CU
-template <int G, int R>
-static int launch_tiled_layout(int loss, int kind, const TiledArgs& a, hipStream_t st) {
-  constexpr int T = glrm_tile_rows(G * R);
-  switch (loss) {
-    case LOSS_QUAD_UNIFORM: return launch_tiled_inst<G, R, 16, T, 0>(kind, a, st);
-    case LOSS_SEGMENT: return launch_tiled_inst<G, R, 16, T, 1>(kind, a, st);
-    case LOSS_SEGMENT_NOTRIG: return launch_tiled_inst<G, R, 16, T, 3>(kind, a, st);
-    case LOSS_PER_OBS_NOTRIG: return launch_tiled_inst<G, R, 16, T, 4>(kind, a, st);
-    default: return launch_tiled_inst<G, R, 16, T, 2>(kind, a, st);
-  }
-}
-
 static int launch_tiled(glrm_handle* h, int loss, int kind, const TiledArgs& a) {
-  switch (h->tG * 100 + h->tR) {
-    case 402: return launch_tiled_layout<4, 2>(loss, kind, a, h->stream);
-    case 404: return launch_tiled_layout<4, 4>(loss, kind, a, h->stream);
-    case 408: return launch_tiled_layout<4, 8>(loss, kind, a, h->stream);
-    case 808: return launch_tiled_layout<8, 8>(loss, kind, a, h->stream);
-    case 1608: return launch_tiled_layout<16, 8>(loss, kind, a, h->stream);
-    default: return fail(GLRM_ERR_UNSUPPORTED, "no tiled kernel for lane layout G=%d R=%d", h->tG, h->tR);
-  }
-}
-
-template <int G, int R>
-static void launch_col_small(int which, const TiledArgs& a, hipStream_t st) {
-  const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
-  if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+  auto by_layout = [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value, T = glrm_tile_rows(G * R);
+    auto by_loss = [&](auto LOSS) { return launch_tiled_inst<G, R, 16, T, decltype(LOSS)::value>(kind, a, h->stream); };
+    return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
+  };
+  return glrm_dispatch_layout<8, 16, 32, 64, 128>(h->tG, h->tR, by_layout, [&] { return fail(GLRM_ERR_UNSUPPORTED, "no tiled kernel for lane layout G=%d R=%d", h->tG, h->tR); });
 }
 
 void glrm_launch_col_small(int kp, int which, const TiledArgs& a, hipStream_t st) {
-  switch (kp) {
-    case 8: launch_col_small<4, 2>(which, a, st); break;
-    case 16: launch_col_small<4, 4>(which, a, st); break;
-    case 32: launch_col_small<4, 8>(which, a, st); break;
-    case 64: launch_col_small<8, 8>(which, a, st); break;
-    default: launch_col_small<16, 8>(which, a, st); break;
-  }
+  auto by_layout = [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
+    if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+    return GLRM_OK;
+  };
+  glrm_dispatch_layout<8, 16, 32, 64>(glrm_layout_g(kp), glrm_layout_r(kp), by_layout, [&] { return by_layout(glrm_const<16>{}, glrm_const<8>{}); });
 }
-
-static void launch_col_small_any(glrm_handle* h, int which, const TiledArgs& a) { glrm_launch_col_small(h->kp, which, a, h->stream); }
 
 // The tiled variants of run_sweep's launch.  Rows: one kernel.  Columns: pass 1 -> reduce -> rounds of
 // (trial pass, decide) until no column is still searching (the count is read back once per round).
 int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
   TiledArgs a{};
-  a.nseg = rows ? h->ml : h->nl;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
-  a.n_other = rows ? h->n : h->m;
-  a.alpha = rows ? h->alpharow : h->alphacol;
-  a.obj = rows ? nullptr : h->objcol;
-  a.losses = h->losses;
+  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
   a.loss_by_segment = loss_by_segment;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  a.k = h->k;
-  a.min_stepsize = min_stepsize;
-  a.trials = rows ? h->trials_r : h->trials_c;
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
-  a.eval_only = eval_only;
-  a.fixed_alpha = eval_only ? 0.0 : h->fixed_alpha;
   a.descid = rows ? h->rowdescid : nullptr;
   a.udesc = h->udesc;
   a.n_udesc = h->n_udesc;
-  if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range
-    const int64_t s0 = h->rng_b;
-    a.nseg = h->rng_e - s0;
+  const bool range = rows && h->rng_e >= 0; // glrm_hip_step_x_range
+  if (range) {
+    glrm_apply_row_range(a, h->rng_b, h->rng_e);
     if (a.nseg <= 0) return GLRM_OK;
-    a.ptr += s0; a.alpha += s0; a.own_offset += s0;
-    if (!a.reg_single) a.regs += s0;
-    a.trials += s0; a.accepts += s0;
   }
+  const glrm_act_lists lists = glrm_active_lists(h, rows, a.nseg);
   const bool row_rounds = rows && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
   // lane-per-segment passes (glrm_lane.hpp): the ProxGradParams half-steps and the evaluation pass of the sides that run that family
   const bool lane_here = h->lane[rows ? 0 : 1] && glrm_lane_loss_ok(h, loss) && a.fixed_alpha <= 0.0 && (rows ? row_rounds : true);
-  if (rows && !row_rounds) {
-    a.segperm = h->rng_e >= 0 ? nullptr : h->rowperm; // a sub-range sweep keeps the natural order
-    return launch_tiled(h, loss, 0, a);
-  }
-  if (rows) { // pass buffers of the row rounds (one super-tile, glrm_setup_tiled)
-    const int64_t s0 = h->rng_e >= 0 ? h->rng_b : 0;
-    a.nsup = h->nsup_r;
-    a.tiles_per_sup = h->tiles_per_sup_r;
-    a.part = h->part_r + s0 * (int64_t)h->nsup_r * (h->kp + 2); a.gsum = h->gsum_r + s0 * (int64_t)h->kp; a.trial = h->trial_r + s0 * (int64_t)h->kp;
-    a.jold = h->jold_r + s0; a.active = h->active_r + s0; a.ntrial = h->ntrial_r + s0; a.nactive = h->nactive;
-    a.segperm = h->rng_e >= 0 ? nullptr : h->rowperm;
-  } else {
-    a.nsup = h->nsup;
-    a.tiles_per_sup = h->tiles_per_sup;
-    a.part = h->part; a.gsum = h->gsum; a.trial = h->trialbuf; a.jold = h->joldbuf;
-    a.active = h->activebuf; a.ntrial = h->ntrialbuf; a.nactive = h->nactive;
-    a.segperm = h->colperm;
-    if (h->blk_nlong_c > 0) { // the columns at or above long_from run on the gather sweep beside the passes (run_sweep, glrm_hip.hip)
-      a.long_from = h->blk_long_from;
-      a.npass = h->blk_nshort_c;
-      if (a.npass == 0) { // every local column is diverted
-        HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-        return GLRM_OK;
-      }
+  a.segperm = rows ? (range ? nullptr : h->rowperm) : h->colperm; // a sub-range sweep keeps the natural order
+  if (rows && !row_rounds) return launch_tiled(h, loss, 0, a);
+  glrm_bind_pass_buffers(a, h, rows ? 0 : 1, range ? h->rng_b : 0); // (rows: one super-tile, glrm_setup_tiled)
+  if (!rows && h->blk_nlong_c > 0) { // the columns at or above long_from run on the gather sweep beside the passes (run_sweep, glrm_hip.hip)
+    a.long_from = h->blk_long_from;
+    a.npass = h->blk_nshort_c;
+    if (a.npass == 0) { // every local column is diverted
+      HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
+      return GLRM_OK;
     }
   }
   if (lane_here) return glrm_run_lane(h, rows, loss, a, min_stepsize, eval_only);
   int rc;
-  const bool lists = h->actlist && (rows ? (h->tile_rounds & 1) != 0 : (h->tile_rounds & 2) != 0) && a.nseg <= h->actlist_cap;
-  int32_t* list[2] = {lists ? h->actlist : nullptr, lists ? h->actlist + h->actlist_cap : nullptr};
-  int cur = 0; // the list the kernels of this stage append to
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-  a.actlist_out = list[cur];
+  a.actlist_out = lists.list[0]; // the list the kernels of this stage append to
   if (rows) {
     if ((rc = launch_tiled(h, loss, 3, a))) return rc; // gradient pass + first trial; rejected rows are listed
   } else {
@@ -457,43 +366,22 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
       return launch_tiled(h, loss, 1, r);
     });
     if (rc) return rc;
-    launch_col_small_any(h, 0, a);
+    glrm_launch_col_small(h->kp, 0, a, h->stream);
   }
   HIPCK(hipGetLastError());
   if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
-  const TiledArgs full = a;
-  // A segment leaves the search when a trial is accepted or its step size is no longer above min_stepsize (`while alpha > min_stepsize`,
-  // proxgrad.jl:136,180): at most log(alpha / min_stepsize) / log(1 / 0.7) rounds (13 from alpha = 1 and the default 0.01).  With
-  // min_stepsize = 0 a search whose trials are all rejected never ends in the reference either: 0.7 x 4.9e-324 rounds back to 4.9e-324,
-  // alpha never reaches 0 (~2 090 rounds from alpha = 1 to the smallest denormal, then forever).  The bound below is a guard against
-  // exactly that loop, never a silent cut: running into it is an error where the reference would hang.
-  constexpr int MAX_ROUNDS = 4096;
-  for (int round = 0;; ++round) {
-    if (round == MAX_ROUNDS) return fail(GLRM_ERR_INVALID, "line search still running after %d rounds (min_stepsize %g)", MAX_ROUNDS, min_stepsize);
-    unsigned int nact = 0;
-    HIPCK(hipMemcpyAsync(&nact, h->nactive, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    if (nact == 0) break;
-    HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-    TiledArgs t = full;
-    // the trial pass: over the listed segments when they are the minority (a full grid keeps the length / kind order of segperm, which
-    // pays while nearly every segment still takes part: the first trial of the columns)
-    const bool compact = lists && (rows || (int64_t)nact * 4 < full.nseg * 3);
-    if (compact) {
-      t.segperm = list[cur];
-      t.nseg = nact;
-      t.npass = 0;
-    }
-    if ((rc = launch_tiled(h, loss, rows ? 4 : 2, t))) return rc;
-    TiledArgs d = full;
-    if (lists) {
-      d.actlist_in = list[cur];
-      d.nact_in = nact;
-      d.actlist_out = list[cur ^ 1];
-      cur ^= 1;
-    }
-    launch_col_small_any(h, 1, d);
-    HIPCK(hipGetLastError());
-  }
-  return GLRM_OK;
+  return glrm_run_rounds(
+      h, a, min_stepsize, lists,
+      [&](int, unsigned int nact, int32_t* list) {
+        TiledArgs t = a;
+        // the trial pass: over the listed segments when they are the minority (a full grid keeps the length / kind order of segperm, which
+        // pays while nearly every segment still takes part: the first trial of the columns)
+        if (list && (rows || (int64_t)nact * 4 < a.nseg * 3)) {
+          t.segperm = list;
+          t.nseg = nact;
+          t.npass = 0;
+        }
+        return launch_tiled(h, loss, rows ? 4 : 2, t);
+      },
+      [&](const TiledArgs& d) { glrm_launch_col_small(h->kp, 1, d, h->stream); });
 }
