@@ -19,6 +19,7 @@ PROBLEM_DEVICE_ARRAYS = 1
 PROBLEM_DEFER_SETUP = 2
 PROBLEM_BORROW_DEVICE_ARRAYS = 4
 PROBLEM_ROWS_FROM_COLS = 8   # Omega is a sparse matrix's pattern: hand over the column view only, the engine derives the row view
+SCALE_EQUILIBRATE, SCALE_PROB = 0, 1   # include/glrm_hip_scale.h: equilibrate_variance! / prob_scale!
 
 
 class GLRMError(RuntimeError):
@@ -145,6 +146,10 @@ ABI_SYMBOLS = (
     "multi_create", "multi_fit", "multi_set_regularizers", "multi_info", "multi_destroy",
 )
 
+#: the scaling extension, include/glrm_hip_scale.h: NOT part of the 37-symbol boundary above, bound only where the library has it
+#: (the HIP engine; the CPU oracle does not restate it)
+SCALE_SYMBOLS = ("scale_columns",)
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -235,6 +240,15 @@ class Api:
             fn = getattr(lib, prefix + name)
             fn.restype, fn.argtypes = res, args
             self._f[name] = fn
+        ext = {
+            "scale_columns": (C.c_int, [C.POINTER(CProblem), C.POINTER(COptions), C.c_int32] + [C.c_void_p] * 5),
+        }
+        assert tuple(ext) == SCALE_SYMBOLS
+        for name, (res, args) in ext.items():
+            fn = getattr(lib, prefix + name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
+                self._f[name] = fn
         v = self._f["version"]()
         if v != ABI_VERSION:
             raise RuntimeError(f"{prefix}version() = {v}, this host layer speaks ABI {ABI_VERSION}")
@@ -462,6 +476,26 @@ class Api:
         o = CSumOrder()
         self._ck(self._f["sum_order"](h, int(which), C.byref(o)))
         return o
+
+    # -- scaling extension (include/glrm_hip_scale.h) ---------------------------------------
+    def scale_columns(self, prob: "ProblemArrays", mode, device_id=-1, stream=None, diagnostics=False):
+        """glrm_hip_scale_columns on the column view of ``prob`` (its row view may be None): the NEW loss and Y-regularizer scales of the
+        columns [col_begin, col_end) under equilibrate_variance! (``SCALE_EQUILIBRATE``) or prob_scale! (``SCALE_PROB``).  Returns
+        (loss_scale, ry_scale), with ``diagnostics`` also a dict of the per-column m_est / avg_loss / variance."""
+        fn = self._f.get("scale_columns")
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}scale_columns: this engine does not have the scaling extension "
+                                             "(include/glrm_hip_scale.h is implemented by the HIP engine only)")
+        p = self._cproblem(prob)
+        o = COptions(device_id, 0, 0, 0, (stream or None), 0 if stream is None else 1, 0, 0, 0, 0, 0)
+        nl = prob.col_end - prob.col_begin
+        out = [np.full(max(nl, 1), np.nan) for _ in range(5 if diagnostics else 2)]
+        ptrs = [_ptr(x) for x in out] + [None] * (5 - len(out))
+        self._ck(fn(C.byref(p), C.byref(o), int(mode), *ptrs))
+        out = [x[:nl] for x in out]
+        if diagnostics:
+            return out[0], out[1], dict(m_est=out[2], avg_loss=out[3], variance=out[4])
+        return out[0], out[1]
 
 
 class ProblemArrays:
