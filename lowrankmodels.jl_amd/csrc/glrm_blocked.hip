@@ -41,6 +41,48 @@ constexpr int BNW = 1;                                                     // wa
 // against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).
 constexpr int BLOCKED_GATE_DEFAULT = 8192;
 
+// suppos[seg * nsup + sup] = lower_bound_idx(segment seg's list, first row of super-tile sup) - ptr[seg]: the pass kernel's own search, so
+// that lists ordered by tile only get exactly the position the kernel would find.  *too_long is set where a segment does not fit int32.
+static __global__ void __launch_bounds__(256) suppos_kernel(const int64_t* ptr, const int32_t* idx, int64_t nseg, int nsup, int64_t rows_per_sup,
+                                                            int32_t* suppos, unsigned int* too_long) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= nseg * nsup) return;
+  const int64_t seg = t / nsup, b = ptr[seg], e = ptr[seg + 1];
+  const int sup = (int)(t - seg * nsup);
+  if (e - b > 0x7fffffff) { *too_long = 1; return; }
+  suppos[t] = (int32_t)(lower_bound_idx<1>(idx, b, e, sup * rows_per_sup) - b);
+}
+
+// Start table of one side (PassBuffers::suppos), built once: Omega never changes for the life of a handle, and every launch of the passes
+// began with the same ~14 dependent loads per lane group (624 launches per C4 iteration), which also let the groups of a launch start their
+// walks microseconds apart.  GLRM_HIP_BLOCKED_SUPPOS (read here and at every pass): 0 the kernels search, 1 (default) the table where it
+// takes at most 1/16 of the view's list bytes (C4 columns: 15.6 MB beside 12 GB), 2 the table whatever its size (tests on tiny shapes).
+// Measured, C4, same box (profiles/r09_c4_ab.txt, r09_c4_launch_split_*.md): every launch 5-6 us shorter (full super-tile 176.9 -> 170.6 us,
+// the last one 38.8 -> 33.9 us), Y half-step 118.0 -> 114.1 ms, iteration 192.9 -> 188.8 ms; the L2 hit rate hardly moves (0.29 -> 0.29 / 0.30
+// -> 0.31).  Changes no sum.
+static int build_suppos(glrm_handle* h, int side) {
+  glrm_handle::PassBuffers& b = h->pass[side];
+  const int mode = env_int("GLRM_HIP_BLOCKED_SUPPOS", 1);
+  const int64_t nseg = side == 0 ? h->ml : h->nl, nnz = side == 0 ? h->nnz_r : h->nnz_c, cells = nseg * b.nsup;
+  const bool fits = (double)cells * 4.0 * 16.0 <= 12.0 * (double)nnz;
+  const bool build = mode != 0 && cells > 0 && (fits || mode >= 2);
+  if (build) {
+    unsigned int too_long = 0;
+    HIPCK(hipMalloc((void**)&b.suppos, (size_t)cells * 4));
+    HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
+    hipLaunchKernelGGL(suppos_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, side == 0 ? h->rowptr : h->colptr,
+                       side == 0 ? h->colidx : h->rowidx, nseg, b.nsup, (int64_t)b.tiles_per_sup * glrm_tile_rows(h->kp), b.suppos, h->nactive);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(&too_long, h->nactive, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    if (too_long) return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: a %s holds 2^31 observations or more", side == 0 ? "row" : "column");
+  }
+  if (env_int("GLRM_HIP_BLOCKED_TRACE", 0))
+    fprintf(stderr, "[glrm blocked] %s view: %d super-tiles x %lld segments, start table %s (%.1f MB, lists %.1f MB)\n", side == 0 ? "row" : "column", b.nsup,
+            (long long)nseg, build ? "built" : (mode == 0 ? "off: the passes search" : "over 1/16 of the lists: the passes search"), (double)cells * 4e-6, 12e-6 * (double)nnz);
+  return GLRM_OK;
+}
+
 int glrm_setup_blocked(glrm_handle* h) {
   h->blocked_row = h->blocked_col = 0;
   const int want = env_int("GLRM_HIP_BLOCKED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
@@ -79,10 +121,12 @@ int glrm_setup_blocked(glrm_handle* h) {
   };
   if (br) {
     if ((rc = buffers(0, h->n))) return rc;
+    if ((rc = build_suppos(h, 0))) return rc;
     h->blocked_row = 1;
   }
   if (bc) {
     if ((rc = buffers(1, h->m))) return rc;
+    if ((rc = build_suppos(h, 1))) return rc;
     HIPCK(hipMemsetAsync(h->pass[1].active, 0, (size_t)(h->nl > 0 ? h->nl : 1) * 4, h->stream)); // diverted columns are never touched by col_reduce: they must read "not searching"
     h->blocked_col = 1;
     // Skewed column lengths (power-law Omega; round 5).  A launch covers one super-tile x a slice of the columns, one lane group per column:
@@ -147,6 +191,7 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
   // that cannot fill the chip)
   const int64_t nslices = (nseg + cap - 1) / cap;
   const int64_t per = nslices > 0 ? ((nseg + nslices - 1) / nslices + SPB - 1) / SPB * SPB : cap;
+  if (!env_int("GLRM_HIP_BLOCKED_SUPPOS", 1)) a.suppos = nullptr;
   // glrm_hip_step_y_arrival: the gradient pass of the column view walks the super-tiles in the order their rows of X arrive, each behind
   // the events of the blocks it touches (h->sup_order, glrm_run_blocked); the partial sums are per (segment, super-tile) and col_reduce
   // adds them in super-tile order, so the launch order changes no bit

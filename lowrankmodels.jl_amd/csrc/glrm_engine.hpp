@@ -71,6 +71,9 @@ struct glrm_handle {
     double *part = nullptr, *gsum = nullptr, *trial = nullptr, *jold = nullptr;
     int32_t *active = nullptr, *ntrial = nullptr;
     int nsup = 0, tiles_per_sup = 0;
+    // phase-aligned passes (glrm_blocked.hip).  suppos[seg * nsup + sup]: offset inside segment seg's list of its first entry of super-tile
+    // sup (what the pass kernel's search would find; nullptr = the kernel searches)
+    int32_t* suppos = nullptr;
   } pass[2];
   unsigned int* nactive = nullptr;    // segments still searching (one counter: a half-step at a time)
   int* dflag = nullptr;

@@ -577,7 +577,7 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
                   h->alpharow, h->alphacol, h->oX, h->oY, h->oobjcol, h->oobjrow, h->partials, h->dscalar, h->dcount,
                   h->trials_r, h->accepts_r, h->trials_c, h->accepts_c, h->pass[0].part, h->pass[0].gsum, h->pass[0].trial,
                   h->pass[0].jold, h->pass[0].active, h->pass[0].ntrial, h->pass[1].part, h->pass[1].gsum, h->pass[1].trial, h->pass[1].jold,
-                  h->pass[1].active, h->pass[1].ntrial, h->nactive, h->dflag, h->Arow, h->Acol, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
+                  h->pass[1].active, h->pass[1].ntrial, h->pass[0].suppos, h->pass[1].suppos, h->nactive, h->dflag, h->Arow, h->Acol, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
                   h->mobjold, h->mactive, h->mnactive, h->colperm, h->rowperm, h->seglist_r, h->seglist_c, h->rowdescid, h->udesc,
                   h->gramH, h->gram_part, h->jloss_r, h->jloss_c, h->actlist, h->blk_perm_c, h->blk_long_c,
                   h->lane_bptr[0], h->lane_bptr[1], h->lane_off[0], h->lane_off[1], h->lane_val[0], h->lane_val[1],

@@ -69,6 +69,7 @@ void glrm_bind_pass_buffers(A& a, const glrm_handle* h, int side, int64_t s0 = 0
   a.jold = b.jold + s0;
   a.active = b.active + s0;
   a.ntrial = b.ntrial + s0;
+  a.suppos = b.suppos ? b.suppos + s0 * (int64_t)b.nsup : nullptr;
   a.nactive = h->nactive;
 }
 

@@ -89,6 +89,8 @@ struct TiledArgs {
   int64_t nact_in;
   int gate;                   // phase-aligned passes (tiled_pass<..., L2 = true>): a lane group whose next observation lies more than `gate` rows
                               // past the wave's trailing group sits the step out (0 = off; see tiled_pass)
+  const int32_t* suppos;      // phase-aligned passes: [nseg][nsup] offset inside the segment's list of its first entry of the super-tile, i.e.
+                              // what lower_bound_idx finds at every launch (the lists never change); nullptr = search
 };
 
 // v from lane (lane ^ X) for X = 4 or 8 (ds_swizzle bit-mask mode: and 0x1F, or 0, xor X; no LDS memory touched)
@@ -677,7 +679,11 @@ __global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(con
   for (int i = 0; i < R / 2; ++i) x.v[i] = have ? xp[(i ^ rot) * G + j] : make_double2(0.0, 0.0);
   LossDesc segloss = LossDesc{0, 1.0, 0.0, 0.0};
   if constexpr (loss_mode(LOSS) != 2) segloss = load_loss(a.losses, (a.loss_by_segment && have) ? gseg : 0);
-  int64_t pos = have ? lower_bound_idx<G>(a.idx, beg, end, (int64_t)tb * TILE) : 0;
+  int64_t pos = 0; // first entry of the super-tile: from the start table where the side has one (L2), else the search
+  if (have) {
+    if (L2 && a.suppos) pos = beg + a.suppos[seg * (int64_t)a.nsup + sup];
+    else pos = lower_bound_idx<G>(a.idx, beg, end, (int64_t)tb * TILE);
+  }
   double J;
   tiled_pass<G, R, NW, TILE, LOSS, GRAD, L2, ROT>(a, lds, x, g, J, have, pos, end, tb, te, segloss, lane, j, rot);
   if (have) {
