@@ -90,7 +90,15 @@ typedef enum glrm_reg_kind {
   GLRM_REG_ONE = 2,             /* OneReg(scale)           :79-88   */
   GLRM_REG_NONNEG = 3,          /* NonNegConstraint        :101-114 */
   GLRM_REG_UNIT_ONE_SPARSE = 4, /* UnitOneSparseConstraint :295-318 */
-  GLRM_REG_KIND_COUNT = 5
+  GLRM_REG_KIND_COUNT = 5,      /* the kinds the CPU oracle restates (oracle/glrm_oracle.c validates against this bound) */
+  /* vector regularizers: k-vectors only (every rx, ry of a scalar-loss column; also as the base of lastentry1 / lastentry_unpenalized).
+   * On the k x d block of a multi-dimensional column, or under OrdinalReg / MNLOrdinalReg, they are GLRM_ERR_UNSUPPORTED. */
+  GLRM_REG_QUAD_CONSTRAINT = 5, /* QuadConstraint(max_2norm)  :68-76    scale = max_2norm (> 0, finite) */
+  GLRM_REG_NONNEG_ONE = 6,      /* NonNegOneReg(scale)        :118-138  prox ignores scale, like the reference */
+  GLRM_REG_ONE_SPARSE = 7,      /* OneSparseConstraint        :235-255  scale unused (1.0) */
+  GLRM_REG_K_SPARSE = 8,        /* KSparseConstraint(r)       :258-291  scale = r, integral, 1 <= r <= length the base sees; ties in |u| keep the lower index */
+  GLRM_REG_SIMPLEX = 9,         /* SimplexConstraint          :323-348  scale unused (1.0) */
+  GLRM_REG_KIND_END = 10        /* the engine accepts kinds in [0, GLRM_REG_KIND_END) */
 } glrm_reg_kind;
 
 #define GLRM_MAX_EMBEDDING_DIM 32

@@ -4,6 +4,7 @@
 import LowRankModels: Loss, Regularizer, QuadLoss, L1Loss, HuberLoss, QuantileLoss, PeriodicLoss, PoissonLoss, OrdinalHingeLoss,
                       LogisticLoss, WeightedHingeLoss, MultinomialLoss, OvALoss, BvSLoss, OrdisticLoss, MultinomialOrdinalLoss,
                       embedding_dim, ZeroReg, QuadReg, OneReg, NonNegConstraint, UnitOneSparseConstraint,
+                      QuadConstraint, NonNegOneReg, OneSparseConstraint, KSparseConstraint, SimplexConstraint,
                       lastentry1, lastentry_unpenalized, OrdinalReg, MNLOrdinalReg
 
 closs(l::QuadLoss) = CLoss(0, 0, l.scale, 0, 0)                               # src/losses.jl:138-148
@@ -30,7 +31,13 @@ creg(r::QuadReg) = CReg(1, 0, r.scale)                                        # 
 creg(r::OneReg) = CReg(2, 0, r.scale)                                         # :79-88
 creg(r::NonNegConstraint) = CReg(3, 0, 1.0)                                   # :101-114
 creg(r::UnitOneSparseConstraint) = CReg(4, 0, 1.0)                            # :295-318
-# wrappers around one of the five base regularizers (src/regularizers.jl:163-189,356-411)
+# the vector regularizers (GLRM_REG_QUAD_CONSTRAINT .. GLRM_REG_SIMPLEX): k-vectors only, see vector_ok below
+creg(r::QuadConstraint) = CReg(5, 0, r.max_2norm)                             # :68-76
+creg(r::NonNegOneReg) = CReg(6, 0, r.scale)                                   # :118-138
+creg(r::OneSparseConstraint) = CReg(7, 0, 1.0)                                # :235-255
+creg(r::KSparseConstraint) = CReg(8, 0, Float64(r.k))                         # :258-291
+creg(r::SimplexConstraint) = CReg(9, 0, 1.0)                                  # :323-348
+# wrappers around one of the base regularizers (src/regularizers.jl:163-189,356-411)
 wrapped(r, flag) = (b = creg(r.r); (b === nothing || b.wrap != 0) ? nothing : CReg(b.kind, flag, b.scale))
 creg(r::lastentry1) = wrapped(r, 1)
 creg(r::lastentry_unpenalized) = wrapped(r, 2)
@@ -45,10 +52,23 @@ collapse(v) = all(==(v[1]), v) ? v[1:1] : v          # one descriptor when every
 fallback(glrm, p; kw...) = fit!(glrm, ProxGradParams(p.stepsize; max_iter=p.max_iter, inner_iter_X=p.inner_iter_X, inner_iter_Y=p.inner_iter_Y,
                                              abs_tol=p.abs_tol, rel_tol=p.rel_tol, min_stepsize=p.min_stepsize); kw...)
 
+# A vector regularizer the engine takes: not under OrdinalReg / MNLOrdinalReg, not on the block of a multi-dimensional column (dim > 1),
+# KSparseConstraint(r) with 1 <= r <= the length its base sees, QuadConstraint with a finite max_2norm > 0.  Where this fails the
+# reference throws inside fit! (sort / partialsortperm on a matrix, BoundsError) or divides by zero: it is left to do so.
+function vector_ok(c, k, dim)
+    c.kind < 5 && return true
+    (c.wrap & 12 != 0 || dim > 1) && return false
+    len = c.wrap != 0 ? k - 1 : k
+    c.kind == 8 && return 1 <= c.scale <= len
+    c.kind == 5 && return 0 < c.scale < Inf
+    true
+end
+
 # descriptors of a model, or nothing if some loss / regularizer type is outside include/glrm_hip.h
 function descriptors(glrm::GLRM)
     cl = map(closs, glrm.losses); crx = map(creg, glrm.rx); cry = map(creg, glrm.ry)
     (any(isnothing, cl) || any(isnothing, crx) || any(isnothing, cry)) && return nothing
+    (all(c -> vector_ok(c, glrm.k, 1), crx) && all(j -> vector_ok(cry[j], glrm.k, max(cl[j].dim, 1)), eachindex(cry))) || return nothing
     n = size(glrm.A, 2)
     general = embedding_dim(glrm.losses) != n || any(c -> c.wrap != 0, crx) || any(c -> c.wrap != 0, cry)
     (general && glrm.k > 64) && return nothing

@@ -19,8 +19,9 @@ from .losses import (BvSLoss, HingeLoss, HuberLoss, L1Loss, LogisticLoss, Loss, 
                      OrdinalHingeLoss, OrdisticLoss, OvALoss, PeriodicLoss, PoissonLoss, QuadLoss, QuantileLoss,
                      WeightedHingeLoss, embedding_dim, evaluate, get_yidxs, grad)
 from .params import AbstractParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams
-from .regularizers import (MNLOrdinalReg, NonNegConstraint, OneReg, OrdinalReg, QuadReg, Regularizer, UnitOneSparseConstraint,
-                           ZeroReg, lastentry1, lastentry_unpenalized, prox)
+from .regularizers import (KSparseConstraint, MNLOrdinalReg, NonNegConstraint, NonNegOneReg, OneReg, OneSparseConstraint, OrdinalReg,
+                           QuadConstraint, QuadReg, Regularizer, SimplexConstraint, UnitOneSparseConstraint, ZeroReg, lastentry1,
+                           lastentry_unpenalized, prox)
 
 fit_inplace = fit_b  # Julia's `fit!`
 

@@ -49,6 +49,7 @@ struct CachedArgs {
   const int32_t* seglist; // nullable: the launch covers the local rows seglist[0..nseg) -- the rows short enough for the cached
                           // sweep when the shard also holds longer ones -- restricted to [seg_lo, seg_hi) (glrm_hip_step_x_range)
   int64_t seg_lo, seg_hi;
+  int vecreg;            // 1: some rx names a vector regularizer -- the VR = true kernels
 };
 
 __device__ __forceinline__ int64_t cached_segment(const CachedArgs& a, int64_t slot) { // -1: nothing to do for this workgroup
@@ -132,7 +133,7 @@ __device__ __forceinline__ double cached_pass(const CachedArgs& a, const char* _
 }
 
 // One wave (= one workgroup) per row.  Dynamic LDS: [cap vectors][cap values][cap indices].
-template <int G, int R, int LOSS>
+template <int G, int R, int LOSS, bool VR = false>
 __global__ void __launch_bounds__(64) cached_sweep_kernel(const CachedArgs a) {
   constexpr int KP = G * R, KPB = KP * 8, CPV = KPB / 16, VPI = 64 / CPV; // 16-byte chunks per vector, vectors per DMA instruction
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -189,14 +190,14 @@ __global__ void __launch_bounds__(64) cached_sweep_kernel(const CachedArgs a) {
       xn.v[i].x = x.v[i].x + g.v[i].x * (-s);
       xn.v[i].y = x.v[i].y + g.v[i].y * (-s);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     if (gi == 0) {
 #pragma unroll
       for (int i = 0; i < R / 2; ++i) ownp[i * G + j] = xn.v[i];
     }
     return;
   }
-  Jold += reg_eval<G, R>(rd, x, j, a.k);
+  Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
 
   // backtracking line search (proxgrad.jl:136-155); every trial reads the cached vectors
   double alpha = alpha0;
@@ -211,9 +212,9 @@ __global__ void __launch_bounds__(64) cached_sweep_kernel(const CachedArgs a) {
       xn.v[i].x = fma(-s, g.v[i].x, x.v[i].x);
       xn.v[i].y = fma(-s, g.v[i].y, x.v[i].y);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     double Jn = cached_pass<G, R, LOSS, false>(a, ybuf, lval, lidx, xn, dummy, len, gi, j, segloss);
-    Jn += reg_eval<G, R>(rd, xn, j, a.k);
+    Jn += reg_eval<G, R, VR>(rd, xn, j, a.k);
     ++ntrials;
     if (Jn < Jold) { // strict; false for NaN and for Inf < Inf
       x = xn;
@@ -338,7 +339,7 @@ __device__ __forceinline__ double row_combine(double J, Vec<G, R>& g, double* re
 }
 
 // WAVES waves (= one workgroup) per row; wave w holds the observations (t * WAVES + w) * (64 / G) + group, t = 0 .. MAXT - 1.
-template <int G, int R, int LOSS, int MAXT, int WAVES>
+template <int G, int R, int LOSS, int MAXT, int WAVES, bool VR = false>
 __global__ void __launch_bounds__(WAVES * 64) regcached_sweep_kernel(const CachedArgs a) {
   constexpr int KP = G * R, NG = (64 / G) * WAVES;
   __shared__ __attribute__((aligned(16))) double red[WAVES == 1 ? 2 : WAVES * (KP + 2)];
@@ -389,14 +390,14 @@ __global__ void __launch_bounds__(WAVES * 64) regcached_sweep_kernel(const Cache
       xn.v[i].x = x.v[i].x + g.v[i].x * (-s);
       xn.v[i].y = x.v[i].y + g.v[i].y * (-s);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     if (gi == 0) {
 #pragma unroll
       for (int i = 0; i < R / 2; ++i) ownp[i * G + j] = xn.v[i];
     }
     return;
   }
-  Jold += reg_eval<G, R>(rd, x, j, a.k);
+  Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
   double alpha = a.alpha[seg];
   const double l = (double)len + 1.0;
   int ntrials = 0;
@@ -409,10 +410,10 @@ __global__ void __launch_bounds__(WAVES * 64) regcached_sweep_kernel(const Cache
       xn.v[i].x = fma(-s, g.v[i].x, x.v[i].x);
       xn.v[i].y = fma(-s, g.v[i].y, x.v[i].y);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     double Jn = reg_pass<G, R, LOSS, MAXT, false, WAVES>(a, y, av, cc, xn, dummy, len, gi, segloss);
     Jn = row_combine<G, R, WAVES, false>(Jn, dummy, red, wave, lane);
-    Jn += reg_eval<G, R>(rd, xn, j, a.k);
+    Jn += reg_eval<G, R, VR>(rd, xn, j, a.k);
     ++ntrials;
     if (Jn < Jold) {
       x = xn;
@@ -446,7 +447,7 @@ __global__ void __launch_bounds__(WAVES * 64) regcached_sweep_kernel(const Cache
 // row are scalar loads issued one row ahead, its list is requested right behind the current row's gathers (3 * PF dwords per lane, the
 // only extra registers) and reaches the lanes through LDS after the current row's passes: the chain per row is ONE round trip, the
 // gathers.  Which lane group adds which observation, and in which order, is unchanged: same bits as the kernel above.
-template <int G, int R, int LOSS, int MAXT>
+template <int G, int R, int LOSS, int MAXT, bool VR = false>
 __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedArgs a) {
   constexpr int WAVES = 2, KP = G * R, NG = (64 / G) * WAVES, MAXLEN = MAXT * NG, PF = (MAXLEN + 127) / 128;
   // ONE shared array (a second __shared__ object makes hipcc drain the load queue before every LDS read, cdna_hip_programming.md):
@@ -542,13 +543,13 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
           xn.v[i].x = x.v[i].x + g.v[i].x * (-s);
           xn.v[i].y = x.v[i].y + g.v[i].y * (-s);
         }
-        reg_prox<G, R>(rd, xn, s, j, a.k);
+        reg_prox<G, R, VR>(rd, xn, s, j, a.k);
         if (gi == 0) {
 #pragma unroll
           for (int i = 0; i < R / 2; ++i) ownp[i * G + j] = xn.v[i];
         }
       } else {
-        Jold += reg_eval<G, R>(rd, x, j, a.k);
+        Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
         double alpha = a.alpha[seg];
         const double l = (double)len + 1.0;
         int ntrials = 0;
@@ -561,10 +562,10 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
             xn.v[i].x = fma(-s, g.v[i].x, x.v[i].x);
             xn.v[i].y = fma(-s, g.v[i].y, x.v[i].y);
           }
-          reg_prox<G, R>(rd, xn, s, j, a.k);
+          reg_prox<G, R, VR>(rd, xn, s, j, a.k);
           double Jn = reg_pass<G, R, LOSS, MAXT, false, WAVES>(a, y, av, cc, xn, dummy, len, gi, segloss);
           Jn = row_combine<G, R, WAVES, false>(Jn, dummy, red, wave, lane);
-          Jn += reg_eval<G, R>(rd, xn, j, a.k);
+          Jn += reg_eval<G, R, VR>(rd, xn, j, a.k);
           ++ntrials;
           if (Jn < Jold) {
             x = xn;
@@ -600,7 +601,7 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
   }
 }
 
-template <int G, int R, int LOSS>
+template <int G, int R, int LOSS, bool VR>
 int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.cap = trips of one wave the longest row needs (64 / G observations each)
   // Two waves per row (each holds every other trip's vectors: half the registers, two waves per SIMD, so one wave's loads overlap the
   // other's arithmetic).  Measured at C4, X half-step: one wave per row 101.5 ms, two 85.4 ms, four 130.3 ms (phase-aligned passes 120.6).
@@ -610,12 +611,12 @@ int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.
   if (waves == 2 && env_int("GLRM_HIP_CACHED_PERSIST", 1)) { // the persistent form of the two-wave kernel (same bits)
     // resident grid per handle (its device's CU count, its loss variant's occupancy, the fill percentage at its first sweep)
     const bool small = (a.cap + 1) / 2 <= 4;
-    int& cache = h->cached_grid[small ? 1 : 0];
+    int& cache = h->cached_grid[(small ? 1 : 0) + (VR ? 2 : 0)];
     int nb = cache;
     if (nb == 0) {
       int per_cu = 0;
       hipDeviceProp_t prop;
-      const void* k = small ? (const void*)regcached_persist_kernel<G, R, LOSS, 4> : (const void*)regcached_persist_kernel<G, R, LOSS, 7>;
+      const void* k = small ? (const void*)regcached_persist_kernel<G, R, LOSS, 4, VR> : (const void*)regcached_persist_kernel<G, R, LOSS, 7, VR>;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 128, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
       int cus = 256;
       if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
@@ -624,29 +625,29 @@ int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.
       cache = nb;
     }
     const unsigned grid = (unsigned)std::min<int64_t>(a.nseg, nb);
-    if (small) hipLaunchKernelGGL((regcached_persist_kernel<G, R, LOSS, 4>), dim3(grid), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((regcached_persist_kernel<G, R, LOSS, 7>), dim3(grid), dim3(128), 0, st, a);
+    if (small) hipLaunchKernelGGL((regcached_persist_kernel<G, R, LOSS, 4, VR>), dim3(grid), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((regcached_persist_kernel<G, R, LOSS, 7, VR>), dim3(grid), dim3(128), 0, st, a);
     return GLRM_OK;
   }
   if (waves == 4 && (a.cap + 3) / 4 <= 4) {
-    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 4, 4>), dim3((unsigned)a.nseg), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 4, 4, VR>), dim3((unsigned)a.nseg), dim3(256), 0, st, a);
   } else if (waves == 1) {
-    if (a.cap <= 7) hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 7, 1>), dim3((unsigned)a.nseg), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 13, 1>), dim3((unsigned)a.nseg), dim3(64), 0, st, a);
+    if (a.cap <= 7) hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 7, 1, VR>), dim3((unsigned)a.nseg), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 13, 1, VR>), dim3((unsigned)a.nseg), dim3(64), 0, st, a);
   } else if ((a.cap + 1) / 2 <= 4) {
-    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 4, 2>), dim3((unsigned)a.nseg), dim3(128), 0, st, a);
+    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 4, 2, VR>), dim3((unsigned)a.nseg), dim3(128), 0, st, a);
   } else {
-    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 7, 2>), dim3((unsigned)a.nseg), dim3(128), 0, st, a);
+    hipLaunchKernelGGL((regcached_sweep_kernel<G, R, LOSS, 7, 2, VR>), dim3((unsigned)a.nseg), dim3(128), 0, st, a);
   }
   return GLRM_OK;
 }
 
-template <int G, int R, int LOSS>
+template <int G, int R, int LOSS, bool VR>
 int launch_inst(const CachedArgs& a, hipStream_t st) {
   const int lds = a.cap * (G * R * 8 + 12);
   if (lds > 65536)
-    HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(cached_sweep_kernel<G, R, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL((cached_sweep_kernel<G, R, LOSS>), dim3((unsigned)a.nseg), dim3(64), lds, st, a);
+    HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(cached_sweep_kernel<G, R, LOSS, VR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL((cached_sweep_kernel<G, R, LOSS, VR>), dim3((unsigned)a.nseg), dim3(64), lds, st, a);
   return GLRM_OK;
 }
 
@@ -713,7 +714,8 @@ int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     auto by_loss = [&](auto LOSS) {
       constexpr int L = decltype(LOSS)::value;
-      return h->cached_row == 2 ? launch_reg_inst<G, R, L>(a, st, h) : launch_inst<G, R, L>(a, st);
+      if (a.vecreg) return h->cached_row == 2 ? launch_reg_inst<G, R, L, true>(a, st, h) : launch_inst<G, R, L, true>(a, st);
+      return h->cached_row == 2 ? launch_reg_inst<G, R, L, false>(a, st, h) : launch_inst<G, R, L, false>(a, st);
     };
     return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
   };

@@ -209,9 +209,160 @@ struct Vec {
 template <int G, int R>
 __device__ __forceinline__ int comp_index(int i, int j, int h) { return i * 2 * G + 2 * j + h; }
 
-// prox(r, u, alpha) on the distributed vector (src/regularizers.jl:34,56,83-86,93,103,297);
-// components >= k (padding) are forced to 0.
+// One step of an ordered selection on the distributed vector (K-sparse, simplex): among the components c < k
+// that are not taken yet, the one with the largest key -- |u_c| (ABS) or u_c -- and the lowest index among equal keys.  Its owner
+// marks it taken (bit 2 i + h of the lane's mask); every lane of the group returns the same key.  Padding never takes part.  The
+// merge is the argmax butterfly of UnitOneSparse: DPP inside the group only, so groups of a wave may take different trip counts.
+constexpr int NO_COMP = 0x7fffffff;
+template <int G, int R, bool ABS>
+__device__ __forceinline__ double select_next(const Vec<G, R>& u, unsigned& taken, int j, int k) {
+  double best = -__builtin_inf();
+  int bi = NO_COMP;
+#pragma unroll
+  for (int i = 0; i < R / 2; ++i) {
+    const int c0 = comp_index<G, R>(i, j, 0);
+    double a = ABS ? fabs(u.v[i].x) : u.v[i].x, b = ABS ? fabs(u.v[i].y) : u.v[i].y;
+    a = a == a ? a : -__builtin_inf(); // a NaN entry (non-finite data; the trial is rejected anyway) orders last: every comparison below
+    b = b == b ? b : -__builtin_inf(); // then has one answer, the lanes of a group agree on (key, index) and leave the loops together
+    if (c0 < k && !((taken >> (2 * i)) & 1u) && (a > best || bi == NO_COMP)) { best = a; bi = c0; }
+    if (c0 + 1 < k && !((taken >> (2 * i + 1)) & 1u) && (b > best || bi == NO_COMP)) { best = b; bi = c0 + 1; }
+  }
+  auto merge = [&](double ob, int oi) {
+    if (oi != NO_COMP && (bi == NO_COMP || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+  };
+  if constexpr (G >= 2) merge(dpp_f64<DPP_XOR1>(best), dpp_i32<DPP_XOR1>(bi));
+  if constexpr (G >= 4) merge(dpp_f64<DPP_XOR2>(best), dpp_i32<DPP_XOR2>(bi));
+  if constexpr (G >= 8) merge(dpp_f64<DPP_HALF_MIRROR>(best), dpp_i32<DPP_HALF_MIRROR>(bi));
+  if constexpr (G >= 16) merge(dpp_f64<DPP_MIRROR>(best), dpp_i32<DPP_MIRROR>(bi));
+#pragma unroll
+  for (int i = 0; i < R / 2; ++i) {
+    const int c0 = comp_index<G, R>(i, j, 0);
+    if (c0 == bi) taken |= 1u << (2 * i);
+    if (c0 + 1 == bi) taken |= 1u << (2 * i + 1);
+  }
+  return best;
+}
+
+// The vector regularizers (kinds >= GLRM_REG_QUAD_CONSTRAINT).  The sweep kernels' register budgets are tuned, and the selection code below
+// needs more registers than the five element-wise kinds: it is compiled into the VR = true instantiation of a kernel only (reg_prox /
+// reg_eval below), which a half-step launches when a descriptor of its side names one of these kinds.  Both instantiations run the same
+// expressions for the other kinds, so which one a shard launches does not show in the bits.  DESIGN.md section 4.11 has the resource table.
+// prox leaves the padding to the caller, which zeroes it.
 template <int G, int R>
+__device__ __forceinline__ Vec<G, R> reg_prox_vector(int kind, double scale, Vec<G, R> u, double alpha, int j, int k) {
+  switch (kind) {
+    case GLRM_REG_QUAD_CONSTRAINT: { // (c / norm(u)) u: onto the sphere, always; the zero vector becomes NaN and the trial is rejected
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        s = fma(u.v[i].x, u.v[i].x, s);
+        s = fma(u.v[i].y, u.v[i].y, s);
+      }
+      const double f = scale / sqrt(group_sum<G>(s));
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        u.v[i].x = f * u.v[i].x;
+        u.v[i].y = f * u.v[i].y;
+      }
+      break;
+    }
+    case GLRM_REG_NONNEG_ONE: { // max(u - alpha, 0): the reference leaves scale out
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        const double a = u.v[i].x - alpha, b = u.v[i].y - alpha;
+        u.v[i].x = a > 0 ? a : 0.0;
+        u.v[i].y = b > 0 ? b : 0.0;
+      }
+      break;
+    }
+    case GLRM_REG_K_SPARSE: { // the r entries of largest |u| stay (ties: lower index)
+      const int nkeep = scale < (double)k ? (int)scale : k;
+      unsigned taken = 0;
+      for (int p = 0; p < nkeep; ++p) (void)select_next<G, R, true>(u, taken, j, k);
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        if (!((taken >> (2 * i)) & 1u)) u.v[i].x = 0.0;
+        if (!((taken >> (2 * i + 1)) & 1u)) u.v[i].y = 0.0;
+      }
+      break;
+    }
+    case GLRM_REG_SIMPLEX: { // Chen & Ye: y = sort(u, rev), ysum = cumsum(y) one term per step, the same on every lane of the group
+      unsigned taken = 0;
+      double ysum = 0.0, t = 0.0;
+      bool found = false;
+      for (int p = 0; p < k && !found; ++p) {
+        const double y = select_next<G, R, false>(u, taken, j, k); // y[p + 1] of the reference
+        if (p >= 1) {
+          const double cand = (ysum - 1) / p;
+          if (cand >= y) { t = cand; found = true; }
+        }
+        ysum += y;
+      }
+      if (!found) t = (ysum - 1) / k;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        const double a = u.v[i].x - t, b = u.v[i].y - t;
+        u.v[i].x = a > 0 ? a : 0.0;
+        u.v[i].y = b > 0 ? b : 0.0;
+      }
+      break;
+    }
+    case GLRM_REG_ONE_SPARSE: { // u[argmax u] e_{argmax u}: the first largest SIGNED entry stays
+      unsigned taken = 0;
+      if (k > 0) (void)select_next<G, R, false>(u, taken, j, k);
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        if (!((taken >> (2 * i)) & 1u)) u.v[i].x = 0.0;
+        if (!((taken >> (2 * i + 1)) & 1u)) u.v[i].y = 0.0;
+      }
+      break;
+    }
+    default:
+      break;
+  }
+  return u;
+}
+
+template <int G, int R>
+__device__ __forceinline__ double reg_eval_vector(int kind, double scale, Vec<G, R> x, int j, int k) {
+  switch (kind) {
+    case GLRM_REG_QUAD_CONSTRAINT: { // norm(u) > c + TOL
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        s = fma(x.v[i].x, x.v[i].x, s);
+        s = fma(x.v[i].y, x.v[i].y, s);
+      }
+      return sqrt(group_sum<G>(s)) > scale + 1e-12 ? __builtin_inf() : 0.0;
+    }
+    case GLRM_REG_NONNEG_ONE:
+    case GLRM_REG_SIMPLEX: { // any entry < 0: Inf; else scale * sum(a) / abs(sum(a) - 1) > TOL (the padding is 0)
+      double s = 0.0, neg = 0.0;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) {
+        s += x.v[i].x + x.v[i].y;
+        neg += (x.v[i].x < 0 ? 1.0 : 0.0) + (x.v[i].y < 0 ? 1.0 : 0.0);
+      }
+      s = group_sum<G>(s);
+      if (group_sum<G>(neg) > 0) return __builtin_inf();
+      if (kind == GLRM_REG_NONNEG_ONE) return scale * s;
+      return fabs(s - 1) > 1e-12 ? __builtin_inf() : 0.0;
+    }
+    case GLRM_REG_ONE_SPARSE:
+    case GLRM_REG_K_SPARSE: { // more than 1 / r nonzero entries (the padding is 0)
+      double nz = 0.0;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) nz += (x.v[i].x != 0 ? 1.0 : 0.0) + (x.v[i].y != 0 ? 1.0 : 0.0);
+      return group_sum<G>(nz) > (kind == GLRM_REG_ONE_SPARSE ? 1.0 : scale) ? __builtin_inf() : 0.0;
+    }
+    default:
+      return 0.0;
+  }
+}
+
+// prox(r, u, alpha) on the distributed vector (src/regularizers.jl:34,56,72,83-86,93,103,122,237,277-283,297,325-337);
+// components >= k (padding) are forced to 0.
+template <int G, int R, bool VR = false>
 __device__ __forceinline__ void reg_prox(const RegDesc& r, Vec<G, R>& u, double alpha, int j, int k) {
   switch (r.kind) {
     case GLRM_REG_QUAD: {
@@ -264,7 +415,10 @@ __device__ __forceinline__ void reg_prox(const RegDesc& r, Vec<G, R>& u, double 
       }
       break;
     }
-    default: // GLRM_REG_ZERO
+    default: // GLRM_REG_ZERO, or a vector kind
+      if constexpr (VR) {
+        if (r.kind >= GLRM_REG_QUAD_CONSTRAINT) u = reg_prox_vector<G, R>(r.kind, r.scale, u, alpha, j, k);
+      }
       break;
   }
 #pragma unroll
@@ -276,8 +430,8 @@ __device__ __forceinline__ void reg_prox(const RegDesc& r, Vec<G, R>& u, double 
 }
 
 // evaluate(r, x) on the distributed vector; every lane of the group returns the same value
-// (src/regularizers.jl:58,88,95,103-112,300-316).
-template <int G, int R>
+// (src/regularizers.jl:58,74,88,95,103-112,129-136,239-253,261-276,300-316,338-346).
+template <int G, int R, bool VR = false>
 __device__ __forceinline__ double reg_eval(const RegDesc& r, const Vec<G, R>& x, int j, int k) {
   switch (r.kind) {
     case GLRM_REG_QUAD: {
@@ -313,7 +467,10 @@ __device__ __forceinline__ double reg_eval(const RegDesc& r, const Vec<G, R>& x,
       code = group_sum<G>(code);
       return (code >= 4096.0 || code > 1.0) ? __builtin_inf() : 0.0;
     }
-    default:
+    default: // GLRM_REG_ZERO, or a vector kind
+      if constexpr (VR) {
+        if (r.kind >= GLRM_REG_QUAD_CONSTRAINT) return reg_eval_vector<G, R>(r.kind, r.scale, x, j, k);
+      }
       return 0.0;
   }
 }

@@ -154,7 +154,7 @@ struct glrm_handle {
   int32_t *blk_perm_c = nullptr, *blk_long_c = nullptr;
   int64_t blk_nshort_c = 0, blk_nlong_c = 0, blk_long_from = 0;
   int64_t blocked_cap[2][2] = {{0, 0}, {0, 0}}; // phase-aligned passes: segments per launch slice, [row / column view][gradient / trial instantiation]
-  int cached_grid[2] = {0, 0};        // persistent cached row sweep: resident workgroups, MAXT = 7 / 4 instantiation
+  int cached_grid[4] = {0, 0, 0, 0};      // persistent cached row sweep: resident workgroups of the MAXT = 7 / 4 instantiation; [2], [3]: of their VR = true twins
   glrm_signature sig_local{}, sig{};  // this shard's contribution / the whole problem's
   hipStream_t side_stream = nullptr;  // the launches of the minority classes run beside the main launch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -179,6 +179,7 @@ struct glrm_handle {
   int wr_opt = 0, wc_opt = 0;
   std::vector<glrm_loss> losses_h;
   std::vector<glrm_reg> rx_h, ry_h;
+  bool vecreg_x = false, vecreg_y = false; // some rx / ry of this handle is a vector regularizer (kind >= GLRM_REG_QUAD_CONSTRAINT): VR kernels
   struct Ev { hipEvent_t a, b; int which; };
   std::vector<Ev> pending, pool;
   int64_t launches_x = 0, launches_y = 0;
@@ -233,6 +234,7 @@ int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_
 // reference-order validation sweeps (glrm_reforder.hip; glrm_options.sum_order = 1)
 // test hooks (csrc/glrm_testhooks.hip): constant in the product library, environment-driven in the test build (-DGLRM_HIP_TESTING)
 int glrm_test_fail_finalize();                        // 1 = glrm_hip_finalize fails half way (the set-up-failed latch cannot be reached otherwise)
+int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry); // set_regularizers' refusals, no side effect
 int glrm_setup_reforder(glrm_handle* h);               // finalize: refuses what the mode does not cover
 int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
 int glrm_reforder_sum(glrm_handle* h, const void* dvec, int64_t n, double* out); // Julia's pairwise sum(::Vector{Float64})

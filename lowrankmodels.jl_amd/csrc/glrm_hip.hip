@@ -60,6 +60,7 @@ struct SweepArgs {
   const int32_t* seglist; // nullable: the launch covers the local segments seglist[0..nseg) instead of 0..nseg -- the segments of ONE
                           // wave class when the shard holds several (glrm_handle::seglist_r) -- restricted to [seg_lo, seg_hi)
   int64_t seg_lo, seg_hi; // (glrm_hip_step_x_range on such a shard; otherwise [0, local segments))
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels (csrc/glrm_device.hpp)
 };
 
 
@@ -249,7 +250,7 @@ __device__ __forceinline__ double block_combine(double J, Vec<G, R>& g, double* 
 
 // EVAL = true is the one-pass objective evaluation (obj[seg] = sum of losses); it is a separate
 // instantiation so that profiles list it apart from the two-pass half-step sweeps.
-template <int G, int R, int WAVES, int LOSS, int U, bool EVAL>
+template <int G, int R, int WAVES, int LOSS, int U, bool EVAL, bool VR = false>
 __global__ void __launch_bounds__(WAVES == 1 ? 256 : WAVES * 64) sweep_kernel(const SweepArgs a) {
   constexpr int KP = G * R, NG = 64 / G;
   __shared__ __attribute__((aligned(16))) double red[WAVES == 1 ? 2 : WAVES * (KP + 2)];
@@ -291,14 +292,14 @@ __global__ void __launch_bounds__(WAVES == 1 ? 256 : WAVES * 64) sweep_kernel(co
       xn.v[i].x = x.v[i].x + g.v[i].x * (-s);
       xn.v[i].y = x.v[i].y + g.v[i].y * (-s);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     if (wave == (WAVES == 1 ? wave : 0) && gi == 0) {
 #pragma unroll
       for (int i = 0; i < R / 2; ++i) ownp[i * G + j] = xn.v[i];
     }
     return;
   }
-  Jold += reg_eval<G, R>(rd, x, j, a.k);
+  Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
 
   // backtracking line search (proxgrad.jl:136-155 / :179-200); g is NOT recomputed between trials
   double alpha = a.alpha[seg];
@@ -313,10 +314,10 @@ __global__ void __launch_bounds__(WAVES == 1 ? 256 : WAVES * 64) sweep_kernel(co
       xn.v[i].x = fma(-s, g.v[i].x, x.v[i].x);
       xn.v[i].y = fma(-s, g.v[i].y, x.v[i].y);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k); // prox!(r, newx, stepsize)
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k); // prox!(r, newx, stepsize)
     double Jn = sweep_pass<G, R, WAVES, LOSS, U, false>(a, xn, dummy, beg, len, gg, j, segloss);
     Jn = block_combine<G, R, WAVES, false>(Jn, dummy, red, wave, lane);
-    Jn += reg_eval<G, R>(rd, xn, j, a.k);
+    Jn += reg_eval<G, R, VR>(rd, xn, j, a.k);
     ++ntrials;
     if (Jn < Jold) { // strict; false for NaN and for Inf < Inf
       x = xn;
@@ -378,6 +379,33 @@ __global__ void penalty_kernel(const double* fac, int ld, int k, int64_t offset,
         if (x[c] == 1) ++ones; else ++other;
       }
       if (other > 0 || ones > 1) v = __builtin_inf();
+      break;
+    }
+    case GLRM_REG_QUAD_CONSTRAINT: {
+      double acc = 0.0;
+      for (int c = 0; c < k; ++c) acc += x[c] * x[c];
+      if (sqrt(acc) > r.scale + 1e-12) v = __builtin_inf();
+      break;
+    }
+    case GLRM_REG_NONNEG_ONE:
+    case GLRM_REG_SIMPLEX: {
+      double acc = 0.0;
+      bool neg = false;
+      for (int c = 0; c < k; ++c) {
+        acc += x[c];
+        neg = neg || x[c] < 0;
+      }
+      if (neg) v = __builtin_inf();
+      else if (r.kind == GLRM_REG_NONNEG_ONE) v = r.scale * acc;
+      else if (fabs(acc - 1) > 1e-12) v = __builtin_inf();
+      break;
+    }
+    case GLRM_REG_ONE_SPARSE:
+    case GLRM_REG_K_SPARSE: {
+      int nz = 0;
+      for (int c = 0; c < k; ++c)
+        if (x[c] != 0) ++nz;
+      if ((double)nz > (r.kind == GLRM_REG_ONE_SPARSE ? 1.0 : r.scale)) v = __builtin_inf();
       break;
     }
     default:
@@ -536,6 +564,52 @@ static bool wrap_ok(int w) {
   return w == 0 || w == GLRM_WRAP_LASTENTRY1 || w == GLRM_WRAP_LASTENTRY_UNPENALIZED || w == GLRM_WRAP_ORDINAL || w == GLRM_WRAP_MNL_ORDINAL;
 }
 
+static const char* reg_kind_name(int kind) {
+  static const char* const names[GLRM_REG_KIND_END] = {"ZeroReg", "QuadReg", "OneReg", "NonNegConstraint", "UnitOneSparseConstraint",
+                                                      "QuadConstraint", "NonNegOneReg", "OneSparseConstraint", "KSparseConstraint", "SimplexConstraint"};
+  return kind >= 0 && kind < GLRM_REG_KIND_END ? names[kind] : "?";
+}
+
+// One side's regularizer descriptors (create and set_regularizers).  losses != NULL: the side is ry, descriptor i belongs to column
+// col_begin + i (one descriptor: to all ncols local columns).  The kinds >= GLRM_REG_QUAD_CONSTRAINT are VECTOR regularizers: the reference's
+// sort / partialsortperm / norm act on a vector, so the block of a multi-dimensional column and the base of OrdinalReg / MNLOrdinalReg are
+// refused; KSparseConstraint(r) with r outside 1 .. length is the reference's BoundsError inside the fit, refused here.
+static int check_regs(const char* side, const glrm_reg* r, int64_t cnt, int k, const glrm_loss* losses, int64_t n_losses, int64_t col_begin,
+                      int64_t ncols) {
+  for (int64_t i = 0; i < cnt; ++i) {
+    const int kind = r[i].kind, wrap = r[i].wrap;
+    if (kind < 0 || kind >= GLRM_REG_KIND_END) return fail(GLRM_ERR_UNSUPPORTED, "%s regularizer kind %d is not supported", side, kind);
+    if (!wrap_ok(wrap)) return fail(GLRM_ERR_INVALID, "glrm_reg.wrap must be 0 or one GLRM_WRAP_* flag");
+    if (kind < GLRM_REG_QUAD_CONSTRAINT) continue;
+    if (wrap & (GLRM_WRAP_ORDINAL | GLRM_WRAP_MNL_ORDINAL))
+      return fail(GLRM_ERR_UNSUPPORTED, "%s[%lld]: %s is a vector regularizer and cannot be the base of OrdinalReg / MNLOrdinalReg", side,
+                  (long long)i, reg_kind_name(kind));
+    if (losses) {
+      const int64_t f0 = cnt == 1 ? col_begin : col_begin + i, f1 = cnt == 1 ? col_begin + ncols : f0 + 1;
+      for (int64_t f = f0; f < f1; ++f) {
+        const glrm_loss& l = n_losses == 1 ? losses[0] : losses[f];
+        if (l.dim > 1)
+          return fail(GLRM_ERR_UNSUPPORTED, "%s: %s is a vector regularizer and cannot regularize the %d-column block of column %lld", side,
+                      reg_kind_name(kind), l.dim, (long long)f);
+        if (n_losses == 1) break;
+      }
+    }
+    const int len = wrap ? k - 1 : k; // what the base regularizer sees
+    if (kind == GLRM_REG_K_SPARSE && !(r[i].scale >= 1.0 && r[i].scale <= (double)len && r[i].scale == std::floor(r[i].scale)))
+      return fail(GLRM_ERR_INVALID, "%s[%lld]: KSparseConstraint keeps r = %g entries; r must be an integer in 1..%d", side, (long long)i,
+                  r[i].scale, len);
+    if (kind == GLRM_REG_QUAD_CONSTRAINT && !(r[i].scale > 0.0 && std::isfinite(r[i].scale)))
+      return fail(GLRM_ERR_INVALID, "%s[%lld]: QuadConstraint needs a finite max_2norm > 0 (got %g)", side, (long long)i, r[i].scale);
+  }
+  return GLRM_OK;
+}
+
+static bool any_vector_reg(const std::vector<glrm_reg>& r) {
+  for (const glrm_reg& x : r)
+    if (x.kind >= GLRM_REG_QUAD_CONSTRAINT) return true;
+  return false;
+}
+
 static int check_desc(const glrm_problem* p) {
   const int64_t ml = p->row_end - p->row_begin, nl = p->col_end - p->col_begin;
   if (!p->losses || !(p->n_losses == 1 || p->n_losses == p->n))
@@ -555,14 +629,8 @@ static int check_desc(const glrm_problem* p) {
         !(p->losses[i].p1 == GLRM_LOSS_LOGISTIC || p->losses[i].p1 == GLRM_LOSS_WEIGHTED_HINGE))
       return fail(GLRM_ERR_UNSUPPORTED, "bin_loss of OvALoss / BvSLoss must be LogisticLoss or HingeLoss");
   }
-  for (int64_t i = 0; i < p->n_rx; ++i) {
-    if (p->rx[i].kind < 0 || p->rx[i].kind >= GLRM_REG_KIND_COUNT) return fail(GLRM_ERR_UNSUPPORTED, "rx regularizer kind %d is not supported", p->rx[i].kind);
-    if (!wrap_ok(p->rx[i].wrap)) return fail(GLRM_ERR_INVALID, "glrm_reg.wrap must be 0 or one GLRM_WRAP_* flag");
-  }
-  for (int64_t i = 0; i < p->n_ry; ++i) {
-    if (p->ry[i].kind < 0 || p->ry[i].kind >= GLRM_REG_KIND_COUNT) return fail(GLRM_ERR_UNSUPPORTED, "ry regularizer kind %d is not supported", p->ry[i].kind);
-    if (!wrap_ok(p->ry[i].wrap)) return fail(GLRM_ERR_INVALID, "glrm_reg.wrap must be 0 or one GLRM_WRAP_* flag");
-  }
+  if (const int rc = check_regs("rx", p->rx, p->n_rx, p->k, nullptr, 0, 0, 0)) return rc;
+  if (const int rc = check_regs("ry", p->ry, p->n_ry, p->k, p->losses, p->n_losses, p->col_begin, nl)) return rc;
   return GLRM_OK;
 }
 
@@ -736,6 +804,8 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
   h->losses_h.assign(p->losses, p->losses + p->n_losses);
   h->rx_h.assign(p->rx, p->rx + p->n_rx);
   h->ry_h.assign(p->ry, p->ry + p->n_ry);
+  h->vecreg_x = any_vector_reg(h->rx_h);
+  h->vecreg_y = any_vector_reg(h->ry_h);
   if (o && (o->stream || o->caller_stream)) {
     h->stream = (hipStream_t)o->stream; // may be NULL = the legacy default stream (caller_stream)
   } else {
@@ -1000,26 +1070,39 @@ extern "C" int glrm_hip_reset_stepsizes(glrm_handle* h, double stepsize) {
   return GLRM_OK;
 }
 
-extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
+static bool any_wrapped(const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
+  for (int64_t i = 0; i < n_rx; ++i) if (rx[i].wrap != 0) return true;
+  for (int64_t i = 0; i < n_ry; ++i) if (ry[i].wrap != 0) return true;
+  return false;
+}
+
+// Everything glrm_hip_set_regularizers refuses, without touching the handle: the multi-device entry point checks every shard's slice
+// with it before it replaces any (csrc/glrm_multigpu.hip).
+int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
   if (!h || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
   if (n_rx != h->n_rx || n_ry != h->n_ry)
     return fail(GLRM_ERR_INVALID, "regularizer counts must match the handle (rx %lld, ry %lld)", (long long)h->n_rx, (long long)h->n_ry);
-  for (int64_t i = 0; i < n_rx; ++i)
-    if (rx[i].kind < 0 || rx[i].kind >= GLRM_REG_KIND_COUNT || !wrap_ok(rx[i].wrap)) return fail(GLRM_ERR_UNSUPPORTED, "rx regularizer kind %d is not supported", rx[i].kind);
-  for (int64_t i = 0; i < n_ry; ++i)
-    if (ry[i].kind < 0 || ry[i].kind >= GLRM_REG_KIND_COUNT || !wrap_ok(ry[i].wrap)) return fail(GLRM_ERR_UNSUPPORTED, "ry regularizer kind %d is not supported", ry[i].kind);
-  if (!h->multi) { // a handle created on the scalar fast paths moves to the general sweeps when a wrapper appears
-    bool wrapped = false;
-    for (int64_t i = 0; i < n_rx; ++i) wrapped |= rx[i].wrap != 0;
-    for (int64_t i = 0; i < n_ry; ++i) wrapped |= ry[i].wrap != 0;
-    if (wrapped) {
-      if (h->dense || h->kp > 64) return fail(GLRM_ERR_UNSUPPORTED, "wrapped regularizers need a sparse-view handle with k <= 64");
-      h->multi = true;
-    }
-  }
+  if (const int rc = check_regs("rx", rx, n_rx, h->k, nullptr, 0, 0, 0)) return rc;
+  if (const int rc = check_regs("ry", ry, n_ry, h->k, h->losses_h.data(), (int64_t)h->losses_h.size(), h->cb, h->nl)) return rc;
+  // a handle created on the scalar fast paths moves to the general sweeps when a wrapper appears
+  if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry) && (h->dense || h->kp > 64))
+    return fail(GLRM_ERR_UNSUPPORTED, "wrapped regularizers need a sparse-view handle with k <= 64");
+  return GLRM_OK;
+}
+
+extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
+  if (const int rc = glrm_check_regularizers(h, rx, n_rx, ry, n_ry)) return rc;
+  if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry)) h->multi = true; // checked above: this handle can run the general sweeps
   DeviceGuard dg(h->device);
   h->rx_h.assign(rx, rx + n_rx);
   h->ry_h.assign(ry, ry + n_ry);
+  const bool vx = any_vector_reg(h->rx_h), vy = any_vector_reg(h->ry_h);
+  if ((vx != h->vecreg_x || vy != h->vecreg_y) && h->iter_exec) { // the captured iteration holds the other instantiation's launches
+    (void)hipGraphExecDestroy(h->iter_exec);
+    h->iter_exec = nullptr;
+  }
+  h->vecreg_x = vx;
+  h->vecreg_y = vy;
   HIPCK(hipMemcpyAsync(h->rx, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemcpyAsync(h->ry, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
@@ -1041,7 +1124,8 @@ static void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream
   const unsigned grid = (unsigned)(WAVES == 1 ? (a.nseg + 3) / 4 : a.nseg);
   const dim3 block(WAVES == 1 ? 256 : WAVES * 64);
   auto launch = [&](auto LOSS, auto U) {
-    if (a.eval_only) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, 1, true>), dim3(grid), block, 0, st, a);
+    if (a.eval_only) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, 1, true>), dim3(grid), block, 0, st, a); // losses only: no regularizer
+    else if (a.vecreg) hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, U, false, true>), dim3(grid), block, 0, st, a);
     else hipLaunchKernelGGL((sweep_kernel<G, R, WAVES, LOSS, U, false>), dim3(grid), block, 0, st, a);
     return GLRM_OK;
   };

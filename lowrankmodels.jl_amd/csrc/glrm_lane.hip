@@ -72,7 +72,9 @@ int launch_lane_tail(int loss, const TiledArgs& a, const int32_t* list, int64_t 
 void launch_small(int which, const TiledArgs& a, hipStream_t st) {
   constexpr int G = 2, R = 16;
   const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
-  if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+  if (which == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
+  else if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+  else if (a.vecreg) hipLaunchKernelGGL((col_decide_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
 }
 

@@ -20,6 +20,8 @@ template <class A, class V> auto set_eval_only(A& a, V v, int) -> decltype(void(
 template <class A, class V> void set_eval_only(A&, V, long) {}
 template <class A, class V> auto set_fixed_alpha(A& a, V v, int) -> decltype(void(a.fixed_alpha = v)) { a.fixed_alpha = v; }
 template <class A, class V> void set_fixed_alpha(A&, V, long) {}
+template <class A, class V> auto set_vecreg(A& a, V v, int) -> decltype(void(a.vecreg = v)) { a.vecreg = v; }
+template <class A, class V> void set_vecreg(A&, V, long) {}
 } // namespace glrm_detail
 
 // The view, factors, step sizes, descriptors and counters of the row (X half-step) or column (Y half-step) side.  What a family does
@@ -37,6 +39,7 @@ void glrm_fill_side(A& a, const glrm_handle* h, bool rows, double min_stepsize, 
   a.losses = h->losses;
   a.regs = rows ? h->rx : h->ry;
   a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
+  glrm_detail::set_vecreg(a, (rows ? h->vecreg_x : h->vecreg_y) ? 1 : 0, 0);
   a.k = h->k;
   a.min_stepsize = min_stepsize;
   a.trials = rows ? h->trials_r : h->trials_c;

@@ -7,6 +7,19 @@
 
 using namespace glrm;
 
+// The kernels that apply a regularizer exist twice: VR = true holds the vector regularizers and is launched when a descriptor of the
+// side names one (glrm_handle::vecreg_x / vecreg_y -> MultiArgs::vecreg; csrc/glrm_device.hpp).
+#define MULTI_SWEEP(threads, ...)                                                                                                        \
+  do {                                                                                                                                   \
+    if (a.vecreg) hipLaunchKernelGGL((multi_sweep_kernel<true, __VA_ARGS__>), dim3((unsigned)a.nseg), dim3(threads), lds, h->stream, a);  \
+    else hipLaunchKernelGGL((multi_sweep_kernel<false, __VA_ARGS__>), dim3((unsigned)a.nseg), dim3(threads), lds, h->stream, a);          \
+  } while (0)
+#define MULTI_COLDECIDE(...)                                                                  \
+  do {                                                                                        \
+    if (sa.m.vecreg) hipLaunchKernelGGL(multi_coldecide_kernel<true>, __VA_ARGS__, sa);       \
+    else hipLaunchKernelGGL(multi_coldecide_kernel<false>, __VA_ARGS__, sa);                  \
+  } while (0)
+
 // Column spans of Y (get_yidxs, src/losses.jl:76-93) and the routing decision.  Called for every handle: the spans
 // are also what a scalar problem uses (ystart[f] = f) if its regularizers are later replaced by wrapped ones.
 int glrm_setup_multi(glrm_handle* h, const glrm_problem* p) {
@@ -103,14 +116,14 @@ static int run_split_cols(glrm_handle* h, const MultiArgs& a) {
   if (a.mode == 1) { // losses only
     sa.round = -1;
     launch_colpass<false>(small, h->has_trig, kind_class(h), grid, lds_pass, st, sa);
-    hipLaunchKernelGGL(multi_coldecide_kernel, dim3((unsigned)a.nseg), dim3(512), lds_dec, st, sa);
+    MULTI_COLDECIDE(dim3((unsigned)a.nseg), dim3(512), lds_dec, st);
     HIPCK(hipGetLastError());
     return GLRM_OK;
   }
   sa.round = 0;
   HIPCK(hipMemsetAsync(h->mnactive, 0, 4, st));
   launch_colpass<true>(small, h->has_trig, kind_class(h), grid, lds_pass, st, sa);
-  hipLaunchKernelGGL(multi_coldecide_kernel, dim3((unsigned)a.nseg), dim3(512), lds_dec, st, sa);
+  MULTI_COLDECIDE(dim3((unsigned)a.nseg), dim3(512), lds_dec, st);
   HIPCK(hipGetLastError());
   if (a.mode == 2) return GLRM_OK;
   sa.point = h->mtrial;
@@ -122,7 +135,7 @@ static int run_split_cols(glrm_handle* h, const MultiArgs& a) {
     sa.round = round;
     HIPCK(hipMemsetAsync(h->mnactive, 0, 4, st));
     launch_colpass<false>(small, h->has_trig, kind_class(h), grid, lds_pass, st, sa);
-    hipLaunchKernelGGL(multi_coldecide_kernel, dim3((unsigned)a.nseg), dim3(512), lds_dec, st, sa);
+    MULTI_COLDECIDE(dim3((unsigned)a.nseg), dim3(512), lds_dec, st);
     HIPCK(hipGetLastError());
   }
   return GLRM_OK;
@@ -146,13 +159,13 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
     const bool regs = h->dmax <= 8 && env_int("GLRM_HIP_MULTI_REGS", 1);
     const int kc = kind_class(h);
     if (regs) {
-      if (h->has_trig) hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, true, 8>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-      else if (kc == 1) hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_MNL>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-      else if (kc == 2) hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_MNL | MULTI_KM_SCALAR>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-      else if (kc == 3) hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_ORD>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-      else hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-    } else if (h->has_trig) hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, true>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
-    else hipLaunchKernelGGL((multi_sweep_kernel<true, 1, GLRM_MAX_EMBEDDING_DIM, false>), dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
+      if (h->has_trig) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, true, 8);
+      else if (kc == 1) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_MNL);
+      else if (kc == 2) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_MNL | MULTI_KM_SCALAR);
+      else if (kc == 3) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8, MULTI_KM_ORD);
+      else MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false, 8);
+    } else if (h->has_trig) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, true);
+    else MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false);
   } else {
     const int rc = setup_split(h); // decides once per handle whether the columns are long enough to split
     if (rc) return rc;
@@ -160,14 +173,14 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
     const size_t lds = multi_lds_doubles(false, 8, h->kp, h->dmax, a.lgP) * 8;
     if (h->dmax <= 8) {
       const int kc = kind_class(h);
-      if (h->has_trig) hipLaunchKernelGGL((multi_sweep_kernel<false, 8, 8, true, 8>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
-      else if (kc == 1) hipLaunchKernelGGL((multi_sweep_kernel<false, 8, 8, false, 8, MULTI_KM_MNL>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
-      else if (kc == 2) hipLaunchKernelGGL((multi_sweep_kernel<false, 8, 8, false, 8, MULTI_KM_MNL | MULTI_KM_SCALAR>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
-      else if (kc == 3) hipLaunchKernelGGL((multi_sweep_kernel<false, 8, 8, false, 8, MULTI_KM_ORD>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
-      else hipLaunchKernelGGL((multi_sweep_kernel<false, 8, 8, false, 8>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
+      if (h->has_trig) MULTI_SWEEP(512, false, 8, 8, true, 8);
+      else if (kc == 1) MULTI_SWEEP(512, false, 8, 8, false, 8, MULTI_KM_MNL);
+      else if (kc == 2) MULTI_SWEEP(512, false, 8, 8, false, 8, MULTI_KM_MNL | MULTI_KM_SCALAR);
+      else if (kc == 3) MULTI_SWEEP(512, false, 8, 8, false, 8, MULTI_KM_ORD);
+      else MULTI_SWEEP(512, false, 8, 8, false, 8);
     } else {
-      if (h->has_trig) hipLaunchKernelGGL((multi_sweep_kernel<false, 8, GLRM_MAX_EMBEDDING_DIM, true>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
-      else hipLaunchKernelGGL((multi_sweep_kernel<false, 8, GLRM_MAX_EMBEDDING_DIM, false>), dim3((unsigned)a.nseg), dim3(512), lds, h->stream, a);
+      if (h->has_trig) MULTI_SWEEP(512, false, 8, GLRM_MAX_EMBEDDING_DIM, true);
+      else MULTI_SWEEP(512, false, 8, GLRM_MAX_EMBEDDING_DIM, false);
     }
   }
   HIPCK(hipGetLastError());
@@ -186,7 +199,9 @@ int glrm_run_multi_penalty(glrm_handle* h, bool rows) {
   a.k = h->k; a.kp = h->kp;
   a.out = rows ? h->objrow : h->objcol;
   const size_t lds = ((size_t)(rows ? 1 : h->dmax) * (h->kp + 1) + 16) * 8;
-  hipLaunchKernelGGL(multi_penalty_kernel, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
+  a.vecreg = (rows ? h->vecreg_x : h->vecreg_y) ? 1 : 0;
+  if (a.vecreg) hipLaunchKernelGGL(multi_penalty_kernel<true>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
+  else hipLaunchKernelGGL(multi_penalty_kernel<false>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
   HIPCK(hipGetLastError());
   return GLRM_OK;
 }

@@ -17,6 +17,7 @@
 #pragma once
 
 #include "glrm_device.hpp"
+#include "glrm_blockreg.hpp"
 
 namespace glrm {
 
@@ -41,6 +42,7 @@ struct MultiArgs {
   double fixed_alpha, min_stepsize;
   int32_t* trials;
   int32_t* accepts;
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels
 };
 
 struct PenaltyArgs {
@@ -52,28 +54,13 @@ struct PenaltyArgs {
   int reg_single;
   int k, kp;
   double* out;           // global segment index
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels
 };
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Sum over all threads of the workgroup; every thread returns the same value.  Wave butterfly, then the wave
-// partials in wave order.
-template <int NW>
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  if constexpr (NW == 1) return v;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += red[w];
-  return t;
 }
 
 // ---------------------------------------------------------------- multi-dimensional losses (u lives in LDS)
@@ -179,119 +166,6 @@ __device__ inline double vloss_grad(const LossDesc& l, const double* u, int d, i
       return -s * g;
     }
   }
-}
-
-// ---------------------------------------------------------------- block regularizers (block in LDS, stride S)
-
-// evaluate(r, block): every thread returns the same value.
-template <int NW>
-__device__ inline double block_reg_eval(const double* blk, int S, int k, int DO, const glrm_reg rg, double* red) {
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x;
-  const int kr = rg.wrap ? k - 1 : k;                                                        // rows the base regularizer sees
-  const int jc = (rg.wrap & (GLRM_WRAP_ORDINAL | GLRM_WRAP_MNL_ORDINAL)) ? 1 : DO;          // evaluate(r.r, a[1:end-1, 1])
-  double bad = 0.0, v = 0.0;
-  if (rg.wrap == GLRM_WRAP_LASTENTRY1)
-    for (int j = tid; j < DO; j += NT) bad += blk[j * S + k - 1] != 1.0 ? 1.0 : 0.0;
-  for (int i = tid; i < kr * jc; i += NT) {
-    const int j = i / kr, c = i - j * kr;
-    const double x = blk[j * S + c];
-    switch (rg.kind) {
-      case GLRM_REG_QUAD: v = fma(x, x, v); break;
-      case GLRM_REG_ONE: v += fabs(x); break;
-      case GLRM_REG_NONNEG: v += x < 0 ? 1.0 : 0.0; break;
-      case GLRM_REG_UNIT_ONE_SPARSE: v += x == 0 ? 0.0 : (x == 1 ? 1.0 : 4096.0); break;
-      default: break;
-    }
-  }
-  bad = block_sum<NW>(bad, red);
-  v = block_sum<NW>(v, red);
-  if (bad > 0) return __builtin_inf();
-  switch (rg.kind) {
-    case GLRM_REG_QUAD:
-    case GLRM_REG_ONE: return rg.scale * v;
-    case GLRM_REG_NONNEG: return v > 0 ? __builtin_inf() : 0.0;
-    case GLRM_REG_UNIT_ONE_SPARSE: return (v >= 4096.0 || v > 1.0) ? __builtin_inf() : 0.0;
-    default: return 0.0;
-  }
-}
-
-// prox of the base regularizer on rows [0, kr) of DO columns.  whole: UnitOneSparse picks one entry of the whole
-// sub-block (column-major first maximum), otherwise one per column.
-template <int NW>
-__device__ inline void base_prox_region(double* blk, int S, int kr, int DO, const glrm_reg rg, double alpha, bool whole) {
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x;
-  switch (rg.kind) {
-    case GLRM_REG_QUAD: {
-      const double f = 1 / (1 + 2 * alpha * rg.scale);
-      for (int i = tid; i < kr * DO; i += NT) { const int j = i / kr, c = i - j * kr; blk[j * S + c] = f * blk[j * S + c]; }
-      break;
-    }
-    case GLRM_REG_ONE: {
-      const double t = rg.scale * alpha;
-      for (int i = tid; i < kr * DO; i += NT) {
-        const int j = i / kr, c = i - j * kr;
-        const double x = blk[j * S + c];
-        blk[j * S + c] = fmax(x - t, 0.0) + fmin(x + t, 0.0);
-      }
-      break;
-    }
-    case GLRM_REG_NONNEG:
-      for (int i = tid; i < kr * DO; i += NT) { const int j = i / kr, c = i - j * kr; const double x = blk[j * S + c]; blk[j * S + c] = x > 0 ? x : 0.0; }
-      break;
-    case GLRM_REG_UNIT_ONE_SPARSE:
-      if (tid == 0 && kr > 0) {
-        if (whole) {
-          int bj = 0, bc = 0;
-          for (int j = 0; j < DO; ++j)
-            for (int c = 0; c < kr; ++c)
-              if (blk[j * S + c] > blk[bj * S + bc]) { bj = j; bc = c; }
-          for (int j = 0; j < DO; ++j)
-            for (int c = 0; c < kr; ++c) blk[j * S + c] = 0.0;
-          blk[bj * S + bc] = 1.0;
-        } else {
-          for (int j = 0; j < DO; ++j) {
-            int bc = 0;
-            for (int c = 1; c < kr; ++c) if (blk[j * S + c] > blk[j * S + bc]) bc = c;
-            for (int c = 0; c < kr; ++c) blk[j * S + c] = c == bc ? 1.0 : 0.0;
-          }
-        }
-      }
-      break;
-    default: break;
-  }
-}
-
-// prox!(r, block, alpha) (src/regularizers.jl:34-114,163-189,295-318,356-405); ends with a workgroup barrier.
-template <int NW>
-__device__ inline void block_prox(double* blk, int S, int k, int DO, const glrm_reg rg, double alpha, double* tmp) {
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x;
-  const int kr = rg.wrap ? k - 1 : k;
-  if (rg.wrap & (GLRM_WRAP_ORDINAL | GLRM_WRAP_MNL_ORDINAL)) {
-    if (tid < kr) { // um = mean(u[1:end-1, :], dims=2)
-      double acc = 0.0;
-      for (int j = 0; j < DO; ++j) acc += blk[j * S + tid];
-      tmp[tid] = acc / DO;
-    }
-    __syncthreads();
-    base_prox_region<NW>(tmp, 0, kr, 1, rg, alpha, false);
-    __syncthreads();
-    for (int i = tid; i < kr * DO; i += NT) { const int j = i / kr, c = i - j * kr; blk[j * S + c] = tmp[c]; }
-    if ((rg.wrap & GLRM_WRAP_MNL_ORDINAL) && tid == 0) { // decreasing, negative last row (not exactly the prox, :400-404)
-      const double TOL = 1e-3;
-      double* last = blk + (k - 1);
-      last[0] = last[0] < -TOL ? last[0] : -TOL;
-      for (int j = 1; j < DO; ++j) last[j * S] = last[j * S] < last[(j - 1) * S] - TOL ? last[j * S] : last[(j - 1) * S] - TOL;
-    }
-    __syncthreads();
-    return;
-  }
-  base_prox_region<NW>(blk, S, kr, DO, rg, alpha, !(rg.wrap == GLRM_WRAP_LASTENTRY1 || DO == 1));
-  if (rg.wrap == GLRM_WRAP_LASTENTRY1)
-    for (int j = tid; j < DO; j += NT) blk[j * S + k - 1] = 1.0;
-  __syncthreads();
 }
 
 // ---------------------------------------------------------------- slot reductions
@@ -620,7 +494,8 @@ __host__ __device__ inline size_t multi_lds_doubles(bool rows, int nw, int kp, i
 }
 
 // TRIG = false: the scalar-loss columns of the model hold no PeriodicLoss (LOSS_*_NOTRIG in glrm_engine.hpp)
-template <bool ROWS, int NW, int GDC, bool TRIG, int RD = 0, int KM = MULTI_KM_ALL>
+// VR: the side has vector regularizers (csrc/glrm_device.hpp, csrc/glrm_blockreg.hpp)
+template <bool VR, bool ROWS, int NW, int GDC, bool TRIG, int RD = 0, int KM = MULTI_KM_ALL>
 __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(const MultiArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int NT = NW * 64;
@@ -665,11 +540,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(c
       if (c < k) { const double g = Gt[j * S + c] * (-st); ownA[j * S + c] = ownA[j * S + c] + g; }
     }
     __syncthreads();
-    block_prox<NW>(ownA, S, k, DO, rg, st, tmp);
+    block_prox<NW, VR>(ownA, S, k, DO, rg, st, tmp);
     for (int i = tid; i < DO * kp; i += NT) { const int j = i / kp, c = i - j * kp; ownp[i] = ownA[j * S + c]; }
     return;
   }
-  double obj = loss_old + block_reg_eval<NW>(ownA, S, k, DO, rg, red);
+  double obj = loss_old + block_reg_eval<NW, VR>(ownA, S, k, DO, rg, red);
   double alpha = a.alpha[s];
   int ntr = 0, nacc = 0;
   while (alpha > a.min_stepsize) { // proxgrad.jl:137-155 / :180-200
@@ -679,9 +554,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(c
       ownB[j * S + c] = c < k ? fma(-stepsize, Gt[j * S + c], ownA[j * S + c]) : 0.0;
     }
     __syncthreads();
-    block_prox<NW>(ownB, S, k, DO, rg, stepsize, tmp);
+    block_prox<NW, VR>(ownB, S, k, DO, rg, stepsize, tmp);
     const double nloss = multi_pass<ROWS, NW, false, GDC, TRIG, RD, KM>(a, b, e, ownB, wbase, Gt, red, lseg, dseg);
-    const double nobj = nloss + block_reg_eval<NW>(ownB, S, k, DO, rg, red);
+    const double nobj = nloss + block_reg_eval<NW, VR>(ownB, S, k, DO, rg, red);
     ++ntr;
     if (nobj < obj) {
       for (int i = tid; i < DO * kp; i += NT) { const int j = i / kp, c = i - j * kp; ownp[i] = ownB[j * S + c]; }
@@ -760,6 +635,7 @@ __global__ void __launch_bounds__(512, (GRAD && GDC > 8) ? 2 : 4) multi_colpass_
 
 // One workgroup per column, same shape (8 waves) and the same block_prox / block_reg_eval instantiations as the one-kernel
 // sweep: a column whose list fits one chunk gets bit-identical results on either path.
+template <bool VR>
 __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const MultiArgs& a = sa.m;
@@ -802,18 +678,18 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
         if (c < k) { const double g = gt[i] * (-st); blkA[j * S + c] = blkA[j * S + c] + g; }
       }
       __syncthreads();
-      block_prox<8>(blkA, S, k, DO, rg, st, tmp);
+      block_prox<8, VR>(blkA, S, k, DO, rg, st, tmp);
       for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; ownp[i] = blkA[j * S + c]; }
       if (tid == 0) sa.active[s] = 0;
       return;
     }
     __syncthreads();
-    obj = loss + block_reg_eval<8>(blkA, S, k, DO, rg, red);
+    obj = loss + block_reg_eval<8, VR>(blkA, S, k, DO, rg, red);
     if (!(alpha > a.min_stepsize)) finished = true;
   } else {
     for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; blkB[j * S + c] = trialp[i]; }
     __syncthreads();
-    const double nobj = loss + block_reg_eval<8>(blkB, S, k, DO, rg, red);
+    const double nobj = loss + block_reg_eval<8, VR>(blkB, S, k, DO, rg, red);
     obj = sa.objold[s];
     ntr = 1;
     if (nobj < obj) {
@@ -835,7 +711,7 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
       blkB[j * S + c] = c < k ? fma(-stepsize, gt[i], blkA[j * S + c]) : 0.0;
     }
     __syncthreads();
-    block_prox<8>(blkB, S, k, DO, rg, stepsize, tmp);
+    block_prox<8, VR>(blkB, S, k, DO, rg, stepsize, tmp);
     for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; trialp[i] = blkB[j * S + c]; }
   }
   if (tid == 0) {
@@ -850,6 +726,7 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
 }
 
 // calc_penalty pieces (src/evaluate_fit.jl:91-104) for wrapped / block regularizers: one wave per segment
+template <bool VR>
 __global__ void __launch_bounds__(64) multi_penalty_kernel(const PenaltyArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, S = a.kp + 1, kp = a.kp;
@@ -862,7 +739,7 @@ __global__ void __launch_bounds__(64) multi_penalty_kernel(const PenaltyArgs a) 
   for (int i = tid; i < DO * kp; i += 64) { const int j = i / kp, c = i - j * kp; blk[j * S + c] = src[i]; }
   __syncthreads();
   const glrm_reg rg = a.regs[a.reg_single ? 0 : s];
-  const double v = block_reg_eval<1>(blk, S, a.k, DO, rg, red);
+  const double v = block_reg_eval<1, VR>(blk, S, a.k, DO, rg, red);
   if (tid == 0) a.out[gseg] = v;
 }
 

@@ -738,12 +738,14 @@ extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, co
 extern "C" int glrm_hip_multi_set_regularizers(glrm_multi* mh, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
   if (!mh || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
   if (n_rx != mh->n_rx || n_ry != mh->n_ry) return fail(GLRM_ERR_INVALID, "regularizer counts must match the create call");
-  for (int s = 0; s < mh->n; ++s) {
-    const glrm_reg* sx = n_rx == 1 ? rx : rx + mh->rbs[s];
-    const glrm_reg* sy = n_ry == 1 ? ry : ry + mh->cbs[s];
-    const int rc = glrm_hip_set_regularizers(mh->sh[s], sx, n_rx == 1 ? 1 : mh->rbs[s + 1] - mh->rbs[s], sy, n_ry == 1 ? 1 : mh->cbs[s + 1] - mh->cbs[s]);
-    if (rc) return rc;
-  }
+  for (int pass = 0; pass < 2; ++pass) // every shard's slice is checked before any shard is changed: a refusal leaves the model as it was
+    for (int s = 0; s < mh->n; ++s) {
+      const glrm_reg* sx = n_rx == 1 ? rx : rx + mh->rbs[s];
+      const glrm_reg* sy = n_ry == 1 ? ry : ry + mh->cbs[s];
+      const int64_t nx = n_rx == 1 ? 1 : mh->rbs[s + 1] - mh->rbs[s], ny = n_ry == 1 ? 1 : mh->cbs[s + 1] - mh->cbs[s];
+      const int rc = pass == 0 ? glrm_check_regularizers(mh->sh[s], sx, nx, sy, ny) : glrm_hip_set_regularizers(mh->sh[s], sx, nx, sy, ny);
+      if (rc) return rc;
+    }
   return GLRM_OK;
 }
 

@@ -29,6 +29,7 @@
 
 #include "glrm_device.hpp"
 #include "glrm_engine.hpp"
+#include "glrm_refreg.hpp"
 #include "glrm_launch.hpp"
 
 using namespace glrm;
@@ -54,85 +55,8 @@ struct RefArgs {
   int32_t* trials;
   int32_t* accepts;
   int eval_only;         // columns: obj[seg] = loss sum at the current point, nothing else
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels
 };
-
-// glrm_cpu_reg_evaluate, oracle/glrm_oracle.c (src/regularizers.jl:58,88,95,103-112,300-316): component order, multiply then add
-template <int KP>
-__device__ __forceinline__ double ref_reg_eval(const RegDesc& r, const double (&x)[KP], int k) {
-  switch (r.kind) {
-    case GLRM_REG_QUAD: {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < KP; ++c)
-        if (c < k) s += x[c] * x[c];
-      return r.scale * s;
-    }
-    case GLRM_REG_ONE: {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < KP; ++c)
-        if (c < k) s += fabs(x[c]);
-      return r.scale * s;
-    }
-    case GLRM_REG_NONNEG: {
-      bool neg = false;
-#pragma unroll
-      for (int c = 0; c < KP; ++c) neg = neg || (c < k && x[c] < 0);
-      return neg ? __builtin_inf() : 0.0;
-    }
-    case GLRM_REG_UNIT_ONE_SPARSE: {
-      int ones = 0;
-      bool other = false;
-#pragma unroll
-      for (int c = 0; c < KP; ++c)
-        if (c < k && x[c] != 0) {
-          if (x[c] == 1) ++ones; else other = true;
-        }
-      return (other || ones > 1) ? __builtin_inf() : 0.0;
-    }
-    default:
-      return 0.0;
-  }
-}
-
-// glrm_cpu_reg_prox (src/regularizers.jl:34,56,83-86,93,103,297)
-template <int KP>
-__device__ __forceinline__ void ref_reg_prox(const RegDesc& r, double (&u)[KP], int k, double alpha) {
-  switch (r.kind) {
-    case GLRM_REG_QUAD: {
-      const double f = 1 / (1 + 2 * alpha * r.scale);
-#pragma unroll
-      for (int c = 0; c < KP; ++c) u[c] = f * u[c];
-      break;
-    }
-    case GLRM_REG_ONE: {
-      const double t = r.scale * alpha;
-#pragma unroll
-      for (int c = 0; c < KP; ++c) u[c] = fmax(u[c] - t, 0.0) + fmin(u[c] + t, 0.0);
-      break;
-    }
-    case GLRM_REG_NONNEG: {
-#pragma unroll
-      for (int c = 0; c < KP; ++c) u[c] = u[c] > 0 ? u[c] : 0.0;
-      break;
-    }
-    case GLRM_REG_UNIT_ONE_SPARSE: { // e_{argmax u}, first maximal index
-      int idx = 0;
-      double best = u[0];
-#pragma unroll
-      for (int c = 1; c < KP; ++c)
-        if (c < k && u[c] > best) { best = u[c]; idx = c; }
-#pragma unroll
-      for (int c = 0; c < KP; ++c) u[c] = c == idx ? 1.0 : 0.0;
-      break;
-    }
-    default:
-      break;
-  }
-#pragma unroll
-  for (int c = 0; c < KP; ++c)
-    if (c >= k) u[c] = 0.0; // the padding stays exactly zero
-}
 
 // <x, y>: s = fma(x[c], y[c], s), c = 0 .. k-1 (the oracle's dotk); y is a row of the opposing factor in memory
 template <int KP>
@@ -169,7 +93,7 @@ __device__ __forceinline__ void store_vec(double* p, const double (&x)[KP]) {
 
 // ------------------------------------------------------------------------------------------------------------------------ rows
 // src/algorithms/proxgrad.jl:118-156 for one row per lane
-template <int KP, bool TRIG>
+template <int KP, bool TRIG, bool VR>
 __global__ void __launch_bounds__(64) ref_row_kernel(const RefArgs a) {
   const int64_t el = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (el >= a.nseg) return;
@@ -199,7 +123,7 @@ __global__ void __launch_bounds__(64) ref_row_kernel(const RefArgs a) {
     }
   }
   const RegDesc rd = load_reg(a.regs, a.reg_single ? 0 : el);
-  Jold += ref_reg_eval<KP>(rd, x, k);
+  Jold += ref_reg_eval<KP, VR>(rd, x, k);
   const double l = (double)(e - b) + 1; // :134
   double alpha = a.alpha[el];
   int ntr = 0, nacc = 0;
@@ -207,7 +131,7 @@ __global__ void __launch_bounds__(64) ref_row_kernel(const RefArgs a) {
     const double stepsize = alpha / l;
 #pragma unroll
     for (int c = 0; c < KP; ++c) xn[c] = fma(-stepsize, g[c], x[c]); // :140
-    ref_reg_prox<KP>(rd, xn, k, stepsize);                            // :142
+    ref_reg_prox<KP, VR>(rd, xn, k, stepsize);                            // :142
     double Jn = 0.0;
     for (int64_t t = b; t < e; ++t) {
       const int64_t f = a.idx[t];
@@ -217,7 +141,7 @@ __global__ void __launch_bounds__(64) ref_row_kernel(const RefArgs a) {
       loss_both<false, TRIG>(lo, u, a.vals[t], L, dL);
       Jn += L;
     }
-    Jn += ref_reg_eval<KP>(rd, xn, k);
+    Jn += ref_reg_eval<KP, VR>(rd, xn, k);
     ++ntr;
     if (Jn < Jold) { // :143
       store_vec<KP>(xp, xn);
@@ -302,7 +226,7 @@ __device__ __forceinline__ double ref_col_loss(const RefArgs& a, const LossDesc&
 }
 
 // src/algorithms/proxgrad.jl:162-201 for one column per lane
-template <int KP, bool TRIG>
+template <int KP, bool TRIG, bool VR>
 __global__ void __launch_bounds__(64) ref_col_kernel(const RefArgs a) {
   const int64_t fl = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (fl >= a.nseg) return;
@@ -330,7 +254,7 @@ __global__ void __launch_bounds__(64) ref_col_kernel(const RefArgs a) {
   // gradient (:165-175) and the loss sum of col_objective at y (:178) in one walk
   double obj = 0.0;
   obj += ref_col_loss<KP, TRIG, true>(a, lo, b, e, y, G);
-  obj += ref_reg_eval<KP>(rd, y, k);
+  obj += ref_reg_eval<KP, VR>(rd, y, k);
   const double l = (double)(e - b) + 1; // :177
   double alpha = a.alpha[fl];
   int ntr = 0, nacc = 0;
@@ -338,10 +262,10 @@ __global__ void __launch_bounds__(64) ref_col_kernel(const RefArgs a) {
     const double stepsize = alpha / l;
 #pragma unroll
     for (int c = 0; c < KP; ++c) yn[c] = fma(-stepsize, G[c], y[c]); // :183
-    ref_reg_prox<KP>(rd, yn, k, stepsize);                            // :185
+    ref_reg_prox<KP, VR>(rd, yn, k, stepsize);                            // :185
     double nobj = 0.0;
     nobj += ref_col_loss<KP, TRIG, false>(a, lo, b, e, yn, G);
-    nobj += ref_reg_eval<KP>(rd, yn, k);
+    nobj += ref_reg_eval<KP, VR>(rd, yn, k);
     ++ntr;
     if (nobj < obj) { // :187-191
       store_vec<KP>(yp, yn);
@@ -395,13 +319,17 @@ int launch_ref_terms(bool trig, const RefArgs& a, int64_t t0, int64_t t1, double
 template <int KP>
 int launch_ref(bool rows, bool trig, const RefArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)((a.nseg + 63) / 64);
-  if (rows) {
-    if (trig) hipLaunchKernelGGL((ref_row_kernel<KP, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((ref_row_kernel<KP, false>), dim3(grid), dim3(64), 0, st, a);
-  } else {
-    if (trig) hipLaunchKernelGGL((ref_col_kernel<KP, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((ref_col_kernel<KP, false>), dim3(grid), dim3(64), 0, st, a);
-  }
+  auto go = [&](auto VR) {
+    constexpr bool V = decltype(VR)::value;
+    if (rows) {
+      if (trig) hipLaunchKernelGGL((ref_row_kernel<KP, true, V>), dim3(grid), dim3(64), 0, st, a);
+      else hipLaunchKernelGGL((ref_row_kernel<KP, false, V>), dim3(grid), dim3(64), 0, st, a);
+    } else {
+      if (trig) hipLaunchKernelGGL((ref_col_kernel<KP, true, V>), dim3(grid), dim3(64), 0, st, a);
+      else hipLaunchKernelGGL((ref_col_kernel<KP, false, V>), dim3(grid), dim3(64), 0, st, a);
+    }
+  };
+  if (a.vecreg) go(std::true_type{}); else go(std::false_type{});
   HIPCK(hipGetLastError());
   return GLRM_OK;
 }

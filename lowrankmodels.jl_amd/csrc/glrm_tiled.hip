@@ -279,15 +279,23 @@ static int launch_tiled_inst(int kind, const TiledArgs& a, hipStream_t st) {
   const int lds = tile_lds_bytes<G, R, TILE>() + (loss_mode(LOSS) == 2 && a.descid ? a.n_udesc * 32 : 0);
   const unsigned gx = (unsigned)(((a.npass > 0 ? a.npass : a.nseg) + SPB - 1) / SPB);
   int rc = GLRM_OK;
+  auto sweep = [&](auto FIXED, auto ROUNDS) { // the whole-sweep kernel; VR: the side has vector regularizers (csrc/glrm_device.hpp)
+    auto go = [&](auto kernel) {
+      if ((rc = set_lds(kernel, lds))) return;
+      hipLaunchKernelGGL(kernel, dim3(gx), dim3(NW * 64), lds, st, a);
+    };
+    if (a.vecreg) go(tiled_sweep_kernel<G, R, NW, TILE, LOSS, decltype(FIXED)::value, decltype(ROUNDS)::value, true>);
+    else go(tiled_sweep_kernel<G, R, NW, TILE, LOSS, decltype(FIXED)::value, decltype(ROUNDS)::value>);
+  };
   if (kind == 0 && a.fixed_alpha > 0.0) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, true>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, true>), dim3(gx), dim3(NW * 64), lds, st, a);
+    sweep(std::true_type{}, std::false_type{});
+    if (rc) return rc;
   } else if (kind == 0) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false>), dim3(gx), dim3(NW * 64), lds, st, a);
+    sweep(std::false_type{}, std::false_type{});
+    if (rc) return rc;
   } else if (kind == 3) {
-    if ((rc = set_lds(tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, true>, lds))) return rc;
-    hipLaunchKernelGGL((tiled_sweep_kernel<G, R, NW, TILE, LOSS, false, true>), dim3(gx), dim3(NW * 64), lds, st, a);
+    sweep(std::false_type{}, std::true_type{});
+    if (rc) return rc;
   } else if (kind == 4) {
     if ((rc = set_lds(tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, true>, lds))) return rc;
     hipLaunchKernelGGL((tiled_col_pass_kernel<G, R, NW, TILE, LOSS, false, false, true>), dim3(gx, (unsigned)(a.nsup_launch > 0 ? a.nsup_launch : a.nsup)), dim3(NW * 64), lds, st, a);
@@ -315,7 +323,9 @@ void glrm_launch_col_small(int kp, int which, const TiledArgs& a, hipStream_t st
   auto by_layout = [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
-    if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+    if (which == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
+    else if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+    else if (a.vecreg) hipLaunchKernelGGL((col_decide_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
     return GLRM_OK;
   };

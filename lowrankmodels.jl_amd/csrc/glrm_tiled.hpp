@@ -91,6 +91,7 @@ struct TiledArgs {
                               // past the wave's trailing group sits the step out (0 = off; see tiled_pass)
   const int32_t* suppos;      // phase-aligned passes: [nseg][nsup] offset inside the segment's list of its first entry of the super-tile, i.e.
                               // what lower_bound_idx finds at every launch (the lists never change); nullptr = search
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels (csrc/glrm_device.hpp)
 };
 
 // v from lane (lane ^ X) for X = 4 or 8 (ds_swizzle bit-mask mode: and 0x1F, or 0, xor X; no LDS memory touched)
@@ -503,7 +504,7 @@ __device__ __forceinline__ void stage_udesc(const TiledArgs& a, char* lds) {
 // leaves its state -- gradient, J_old, shrunk step size, next trial point -- in the pass buffers (gsum, jold, alpha, trial, ntrial,
 // active) and its id in actlist_out, and the host runs the remaining trials as rounds of (tiled_col_pass_kernel<GRAD = false, ROWS> over
 // the listed segments, col_decide_kernel): only workgroups made of still-searching rows stage tiles again.  Same sums, same bits.
-template <int G, int R, int NW, int TILE, int LOSS, bool FIXED, bool ROUNDS = false>
+template <int G, int R, int NW, int TILE, int LOSS, bool FIXED, bool ROUNDS = false, bool VR = false>
 __global__ void __launch_bounds__(NW * 64, 4) tiled_sweep_kernel(const TiledArgs a) {
   constexpr int KP = G * R, NGW = 64 / G, SPB = NW * NGW;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -538,14 +539,14 @@ __global__ void __launch_bounds__(NW * 64, 4) tiled_sweep_kernel(const TiledArgs
         xn.v[i].x = x.v[i].x + g.v[i].x * (-s);
         xn.v[i].y = x.v[i].y + g.v[i].y * (-s);
       }
-      reg_prox<G, R>(rd, xn, s, j, a.k);
+      reg_prox<G, R, VR>(rd, xn, s, j, a.k);
       if (have) {
 #pragma unroll
         for (int i = 0; i < R / 2; ++i) ownp[i * G + j] = xn.v[i];
       }
       return;
     }
-    Jold += reg_eval<G, R>(rd, x, j, a.k);
+    Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
   }
 
   // Backtracking line search.  The current point is NOT kept in registers across the trial passes: it is re-read
@@ -565,12 +566,12 @@ __global__ void __launch_bounds__(NW * 64, 4) tiled_sweep_kernel(const TiledArgs
       xn.v[i].x = fma(-s, g.v[i].x, xi.x);
       xn.v[i].y = fma(-s, g.v[i].y, xi.y);
     }
-    reg_prox<G, R>(rd, xn, s, j, a.k);
+    reg_prox<G, R, VR>(rd, xn, s, j, a.k);
     double Jn;
     Vec<G, R> dummy;
     pos = beg;
     tiled_pass<G, R, NW, TILE, LOSS, false>(a, lds, xn, dummy, Jn, searching, pos, end, 0, ntiles, segloss, lane, j);
-    Jn += reg_eval<G, R>(rd, xn, j, a.k);
+    Jn += reg_eval<G, R, VR>(rd, xn, j, a.k);
     if (searching) {
       ++ntrials;
       if (Jn < Jold) {
@@ -601,7 +602,7 @@ __global__ void __launch_bounds__(NW * 64, 4) tiled_sweep_kernel(const TiledArgs
           xn.v[i].x = fma(-s, g.v[i].x, xi.x);
           xn.v[i].y = fma(-s, g.v[i].y, xi.y);
         }
-        reg_prox<G, R>(rd, xn, s, j, a.k);
+        reg_prox<G, R, VR>(rd, xn, s, j, a.k);
         double2* gp = reinterpret_cast<double2*>(a.gsum + seg * (int64_t)KP);
         double2* tp = reinterpret_cast<double2*>(a.trial + seg * (int64_t)KP);
 #pragma unroll
@@ -697,7 +698,7 @@ __global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(con
 }
 
 // After pass 1: reduce the partials in super-tile order, J_old = loss + r(y), first trial point.
-template <int G, int R>
+template <int G, int R, bool VR = false>
 __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
   constexpr int KP = G * R, NGW = 64 / G, PSTRIDE = KP + 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -736,14 +737,14 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
       yn.v[i].x = y.v[i].x + g.v[i].x * (-s0);
       yn.v[i].y = y.v[i].y + g.v[i].y * (-s0);
     }
-    reg_prox<G, R>(rd, yn, s0, j, a.k);
+    reg_prox<G, R, VR>(rd, yn, s0, j, a.k);
     double2* yw = reinterpret_cast<double2*>(a.own + gseg * KP);
 #pragma unroll
     for (int i = 0; i < R / 2; ++i) yw[i * G + j] = yn.v[i];
     if (j == 0) a.active[seg] = 0;
     return;
   }
-  const double Jold = J + reg_eval<G, R>(rd, y, j, a.k);
+  const double Jold = J + reg_eval<G, R, VR>(rd, y, j, a.k);
   if (a.jloss && j == 0) a.jloss[seg] = J;
   const double alpha = a.alpha[seg];
   const double l = (double)(a.ptr ? a.ptr[seg + 1] - a.ptr[seg] : a.dense_len) + 1.0;
@@ -754,7 +755,7 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
     yn.v[i].x = fma(-s, g.v[i].x, y.v[i].x);
     yn.v[i].y = fma(-s, g.v[i].y, y.v[i].y);
   }
-  reg_prox<G, R>(rd, yn, s, j, a.k);
+  reg_prox<G, R, VR>(rd, yn, s, j, a.k);
   double2* gp = reinterpret_cast<double2*>(a.gsum + seg * (int64_t)KP);
   double2* tp = reinterpret_cast<double2*>(a.trial + seg * (int64_t)KP);
 #pragma unroll
@@ -775,7 +776,7 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
 }
 
 // After a trial pass: J' = sum of partial losses + r(y'); accept / shrink / give up; next trial point.
-template <int G, int R>
+template <int G, int R, bool VR = false>
 __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
   constexpr int KP = G * R, NGW = 64 / G, PSTRIDE = KP + 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -797,7 +798,7 @@ __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
 #pragma unroll
   for (int i = 0; i < R / 2; ++i) yn.v[i] = tp[i * G + j];
   const RegDesc rd = load_reg(a.regs, a.reg_single ? 0 : seg);
-  Jn += reg_eval<G, R>(rd, yn, j, a.k);
+  Jn += reg_eval<G, R, VR>(rd, yn, j, a.k);
   const double Jold = a.jold[seg];
   double alpha = a.alpha[seg];
   int still = 0, acc = 0;
@@ -822,7 +823,7 @@ __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
         yn.v[i].x = fma(-s, g.v[i].x, y.v[i].x);
         yn.v[i].y = fma(-s, g.v[i].y, y.v[i].y);
       }
-      reg_prox<G, R>(rd, yn, s, j, a.k);
+      reg_prox<G, R, VR>(rd, yn, s, j, a.k);
 #pragma unroll
       for (int i = 0; i < R / 2; ++i) tp[i * G + j] = yn.v[i];
     }

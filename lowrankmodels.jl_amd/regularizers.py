@@ -12,6 +12,8 @@ import numpy as np
 from ._capi import REG_DTYPE, bump_epoch as _bump_epoch
 
 ZERO, QUAD, ONE, NONNEG, UNIT_ONE_SPARSE = range(5)
+QUAD_CONSTRAINT, NONNEG_ONE, ONE_SPARSE, K_SPARSE, SIMPLEX = range(5, 10)  # the vector regularizers (GLRM_REG_KIND_END = 10)
+TOL = 1e-12  # src/regularizers.jl:25
 
 
 class Regularizer:
@@ -127,12 +129,182 @@ class UnitOneSparseConstraint(_Unscaled):  # :295-318
         return v
 
 
+# ------------------------------------------------------------------------- vector regularizers (kinds 5-9)
+# They act on a k-vector: every rx, the ry of a scalar-loss column, and the base of lastentry1 / lastentry_unpenalized.  The engine refuses
+# them on the k x d block of a multi-dimensional column and under OrdinalReg / MNLOrdinalReg (the reference's sort / partialsortperm throw
+# on a matrix).  For all five `mul!` is a no-op and scale() is 1 (src/regularizers.jl:75-76,137-138,254-255,347-348; KSparseConstraint has
+# no `scale` field at all), and `newscale * r` builds `typeof(r)()` (:40), i.e. an object with the DEFAULT parameter.
+
+
+class _VectorReg(Regularizer):
+    def mul_(self, newscale):  # mul!(r, newscale) = 1: nothing changes
+        return self
+
+    def __rmul__(self, newscale):  # *(newscale, r) = typeof(r)() followed by the no-op mul! (:40)
+        return type(self)()
+
+
+class QuadConstraint(_VectorReg):  # :68-76
+    """Indicator of the ball ||x|| <= max_2norm (max-norm regularization).  ``prox`` rescales ONTO the sphere, always -- also from inside the
+    ball -- and turns the zero vector into NaN (:72); ``mul_`` is a no-op (:76) and ``newscale * r`` is ``QuadConstraint()``, which
+    resets max_2norm to 1 (:40,:71)."""
+    kind = QUAD_CONSTRAINT
+
+    def __init__(self, max_2norm=1):
+        object.__setattr__(self, "max_2norm", float(max_2norm))
+        _bump_epoch()
+
+    scale = property(lambda self: 1.0)  # scale(r::QuadConstraint) = 1, :75
+
+    def descriptor(self):
+        return (self.kind, 0, self.max_2norm)
+
+    def evaluate(self, u):
+        u = np.asarray(u, dtype=float).ravel()
+        return float("inf") if np.sqrt(np.sum(u * u)) > self.max_2norm + TOL else 0
+
+    def prox(self, u, alpha=0):
+        u = np.asarray(u, dtype=float)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (self.max_2norm / np.sqrt(np.sum(u * u))) * u
+
+    def __repr__(self):
+        return f"QuadConstraint({self.max_2norm})"
+
+
+class NonNegOneReg(_VectorReg):  # :118-138
+    """scale * sum(a) on the nonnegative orthant (sparse NNMF).  ``prox`` is max(u - alpha, 0): the reference leaves ``scale`` out of it
+    (:122); ``mul_`` is a no-op (:138) and ``newscale * r`` is ``NonNegOneReg()``, which resets the parameter to 1 (:40,:121)."""
+    kind = NONNEG_ONE
+
+    def __init__(self, scale=1):
+        object.__setattr__(self, "param", float(scale))
+        _bump_epoch()
+
+    scale = property(lambda self: 1.0)  # scale(r::NonNegOneReg) = 1 (:137); the struct field is `param` here
+
+    def descriptor(self):
+        return (self.kind, 0, self.param)
+
+    def evaluate(self, a):
+        a = np.asarray(a, dtype=float).ravel()
+        return float("inf") if np.any(a < 0) else self.param * float(np.sum(a))
+
+    def prox(self, u, alpha):
+        return np.maximum(np.asarray(u, dtype=float) - alpha, 0)
+
+    def __repr__(self):
+        return f"NonNegOneReg({self.param})"
+
+
+class OneSparseConstraint(_VectorReg):  # :235-255
+    """Indicator of vectors with at most one nonzero entry (orthogonal NNMF).  ``prox`` keeps the first LARGEST SIGNED entry (argmax u, not
+    argmax |u|, :237); ``mul_`` is a no-op (:255) and ``newscale * r`` is a fresh ``OneSparseConstraint()`` (:40)."""
+    kind = ONE_SPARSE
+
+    def __init__(self):
+        pass
+
+    scale = property(lambda self: 1.0)
+
+    def descriptor(self):
+        return (self.kind, 0, 1.0)
+
+    def evaluate(self, a):
+        return float("inf") if np.count_nonzero(np.asarray(a, dtype=float)) > 1 else 0
+
+    def prox(self, u, alpha=0):
+        u = np.asarray(u, dtype=float)
+        v = np.zeros_like(u)
+        i = int(np.argmax(u))
+        v.flat[i] = u.flat[i]
+        return v
+
+    def __repr__(self):
+        return "OneSparseConstraint()"
+
+
+class KSparseConstraint(_VectorReg):  # :258-291
+    """Indicator of vectors with at most r nonzero entries.  ``prox`` keeps the r entries of largest |u|; among equal |u| the lower index
+    stays (the reference's partialsortperm leaves ties open).  The reference defines neither ``scale`` nor ``mul!`` nor a zero-argument
+    constructor for it: ``mul_`` is a no-op here and ``newscale * r`` raises, like ``typeof(r)()`` does (:40)."""
+    kind = K_SPARSE
+
+    def __init__(self, k):
+        if int(k) != k:
+            raise TypeError("KSparseConstraint(k): k::Int")
+        object.__setattr__(self, "k", int(k))
+        _bump_epoch()
+
+    scale = property(lambda self: 1.0)
+
+    def __rmul__(self, newscale):
+        raise TypeError("no method matching KSparseConstraint() (src/regularizers.jl:40)")
+
+    def descriptor(self):
+        return (self.kind, 0, float(self.k))
+
+    def evaluate(self, a):
+        return float("inf") if np.count_nonzero(np.asarray(a, dtype=float)) > self.k else 0
+
+    def prox(self, u, alpha=0):
+        u = np.asarray(u, dtype=float)
+        ids = np.argsort(-np.abs(u.ravel()), kind="stable")[: self.k]
+        if len(ids) < self.k:
+            raise IndexError("KSparseConstraint: k exceeds the length of the vector (BoundsError)")
+        v = np.zeros_like(u)
+        v.flat[ids] = u.flat[ids]
+        return v
+
+    def __repr__(self):
+        return f"KSparseConstraint({self.k})"
+
+
+class SimplexConstraint(_VectorReg):  # :323-348
+    """Indicator of the probability simplex (soft k-means).  ``prox`` is Chen & Ye's projection exactly as the reference computes it: sort
+    descending, SEQUENTIAL cumulative sum, first index whose running threshold reaches the next entry (:325-337); ``mul_`` is a no-op
+    (:348) and ``newscale * r`` is a fresh ``SimplexConstraint()`` (:40)."""
+    kind = SIMPLEX
+
+    def __init__(self):
+        pass
+
+    scale = property(lambda self: 1.0)
+
+    def descriptor(self):
+        return (self.kind, 0, 1.0)
+
+    def evaluate(self, a):
+        a = np.asarray(a, dtype=float).ravel()
+        if abs(float(np.sum(a)) - 1) > TOL:
+            return float("inf")
+        return float("inf") if np.any(a < 0) else 0
+
+    def prox(self, u, alpha=0):
+        u = np.asarray(u, dtype=float)
+        y = np.sort(u.ravel())[::-1]
+        n = len(y)
+        ysum = 0.0
+        t = None
+        for i in range(n):  # ysum = y[0] + ... + y[i-1], one term per step
+            if i >= 1 and (ysum - 1) / i >= y[i]:
+                t = (ysum - 1) / i
+                break
+            ysum += float(y[i])
+        if t is None:
+            t = (ysum - 1) / n
+        return np.maximum(u - t, 0)
+
+    def __repr__(self):
+        return "SimplexConstraint()"
+
+
 # ------------------------------------------------------------------------- wrappers / block regularizers
 WRAP_LASTENTRY1, WRAP_LASTENTRY_UNPENALIZED, WRAP_ORDINAL, WRAP_MNL_ORDINAL = 1, 2, 4, 8
 
 
 class _Wrapper(Regularizer):
-    """A regularizer around a base regularizer r (one of the five above).  Arrays are k-vectors or k x d blocks
+    """A regularizer around a base regularizer r (one of the kinds above).  Arrays are k-vectors or k x d blocks
     (first axis = latent component), like the views the reference passes."""
     wrap = 0
 
