@@ -78,3 +78,21 @@ mkpath(ARGS[3])
 for f in (isdir(ARGS[2]) ? sort(filter(x -> endswith(x, ".bin"), readdir(ARGS[2]; join=true))) : [ARGS[2]])
     crosscheck(f, ARGS[3])
 end
+
+# ---- init_kmeanspp! (src/initialize.jl:8-33) against hip_init_kmeanspp! (julia/HipGLRMInit.jl) under ONE seeded generator:
+#   julia julia/crosscheck.jl /path/to/LowRankModels.jl tests/golden/bin tests/golden/ref kmeanspp
+# UNVERIFIED: like the rest of this file it has never run (no julia binary in the build image or on the GPU box).  The comparison rests on
+# two things that were recalled, not read (StatsBase is not part of the reference tree): sample(1:m) consumes the generator like
+# rand(1:m), and wsample(1:m, w) consumes exactly ONE rand() -- t = rand() * sum(w), then the walk `while cw < t && i < m` that
+# include/glrm_hip_init.h describes.  If either is wrong the two Y differ from the first centre on and this block says so.
+if length(ARGS) >= 4 && ARGS[4] == "kmeanspp"
+    include(joinpath(@__DIR__, "HipGLRM.jl")); include(joinpath(@__DIR__, "HipGLRMInit.jl"))
+    using Random, .HipGLRM, .HipGLRMInit
+    A = [randn(MersenneTwister(1), 100, 2) .+ 5; randn(MersenneTwister(2), 50, 2) .- 5]     # the two blobs of test/runtests.jl:19-25
+    for k in (2, 5)
+        ref = GLRM(A, QuadLoss(), ZeroReg(), ZeroReg(), k); dev = GLRM(copy(A), QuadLoss(), ZeroReg(), ZeroReg(), k)
+        Random.seed!(20261017); init_kmeanspp!(ref)
+        Random.seed!(20261017); hip_init_kmeanspp!(dev)                                      # rng = Random.default_rng(): the same stream
+        println("init_kmeanspp! k = $k: Y ", ref.Y == dev.Y ? "bit-equal" : "DIFFERS (max abs $(maximum(abs.(ref.Y .- dev.Y))))")
+    end
+end

@@ -150,6 +150,9 @@ ABI_SYMBOLS = (
 #: (the HIP engine; the CPU oracle does not restate it)
 SCALE_SYMBOLS = ("scale_columns",)
 
+#: the initialization extension, include/glrm_hip_init.h: outside the boundary as well, bound only where the library has it
+INIT_SYMBOLS = ("init_kmeanspp",)
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -242,8 +245,9 @@ class Api:
             self._f[name] = fn
         ext = {
             "scale_columns": (C.c_int, [C.POINTER(CProblem), C.POINTER(COptions), C.c_int32] + [C.c_void_p] * 5),
+            "init_kmeanspp": (C.c_int, [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -496,6 +500,31 @@ class Api:
         if diagnostics:
             return out[0], out[1], dict(m_est=out[2], avg_loss=out[3], variance=out[4])
         return out[0], out[1]
+
+    # -- initialization extension (include/glrm_hip_init.h) ---------------------------------
+    def init_kmeanspp(self, h, Y, first, u, want_weights=False, m=None):
+        """glrm_hip_init_kmeanspp on the handle's resident lists.  ``Y``: the randn(k, n) draw, Fortran-ordered float64, overwritten
+        with the initialized factor; ``first``: the 0-based first centre; ``u``: the k-1 uniform draws of the rounds.  Returns
+        (centers, weights): the k chosen rows and, with ``want_weights`` (which needs ``m``, the rows of the handle's problem), the
+        (k-1) x m array of every round's sampling weights (else None)."""
+        fn = self._f.get("init_kmeanspp")
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}init_kmeanspp: this engine does not have the initialization extension "
+                                             "(include/glrm_hip_init.h is implemented by the HIP engine only)")
+        if not (isinstance(Y, np.ndarray) and Y.dtype == np.float64 and Y.ndim == 2 and Y.flags.f_contiguous):
+            raise ValueError("Y must be a Fortran-ordered float64 k x n array (it is overwritten in place)")
+        k, n = Y.shape
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if len(u) != k - 1:
+            raise ValueError(f"u must hold k - 1 = {k - 1} draws, got {len(u)}")
+        centers = np.full(k, -1, dtype=np.int64)
+        weights = None
+        if want_weights:
+            if m is None:
+                raise ValueError("want_weights needs m, the number of rows of the handle's problem (the buffer is (k-1) x m)")
+            weights = np.full((k - 1, int(m)), np.nan)
+        self._ck(fn(h, _ptr(Y), int(first), _ptr(u) if k > 1 else None, _ptr(centers), _ptr(weights) if k > 1 else None))
+        return centers, weights
 
 
 class ProblemArrays:
