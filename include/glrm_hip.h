@@ -241,7 +241,10 @@ typedef struct glrm_options {
                         gather per observation and pass); exists so that a checker can hold the engine against the REFERENCE-order
                         oracle to rounding on trajectories that amplify summation order.  Scalar losses, list
                         problems. */
-  int32_t reserved0; /* must be 0 */
+  int32_t storage;   /* SURVEY.md section 8(b) fp32 storage.  0 = GLRM_STORAGE_F64: A, X and Y are stored as doubles.  1 = GLRM_STORAGE_F32: they
+                        are stored as floats and every sum, loss, regularizer and line-search decision stays fp64 (gather sweeps only;
+                        include/glrm_hip_storage.h has the contract and the list of what such a handle refuses).  Anything else is
+                        GLRM_ERR_INVALID.  Default 0. */
   int32_t reserved;  /* must be 0 */
 } glrm_options; /* 48 bytes */
 
@@ -314,6 +317,8 @@ int glrm_hip_objective(glrm_handle* h, const double* X, const double* Y, int inc
  *   row_penalties -> dObjRow[row_begin:row_end]    (rx_e(x_e))
  *   col_penalties -> dObjCol[col_begin:col_end]    (ry_f(y_f))
  * All launches are asynchronous on the handle's stream.
+ * On a glrm_options.storage = 1 handle dX and dY are FLOAT buffers of ld*m and ld*n elements (same ld, same zero padding);
+ * dObjCol and dObjRow stay doubles (include/glrm_hip_storage.h).
  */
 int glrm_hip_factor_ld(glrm_handle* h);
 int glrm_hip_bind_buffers(glrm_handle* h, void* dX, void* dY, void* dObjCol, void* dObjRow);

@@ -14,11 +14,11 @@ hip_release!(glrm::GLRM) = (haskey(CACHE, glrm) && (destroy(CACHE[glrm]); delete
 # what the device copy depends on (data, Omega, losses, placement, options) / what set_regularizers can replace
 hardkey(glrm, desc, p, dense) = hash((objectid(glrm.A), size(glrm.A), glrm.k, objectid(glrm.observed_features), objectid(glrm.observed_examples),
                                       sum(length, glrm.observed_features), sum(length, glrm.observed_examples), desc[1], length(desc[2]), length(desc[3]),
-                                      p.device_id, p.ngpus, p.device_ids, p.exchange, p.x_chunks, dense, p.quad_gram, p.mode))
+                                      p.device_id, p.ngpus, p.device_ids, p.exchange, p.x_chunks, dense, p.quad_gram, p.mode, p.storage))
 softkey(desc) = hash((desc[2], desc[3]))
 
 function handle(glrm::GLRM, desc, p)
-    dense = dense_ok(glrm, desc, p); multi = p.ngpus > 1
+    dense = dense_ok(glrm, desc, p) && p.storage == :f64; multi = p.ngpus > 1   # (float storage runs on the observation lists)
     hard, soft = hardkey(glrm, desc, p, dense), softkey(desc)
     e = get(CACHE, glrm, nothing)
     if e !== nothing && e.hard == hard

@@ -73,10 +73,11 @@ class CSparseParams(C.Structure):
 class COptions(C.Structure):
     _fields_ = [("device_id", C.c_int32), ("profile", C.c_int32), ("waves_row", C.c_int32), ("waves_col", C.c_int32),
                 ("stream", C.c_void_p), ("caller_stream", C.c_int32), ("tiled", C.c_int32), ("quad_gram", C.c_int32),
-                ("sum_order", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_int32)]
+                ("sum_order", C.c_int32), ("storage", C.c_int32), ("reserved", C.c_int32)]
 
 
-assert C.sizeof(COptions) == 48
+assert C.sizeof(COptions) == 48 and COptions.storage.offset == 40
+STORAGE_F64, STORAGE_F32 = 0, 1   # include/glrm_hip_storage.h: glrm_options.storage
 
 
 class CArrival(C.Structure):
@@ -152,6 +153,9 @@ SCALE_SYMBOLS = ("scale_columns",)
 
 #: the initialization extension, include/glrm_hip_init.h: outside the boundary as well, bound only where the library has it
 INIT_SYMBOLS = ("init_kmeanspp",)
+
+#: the storage extension, include/glrm_hip_storage.h (fp32 storage of A, X and Y): outside the boundary, bound only where the library has it
+STORAGE_SYMBOLS = ("storage",)
 
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
@@ -246,8 +250,9 @@ class Api:
         ext = {
             "scale_columns": (C.c_int, [C.POINTER(CProblem), C.POINTER(COptions), C.c_int32] + [C.c_void_p] * 5),
             "init_kmeanspp": (C.c_int, [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "storage": (C.c_int, [H]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -282,20 +287,22 @@ class Api:
         return p
 
     def create(self, prob: "ProblemArrays", device_id=-1, profile=0, waves_row=0, waves_col=0, stream=None, tiled=0, quad_gram=0, defer=False,
-               sum_order=0):
+               sum_order=0, storage=0):
         """``stream=None``: the handle creates a private stream.  ``stream=<int>``: launch on exactly that
         hipStream_t -- 0 is the legacy default stream (what torch.cuda.current_stream().cuda_stream returns
         for the default stream), so kernels stay ordered with the caller's other work on it.
         ``defer=True`` (one shard of a sharded fit): only upload; the host combines :meth:`signature` over the shards and
         calls :meth:`finalize` on every one of them (GLRM_PROBLEM_DEFER_SETUP).
-        ``sum_order=1``: the reference-order validation sweeps (glrm_options.sum_order)."""
+        ``sum_order=1``: the reference-order validation sweeps (glrm_options.sum_order).
+        ``storage=1``: A, X and Y stored as floats on the gather sweeps, arithmetic in fp64 (glrm_options.storage,
+        include/glrm_hip_storage.h); the factors cross this boundary as float64 arrays either way."""
         if prob.dense_A is not None and not self.dense_ok:
             raise GLRMError(ERR_UNSUPPORTED, "this engine takes observation lists only")
         p = self._cproblem(prob)
         if defer:
             p.flags |= PROBLEM_DEFER_SETUP
         o = COptions(device_id, profile, waves_row, waves_col, (stream or None), 0 if stream is None else 1, tiled, int(quad_gram), int(sum_order),
-                     0, 0)
+                     int(storage), 0)
         h = C.c_void_p()
         self._ck(self._f["create"](C.byref(h), C.byref(p), C.byref(o)))
         return h
@@ -310,12 +317,12 @@ class Api:
 
     # -- one process, several devices (glrm_*_multi_*) -----------------------------------------
     def multi_create(self, prob: "ProblemArrays", n_shards, device_ids=None, exchange=0, x_chunks=0, profile=0, waves_row=0,
-                     waves_col=0, tiled=0, quad_gram=0, arrival=0, sum_order=0):
+                     waves_col=0, tiled=0, quad_gram=0, arrival=0, sum_order=0, storage=0):
         """The whole problem (host arrays), sharded by the library over ``device_ids`` (default 0..n_shards-1; ids may repeat)."""
         if prob.dense_A is not None and not self.dense_ok:
             raise GLRMError(ERR_UNSUPPORTED, "this engine takes observation lists only")
         p = self._cproblem(prob)
-        o = COptions(-1, profile, waves_row, waves_col, None, 0, tiled, int(quad_gram), int(sum_order), 0, 0)
+        o = COptions(-1, profile, waves_row, waves_col, None, 0, tiled, int(quad_gram), int(sum_order), int(storage), 0)  # (storage = 1 is refused)
         ids = None if device_ids is None else np.ascontiguousarray(device_ids, dtype=np.int32)
         if ids is not None and len(ids) != n_shards:
             raise ValueError("device_ids must have n_shards entries")
@@ -481,8 +488,19 @@ class Api:
         self._ck(self._f["sum_order"](h, int(which), C.byref(o)))
         return o
 
+    # -- storage extension (include/glrm_hip_storage.h) -------------------------------------
+    def storage(self, h) -> int:
+        """glrm_hip_storage: STORAGE_F64 or STORAGE_F32 (an engine without the extension stores fp64)."""
+        fn = self._f.get("storage")
+        if fn is None:
+            return STORAGE_F64
+        s = fn(h)
+        if s < 0:
+            raise GLRMError(s, self.last_error())
+        return s
+
     # -- scaling extension (include/glrm_hip_scale.h) ---------------------------------------
-    def scale_columns(self, prob: "ProblemArrays", mode, device_id=-1, stream=None, diagnostics=False):
+    def scale_columns(self, prob: "ProblemArrays", mode, device_id=-1, stream=None, diagnostics=False, storage=0):
         """glrm_hip_scale_columns on the column view of ``prob`` (its row view may be None): the NEW loss and Y-regularizer scales of the
         columns [col_begin, col_end) under equilibrate_variance! (``SCALE_EQUILIBRATE``) or prob_scale! (``SCALE_PROB``).  Returns
         (loss_scale, ry_scale), with ``diagnostics`` also a dict of the per-column m_est / avg_loss / variance."""
@@ -491,7 +509,7 @@ class Api:
             raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}scale_columns: this engine does not have the scaling extension "
                                              "(include/glrm_hip_scale.h is implemented by the HIP engine only)")
         p = self._cproblem(prob)
-        o = COptions(device_id, 0, 0, 0, (stream or None), 0 if stream is None else 1, 0, 0, 0, 0, 0)
+        o = COptions(device_id, 0, 0, 0, (stream or None), 0 if stream is None else 1, 0, 0, 0, int(storage), 0)  # (storage = 1 is refused)
         nl = prob.col_end - prob.col_begin
         out = [np.full(max(nl, 1), np.nan) for _ in range(5 if diagnostics else 2)]
         ptrs = [_ptr(x) for x in out] + [None] * (5 - len(out))

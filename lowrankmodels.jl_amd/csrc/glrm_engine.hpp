@@ -7,6 +7,7 @@
 //   glrm_transpose.hip  row view from column view   glrm_subset.hip     child handles (cross-validation)
 //   glrm_svd.hip        SVD initialisation          glrm_impute.hip     imputation
 //   glrm_multigpu.hip   sharded fits                glrm_testhooks.hip  test hooks (constant in the product library)
+//   glrm_storage.hip    fp32 storage: the float gather sweeps, narrowing / widening copies (include/glrm_hip_storage.h)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 #pragma once
 
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/glrm_hip.h"
+#include "../../include/glrm_hip_storage.h"
 
 // kernel variants by loss model.  The *_NOTRIG variants are compiled without PeriodicLoss (its sin / cos with full range reduction
 // costs ~60 VGPRs of pressure in every kernel that merely CONTAINS the case); models without a PeriodicLoss column use them.
@@ -168,6 +170,9 @@ struct glrm_handle {
   std::vector<int> sup_order;
   double ms_wait = 0;                 // profile: time the launch stream stood in those waits
   int sum_order_opt = 0;              // glrm_options.sum_order (1: reference-order validation sweeps, glrm_reforder.hip)
+  // glrm_options.storage.  GLRM_STORAGE_F32: rowvals / colvals / X / Y / oX / oY below hold FLOATS behind their double* type (the same
+  // element counts); only the float gather sweeps and the copy kernels of glrm_storage.hip read them, every other family is refused.
+  int storage = 0;
   // hipGraph of one outer iteration (gather sweeps on a private stream): small fits are launch bound
   hipGraph_t iter_graph = nullptr;
   hipGraphExec_t iter_exec = nullptr;
@@ -239,6 +244,19 @@ int glrm_setup_reforder(glrm_handle* h);               // finalize: refuses what
 int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
 int glrm_reforder_sum(glrm_handle* h, const void* dvec, int64_t n, double* out); // Julia's pairwise sum(::Vector{Float64})
 int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out);       // objective(): ONE accumulator over all observations, then the penalties
+
+// fp32 storage (glrm_storage.hip).  An entry point that reads fp64 lists or factors refuses a float handle before it touches it:
+#define GLRM_REFUSE_F32(h, what) \
+  do { if ((h) && (h)->storage == GLRM_STORAGE_F32) return fail(GLRM_ERR_UNSUPPORTED, "%s is not available with storage = f32 (glrm_options.storage = 1): %s", what, "it reads or reverts fp64 lists and factors"); } while (0)
+namespace glrm { struct SweepArgs; }
+int glrm_check_storage(const glrm_problem* p, const glrm_options* o);   // create: the option's range and everything a float handle refuses
+int glrm_check_storage_regs(const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry); // wrapped / vector regularizers
+int glrm_narrow_views(glrm_handle* h);                                  // end of create: rowvals / colvals double -> float arrays of the handle's own
+int glrm_narrow_factor(glrm_handle* h, const double* host, void* dev, int64_t nvec); // host k x nvec doubles -> device floats, ld kp, zero padded
+int glrm_widen_factor(glrm_handle* h, const void* dev, double* host, int64_t nvec);  // and back
+int glrm_check_narrowable(const char* name, const double* v, int64_t n);             // GLRM_ERR_NONFINITE for a finite value beyond float's range
+void glrm_launch_sweep_f32(int G, int R, int waves, int loss, bool rows, const glrm::SweepArgs& a, hipStream_t st);
+void glrm_launch_penalty_f32(glrm_handle* h, bool rows);
 
 // GLRM_PROBLEM_ROWS_FROM_COLS (glrm_transpose.hip): the row view derived on the device from the uploaded column view
 int glrm_rows_from_cols(glrm_handle* h);

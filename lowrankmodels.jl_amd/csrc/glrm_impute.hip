@@ -133,6 +133,7 @@ int prepare(glrm_handle* h, const double* X, const double* Y, const glrm_domain*
 
 extern "C" int glrm_hip_error_metric(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, int32_t standardize, double* out) {
   if (!h || !X || !Y || !domains || !out) return fail(GLRM_ERR_INVALID, "NULL argument");
+  GLRM_REFUSE_F32(h, "glrm_hip_error_metric");
   if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   EvalArgs a{};
   glrm_domain* ddom = nullptr;
@@ -169,6 +170,7 @@ extern "C" int glrm_hip_error_metric(glrm_handle* h, const double* X, const doub
 
 extern "C" int glrm_hip_impute(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, double* Ahat) {
   if (!h || !X || !Y || !domains || !Ahat) return fail(GLRM_ERR_INVALID, "NULL argument");
+  GLRM_REFUSE_F32(h, "glrm_hip_impute");
   if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   EvalArgs a{};
   glrm_domain* ddom = nullptr;

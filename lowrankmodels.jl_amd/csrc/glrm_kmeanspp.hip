@@ -239,6 +239,7 @@ struct KmWork {
 
 extern "C" int glrm_hip_init_kmeanspp(glrm_handle* h, double* Y, int64_t first_center, const double* u, int64_t* centers, double* weights) {
   if (!h) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp: NULL handle");
+  GLRM_REFUSE_F32(h, "glrm_hip_init_kmeanspp");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_init_kmeanspp works on the observation lists (create the handle without dense_A)");
   if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp needs a single-shard handle");
   if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");

@@ -661,6 +661,8 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
 extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, const glrm_options* o, const glrm_multi_options* mo) {
   if (!out || !p || !mo) return fail(GLRM_ERR_INVALID, "NULL argument");
   *out = nullptr;
+  if (o && o->storage == GLRM_STORAGE_F32) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_multi_create is not available with storage = f32 (glrm_options.storage = 1): sharded fits have no f32 form");
+  if (o && o->storage != GLRM_STORAGE_F64) return fail(GLRM_ERR_INVALID, "glrm_options.storage must be 0 (f64) or 1 (f32), got %d", o->storage);
   if ((p->flags & GLRM_PROBLEM_ROWS_FROM_COLS) && !(p->flags & GLRM_PROBLEM_DEVICE_ARRAYS)) {
     // Omega is a sparse matrix's pattern, handed over as its column view only: every shard needs its rows' lists, so the row view is
     // built here, once, by a counting transpose on the host (columns in order => every row's list ascending), and the shards are cut

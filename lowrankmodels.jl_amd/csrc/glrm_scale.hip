@@ -281,6 +281,8 @@ extern "C" int glrm_hip_scale_columns(const glrm_problem* p, const glrm_options*
                                       double* m_est, double* avg_loss, double* variance) {
   if (!p) return fail(GLRM_ERR_INVALID, "glrm_hip_scale_columns: NULL problem");
   if (!loss_scale || !ry_scale) return fail(GLRM_ERR_INVALID, "glrm_hip_scale_columns: loss_scale / ry_scale are NULL");
+  if (o && o->storage == GLRM_STORAGE_F32)
+    return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_scale_columns is not available with storage = f32 (glrm_options.storage = 1): it reads the fp64 column lists");
   if (mode != GLRM_SCALE_EQUILIBRATE && mode != GLRM_SCALE_PROB)
     return fail(GLRM_ERR_INVALID, "glrm_hip_scale_columns: mode must be GLRM_SCALE_EQUILIBRATE (0) or GLRM_SCALE_PROB (1), got %d", (int)mode);
   if (p->dense_A)

@@ -156,6 +156,7 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
                                glrm_handle** out) {
   if (!parent || !out) return fail(GLRM_ERR_INVALID, "NULL argument");
   *out = nullptr;
+  GLRM_REFUSE_F32(parent, "glrm_hip_subset");
   if (parent->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_subset needs a list (not dense) parent handle");
   if (!parent->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
   if ((parent->nnz_r > 0 && !row_tags) || (parent->nnz_c > 0 && !col_tags)) return fail(GLRM_ERR_INVALID, "NULL tag array");

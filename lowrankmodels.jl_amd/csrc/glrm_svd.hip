@@ -356,6 +356,7 @@ int orthonormalize(Work& w, double* Z, int64_t nrows, std::vector<double>* ritz 
 extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t max_iter, double tol, uint64_t seed, double* singular_values,
                                  int32_t* iters_done) {
   if (!h || !X || !Y) return fail(GLRM_ERR_INVALID, "NULL argument");
+  GLRM_REFUSE_F32(h, "glrm_hip_init_svd");
   if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_svd needs a single-shard handle");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_init_svd works on the observation lists (create the handle without dense_A)");
   if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");

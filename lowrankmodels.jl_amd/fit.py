@@ -25,7 +25,15 @@ def _engine_opts(params):
     g = lambda k, d: getattr(params, k, d)
     return dict(device_id=g("device_id", -1), profile=1 if g("profile", False) else 0,
                 waves_row=g("waves_row", 0), waves_col=g("waves_col", 0), tiled=g("tiled", 0), quad_gram=1 if g("quad_gram", False) else 0,
-                sum_order=1 if g("mode", "fast") == "reference_order" else 0)
+                sum_order=1 if g("mode", "fast") == "reference_order" else 0, storage=_storage_opt(params))
+
+
+def _storage_opt(params):
+    """glrm_options.storage of a params object (validated here as well: params are plain objects whose fields may have been assigned)."""
+    s = getattr(params, "storage", "f64")
+    if s not in ("f64", "f32"):
+        raise ValueError("storage must be 'f64' or 'f32'")
+    return _capi.STORAGE_F32 if s == "f32" else _capi.STORAGE_F64
 
 
 def _should_stop(i, prev, obj, scaled_abs_tol, rel_tol):
@@ -59,9 +67,11 @@ def _ensure_handle(glrm, api, params, allow_dense=True):
     """The model's engine handle (created on first use, kept on the model: Omega and A stay on the device across fit! calls,
     README.md:337-346 warm starts, cross-validation drivers).  A change of the regularizers only replaces the descriptors
     (scale_regularizer!, regularization_path).  Returns (handle, hard key, soft key)."""
-    use_dense = allow_dense and api.dense_ok and glrm.dense_eligible() and getattr(params, "dense", True)
+    opts = _engine_opts(params)
+    # (fp32 storage runs on observation lists: a fully observed model is handed over as lists, not as dense_A)
+    use_dense = allow_dense and api.dense_ok and glrm.dense_eligible() and getattr(params, "dense", True) and not opts["storage"]
     hard, soft = glrm._descriptor_key()
-    key = (id(api), _engine_opts(params)["device_id"], _engine_opts(params)["quad_gram"], _engine_opts(params)["sum_order"], hard)
+    key = (id(api), opts["device_id"], opts["quad_gram"], opts["sum_order"], opts["storage"], hard)
     cache = glrm._handle_cache
     if cache is not None and (cache[2] != key or cache[4] != use_dense):
         glrm.close()
@@ -99,6 +109,8 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             world = dist.get_world_size(group)
+    if _storage_opt(params) and (world > 1 or getattr(params, "ngpus", 1) > 1):
+        raise ValueError("storage='f32' runs on one device: sharded and multi-GPU fits have no f32 form")
     if world > 1:
         if sparse:
             raise NotImplementedError("SparseProxGradParams runs on a single shard (step-level gradstep_x / gradstep_y exist for hosts)")

@@ -38,13 +38,23 @@ class HipProxGradParams(ProxGradParams):
     factor samples equal the reference-order oracle's to the last bit (tests/test_gpu_jref.py)."""
 
     def __init__(self, stepsize=1.0, *, device_id=-1, profile=False, waves_row=0, waves_col=0, tiled=0, dense=True, ngpus=1,
-                 device_ids=None, exchange="direct", x_chunks=0, quad_gram=False, mode="fast", **kw):
+                 device_ids=None, exchange="direct", x_chunks=0, quad_gram=False, mode="fast", storage="f64", **kw):
         super().__init__(stepsize, **kw)
         # SURVEY.md 8(b) `mode` / `line_search_sum_order`: "fast" = the engine's summation orders; "reference_order" = the validation
         # sweeps that add every sum like the reference does (glrm_options.sum_order = 1: scalar losses, list problems, k <= 64; slow)
         if mode not in ("fast", "reference_order"):
             raise ValueError("mode must be 'fast' or 'reference_order'")
         self.mode = mode
+        # SURVEY.md 8(b) fp32 storage (glrm_options.storage, include/glrm_hip_storage.h): "f32" stores A, X and Y as floats on the gather
+        # sweeps and keeps every sum and the line search in fp64.  One device, fast mode, scalar losses, scales and element-wise
+        # regularizers; the engine refuses everything else (a GLRMError) -- there is no fallback to fp64.
+        if storage not in ("f64", "f32"):
+            raise ValueError("storage must be 'f64' or 'f32'")
+        if storage == "f32" and mode == "reference_order":
+            raise ValueError("storage='f32' has no reference-order mode (mode must be 'fast')")
+        if storage == "f32" and int(ngpus) > 1:
+            raise ValueError("storage='f32' runs on one device (ngpus must be 1)")
+        self.storage = storage
         # fully observed QuadLoss models only (glrm_options.quad_gram, SURVEY.md 7.2 K5): line-search trials from the quadratic form
         # J(x) + g.s + scale s'(YY')s instead of another pass over A; same iterates up to rounding.  Off by default.
         self.quad_gram = bool(quad_gram)
