@@ -441,23 +441,27 @@ __global__ void __launch_bounds__(WAVES * 64) regcached_sweep_kernel(const Cache
   }
 }
 
-// ---- persistent form: a workgroup walks rows slot, slot + gridDim.x, ... and hands the NEXT row's (index, value) list over while it
-// works on the current one.  In the one-row-per-workgroup kernel above a row's life is three dependent memory round trips -- row pointer
-// -> list -> opposing vectors -- before the first FMA, with two waves per SIMD to hide them (244 VGPRs).  Here the pointers of the next
-// row are scalar loads issued one row ahead, its list is requested right behind the current row's gathers (3 * PF dwords per lane, the
-// only extra registers) and reaches the lanes through LDS after the current row's passes: the chain per row is ONE round trip, the
-// gathers.  Which lane group adds which observation, and in which order, is unchanged: same bits as the kernel above.
+// ---- persistent form: a workgroup walks rows slot, slot + gridDim.x, ... and hands the NEXT row's record -- its (index, value) list and
+// its stored stepsize -- over while it works on the current one.  In the one-row-per-workgroup kernel above a row's life is three
+// dependent memory round trips -- row pointer -> list -> opposing vectors -- before the first FMA, a fourth for the stepsize between the
+// gradient pass and the first trial, and two more for the counters at its end, with two waves per SIMD to hide them (244 VGPRs).  Here
+// the pointers of the next row are scalar loads issued one row ahead; its list and stepsize are requested right behind the current row's
+// gathers (3 * PF + 2 dwords per lane, live until the gradient pass has been combined) and reach the lanes through the OTHER of two
+// record buffers in LDS; the counters are result-less atomic adds.  The chain per row is ONE round trip, the gathers, and a row ends
+// with its stores and one barrier: nothing waits for a store.  Which lane group adds which observation, and in which order, is
+// unchanged: same bits as the kernel above.
+// Reading alpha[seg_n] a row early is safe: a row's stepsize is written once per launch, by the workgroup that owns the row (the long
+// rows on the gather sweep write only their own), so until this workgroup reaches the row nobody has written it.
 template <int G, int R, int LOSS, int MAXT, bool VR = false>
 __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedArgs a) {
   constexpr int WAVES = 2, KP = G * R, NG = (64 / G) * WAVES, MAXLEN = MAXT * NG, PF = (MAXLEN + 127) / 128;
   // ONE shared array (a second __shared__ object makes hipcc drain the load queue before every LDS read, cdna_hip_programming.md):
-  // [combine buffer: WAVES * (KP + 2) doubles][values: PF * 128 doubles][indices: PF * 128 ints]
-  constexpr int RED = WAVES * (KP + 2);
-  __shared__ __attribute__((aligned(16))) double sh[RED + PF * 128 + PF * 64];
+  // [combine buffer: WAVES * (KP + 2) doubles] 2 x [values: PF * 128 doubles][stepsize: 128 doubles][indices: PF * 128 ints]
+  // (the stepsize once per thread: every thread parks the copy it loaded and takes it back itself, so no thread skips the wait for its
+  // loads -- with one writer the others would reach the end of the row with a load the compiler still counts, and wait there)
+  constexpr int RED = WAVES * (KP + 2), REC = PF * 128 + 128 + PF * 64;
+  __shared__ __attribute__((aligned(16))) double sh[RED + 2 * REC];
   double* red = sh;
-  double* lvals = sh + RED;
-  int* lidx = reinterpret_cast<int*>(sh + RED + PF * 128);
-  int* lvals_dw = reinterpret_cast<int*>(lvals);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane % G, gi = wave * (64 / G) + lane / G;
   const RegDesc rd0 = load_reg(a.regs, 0);
@@ -465,9 +469,22 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
   if constexpr (loss_mode(LOSS) != LOSS_PER_OBS) segloss = load_loss(a.losses, 0);
   const double2* __restrict__ other2 = reinterpret_cast<const double2*>(a.other);
 
-  // segment of a slot (-1: none / filtered out), its list
-  auto seg_of = [&](int64_t slot) -> int64_t { return cached_segment(a, slot); };
-  auto fetch_list = [&](int64_t beg, int len, int (&pi)[PF], int (&pv)[2 * PF]) { // this lane's share of the row's list, clamped
+  // The row pointers and the row list are read through the constant address space: nothing writes them while the kernel runs, and a
+  // uniform load from there is a SCALAR load.  As ordinary global loads they come out as vector loads inside the row loop (the loop's
+  // stores might alias them), each waited for on the spot -- a round trip at the head of every row that also drains the row's stores.
+  const auto* kptr = (const __attribute__((address_space(4))) int64_t*)a.ptr;
+  const auto* klist = (const __attribute__((address_space(4))) int32_t*)a.seglist;
+  // segment of a slot (-1: none / filtered out; cached_segment), its record
+  auto seg_of = [&](int64_t slot) -> int64_t {
+    if (slot >= a.nseg) return -1;
+    if (!a.seglist) return slot;
+    const int64_t s = klist[slot];
+    return (s < a.seg_lo || s >= a.seg_hi) ? -1 : s;
+  };
+  auto rec_vals = [&](int buf) -> double* { return sh + RED + buf * REC; };
+  auto rec_alpha = [&](int buf) -> double* { return sh + RED + buf * REC + PF * 128; };
+  auto rec_idx = [&](int buf) -> int* { return reinterpret_cast<int*>(sh + RED + buf * REC + PF * 128 + 128); };
+  auto fetch_rec = [&](int64_t sg, int64_t beg, int len, int (&pi)[PF], int (&pv)[2 * PF], double& pa) { // this lane's share, clamped
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       int e = q * 128 + tid;
@@ -476,65 +493,90 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
       const int2 v = len > 0 ? *reinterpret_cast<const int2*>(a.vals + beg + e) : make_int2(0, 0);
       pv[2 * q] = v.x; pv[2 * q + 1] = v.y;
     }
+    pa = a.alpha[sg >= 0 ? sg : 0]; // an empty row still runs its line search; no row: some valid address, never used
   };
-  auto store_list = [&](const int (&pi)[PF], const int (&pv)[2 * PF]) {
+  auto store_rec = [&](int buf, const int (&pi)[PF], const int (&pv)[2 * PF], double pa) {
+    int* li = rec_idx(buf);
+    int* lv = reinterpret_cast<int*>(rec_vals(buf));
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
-      lidx[q * 128 + tid] = pi[q];
-      lvals_dw[2 * (q * 128 + tid)] = pv[2 * q];
-      lvals_dw[2 * (q * 128 + tid) + 1] = pv[2 * q + 1];
+      li[q * 128 + tid] = pi[q];
+      lv[2 * (q * 128 + tid)] = pv[2 * q];
+      lv[2 * (q * 128 + tid) + 1] = pv[2 * q + 1];
     }
+    rec_alpha(buf)[tid] = pa;
   };
 
   int64_t slot = blockIdx.x;
   int64_t seg = seg_of(slot), seg_n = seg_of(slot + gridDim.x);
-  int64_t beg = seg >= 0 ? a.ptr[seg] : 0, beg_n = seg_n >= 0 ? a.ptr[seg_n] : 0;
-  int len = seg >= 0 ? (int)(a.ptr[seg + 1] - beg) : 0, len_n = seg_n >= 0 ? (int)(a.ptr[seg_n + 1] - beg_n) : 0;
+  int64_t beg = seg >= 0 ? kptr[seg] : 0, beg_n = seg_n >= 0 ? kptr[seg_n] : 0; // (a.nseg >= 1: ptr[0] and ptr[1] exist)
+  int len = seg >= 0 ? (int)(kptr[seg + 1] - beg) : 0, len_n = seg_n >= 0 ? (int)(kptr[seg_n + 1] - beg_n) : 0;
   {
     int pi[PF], pv[2 * PF];
-    fetch_list(beg, len, pi, pv);
-    store_list(pi, pv);
+    double pa;
+    fetch_rec(seg, beg, len, pi, pv, pa);
+    store_rec(0, pi, pv, pa);
   }
   __syncthreads();
+  int cur = 0; // the record buffer of the current row; the next row's is written into the other one
   for (; slot < a.nseg; slot += gridDim.x) { // block-uniform
-    // the row after the next one: pointers only (scalar loads, consumed an iteration from now)
-    const int64_t seg_nn = seg_of(slot + 2 * (int64_t)gridDim.x);
-    const int64_t beg_nn = seg_nn >= 0 ? a.ptr[seg_nn] : 0;
-    const int len_nn = seg_nn >= 0 ? (int)(a.ptr[seg_nn + 1] - beg_nn) : 0;
-    int cc[MAXT];
-    double av[MAXT];
-    double2 y[MAXT][R / 2];
+    // the row after the next one: pointers only (scalar loads, consumed an iteration from now; issued behind the gathers, where the wait
+    // for them falls into the gathers' shadow)
+    int64_t seg_nn, beg_nn;
+    int len_nn;
+    auto next_pointers = [&] {
+      seg_nn = seg_of(slot + 2 * (int64_t)gridDim.x);
+      const int64_t p0 = kptr[seg_nn >= 0 ? seg_nn : 0], p1 = kptr[(seg_nn >= 0 ? seg_nn : 0) + 1];
+      beg_nn = seg_nn >= 0 ? p0 : 0;
+      len_nn = seg_nn >= 0 ? (int)(p1 - p0) : 0;
+    };
+    if (seg < 0) { // a slot the row range filters out: only the hand-over
+      int pi[PF], pv[2 * PF];
+      double pa;
+      fetch_rec(seg_n, beg_n, len_n, pi, pv, pa);
+      next_pointers();
+      store_rec(cur ^ 1, pi, pv, pa);
+    } else {
+      const double* lvals = rec_vals(cur);
+      const int* lidx = rec_idx(cur);
+      int cc[MAXT];
+      double av[MAXT];
+      double2 y[MAXT][R / 2];
 #pragma unroll
-    for (int t = 0; t < MAXT; ++t) { // the group's entries out of LDS (clamped: lanes past the end re-read the last entry and are masked)
-      int tt = t * NG + gi;
-      tt = tt < len ? tt : (len > 0 ? len - 1 : 0);
-      cc[t] = lidx[tt];
-      av[t] = lvals[tt];
-    }
-    const int64_t gseg = a.own_offset + (seg >= 0 ? seg : 0);
-    double2* ownp = reinterpret_cast<double2*>(a.own + gseg * KP);
-    Vec<G, R> x, g;
-#pragma unroll
-    for (int i = 0; i < R / 2; ++i) x.v[i] = ownp[i * G + j];
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t) {
-      if (t * NG + wave * (64 / G) < len) { // wave-uniform
-        const double2* yp = other2 + (int64_t)cc[t] * (KP / 2) + j;
-#pragma unroll
-        for (int i = 0; i < R / 2; ++i) y[t][i] = yp[i * G];
-      } else {
-#pragma unroll
-        for (int i = 0; i < R / 2; ++i) y[t][i] = make_double2(0.0, 0.0);
+      for (int t = 0; t < MAXT; ++t) { // the group's entries out of LDS (clamped: lanes past the end re-read the last entry and are masked)
+        int tt = t * NG + gi;
+        tt = tt < len ? tt : (len > 0 ? len - 1 : 0);
+        cc[t] = lidx[tt];
+        av[t] = lvals[tt];
       }
-    }
-    // the next row's list rides behind the gathers
-    int pi[PF], pv[2 * PF];
-    fetch_list(beg_n, len_n, pi, pv);
-    const RegDesc rd = a.reg_single ? rd0 : load_reg(a.regs, seg >= 0 ? seg : 0);
+      const int64_t gseg = a.own_offset + seg;
+      double2* ownp = reinterpret_cast<double2*>(a.own + gseg * KP);
+      Vec<G, R> x, g;
+#pragma unroll
+      for (int i = 0; i < R / 2; ++i) x.v[i] = ownp[i * G + j];
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t) {
+        if (t * NG + wave * (64 / G) < len) { // wave-uniform
+          const double2* yp = other2 + (int64_t)cc[t] * (KP / 2) + j;
+#pragma unroll
+          for (int i = 0; i < R / 2; ++i) y[t][i] = yp[i * G];
+        } else {
+#pragma unroll
+          for (int i = 0; i < R / 2; ++i) y[t][i] = make_double2(0.0, 0.0);
+        }
+      }
+      // the next row's record rides behind the gathers
+      int pi[PF], pv[2 * PF];
+      double pa;
+      fetch_rec(seg_n, beg_n, len_n, pi, pv, pa);
+      next_pointers();
+      const RegDesc rd = a.reg_single ? rd0 : load_reg(a.regs, seg);
 
-    if (seg >= 0) {
       double Jold = reg_pass<G, R, LOSS, MAXT, true, WAVES>(a, y, av, cc, x, g, len, gi, segloss);
       Jold = row_combine<G, R, WAVES, true>(Jold, g, red, wave, lane);
+      // hand the next row's record over now: the loads above are the youngest in the queue and none of this row's stores is in it yet.
+      // The other buffer's readers (the previous row) are behind the barrier that ended their row.
+      store_rec(cur ^ 1, pi, pv, pa);
       if (a.fixed_alpha > 0.0) {
         const double s = a.fixed_alpha / ((double)len + 1.0);
         Vec<G, R> xn;
@@ -550,7 +592,7 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
         }
       } else {
         Jold += reg_eval<G, R, VR>(rd, x, j, a.k);
-        double alpha = a.alpha[seg];
+        double alpha = rec_alpha(cur)[tid]; // fetched a row ago
         const double l = (double)len + 1.0;
         int ntrials = 0;
         bool accepted = false;
@@ -586,16 +628,15 @@ __global__ void __launch_bounds__(128, 2) regcached_persist_kernel(const CachedA
         }
         if (tid == 0) {
           a.alpha[seg] = alpha;
-          if (a.trials) {
-            a.trials[seg] += ntrials;
-            a.accepts[seg] += accepted ? 1 : 0;
+          if (a.trials) { // int32 adds on counters only this workgroup touches in this launch: same values as +=, and nothing to wait for
+            atomicAdd(&a.trials[seg], ntrials);
+            atomicAdd(&a.accepts[seg], accepted ? 1 : 0);
           }
         }
       }
     }
-    __syncthreads();      // everybody has read this row's list out of LDS (and is done with the combine buffer)
-    store_list(pi, pv);   // hand the next row's list over
-    __syncthreads();
+    __syncthreads(); // the next row's record is in place; everybody is done with this row's (and with the combine buffer)
+    cur ^= 1;
     seg = seg_n; beg = beg_n; len = len_n;
     seg_n = seg_nn; beg_n = beg_nn; len_n = len_nn;
   }
