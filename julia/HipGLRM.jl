@@ -60,7 +60,8 @@ mutable struct HipProxGradParams <: AbstractParams
     abs_tol::Float64; rel_tol::Float64; min_stepsize::Float64
     device_id::Int; ngpus::Int; device_ids::Vector{Int32}; exchange::Symbol; x_chunks::Int; dense::Bool; quad_gram::Bool
     # mode: :fast (the engine's summation orders) | :reference_order (validation, glrm_options.sum_order = 1)
-    # storage: :f64 | :f32 (A, X and Y stored as floats on the gather sweeps, fp64 arithmetic: include/glrm_hip_storage.h)
+    # storage: :f64 | :f32 (A, X and Y stored as floats, fp64 arithmetic: include/glrm_hip_storage.h; two kernel families have a float
+    # form, the gather sweeps and the cached row sweep -- GLRM_HIP_CACHED=1 forces the latter, DESIGN.md section 4.13 names the rule)
     mode::Symbol; storage::Symbol
 end
 function HipProxGradParams(stepsize::Number=1.0; max_iter::Int=100, inner_iter_X::Int=1, inner_iter_Y::Int=1,

@@ -294,8 +294,8 @@ class Api:
         ``defer=True`` (one shard of a sharded fit): only upload; the host combines :meth:`signature` over the shards and
         calls :meth:`finalize` on every one of them (GLRM_PROBLEM_DEFER_SETUP).
         ``sum_order=1``: the reference-order validation sweeps (glrm_options.sum_order).
-        ``storage=1``: A, X and Y stored as floats on the gather sweeps, arithmetic in fp64 (glrm_options.storage,
-        include/glrm_hip_storage.h); the factors cross this boundary as float64 arrays either way."""
+        ``storage=1``: A, X and Y stored as floats on the gather sweeps and the cached row sweep, arithmetic in fp64
+        (glrm_options.storage, include/glrm_hip_storage.h); the factors cross this boundary as float64 arrays either way."""
         if prob.dense_A is not None and not self.dense_ok:
             raise GLRMError(ERR_UNSUPPORTED, "this engine takes observation lists only")
         p = self._cproblem(prob)

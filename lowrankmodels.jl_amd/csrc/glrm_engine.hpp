@@ -8,6 +8,7 @@
 //   glrm_svd.hip        SVD initialisation          glrm_impute.hip     imputation
 //   glrm_multigpu.hip   sharded fits                glrm_testhooks.hip  test hooks (constant in the product library)
 //   glrm_storage.hip    fp32 storage: the float gather sweeps, narrowing / widening copies (include/glrm_hip_storage.h)
+//   glrm_cached_f32.hip fp32 storage: the float instantiations of the cached row sweep's register variant (glrm_cached.hpp)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 #pragma once
 
@@ -156,7 +157,7 @@ struct glrm_handle {
   int32_t *blk_perm_c = nullptr, *blk_long_c = nullptr;
   int64_t blk_nshort_c = 0, blk_nlong_c = 0, blk_long_from = 0;
   int64_t blocked_cap[2][2] = {{0, 0}, {0, 0}}; // phase-aligned passes: segments per launch slice, [row / column view][gradient / trial instantiation]
-  int cached_grid[4] = {0, 0, 0, 0};      // persistent cached row sweep: resident workgroups of the MAXT = 7 / 4 instantiation; [2], [3]: of their VR = true twins
+  int cached_grid[6] = {0, 0, 0, 0, 0, 0}; // persistent cached row sweep: resident workgroups of the MAXT = 7 / 4 instantiation; [2], [3]: of their VR = true twins; [4], [5]: of the float ones
   glrm_signature sig_local{}, sig{};  // this shard's contribution / the whole problem's
   hipStream_t side_stream = nullptr;  // the launches of the minority classes run beside the main launch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -171,7 +172,8 @@ struct glrm_handle {
   double ms_wait = 0;                 // profile: time the launch stream stood in those waits
   int sum_order_opt = 0;              // glrm_options.sum_order (1: reference-order validation sweeps, glrm_reforder.hip)
   // glrm_options.storage.  GLRM_STORAGE_F32: rowvals / colvals / X / Y / oX / oY below hold FLOATS behind their double* type (the same
-  // element counts); only the float gather sweeps and the copy kernels of glrm_storage.hip read them, every other family is refused.
+  // element counts); only the float gather sweeps, the float cached row sweep (glrm_cached_f32.hip) and the copy kernels of
+  // glrm_storage.hip read them, every other family is refused.
   int storage = 0;
   // hipGraph of one outer iteration (gather sweeps on a private stream): small fits are launch bound
   hipGraph_t iter_graph = nullptr;
@@ -264,6 +266,10 @@ int glrm_rows_from_cols(glrm_handle* h);
 // cached gather row sweep (glrm_cached.hip)
 int glrm_setup_cached(glrm_handle* h);                 // finalize: cached_want / cached_row from h->sig
 int64_t glrm_cached_maxlen(const glrm_handle* h);      // longest row the cached sweep takes (a function of k and the variant)
+int glrm_cached_variant(const glrm_handle* h);         // cached_row of a handle on the family: 2 registers (always, for float storage), 1 LDS
+int glrm_cached_waves(const glrm_handle* h);           // waves per row of the register variant
+// float storage, GLRM_HIP_CACHED unset: 1 = the fp64 auto rule applies, 0 = the family stays behind GLRM_HIP_CACHED=1
+constexpr int GLRM_CACHED_F32_AUTO = 0;
 void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
 int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)

@@ -536,8 +536,10 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     h->tiled_row = h->tiled_col = h->blocked_row = h->blocked_col = h->cached_row = h->cached_want = 0;
     h->waves_row = h->waves_col = 1;
   } else if (h->storage == GLRM_STORAGE_F32) {
-    // float storage: gather sweeps on both views, short rows on the one-wave sweep (the other families have no float form)
-    h->tiled_row = h->tiled_col = h->blocked_row = h->blocked_col = h->cached_row = h->cached_want = 0;
+    // float storage: gather sweeps on both views; rows of at most glrm_cached_maxlen observations on the cached row sweep where
+    // glrm_setup_cached says so, otherwise on the one-wave sweep (the other families have no float form)
+    h->tiled_row = h->tiled_col = h->blocked_row = h->blocked_col = 0;
+    if ((rc = glrm_setup_cached(h))) return rc;
     if ((rc = build_class_plan(h, true))) return rc;
     if ((rc = build_class_plan(h, false))) return rc;
   } else if (!h->multi && !h->dense) {
@@ -1186,9 +1188,9 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
     o.waves = (forced == 1 || forced == 4 || forced == 8) ? forced : 0;
     if (rows && h->cached_want) { // which rows the cached sweep takes is a function of the row's own length
       const int keep = h->cached_row;   // 0 on a shard that holds no such row: the variant is still the whole problem's
-      if (!keep) h->cached_row = env_int("GLRM_HIP_CACHED_REGS", 1) ? 2 : 1;
+      if (!keep) h->cached_row = glrm_cached_variant(h);
       o.cached_maxlen = glrm_cached_maxlen(h);
-      o.cached_waves = h->cached_row == 2 ? env_int("GLRM_HIP_CACHED_WAVES", 2) : 1;
+      o.cached_waves = h->cached_row == 2 ? glrm_cached_waves(h) : 1;
       h->cached_row = keep;
     }
     // four observations per trip with one loss evaluation per lane (sweep_pass: SCATTER): G == 4 and not the uniform QuadLoss kernel;
