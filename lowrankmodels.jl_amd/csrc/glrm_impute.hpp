@@ -79,11 +79,12 @@ __device__ inline double impute_value(const glrm_domain& D, const LossDesc& l, i
         *bad = 1; // u[a] out of bounds / no evaluate method: the reference throws
         return 0.0;
       }
-      int best = -1;
+      int best = (int)lo;
+      bool first = true; // levels may be negative: a flag, not a sentinel level, marks "nothing yet"
       double bl = 0.0;
       for (int lev = (int)lo; lev <= (int)hi; ++lev) {
         const double v = vloss_eval_strided(l, u, us, d, lev - 1);
-        if (best < 0 || v < bl) { best = lev; bl = v; } // first minimum (NaN never wins after the first)
+        if (first || v < bl) { best = lev; bl = v; first = false; } // first minimum (NaN never wins after the first)
       }
       return (double)best;
     }

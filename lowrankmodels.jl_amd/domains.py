@@ -164,6 +164,8 @@ def impute_entry(D, l, u):
 
 
 def pos_mod(T, x):
+    if math.isinf(x):  # Inf % T is NaN in the reference; math.fmod raises instead
+        return math.nan
     return math.fmod(x, T) if x > 0 else math.fmod(x, T) + T
 
 

@@ -2061,12 +2061,12 @@ static double impute_c(const glrm_domain* D, const glrm_loss* l, const double* u
     }
     if (dk == GLRM_DOMAIN_ORDINAL && (kind == GLRM_LOSS_BVS || kind == GLRM_LOSS_OVA || kind == GLRM_LOSS_MULTINOMIAL)) { /* generic :98-100 */
       if (kind == GLRM_LOSS_MULTINOMIAL && (lo < 1 || hi > d)) { *bad = 1; return 0.0; } /* u[a]: BoundsError in the reference */
-      int best = -1;
+      int best = (int)lo, first = 1; /* levels may be negative: a flag, not a sentinel level, marks "nothing yet" */
       double bl = 0.0, w[GLRM_MAX_EMBEDDING_DIM];
       for (int lev = (int)lo; lev <= (int)hi; ++lev) {
         for (int j = 0; j < d; ++j) w[j] = u[j];
         const double val = glrm_cpu_vloss_evaluate(l, w, (double)lev);
-        if (best < 0 || val < bl) { best = lev; bl = val; }
+        if (first || val < bl) { best = lev; bl = val; first = 0; } /* first minimum */
       }
       return best;
     }
@@ -2111,6 +2111,13 @@ static double entry_error_c(const glrm_domain* D, double imp, double a) {
 double glrm_cpu_impute_entry(const glrm_domain* D, const glrm_loss* l, const double* u, int* bad) {
   *bad = 0;
   return impute_c(D, l, u, bad);
+}
+
+/* probe for the tests: error_metric(D, l, u, a) for one entry */
+double glrm_cpu_error_metric_entry(const glrm_domain* D, const glrm_loss* l, const double* u, double a, int* bad) {
+  *bad = 0;
+  const double imp = impute_c(D, l, u, bad);
+  return entry_error_c(D, imp, a);
 }
 
 static int eval_checks(const glrm_cpu_handle* h, const glrm_domain* domains) {

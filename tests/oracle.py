@@ -170,6 +170,22 @@ def impute_entry(domain, loss, u):
     return v
 
 
+def error_metric_entry(domain, loss, u, a):
+    """error_metric(D, l, u, a) of the oracle for one entry; raises TypeError for pairs the reference has no rule for."""
+    from lowrankmodels.jl_amd import _capi
+    lib = oracle_lib()
+    lib.glrm_cpu_error_metric_entry.restype = C.c_double
+    lib.glrm_cpu_error_metric_entry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int)]
+    st = _loss_struct(loss)
+    dom = np.array([domain.descriptor()], dtype=_capi.DOMAIN_DTYPE)
+    u = np.atleast_1d(np.asarray(u, dtype=np.float64)).copy()
+    bad = C.c_int(0)
+    v = lib.glrm_cpu_error_metric_entry(dom.ctypes.data, C.addressof(st), u.ctypes.data, float(a), C.byref(bad))
+    if bad.value:
+        raise TypeError("no impute rule")
+    return v
+
+
 def reg_evaluate_block(reg, a):
     """evaluate(r, a) for a k x d block (numpy (k, d)); wrappers included."""
     st = _reg_struct(reg)

@@ -7,6 +7,7 @@ import cases
 import lowrankmodels.jl_amd as L
 import oracle as O
 from lowrankmodels.jl_amd import _capi, crossval
+from lowrankmodels.jl_amd.domains import pack_domains
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -231,3 +232,126 @@ def test_fused_and_unfused_drivers_agree_on_the_gpu():
     a = L.cross_validate(g, nfolds=4, params=p, verbose=False, groups=tags, fused=True)
     b = L.cross_validate(g, nfolds=4, params=p, verbose=False, groups=tags, fused=False)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])  # the compacted views are the same arrays
+
+
+# ================================================================== the compaction against a numpy mask, exactly
+# A, X and Y hold small integers, so every probe below is a sum of integers (or one rounding of an integer): free of order, compared with ==.
+WG = 4096   # entries one workgroup of glrm_subset.hip compacts; scan_blocks_kernel carries across blocks of 1024 workgroups
+
+
+def int_model(rng, m, n, observed=None, k=2):
+    A = rng.integers(-9, 10, (m, n)).astype(np.float64)
+    X, Y = rng.integers(-2, 3, (k, m)).astype(np.float64), rng.integers(-2, 3, (k, n)).astype(np.float64)
+    obs = None if observed is None else np.nonzero(observed)
+    return L.GLRM(A, L.QuadLoss(), L.ZeroReg(), L.ZeroReg(), k, obs=obs, X=X, Y=Y)
+
+
+def check_child(api, h, g, sp, rt, match, invert):
+    """The child of `h` under the row-view tags rt (column-view tags rt[perm], the same entries) against the masked lists:
+    the counts; the COLUMN view through error_metric (RealDomain, QuadLoss) at X = 0 -- the sum of a^2 -- and at the model's X, where u_ij
+    depends on i and j, so a value that lost its row index or sits in another column's segment changes the sum; the ROW view through one
+    fixed-size gradient step on X (alpha a power of two, ZeroReg): x_i + (sum_j 2 (u_ij - a_ij) y_j) * (-(alpha / (len_i + 1)))."""
+    rt = np.ascontiguousarray(rt, dtype=np.uint8)
+    keep = (rt == match) != bool(invert)
+    I, J, a = sp.I[keep], sp.J[keep], g._rowvals[keep]
+    X, Y = np.asfortranarray(g.X), np.asfortranarray(g.Y)
+    doms = pack_domains([L.RealDomain()] * g.n)
+    r = np.einsum("ki,ki->i", X[:, I], Y[:, J]) - a
+    G = np.stack([np.bincount(I, weights=2 * r * Y[c, J], minlength=g.m) for c in range(g.k)])
+    alpha = 0.125
+    want_X = X + G * (-(alpha / (np.bincount(I, minlength=g.m) + 1.0)))
+    hc = api.subset(h, rt, rt[sp.perm], match, invert)
+    try:
+        st = api.kernel_stats(hc)
+        assert st["nnz_rows"] == int(keep.sum()) and st["nnz_cols"] == int(keep.sum())
+        assert api.error_metric(hc, np.zeros_like(X), Y, doms, False) == float(np.sum(a * a))
+        assert api.error_metric(hc, X, Y, doms, False) == float(np.sum(r * r))
+        api.set_factors(hc, X, Y)
+        api.gradstep_x(hc, alpha)
+        Xn, Yn = np.zeros_like(X), np.zeros_like(Y)
+        api.get_factors(hc, Xn, Yn)
+        assert np.array_equal(Xn, want_X) and np.array_equal(Yn, Y)
+    finally:
+        api.destroy(hc)
+
+
+@pytest.mark.parametrize("m,n", [(65, 63), (64, 64), (241, 17)], ids=["nnz4095", "nnz4096", "nnz4097"])
+def test_subset_around_one_workgroup(m, n):
+    rng = np.random.default_rng(m)
+    g = int_model(rng, m, n)
+    assert len(g._colidx) in (WG - 1, WG, WG + 1)
+    sp = crossval._Split(g)
+    api = hip()
+    h = api.create(g.problem_arrays())
+    try:
+        rt = rng.integers(0, 3, m * n)
+        for match, invert in ((0, False), (2, True)):
+            check_child(api, h, g, sp, rt, match, invert)
+        last = np.zeros(m * n, np.uint8)
+        last[-1] = 1                                                            # the entry past the workgroup when nnz = 4097
+        check_child(api, h, g, sp, last, 1, False)
+        check_child(api, h, g, sp, last, 1, True)
+    finally:
+        api.destroy(h)
+
+
+def tag_patterns(g, sp):
+    nnz = len(g._colidx)
+    z = np.zeros(nnz, np.uint8)
+    first, last, row, col, head = z.copy(), z.copy(), z.copy(), z.copy(), z.copy()
+    first[0] = 1
+    last[-1] = 1
+    row[sp.I == g.m // 3] = 1                                                   # one whole segment of the row view
+    col[sp.J == g.n // 2] = 1                                                   # one whole segment of the column view
+    head[(sp.I < g.m // 2) & (sp.J < g.n // 2)] = 1                             # the trailing segments of both views come out empty
+    return {"first": first, "last": last, "row": row, "col": col, "head": head}
+
+
+@pytest.mark.parametrize("pattern", ["first", "last", "row", "col", "head"])
+@pytest.mark.parametrize("shape", ["sparse", "full4097"])
+def test_subset_tag_patterns(shape, pattern):
+    """Only the first entry, only the last, one whole segment, everything but them (invert), and children whose trailing segments are empty.
+    The sparse parent's own last three rows and last two columns hold nothing: ptr[s] == nnz for s < nseg."""
+    rng = np.random.default_rng(17)
+    if shape == "sparse":
+        obs = rng.random((90, 70)) < 0.5
+        obs[-3:, :] = False
+        obs[:, -2:] = False
+        g = int_model(rng, 90, 70, obs)
+        assert g._rowptr[-4] == g._rowptr[-1] and g._colptr[-3] == g._colptr[-1]
+    else:
+        g = int_model(rng, 241, 17)
+    sp = crossval._Split(g)
+    rt = tag_patterns(g, sp)[pattern]
+    assert rt.any()
+    api = hip()
+    h = api.create(g.problem_arrays())
+    try:
+        check_child(api, h, g, sp, rt, 1, False)
+        check_child(api, h, g, sp, rt, 1, True)
+    finally:
+        api.destroy(h)
+
+
+def test_subset_carries_across_1024_workgroups():
+    """66000 x 64 fully observed: 4 224 000 observations, 1032 workgroups, so scan_blocks_kernel runs its second block of 1024 and the carry
+    between them.  The tags keep one entry in three before workgroup 1024 of the row view and two in five after it, and what lies past
+    workgroup 1024 of the column view is shifted once more.  Probes only, no fit."""
+    m, n = 66000, 64
+    rng = np.random.default_rng(1032)
+    g = int_model(rng, m, n)
+    nnz = m * n
+    assert (nnz + WG - 1) // WG == 1032
+    sp = crossval._Split(g)
+    t = np.arange(nnz)
+    rt = np.where(t < 1024 * WG, t % 3, (t % 5 < 2).astype(np.int64))
+    colpos = np.empty(nnz, np.int64)
+    colpos[sp.perm] = t                                                         # where the column view lists row-view entry t
+    rt = np.where(colpos >= 1024 * WG, (rt + 1) % 3, rt).astype(np.uint8)
+    api = hip()
+    h = api.create(g.problem_arrays())
+    try:
+        check_child(api, h, g, sp, rt, 1, False)
+        check_child(api, h, g, sp, rt, 1, True)
+    finally:
+        api.destroy(h)
