@@ -98,7 +98,8 @@ typedef enum glrm_reg_kind {
   GLRM_REG_ONE_SPARSE = 7,      /* OneSparseConstraint        :235-255  scale unused (1.0) */
   GLRM_REG_K_SPARSE = 8,        /* KSparseConstraint(r)       :258-291  scale = r, integral, 1 <= r <= length the base sees; ties in |u| keep the lower index */
   GLRM_REG_SIMPLEX = 9,         /* SimplexConstraint          :323-348  scale unused (1.0) */
-  GLRM_REG_KIND_END = 10        /* the engine accepts kinds in [0, GLRM_REG_KIND_END) */
+  GLRM_REG_KIND_END = 10        /* the engine accepts kinds in [0, GLRM_REG_KIND_END); kind 10 (RemQuadReg) carries a vector and exists
+                                 * only in the entry points of the extension header glrm_hip_regvec.h */
 } glrm_reg_kind;
 
 #define GLRM_MAX_EMBEDDING_DIM 32
@@ -116,6 +117,7 @@ typedef struct glrm_loss {
 #define GLRM_WRAP_LASTENTRY_UNPENALIZED 2 /* lastentry_unpenalized(r) :177-189: last row exempt from r (offset, on Y)      */
 #define GLRM_WRAP_ORDINAL 4               /* OrdinalReg(r)            :356-383: block regularizer of ordinal multi-dim losses */
 #define GLRM_WRAP_MNL_ORDINAL 8           /* MNLOrdinalReg(r)         :388-409                                               */
+/* (fixed_latent_features / fixed_last_latent_features, :193-231, carry a vector: flags 16 / 32 of glrm_hip_regvec.h, refused here) */
 
 typedef struct glrm_reg {
   int32_t kind;     /* glrm_reg_kind of the base regularizer */

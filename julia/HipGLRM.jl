@@ -9,6 +9,7 @@
 # This file is the marshalling core (<= 150 code lines, SURVEY.md section 8(b); tests/test_julia_shim.py counts them):
 #   HipGLRMDescriptors.jl  loss / regularizer types -> (kind, dim, scale, p0, p1) / (kind, wrap, scale); which models the engine takes
 #   HipGLRMExtras.jl       init_svd! / error_metric / impute / subset / sum_order on the same cached handle
+#   HipGLRMRegVec.jl       fixed_latent_features / fixed_last_latent_features / RemQuadReg: glrm_hip_set_regularizers_vec
 # Omega at north-star scale (1e9 observations): a `SparseMatrixCSC` whose lists are the constructor's (`findall(!iszero, A)`,
 # src/glrm.jl:46-48) IS the column view -- colptr / rowval / nzval are handed over after one index shift and NOTHING ELSE: the row view
 # (ascending columns per row = the order sort_observations pushes them in, src/modify_glrm.jl:8-12) is derived by the engine on the
@@ -139,6 +140,7 @@ function check_abi()
     v == ABI_VERSION || error("libglrm_hip.so speaks ABI $v, HipGLRM.jl was written against ABI $ABI_VERSION (include/glrm_hip.h)")
 end
 
+include("HipGLRMRegVec.jl")                   # install_regvec!: the regularizers that carry a vector (include/glrm_hip_regvec.h)
 include("HipGLRMHandle.jl")                   # handle(glrm, desc, p): the engine handle cached per model; hip_release!; with_handle
 
 # upload: glrm_problem from the model (Omega views or the dense matrix), glrm_options / glrm_multi_options from the params

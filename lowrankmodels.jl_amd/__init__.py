@@ -14,14 +14,16 @@ from .initialize import init_kmeanspp_, init_svd_
 from .scaling import equilibrate_variance_, prob_scale_
 from .domains import (BoolDomain, CategoricalDomain, CountDomain, Domain, OrdinalDomain, PeriodicDomain, RealDomain, default_domain,
                       error_metric, error_metric_entry, impute, impute_entry, impute_missing)
-from .glrm import GLRM, add_offset_, copy_estimate, parameter_estimate, scale_regularizer_, sort_observations
+from .glrm import GLRM, add_offset_, copy_estimate, fix_latent_features_, parameter_estimate, scale_regularizer_, sort_observations
 from .losses import (BvSLoss, HingeLoss, HuberLoss, L1Loss, LogisticLoss, Loss, MultinomialLoss, MultinomialOrdinalLoss,
                      OrdinalHingeLoss, OrdisticLoss, OvALoss, PeriodicLoss, PoissonLoss, QuadLoss, QuantileLoss,
                      WeightedHingeLoss, embedding_dim, evaluate, get_yidxs, grad)
 from .params import AbstractParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams
 from .regularizers import (KSparseConstraint, MNLOrdinalReg, NonNegConstraint, NonNegOneReg, OneReg, OneSparseConstraint, OrdinalReg,
                            QuadConstraint, QuadReg, Regularizer, SimplexConstraint, UnitOneSparseConstraint, ZeroReg, lastentry1,
-                           lastentry_unpenalized, prox)
+                           lastentry_unpenalized, prox,
+                           FixedLastLatentFeaturesConstraint, FixedLatentFeaturesConstraint, RemQuadReg, fixed_last_latent_features,
+                           fixed_latent_features)
 
 fit_inplace = fit_b  # Julia's `fit!`
 

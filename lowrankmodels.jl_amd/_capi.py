@@ -45,6 +45,11 @@ DOMAIN_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("lo", "<f8"), ("
 assert LOSS_DTYPE.itemsize == C.sizeof(CLoss) == 32 and REG_DTYPE.itemsize == C.sizeof(CReg) == 16
 
 
+class CRegVec(C.Structure):
+    """glrm_regvec (include/glrm_hip_regvec.h): one side's vectors, a k x count column-major table and one int32 length per descriptor."""
+    _fields_ = [("vec", C.c_void_p), ("len", C.c_void_p)]
+
+
 class CProblem(C.Structure):
     _fields_ = [
         ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int32), ("flags", C.c_int32),
@@ -157,6 +162,9 @@ INIT_SYMBOLS = ("init_kmeanspp",)
 #: the storage extension, include/glrm_hip_storage.h (fp32 storage of A, X and Y): outside the boundary, bound only where the library has it
 STORAGE_SYMBOLS = ("storage",)
 
+#: the vector-carrying regularizers, include/glrm_hip_regvec.h: outside the boundary, bound only where the library has them
+REGVEC_SYMBOLS = ("set_regularizers_vec", "multi_set_regularizers_vec")
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -251,8 +259,10 @@ class Api:
             "scale_columns": (C.c_int, [C.POINTER(CProblem), C.POINTER(COptions), C.c_int32] + [C.c_void_p] * 5),
             "init_kmeanspp": (C.c_int, [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
             "storage": (C.c_int, [H]),
+            "set_regularizers_vec": (C.c_int, [H, C.c_void_p, C.c_int64, C.POINTER(CRegVec), C.c_void_p, C.c_int64, C.POINTER(CRegVec)]),
+            "multi_set_regularizers_vec": (C.c_int, [H, C.c_void_p, C.c_int64, C.POINTER(CRegVec), C.c_void_p, C.c_int64, C.POINTER(CRegVec)]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -437,6 +447,30 @@ class Api:
     def set_regularizers(self, h, rx, ry):
         """rx, ry: REG_DTYPE arrays with the same lengths as at create."""
         self._ck(self._f["set_regularizers"](h, _ptr(rx), len(rx), _ptr(ry), len(ry)))
+
+    # -- vector-carrying regularizers (include/glrm_hip_regvec.h) --------------------------------
+    def _set_regs_vec(self, name, h, rx, vx, ry, vy):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the regularizers that carry a vector "
+                                             "(include/glrm_hip_regvec.h is implemented by the HIP engine only)")
+        keep = []  # the arrays must outlive the call
+
+        def side(v):
+            if v is None:
+                return None
+            vec, lens = np.ascontiguousarray(v[0], dtype=np.float64), np.ascontiguousarray(v[1], dtype=np.int32)
+            keep.extend((vec, lens))
+            return C.byref(CRegVec(_ptr(vec), _ptr(lens)))
+        self._ck(fn(h, _ptr(rx), len(rx), side(vx), _ptr(ry), len(ry), side(vy)))
+
+    def set_regularizers_vec(self, h, rx, vx, ry, vy):
+        """glrm_hip_set_regularizers_vec.  rx, ry: REG_DTYPE arrays that may hold the codes of include/glrm_hip_regvec.h; vx, vy: None or
+        (flat k x count column-major table, int32 lengths) for the side."""
+        self._set_regs_vec("set_regularizers_vec", h, rx, vx, ry, vy)
+
+    def multi_set_regularizers_vec(self, mh, rx, vx, ry, vy):
+        self._set_regs_vec("multi_set_regularizers_vec", mh, rx, vx, ry, vy)
 
     def subset(self, h, row_tags, col_tags, match, invert=False):
         """Child handle over the entries whose tag (uint8 per entry of the parent's row view / column view) equals

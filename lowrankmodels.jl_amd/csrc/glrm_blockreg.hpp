@@ -1,9 +1,14 @@
 // glrm_blockreg.hpp -- the regularizers of the general sweeps (csrc/glrm_multi.hpp): evaluate and prox of a k x d block that lives in LDS,
 // by one workgroup; wrappers (lastentry1, lastentry_unpenalized, OrdinalReg, MNLOrdinalReg) around a base regularizer.  A header of its
 // own so that the test hook (csrc/glrm_testhooks.hip) can run them without the sweep kernels.
+//
+// The VR = true instantiations also hold the regularizers that carry a vector (include/glrm_hip_regvec.h): the fixed-features wrappers
+// GLRM_WRAP_FIXED_FIRST / GLRM_WRAP_FIXED_LAST around a base regularizer and RemQuadReg (kind GLRM_REG_REM_QUAD), on k-vectors (DO == 1).
+// `rv` points at the segment's vector and `rl` is its length (nfix, or k for RemQuadReg); the VR = false instantiations never read them.
 #pragma once
 
 #include "glrm_device.hpp"
+#include "../../include/glrm_hip_regvec.h"
 
 namespace glrm {
 
@@ -27,12 +32,24 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 
 // evaluate(r, block): every thread returns the same value.
 template <int NW, bool VR = false>
-__device__ inline double block_reg_eval(const double* blk, int S, int k, int DO, const glrm_reg rg, double* red) {
+__device__ inline double block_reg_eval(const double* blk, int S, int k, int DO, glrm_reg rg, double* red, const double* rv = nullptr, int rl = 0) {
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
+  double bad = 0.0, v = 0.0;
+  if constexpr (VR) {
+    // fixed_latent_features / fixed_last_latent_features (src/regularizers.jl:208,229): the pinned entries must EQUAL y, entry by entry (a
+    // NaN differs from everything); the base then evaluates the other k - nfix entries through the code below, as an unwrapped regularizer
+    if (rg.wrap & (GLRM_WRAP_FIXED_FIRST | GLRM_WRAP_FIXED_LAST)) {
+      const bool first = (rg.wrap & GLRM_WRAP_FIXED_FIRST) != 0;
+      const double* pin = first ? blk : blk + (k - rl);
+      for (int c = tid; c < rl; c += NT) bad += pin[c] != rv[c] ? 1.0 : 0.0;
+      blk = first ? blk + rl : blk;
+      k -= rl;
+      rg.wrap = 0;
+    }
+  }
   const int kr = rg.wrap ? k - 1 : k;                                                        // rows the base regularizer sees
   const int jc = (rg.wrap & (GLRM_WRAP_ORDINAL | GLRM_WRAP_MNL_ORDINAL)) ? 1 : DO;          // evaluate(r.r, a[1:end-1, 1])
-  double bad = 0.0, v = 0.0;
   if (rg.wrap == GLRM_WRAP_LASTENTRY1)
     for (int j = tid; j < DO; j += NT) bad += blk[j * S + k - 1] != 1.0 ? 1.0 : 0.0;
   for (int i = tid; i < kr * jc; i += NT) {
@@ -48,6 +65,7 @@ __device__ inline double block_reg_eval(const double* blk, int S, int k, int DO,
           if (rg.kind == GLRM_REG_QUAD_CONSTRAINT) v = fma(x, x, v);
           else if (rg.kind == GLRM_REG_NONNEG_ONE || rg.kind == GLRM_REG_SIMPLEX) { v += x; bad += x < 0 ? 1.0 : 0.0; }
           else if (rg.kind == GLRM_REG_ONE_SPARSE || rg.kind == GLRM_REG_K_SPARSE) v += x != 0 ? 1.0 : 0.0;
+          else if (rg.kind == GLRM_REG_REM_QUAD) { const double dm = x - rv[c]; v += dm * dm; } // sum(abs2, a - m), :423 (jc == 1, unwrapped)
         }
         break;
     }
@@ -68,6 +86,7 @@ __device__ inline double block_reg_eval(const double* blk, int S, int k, int DO,
           case GLRM_REG_SIMPLEX: return fabs(v - 1) > 1e-12 ? __builtin_inf() : 0.0;
           case GLRM_REG_ONE_SPARSE: return v > 1.0 ? __builtin_inf() : 0.0;
           case GLRM_REG_K_SPARSE: return v > rg.scale ? __builtin_inf() : 0.0;
+          case GLRM_REG_REM_QUAD: return rg.scale * v;
           default: break;
         }
       }
@@ -188,9 +207,36 @@ __device__ inline void base_prox_region(double* blk, int S, int kr, int DO, cons
 
 // prox!(r, block, alpha) (src/regularizers.jl:34-114,163-189,295-318,356-405); ends with a workgroup barrier.
 template <int NW, bool VR = false>
-__device__ inline void block_prox(double* blk, int S, int k, int DO, const glrm_reg rg, double alpha, double* tmp) {
+__device__ inline void block_prox(double* blk, int S, int k, int DO, const glrm_reg rg, double alpha, double* tmp, const double* rv = nullptr, int rl = 0) {
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
+  if constexpr (VR) { // the regularizers that carry a vector (include/glrm_hip_regvec.h): k-vectors, DO == 1
+    if (rg.wrap & (GLRM_WRAP_FIXED_FIRST | GLRM_WRAP_FIXED_LAST)) {
+      const int nb = k - rl; // what the base regularizer sees
+      glrm_reg base = rg;
+      base.wrap = 0;
+      if (rg.wrap & GLRM_WRAP_FIXED_FIRST) { // [y ; prox(r, u[nfix+1:end], alpha)], :202
+        base_prox_region<NW, true>(blk + rl, S, nb, 1, base, alpha, false);
+        for (int c = tid; c < rl; c += NT) blk[c] = rv[c];
+      } else { // [prox(r, u[nfix+1:end], alpha) ; y], :223: the base is fed the LAST k - nfix entries and its result lands in the FIRST
+               // k - nfix positions; the two ranges overlap when nfix < k - nfix, so the input is read out into tmp first
+        for (int c = tid; c < nb; c += NT) tmp[c] = blk[rl + c];
+        __syncthreads();
+        base_prox_region<NW, true>(tmp, 0, nb, 1, base, alpha, false);
+        __syncthreads();
+        for (int c = tid; c < nb; c += NT) blk[c] = tmp[c];
+        for (int c = tid; c < rl; c += NT) blk[nb + c] = rv[c];
+      }
+      __syncthreads();
+      return;
+    }
+    if (rg.kind == GLRM_REG_REM_QUAD) { // (u + 2 * alpha * scale * m) / (1 + 2 * alpha * scale), :417-418: a division per entry
+      const double t = 2 * alpha * rg.scale;
+      for (int c = tid; c < k; c += NT) blk[c] = (blk[c] + t * rv[c]) / (1 + t);
+      __syncthreads();
+      return;
+    }
+  }
   const int kr = rg.wrap ? k - 1 : k;
   if (rg.wrap & (GLRM_WRAP_ORDINAL | GLRM_WRAP_MNL_ORDINAL)) {
     if (tid < kr) { // um = mean(u[1:end-1, :], dims=2)

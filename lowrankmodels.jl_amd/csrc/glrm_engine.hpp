@@ -9,6 +9,7 @@
 //   glrm_multigpu.hip   sharded fits                glrm_testhooks.hip  test hooks (constant in the product library)
 //   glrm_storage.hip    fp32 storage: the float gather sweeps, narrowing / widening copies (include/glrm_hip_storage.h)
 //   glrm_cached_f32.hip fp32 storage: the float instantiations of the cached row sweep's register variant (glrm_cached.hpp)
+//   glrm_regvec.hip     regularizers that carry a vector (include/glrm_hip_regvec.h): checks, the handle's tables, the two entry points
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 #pragma once
 
@@ -22,6 +23,7 @@
 
 #include "../../include/glrm_hip.h"
 #include "../../include/glrm_hip_storage.h"
+#include "../../include/glrm_hip_regvec.h"
 
 // kernel variants by loss model.  The *_NOTRIG variants are compiled without PeriodicLoss (its sin / cos with full range reduction
 // costs ~60 VGPRs of pressure in every kernel that merely CONTAINS the case); models without a PeriodicLoss column use them.
@@ -187,6 +189,12 @@ struct glrm_handle {
   std::vector<glrm_loss> losses_h;
   std::vector<glrm_reg> rx_h, ry_h;
   bool vecreg_x = false, vecreg_y = false; // some rx / ry of this handle is a vector regularizer (kind >= GLRM_REG_QUAD_CONSTRAINT): VR kernels
+  // regularizers that carry a vector (include/glrm_hip_regvec.h, glrm_regvec.hip), [0] rx, [1] ry: nullptr / empty while the side has none.
+  // regvec: k x count doubles (ld k), reglen: count lengths, indexed like rx / ry; rx_h / ry_h then hold the descriptors WITH the new codes
+  double* regvec[2] = {nullptr, nullptr};
+  int32_t* reglen[2] = {nullptr, nullptr};
+  std::vector<double> regvec_h[2];
+  std::vector<int32_t> reglen_h[2];
   struct Ev { hipEvent_t a, b; int which; };
   std::vector<Ev> pending, pool;
   int64_t launches_x = 0, launches_y = 0;
@@ -242,6 +250,14 @@ int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_
 // test hooks (csrc/glrm_testhooks.hip): constant in the product library, environment-driven in the test build (-DGLRM_HIP_TESTING)
 int glrm_test_fail_finalize();                        // 1 = glrm_hip_finalize fails half way (the set-up-failed latch cannot be reached otherwise)
 int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry); // set_regularizers' refusals, no side effect
+// include/glrm_hip_regvec.h (glrm_regvec.hip): everything glrm_hip_set_regularizers_vec refuses, no side effect / the descriptors of the
+// handle with the vector codes taken out (what glrm_hip_create accepts) / the parent's descriptors and vectors installed on a fresh child /
+// the tables dropped (plain set_regularizers, destroy)
+int glrm_check_regularizers_vec(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_regvec* vx, const glrm_reg* ry, int64_t n_ry, const glrm_regvec* vy);
+bool glrm_regvec_carries(const glrm_reg& r);
+void glrm_regvec_placeholders(const std::vector<glrm_reg>& in, std::vector<glrm_reg>& out);
+int glrm_regvec_inherit(glrm_handle* child, const glrm_handle* parent);
+void glrm_regvec_drop(glrm_handle* h);
 int glrm_setup_reforder(glrm_handle* h);               // finalize: refuses what the mode does not cover
 int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
 int glrm_reforder_sum(glrm_handle* h, const void* dvec, int64_t n, double* out); // Julia's pairwise sum(::Vector{Float64})

@@ -276,6 +276,7 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
                   h->lane_inv[0], h->lane_inv[1], h->lane_off16[0], h->lane_off16[1], h->lane_vptr[0], h->lane_vptr[1], h->lane_sval[0], h->lane_sval[1], h->lane_gcnt, h->lane_gbase, h->lane_gtotal, h->lane_glist};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  glrm_regvec_drop(h);
   if (h->iter_exec) (void)hipGraphExecDestroy(h->iter_exec);
   if (h->iter_graph) (void)hipGraphDestroy(h->iter_graph);
   if (h->pinned_obj) (void)hipHostFree(h->pinned_obj);
@@ -758,6 +759,10 @@ extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int
   HIPCK(hipMemcpyAsync(h->rx, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemcpyAsync(h->ry, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
+  if (h->regvec[0] || h->regvec[1]) { // the vectors of an earlier glrm_hip_set_regularizers_vec go with its descriptors (include/glrm_hip_regvec.h)
+    glrm_regvec_drop(h);
+    if (h->iter_exec) { (void)hipGraphExecDestroy(h->iter_exec); h->iter_exec = nullptr; }
+  }
   return GLRM_OK;
 }
 

@@ -8,7 +8,8 @@
 using namespace glrm;
 
 // The kernels that apply a regularizer exist twice: VR = true holds the vector regularizers and is launched when a descriptor of the
-// side names one (glrm_handle::vecreg_x / vecreg_y -> MultiArgs::vecreg; csrc/glrm_device.hpp).
+// side names one or carries a vector (glrm_handle::vecreg_x / vecreg_y -> MultiArgs::vecreg; csrc/glrm_device.hpp, DESIGN.md sections
+// 4.11 and 4.14).
 #define MULTI_SWEEP(threads, ...)                                                                                                        \
   do {                                                                                                                                   \
     if (a.vecreg) hipLaunchKernelGGL((multi_sweep_kernel<true, __VA_ARGS__>), dim3((unsigned)a.nseg), dim3(threads), lds, h->stream, a);  \
@@ -151,7 +152,14 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
   while ((1 << a.lgP) < h->k || (1 << a.lgP) < h->dmax) ++a.lgP;
   a.mode = eval_only ? 1 : (h->fixed_alpha > 0.0 ? 2 : 0);
   if (a.mode != 0) a.trials = a.accepts = nullptr; // the counters belong to the line-search steps
-  if (rows && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e);
+  // the vectors of the side's descriptors (include/glrm_hip_regvec.h), indexed like the descriptors
+  a.regvec = h->regvec[rows ? 0 : 1];
+  a.reglen = h->reglen[rows ? 0 : 1];
+  a.regvec_single = a.reg_single;
+  if (rows && h->rng_e >= 0) {
+    glrm_apply_row_range(a, h->rng_b, h->rng_e);
+    if (a.regvec && !a.reg_single) { a.regvec += h->rng_b * h->k; a.reglen += h->rng_b; }
+  }
   if (a.nseg <= 0) return GLRM_OK;
   if (rows) {
     const size_t lds = multi_lds_doubles(true, 1, h->kp, h->dmax, a.lgP) * 8;
@@ -200,6 +208,9 @@ int glrm_run_multi_penalty(glrm_handle* h, bool rows) {
   a.out = rows ? h->objrow : h->objcol;
   const size_t lds = ((size_t)(rows ? 1 : h->dmax) * (h->kp + 1) + 16) * 8;
   a.vecreg = (rows ? h->vecreg_x : h->vecreg_y) ? 1 : 0;
+  a.regvec = h->regvec[rows ? 0 : 1];
+  a.reglen = h->reglen[rows ? 0 : 1];
+  a.regvec_single = a.reg_single;
   if (a.vecreg) hipLaunchKernelGGL(multi_penalty_kernel<true>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
   else hipLaunchKernelGGL(multi_penalty_kernel<false>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
   HIPCK(hipGetLastError());

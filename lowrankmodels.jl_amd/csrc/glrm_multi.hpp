@@ -42,7 +42,11 @@ struct MultiArgs {
   double fixed_alpha, min_stepsize;
   int32_t* trials;
   int32_t* accepts;
-  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer or carries a vector -- the VR = true kernels
+  // the vectors of the descriptors that carry one (include/glrm_hip_regvec.h); read by the VR = true kernels only.  LAST members: nothing above moves
+  const double* regvec;  // k doubles per descriptor (ld k), local segment index like regs; nullptr: no descriptor of this side carries a vector
+  int regvec_single;     // one descriptor, one vector for the whole side
+  const int32_t* reglen; // nfix of a fixed wrapper, k of RemQuadReg, 0 without a vector
 };
 
 struct PenaltyArgs {
@@ -54,8 +58,21 @@ struct PenaltyArgs {
   int reg_single;
   int k, kp;
   double* out;           // global segment index
-  int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels
+  int vecreg;            // 1: a descriptor of this side names a vector regularizer or carries a vector -- the VR = true kernels
+  const double* regvec;  // as in MultiArgs (LAST members)
+  int regvec_single;
+  const int32_t* reglen;
 };
+
+// The vector of local segment s and its length (VR = true kernels; nullptr / 0 on a side without vectors).
+template <class A>
+__device__ __forceinline__ const double* seg_regvec(const A& a, int64_t s, int k, int& rl) {
+  rl = 0;
+  if (!a.regvec) return nullptr;
+  const int64_t i = a.regvec_single ? 0 : s;
+  rl = a.reglen[i];
+  return a.regvec + i * k;
+}
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -525,6 +542,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(c
   for (int i = tid; i < DO * kp; i += NT) { const int j = i / kp, c = i - j * kp; ownA[j * S + c] = ownp[i]; }
   __syncthreads();
   const glrm_reg rg = a.regs[a.reg_single ? 0 : s];
+  const double* rv = nullptr; // the segment's regularizer vector (include/glrm_hip_regvec.h)
+  int rl = 0;
+  if constexpr (VR) rv = seg_regvec(a, s, k, rl);
 
   if (a.mode == 1) { // losses only
     const double tot = multi_pass<ROWS, NW, false, GDC, TRIG, RD, KM>(a, b, e, ownA, wbase, Gt, red, lseg, dseg);
@@ -540,11 +560,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(c
       if (c < k) { const double g = Gt[j * S + c] * (-st); ownA[j * S + c] = ownA[j * S + c] + g; }
     }
     __syncthreads();
-    block_prox<NW, VR>(ownA, S, k, DO, rg, st, tmp);
+    block_prox<NW, VR>(ownA, S, k, DO, rg, st, tmp, rv, rl);
     for (int i = tid; i < DO * kp; i += NT) { const int j = i / kp, c = i - j * kp; ownp[i] = ownA[j * S + c]; }
     return;
   }
-  double obj = loss_old + block_reg_eval<NW, VR>(ownA, S, k, DO, rg, red);
+  double obj = loss_old + block_reg_eval<NW, VR>(ownA, S, k, DO, rg, red, rv, rl);
   double alpha = a.alpha[s];
   int ntr = 0, nacc = 0;
   while (alpha > a.min_stepsize) { // proxgrad.jl:137-155 / :180-200
@@ -554,9 +574,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 1 ? 4 : 2) multi_sweep_kernel(c
       ownB[j * S + c] = c < k ? fma(-stepsize, Gt[j * S + c], ownA[j * S + c]) : 0.0;
     }
     __syncthreads();
-    block_prox<NW, VR>(ownB, S, k, DO, rg, stepsize, tmp);
+    block_prox<NW, VR>(ownB, S, k, DO, rg, stepsize, tmp, rv, rl);
     const double nloss = multi_pass<ROWS, NW, false, GDC, TRIG, RD, KM>(a, b, e, ownB, wbase, Gt, red, lseg, dseg);
-    const double nobj = nloss + block_reg_eval<NW, VR>(ownB, S, k, DO, rg, red);
+    const double nobj = nloss + block_reg_eval<NW, VR>(ownB, S, k, DO, rg, red, rv, rl);
     ++ntr;
     if (nobj < obj) {
       for (int i = tid; i < DO * kp; i += NT) { const int j = i / kp, c = i - j * kp; ownp[i] = ownB[j * S + c]; }
@@ -656,6 +676,9 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
     return;
   }
   const glrm_reg rg = a.regs[a.reg_single ? 0 : s];
+  const double* rv = nullptr;
+  int rl = 0;
+  if constexpr (VR) rv = seg_regvec(a, s, k, rl);
   double* ownp = a.own + vec0 * kp;
   double* trialp = sa.trial + vec0 * kp;
   double* gt = sa.gtot + (size_t)s * a.dmax * kp;
@@ -678,18 +701,18 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
         if (c < k) { const double g = gt[i] * (-st); blkA[j * S + c] = blkA[j * S + c] + g; }
       }
       __syncthreads();
-      block_prox<8, VR>(blkA, S, k, DO, rg, st, tmp);
+      block_prox<8, VR>(blkA, S, k, DO, rg, st, tmp, rv, rl);
       for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; ownp[i] = blkA[j * S + c]; }
       if (tid == 0) sa.active[s] = 0;
       return;
     }
     __syncthreads();
-    obj = loss + block_reg_eval<8, VR>(blkA, S, k, DO, rg, red);
+    obj = loss + block_reg_eval<8, VR>(blkA, S, k, DO, rg, red, rv, rl);
     if (!(alpha > a.min_stepsize)) finished = true;
   } else {
     for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; blkB[j * S + c] = trialp[i]; }
     __syncthreads();
-    const double nobj = loss + block_reg_eval<8, VR>(blkB, S, k, DO, rg, red);
+    const double nobj = loss + block_reg_eval<8, VR>(blkB, S, k, DO, rg, red, rv, rl);
     obj = sa.objold[s];
     ntr = 1;
     if (nobj < obj) {
@@ -711,7 +734,7 @@ __global__ void __launch_bounds__(512) multi_coldecide_kernel(const SplitArgs sa
       blkB[j * S + c] = c < k ? fma(-stepsize, gt[i], blkA[j * S + c]) : 0.0;
     }
     __syncthreads();
-    block_prox<8, VR>(blkB, S, k, DO, rg, stepsize, tmp);
+    block_prox<8, VR>(blkB, S, k, DO, rg, stepsize, tmp, rv, rl);
     for (int i = tid; i < DO * kp; i += 512) { const int j = i / kp, c = i - j * kp; trialp[i] = blkB[j * S + c]; }
   }
   if (tid == 0) {
@@ -739,7 +762,10 @@ __global__ void __launch_bounds__(64) multi_penalty_kernel(const PenaltyArgs a) 
   for (int i = tid; i < DO * kp; i += 64) { const int j = i / kp, c = i - j * kp; blk[j * S + c] = src[i]; }
   __syncthreads();
   const glrm_reg rg = a.regs[a.reg_single ? 0 : s];
-  const double v = block_reg_eval<1, VR>(blk, S, a.k, DO, rg, red);
+  const double* rv = nullptr;
+  int rl = 0;
+  if constexpr (VR) rv = seg_regvec(a, s, a.k, rl);
+  const double v = block_reg_eval<1, VR>(blk, S, a.k, DO, rg, red, rv, rl);
   if (tid == 0) a.out[gseg] = v;
 }
 

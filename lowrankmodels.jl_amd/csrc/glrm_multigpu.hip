@@ -751,6 +751,27 @@ extern "C" int glrm_hip_multi_set_regularizers(glrm_multi* mh, const glrm_reg* r
   return GLRM_OK;
 }
 
+// include/glrm_hip_regvec.h: the descriptors and their vectors, sliced per shard alike
+extern "C" int glrm_hip_multi_set_regularizers_vec(glrm_multi* mh, const glrm_reg* rx, int64_t n_rx, const glrm_regvec* vx, const glrm_reg* ry,
+                                                   int64_t n_ry, const glrm_regvec* vy) {
+  if (!mh || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
+  if (n_rx != mh->n_rx || n_ry != mh->n_ry) return fail(GLRM_ERR_INVALID, "regularizer counts must match the create call");
+  if ((vx && (!vx->vec || !vx->len)) || (vy && (!vy->vec || !vy->len))) return fail(GLRM_ERR_INVALID, "glrm_regvec.vec / len are NULL");
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
+  for (int pass = 0; pass < 2; ++pass) // every shard's slice is checked before any shard is changed: a refusal leaves the model as it was
+    for (int s = 0; s < mh->n; ++s) {
+      const int64_t ox = n_rx == 1 ? 0 : mh->rbs[s], oy = n_ry == 1 ? 0 : mh->cbs[s];
+      const int64_t nx = n_rx == 1 ? 1 : mh->rbs[s + 1] - mh->rbs[s], ny = n_ry == 1 ? 1 : mh->cbs[s + 1] - mh->cbs[s];
+      const glrm_regvec sx{vx ? vx->vec + ox * mh->k : nullptr, vx ? vx->len + ox : nullptr}, sy{vy ? vy->vec + oy * mh->k : nullptr, vy ? vy->len + oy : nullptr};
+      const int rc = pass == 0 ? glrm_check_regularizers_vec(mh->sh[s], rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr)
+                               : glrm_hip_set_regularizers_vec(mh->sh[s], rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr);
+      if (rc) return rc;
+    }
+  return GLRM_OK;
+}
+
 extern "C" int glrm_hip_multi_info(glrm_multi* mh, int64_t* row_bounds, int64_t* col_bounds, int32_t* exchange_used, double* exchange_ms) {
   if (!mh) return fail(GLRM_ERR_INVALID, "NULL handle");
   if (row_bounds) memcpy(row_bounds, mh->rbs.data(), ((size_t)mh->n + 1) * 8);

@@ -3,6 +3,9 @@
 // (src/cross_validate.jl:9-53,141-240): the folds reuse the values and indices that are already resident in HBM.
 #include "glrm_engine.hpp"
 
+#include <cstring>
+#include <new>
+
 namespace {
 
 constexpr int CT = 256, CI = 16, CB = CT * CI; // 4096 entries per workgroup
@@ -173,8 +176,17 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   p.rowptr = rv.ptr; p.colidx = rv.idx; p.rowvals = rv.vals;
   p.colptr = cv.ptr; p.rowidx = cv.idx; p.colvals = cv.vals;
   p.losses = parent->losses_h.data(); p.n_losses = (int64_t)parent->losses_h.size();
-  p.rx = parent->rx_h.data(); p.n_rx = (int64_t)parent->rx_h.size();
-  p.ry = parent->ry_h.data(); p.n_ry = (int64_t)parent->ry_h.size();
+  // a parent whose descriptors carry vectors (include/glrm_hip_regvec.h): the child is created from the descriptors with the vector codes
+  // taken out and inherits descriptors and vectors afterwards
+  std::vector<glrm_reg> prx, pry;
+  try {
+    glrm_regvec_placeholders(parent->rx_h, prx);
+    glrm_regvec_placeholders(parent->ry_h, pry);
+  } catch (const std::bad_alloc&) {
+    return fail(GLRM_ERR_OOM, "out of host memory");
+  }
+  p.rx = prx.data(); p.n_rx = (int64_t)prx.size();
+  p.ry = pry.data(); p.n_ry = (int64_t)pry.size();
   glrm_options o = parent->opts;
   o.device_id = parent->device;
   // The child of ONE SHARD of a sharded fit is a shard of the subset problem: like its parent it must choose its kernels from the
@@ -183,5 +195,13 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   // parent's child is set up here.
   const bool shard = !(parent->rb == 0 && parent->re == parent->m && parent->cb == 0 && parent->ce == parent->n);
   if (shard) p.flags |= GLRM_PROBLEM_DEFER_SETUP;
-  return glrm_hip_create(out, &p, &o); // copies the compacted views; rv / cv are released on return
+  rc = glrm_hip_create(out, &p, &o); // copies the compacted views; rv / cv are released on return
+  if (!rc && (rc = glrm_regvec_inherit(*out, parent))) {
+    char keep[sizeof g_err];
+    memcpy(keep, g_err, sizeof keep);
+    glrm_hip_destroy(*out);
+    memcpy(g_err, keep, sizeof keep);
+    *out = nullptr;
+  }
+  return rc;
 }

@@ -152,4 +152,64 @@ extern "C" int glrm_test_reg_prox_eval(const glrm_reg* reg, int32_t k, double al
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_reg_prox_eval: %s", hipGetErrorString(e));
   return GLRM_OK;
 }
+
+// ------------------------------------------------------------------ vector-carrying regularizers (tests/test_gpu_regularizers_vec.py)
+// The general sweeps' path (csrc/glrm_blockreg.hpp, VR = true) for a descriptor WITH its vector (include/glrm_hip_regvec.h): like
+// reg_hook_block, one wave per vector, the k x 1 block in LDS with the general sweeps' stride.
+namespace {
+struct RegVecHookArgs {
+  RegHookArgs a;
+  const double* rv; // the descriptor's vector (device, a.k doubles)
+  int rl;           // nfix / k
+};
+
+__global__ void __launch_bounds__(64) reg_hook_block_vec(const RegVecHookArgs h) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const RegHookArgs& a = h.a;
+  const int tid = threadIdx.x, S = a.kp + 1;
+  double* blk = sm;
+  double* tmp = sm + S;
+  double* red = tmp + 64;
+  double* g = a.vec + (int64_t)blockIdx.x * a.kp;
+  for (int c = tid; c < a.kp; c += 64) blk[c] = g[c];
+  __syncthreads();
+  const double e0 = block_reg_eval<1, true>(blk, S, a.k, 1, a.reg, red, h.rv, h.rl);
+  block_prox<1, true>(blk, S, a.k, 1, a.reg, a.alpha, tmp, h.rv, h.rl);
+  const double e1 = block_reg_eval<1, true>(blk, S, a.k, 1, a.reg, red, h.rv, h.rl);
+  for (int c = tid; c < a.kp; c += 64) g[c] = blk[c];
+  if (tid == 0) { a.ein[blockIdx.x] = e0; a.eout[blockIdx.x] = e1; }
+}
+} // namespace
+
+// reg with its vector `rvec` of `rlen` entries (nfix of a fixed wrapper, k of RemQuadReg); kp: the padded rank (k <= kp <= 64).  The
+// descriptor is taken as it is: what glrm_hip_set_regularizers_vec refuses is the caller's business to leave out.
+// u: nvec x k (host), prox_out: nvec x kp (host, the padded vectors as the kernel leaves them), eval_in / eval_out: nvec.
+extern "C" int glrm_test_regvec_prox_eval(const glrm_reg* reg, const double* rvec, int32_t rlen, int32_t k, int32_t kp, double alpha, const double* u,
+                                          int64_t nvec, double* prox_out, double* eval_in, double* eval_out) {
+  if (!reg || !rvec || !u || !prox_out || !eval_in || !eval_out || nvec <= 0 || nvec > (1 << 20)) return fail(GLRM_ERR_INVALID, "bad argument");
+  if (k < 1 || kp < k || kp > 64 || rlen < 1 || rlen > k) return fail(GLRM_ERR_INVALID, "bad rank / length (k %d, kp %d, length %d)", k, kp, rlen);
+  std::vector<double> padded((size_t)nvec * kp, 0.0);
+  for (int64_t v = 0; v < nvec; ++v)
+    for (int c = 0; c < k; ++c) padded[(size_t)v * kp + c] = u[(size_t)v * k + c];
+  double* d = nullptr;
+  const size_t nb = (size_t)nvec * kp * 8, ne = (size_t)nvec * 8;
+  HIPCK(hipMalloc((void**)&d, nb + 2 * ne + (size_t)k * 8));
+  double* drv = d + (size_t)nvec * kp + 2 * nvec;
+  RegVecHookArgs h{RegHookArgs{*reg, k, kp, alpha, nvec, d, d + (size_t)nvec * kp, d + (size_t)nvec * kp + nvec}, drv, rlen};
+  std::vector<double> rvk((size_t)k, 0.0);
+  for (int c = 0; c < rlen; ++c) rvk[(size_t)c] = rvec[c];
+  hipError_t e = hipMemcpy(d, padded.data(), nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(drv, rvk.data(), (size_t)k * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(reg_hook_block_vec, dim3((unsigned)nvec), dim3(64), (size_t)((kp + 1) + 64 + 16) * 8, 0, h);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(prox_out, d, nb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(eval_in, h.a.ein, ne, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(eval_out, h.a.eout, ne, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_regvec_prox_eval: %s", hipGetErrorString(e));
+  return GLRM_OK;
+}
 #endif

@@ -63,6 +63,34 @@ def partition(ptr, parts):
     return b
 
 
+def install_regularizers(api, h, glrm, rows=None, cols=None, multi=False):
+    """The model's regularizers (of rows [rb, re) / columns [cb, ce) for one shard) on a live handle: glrm_hip_set_regularizers, or
+    glrm_hip_set_regularizers_vec when one of them carries a vector (include/glrm_hip_regvec.h).  Every path that slices descriptors
+    slices the vectors here as well."""
+    from .regularizers import pack_reg_vectors, pack_regs
+    rx = glrm.rx if rows is None else (glrm.rx[rows[0]:rows[1]] if rows[1] > rows[0] else glrm.rx[:1])
+    ry = glrm.ry if cols is None else (glrm.ry[cols[0]:cols[1]] if cols[1] > cols[0] else glrm.ry[:1])
+    if not _carries(glrm):
+        (api.multi_set_regularizers if multi else api.set_regularizers)(h, pack_regs(rx), pack_regs(ry))
+        return
+
+    def side(regs):
+        """(descriptors, (table, lengths)); a side (or a shard's slice) without a vector still passes a table of zero lengths: a handle that
+        is given one runs the general sweeps, so every shard of a model lands on the same family (include/glrm_hip_regvec.h)."""
+        v = pack_reg_vectors(regs, glrm.k)
+        if v is None:
+            d = pack_regs(regs)
+            return d, (np.zeros(glrm.k * len(d)), np.zeros(len(d), dtype=np.int32))
+        return v[0], v[1:]
+    (dx, vx), (dy, vy) = side(rx), side(ry)
+    (api.multi_set_regularizers_vec if multi else api.set_regularizers_vec)(h, dx, vx, dy, vy)
+
+
+def _carries(glrm):
+    from .regularizers import carries_vector
+    return carries_vector(list(glrm.rx) + list(glrm.ry))
+
+
 def _ensure_handle(glrm, api, params, allow_dense=True):
     """The model's engine handle (created on first use, kept on the model: Omega and A stay on the device across fit! calls,
     README.md:337-346 warm starts, cross-validation drivers).  A change of the regularizers only replaces the descriptors
@@ -79,11 +107,16 @@ def _ensure_handle(glrm, api, params, allow_dense=True):
     if cache is None:
         # a model built from a sparse matrix's pattern goes over as its column view alone (GLRM_PROBLEM_ROWS_FROM_COLS)
         h = api.create(glrm.problem_arrays(dense=use_dense, cols_only=getattr(glrm, "_pattern_from_csc", False) and not use_dense), **_engine_opts(params))
+        if _carries(glrm):  # created from the placeholder descriptors (regularizers.pack_regs): now the real ones with their vectors
+            try:
+                install_regularizers(api, h, glrm)
+            except Exception:
+                api.destroy(h)
+                raise
         glrm._handle_cache = (api, h, key, soft, use_dense)
     elif cache[3] != soft:
         # only the regularizers changed: keep Omega / A on the device
-        from .regularizers import pack_regs
-        api.set_regularizers(cache[1], pack_regs(glrm.rx), pack_regs(glrm.ry))
+        install_regularizers(api, cache[1], glrm)
         glrm._handle_cache = cache[:3] + (soft,) + tuple(cache[4:])
     return glrm._handle_cache[1], key, soft
 
@@ -160,7 +193,6 @@ def _fit_multi_in_process(glrm, params, ch, verbose, api):
     """``HipProxGradParams(ngpus=N)``: one process, N devices (include/glrm_hip.h, glrm_hip_multi_*).  The multi handle is cached on
     the model like the single-device one (Omega / A stay on the devices across warm starts; new regularizers only replace the
     descriptors)."""
-    from .regularizers import pack_regs
     use_dense = api.dense_ok and glrm.dense_eligible() and getattr(params, "dense", True)
     hard, soft = glrm._descriptor_key()
     key = (id(api), "multi", params.ngpus, tuple(params.device_ids or ()), params.exchange, params.x_chunks, bool(getattr(params, "quad_gram", False)), getattr(params, "mode", "fast"), hard)
@@ -173,9 +205,15 @@ def _fit_multi_in_process(glrm, params, ch, verbose, api):
         mh = api.multi_create(glrm.problem_arrays(dense=use_dense), params.ngpus, params.device_ids, 1 if params.exchange == "rccl" else 0,
                               params.x_chunks, profile=o["profile"], waves_row=o["waves_row"], waves_col=o["waves_col"], tiled=o["tiled"], quad_gram=o["quad_gram"],
                               sum_order=o["sum_order"])
+        if _carries(glrm):
+            try:
+                install_regularizers(api, mh, glrm, multi=True)
+            except Exception:
+                api.multi_destroy(mh)
+                raise
         glrm._handle_cache = (api, mh, key, soft, use_dense, "multi")
     elif cache[3] != soft:
-        api.multi_set_regularizers(cache[1], pack_regs(glrm.rx), pack_regs(glrm.ry))
+        install_regularizers(api, cache[1], glrm, multi=True)
         glrm._handle_cache = cache[:3] + (soft,) + tuple(cache[4:])
     mh = glrm._handle_cache[1]
     X = np.asfortranarray(glrm.X, dtype=np.float64)
@@ -507,6 +545,8 @@ def _fit_distributed(glrm, params, ch, verbose, api, group):
     sf = ShardedFit(api, prob, rbs, cbs, group=group, device=device, stream=stream, opts=opts,
                     x_chunks=int(os.environ.get("GLRM_X_CHUNKS", getattr(params, "x_chunks", 1))))
     try:
+        if _carries(glrm):  # the shard was created from placeholder descriptors: the rank's slice of the real ones and of their vectors
+            install_regularizers(api, sf.h, glrm, rows=(rbs[rank], rbs[rank + 1]), cols=(cbs[rank], cbs[rank + 1]))
         if np.linalg.norm(glrm.Y) == 0:
             raise ValueError("Y is all zeros (the reference cannot start from Y == 0)")
         X = np.asfortranarray(glrm.X, dtype=np.float64)

@@ -19,7 +19,7 @@ import numpy as np
 
 from ._capi import EPOCH, ProblemArrays, TrackedList
 from .losses import Loss, embedding_dim, get_yidxs, pack_losses
-from .regularizers import OrdinalReg, Regularizer, lastentry1, lastentry_unpenalized, pack_regs
+from .regularizers import OrdinalReg, Regularizer, carries_vector, fixed_latent_features, lastentry1, lastentry_unpenalized, pack_reg_vectors, pack_regs
 
 try:  # scipy is optional: only needed for SparseMatrixCSC-like inputs
     import scipy.sparse as _sp
@@ -202,7 +202,8 @@ class GLRM:
         as fused GEMMs on the matrix cores (the `dense_A` hand-over of include/glrm_hip.h)."""
         return (self._fully_observed and not _issparse(self.A) and self.A.dtype != object and 8 < self.k <= 64
                 and len(pack_losses(self.losses)) == 1 and self.losses[0].kind == 0
-                and all(r.wrap == 0 for r in list(self.rx) + list(self.ry)))
+                and all(r.wrap == 0 for r in list(self.rx) + list(self.ry))
+                and not carries_vector(list(self.rx) + list(self.ry)))  # (the vector-carrying regularizers run on the general sweeps)
 
     def problem_arrays(self, rows=None, cols=None, dense=False, cols_only=False) -> ProblemArrays:
         """cols_only (whole problem, sparse-matrix pattern): the column view alone with GLRM_PROBLEM_ROWS_FROM_COLS -- what the Julia shim
@@ -249,7 +250,12 @@ class GLRM:
         if fp is not None and self._dk_cache is not None and self._dk_cache[0] == fp:
             return self._dk_cache[1]
         rx, ry = pack_regs(self.rx), pack_regs(self.ry)
-        key = (pack_losses(self.losses).tobytes(), len(rx), len(ry)), (rx.tobytes(), ry.tobytes())
+        # the soft key also holds the descriptors WITH the codes of include/glrm_hip_regvec.h and the contents of their vectors: a warm handle
+        # gets the new vectors when only an entry of one changed
+        vec = tuple(None if v is None else (v[0].tobytes(), v[1].tobytes(), v[2].tobytes())
+                    for v in (pack_reg_vectors(self.rx, self.k), pack_reg_vectors(self.ry, self.k)))
+        soft = (rx.tobytes(), ry.tobytes()) if vec == (None, None) else (rx.tobytes(), ry.tobytes(), vec)
+        key = (pack_losses(self.losses).tobytes(), len(rx), len(ry)), soft
         self._dk_cache = (fp, key)
         return key
 
@@ -275,6 +281,13 @@ def add_offset_(glrm):
     of Y is not penalised -- an unpenalised per-column offset.  OrdinalReg / MNLOrdinalReg already exempt their last row."""
     glrm.rx = TrackedList(lastentry1(r) for r in glrm.rx)
     glrm.ry = TrackedList(lastentry_unpenalized(r) for r in glrm.ry)
+    return glrm
+
+
+def fix_latent_features_(glrm, n):
+    """fix_latent_features!(glrm, n) (src/modify_glrm.jl:25-29): the first n latent features of every column are fixed to their current
+    values, ry[i] <- fixed_latent_features(ry[i], Y[0:n, i])."""
+    glrm.ry = TrackedList(fixed_latent_features(glrm.ry[i], glrm.Y[:n, i]) for i in range(len(glrm.ry)))
     return glrm
 
 

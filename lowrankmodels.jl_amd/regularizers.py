@@ -312,6 +312,8 @@ class _Wrapper(Regularizer):
         r = ZeroReg() if r is None else r
         if isinstance(r, _Wrapper) or r.kind < 0:
             raise NotImplementedError("nested wrappers are outside the accelerated path")
+        if r.kind == REM_QUAD:
+            raise NotImplementedError("RemQuadReg under a wrapper is outside the accelerated path")
         self.r = r
 
     kind = property(lambda self: self.r.kind)
@@ -386,12 +388,173 @@ class MNLOrdinalReg(OrdinalReg):  # src/regularizers.jl:388-411
         return u
 
 
+# ------------------------------------------------------------------------- regularizers that carry a vector (include/glrm_hip_regvec.h)
+# fixed_latent_features / fixed_last_latent_features (src/regularizers.jl:193-231) and RemQuadReg (:412-423), on k-vectors.  Their vector
+# travels beside the 16-byte descriptor through glrm_hip_set_regularizers_vec; ``descriptor()`` holds the codes only that entry point takes.
+REM_QUAD = 10
+WRAP_FIXED_FIRST, WRAP_FIXED_LAST = 16, 32
+
+
+def _frozen_vector(y):
+    """A private read-only float64 copy: the contents change only by assigning a new array, which ``__setattr__`` sees (``_bump_epoch``)."""
+    v = np.array(y, dtype=np.float64).reshape(-1)
+    v.setflags(write=False)
+    return v
+
+
+class _FixedFeatures(_Wrapper):
+    """Common part of the two fixed-features wrappers: base r, pinned values y (n = len(y)).  ``mul_`` and ``scale`` forward to the base
+    (:209-210,230-231)."""
+
+    def __init__(self, r, y):
+        super().__init__(r)  # nesting with the other wrappers, or RemQuadReg as the base, raises NotImplementedError there
+        self.y = y
+
+    def __rmul__(self, newscale):  # typeof(r)() has no method (:40)
+        raise TypeError(f"no method matching {type(self).__name__}() (src/regularizers.jl:40)")
+
+    def __setattr__(self, name, value):
+        if name == "y":
+            value = _frozen_vector(value)
+        Regularizer.__setattr__(self, name, value)
+
+    n = property(lambda self: len(self.y))
+
+    def vector(self):
+        return self.y
+
+    def _base_prox(self, sub, alpha):
+        """prox(r.r, sub, alpha).  With n = k the base sees an EMPTY vector: in the reference every base then returns the empty vector,
+        except the argmax / partialsortperm kinds, which throw (they are left to raise here; the engine refuses them)."""
+        if len(sub) == 0 and self.r.kind not in (UNIT_ONE_SPARSE, ONE_SPARSE, K_SPARSE):
+            return sub
+        return np.asarray(self.r.prox(sub, alpha), dtype=float)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.r!r}, {self.y.tolist()})"
+
+
+class fixed_latent_features(_FixedFeatures):  # src/regularizers.jl:193-210
+    """The first n entries are fixed to y, the other k - n are regularized by r."""
+    wrap = WRAP_FIXED_FIRST
+
+    def prox(self, u, alpha):  # [r.y; prox(r.r, u[(r.n+1):end], alpha)], :202
+        u = np.asarray(u, dtype=float)
+        return np.concatenate([self.y, self._base_prox(u[self.n:], alpha)])
+
+    def evaluate(self, a):  # a[1:r.n] == r.y ? evaluate(r.r, a[(r.n+1):end]) : Inf, :208
+        a = np.asarray(a, dtype=float)
+        return self.r.evaluate(a[self.n:]) if np.array_equal(a[:self.n], self.y) else float("inf")
+
+
+class fixed_last_latent_features(_FixedFeatures):  # src/regularizers.jl:214-231
+    """The last n entries are fixed to y.  ``prox`` is the reference's, literally (:223): the base is fed ``u[n:]`` -- the LAST k - n entries of
+    u -- and its result becomes the FIRST k - n entries.  Reproduced, not repaired."""
+    wrap = WRAP_FIXED_LAST
+
+    def prox(self, u, alpha):  # [prox(r.r, u[(r.n+1):end], alpha); r.y], :223
+        u = np.asarray(u, dtype=float)
+        return np.concatenate([self._base_prox(u[self.n:], alpha), self.y])
+
+    def evaluate(self, a):  # a[length(a)-r.n+1:end] == r.y ? evaluate(r.r, a[1:length(a)-r.n]) : Inf, :229
+        a = np.asarray(a, dtype=float)
+        cut = len(a) - self.n
+        return self.r.evaluate(a[:cut]) if np.array_equal(a[cut:], self.y) else float("inf")
+
+
+def FixedLatentFeaturesConstraint(y):  # :200
+    return fixed_latent_features(ZeroReg(), y)
+
+
+def FixedLastLatentFeaturesConstraint(y):  # :221
+    return fixed_last_latent_features(ZeroReg(), y)
+
+
+class RemQuadReg(Regularizer):  # src/regularizers.jl:412-423
+    """Quadratic regularization with a non-zero mean: ``RemQuadReg(m)`` or ``RemQuadReg(scale, m)`` (:416).  ``mul_`` sets ``scale`` (the
+    generic mul!, :38); ``newscale * r`` raises, like ``typeof(r)()`` does (:40)."""
+    kind = REM_QUAD
+
+    def __init__(self, *args):
+        if len(args) == 1:
+            scale, m = 1, args[0]
+        elif len(args) == 2:
+            scale, m = args
+        else:
+            raise TypeError("RemQuadReg(m) or RemQuadReg(scale, m)")
+        super().__init__(scale)
+        self.m = m
+
+    def __setattr__(self, name, value):
+        if name == "m":
+            value = _frozen_vector(value)
+        Regularizer.__setattr__(self, name, value)
+
+    def __rmul__(self, newscale):
+        raise TypeError("no method matching RemQuadReg() (src/regularizers.jl:40)")
+
+    def vector(self):
+        return self.m
+
+    def prox(self, u, alpha):  # (u + 2 * alpha * r.scale * r.m) / (1 + 2 * alpha * r.scale), :417-418
+        u = np.asarray(u, dtype=float)
+        t = 2 * alpha * self.scale
+        return (u + t * self.m) / (1 + t)
+
+    def evaluate(self, a):  # r.scale * sum(abs2, a - r.m), :423
+        return self.scale * float(np.sum((np.asarray(a, dtype=float) - self.m) ** 2))
+
+    def __repr__(self):
+        return f"RemQuadReg({self.scale}, {self.m.tolist()})"
+
+
 def prox(r, u, alpha):
     return r.prox(u, alpha)
 
 
-def pack_regs(regs):
+_FIXED = WRAP_FIXED_FIRST | WRAP_FIXED_LAST
+
+
+def _carrier(desc):
+    return desc[0] == REM_QUAD or (desc[1] & _FIXED) != 0
+
+
+def _collapse(regs):
+    """(regularizers, descriptors) as they go over: ONE when every entry is the same regularizer (descriptor and vector alike), else one
+    per entry."""
+    regs = list(regs)
     descs = [r.descriptor() for r in regs]
-    if len(set(descs)) == 1:
-        descs = descs[:1]
+    if len(set(descs)) == 1 and (not _carrier(descs[0]) or len({r.vector().tobytes() for r in regs}) == 1):
+        return regs[:1], descs[:1]
+    return regs, descs
+
+
+def pack_regs(regs):
+    """The descriptors glrm_hip_create / glrm_hip_set_regularizers take.  A regularizer that carries a vector appears as its PLACEHOLDER (the
+    base kind without the fixed-features flag; ZeroReg for RemQuadReg) with the count ``pack_reg_vectors`` uses: creation goes through the
+    placeholders and is followed by glrm_hip_set_regularizers_vec."""
+    descs = _collapse(regs)[1]
+    if any(_carrier(d) for d in descs):
+        descs = [(ZERO, 0, 1.0) if d[0] == REM_QUAD else (d[0], d[1] & ~_FIXED, d[2]) for d in descs]
     return np.array(descs, dtype=REG_DTYPE)
+
+
+def pack_reg_vectors(regs, k):
+    """None when no regularizer of ``regs`` carries a vector; else (descriptors with the codes of include/glrm_hip_regvec.h, the k x count
+    column-major table of their vectors as a flat array, the int32 lengths) -- one side's arguments of glrm_hip_set_regularizers_vec."""
+    regs, descs = _collapse(regs)
+    if not any(_carrier(d) for d in descs):
+        return None
+    k = int(k)
+    table = np.zeros((len(regs), k))
+    lens = np.zeros(len(regs), dtype=np.int32)
+    for i, r in enumerate(regs):
+        if _carrier(descs[i]):
+            v = r.vector()
+            lens[i] = len(v)
+            table[i, :min(len(v), k)] = v[:k]
+    return np.array(descs, dtype=REG_DTYPE), np.ascontiguousarray(table.reshape(-1)), lens
+
+
+def carries_vector(regs):
+    return any(_carrier(r.descriptor()) for r in regs)
