@@ -37,8 +37,9 @@ using namespace glrm;
 // (profiles/r03_c4_blocked_knobs.txt).  Changes no sum (a lane group owns a segment whatever workgroup it sits in).
 constexpr int BNW = 1;                                                     // waves per workgroup
 // GLRM_HIP_BLOCKED_GATE: phase gate of the passes in rows (tiled_pass, L2 = true), 0 = off.  Off is NOT the kernel of round 6: the gated
-// loop is compiled in either way (134 instead of 118 VGPRs, 3 waves per SIMD), and C4's Y half-step runs 134.1 ms with the gate off
-// against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).
+// loop is compiled in either way (134 instead of 118 VGPRs and 3 waves per SIMD when it was built), and C4's Y half-step ran 134.1 ms with
+// the gate off against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).  Since the 32-bit gather offsets the
+// rank-64 QuadLoss gradient kernel is built for 128 VGPRs and 4 waves per SIMD again, gate included (pass_waves_per_simd, glrm_tiled.hpp).
 constexpr int BLOCKED_GATE_DEFAULT = 8192;
 
 // suppos[seg * nsup + sup] = lower_bound_idx(segment seg's list, first row of super-tile sup) - ptr[seg]: the pass kernel's own search, so
@@ -115,6 +116,9 @@ int glrm_setup_blocked(glrm_handle* h) {
     const int64_t ntiles = (nopp + T - 1) / T;
     int64_t t = ((int64_t)128 * 1024 * 1024) / ((int64_t)T * h->kp * 8); // ~128 MB of the opposing factor per super-tile
     t = env_int("GLRM_HIP_BLOCKED_TPS", (int)(t < 1 ? 1 : t));
+    // the passes address an observation's vector by a 32-bit byte offset from the first row of its super-tile (tiled_pass, L2 = true)
+    if ((double)std::min<int64_t>(t * T, nopp) * h->kp * 8 >= 4294967296.0)
+      return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: GLRM_HIP_BLOCKED_TPS=%lld makes a super-tile of 4 GiB or more of the opposing factor", (long long)t);
     h->pass[side].tiles_per_sup = (int)t;
     h->pass[side].nsup = (int)((ntiles + t - 1) / t);
     return glrm_alloc_pass_buffers(h, side);
@@ -168,7 +172,8 @@ static int64_t slice_capacity(K kernel, int device, int spb) {
   // (launches of one stream overlap at their tails), which a slice of exactly the residency cannot do -- C4 Y half-step 143.2 -> 138.4 ms
   // with four-wave workgroups (25 / 33 / 66 / 100 / 200 %: 149.0 / 148.1 / 141.6 / 143.2 / 144.1), and with one-wave workgroups
   // 25 / 33 / 40 / 50 / 60 / 75 / 100 %: 139.7 / 137.0 / 135.6 / 131.0 / 133.0 / 136.9 / 144.4 (profiles/r03_c4_blocked_knobs.txt).
-  // Changes no sum.
+  // With the gradient pass at 4 waves per SIMD (16 384 columns per launch in both passes) 40 / 50 / 60 / 75 %: 116.1 / 110.8 / 117.2 /
+  // 119.7 ms (profiles/r13_c4_ab.txt): half stays.  Changes no sum.
   const int pct = env_int("GLRM_HIP_BLOCKED_FILL", 50);
   return std::max<int64_t>(spb, cap * pct / 100 / spb * spb);
 }

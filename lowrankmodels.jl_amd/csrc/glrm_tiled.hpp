@@ -248,7 +248,13 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
     const int64_t lo = (int64_t)t * TILE;
     const int64_t hi_ = L2 ? (int64_t)tile_end * TILE : lo + TILE;
     const int64_t hi = hi_ < a.n_other ? hi_ : a.n_other;
+    // L2, two-observation step of the uniform QuadLoss model: sup_base is the wave-uniform address of the super-tile's first row, and an
+    // observation's vector sits at a 32-BIT byte offset from it, (row - lo) * ROWB + j * 16, instead of a 64-bit multiply-add per
+    // observation (what kept the rank-64 gradient kernel a wave per SIMD lower, see pass_waves_per_simd).  row >= lo for every consumed
+    // entry -- pos starts at the first entry of the super-tile and the lists are in tile order -- and glrm_setup_blocked refuses a
+    // super-tile of 4 GiB or more.
     const char* const mem = L2 ? reinterpret_cast<const char*>(a.other) : lds;
+    const char* const sup_base = mem + (L2 ? lo * ROWB : 0);
     if constexpr (!L2) {
       __syncthreads(); // everybody is done with the previous tile
       dma_tile_all<G, R, NW, ROT>(a.other, lo, hi, lds, (int)(threadIdx.x >> 6), lane);
@@ -399,8 +405,15 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
         if (ok0) {
           double2 y0[R / 2], y1[R / 2];
           if constexpr (L2) {
-            const char* rp0 = mem + (int64_t)c0 * ROWB + j * 16;
-            const char* rp1 = mem + (int64_t)(ok1 ? c1 : c0) * ROWB + j * 16;
+            const int c1v = ok1 ? c1 : c0; // a clamped lane re-reads the row of a valid entry
+            const char *rp0, *rp1;
+            if constexpr (LOSS == 0) {
+              rp0 = sup_base + ((uint32_t)(c0 - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * 16));
+              rp1 = sup_base + ((uint32_t)(c1v - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * 16));
+            } else { // rank 128 with a loss per column: the 32-bit form costs these kernels SGPR spills
+              rp0 = mem + (int64_t)c0 * ROWB + j * 16;
+              rp1 = mem + (int64_t)c1v * ROWB + j * 16;
+            }
 #pragma unroll
             for (int i = 0; i < R / 2; ++i) y0[i] = *reinterpret_cast<const double2*>(rp0 + i * CB);
 #pragma unroll
@@ -653,8 +666,23 @@ __device__ __forceinline__ int64_t lower_bound_idx(const int32_t* idx, int64_t b
 // L2 = true: the phase-aligned gather pass (no LDS tile, tiled_pass<..., L2>).  One launch covers ONE super-tile (a.sup_fixed) and
 // a slice [a.seg_begin, a.seg_begin + a.nseg_slice) of the segments that is at most what the chip holds at once, so every group of
 // the launch starts its walk through the super-tile at the same moment; the host issues the launches super-tile by super-tile.
+//
+// Waves per SIMD an instantiation is BUILT for (the second launch bound).  The LDS-tiled kernels: 4.  The phase-aligned ones take whatever
+// their registers allow (1), except the GRADIENT pass of the uniform-QuadLoss model at rank 64 and 32: with 32-bit gather offsets
+// (tiled_pass) it fits 128 VGPRs without scratch (132 unbound at rank 64), i.e. 4 waves per SIMD instead of 3, and slice_capacity
+// (glrm_blocked.hip) turns the occupancy into columns per launch -- more columns walking the same window of the opposing factor on an XCD
+// (C4 Y half-step 114.1 -> 110.8 ms).  The trial pass stays at what its 98 / 89 VGPRs give, 4 / 5 waves: held to 96 VGPRs and 5 waves the
+// rank-64 one is clean too, but LOSES (113.0 ms; LABNOTES "phase-aligned passes at 4 / 5 waves per SIMD").  Every other instantiation
+// spills at such bounds (rank 128: 20 / 12 B, LOSS != 0: 28-252 B) and keeps its own; no kernel gains scratch or loses a wave.
+template <int G, int R, int LOSS, bool GRAD, bool L2>
+constexpr int pass_waves_per_simd() {
+  if (!L2) return 4;
+  if (LOSS == 0 && R == 8 && (G == 8 || G == 4) && GRAD) return 4;
+  return 1;
+}
+
 template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROWS = false>
-__global__ void __launch_bounds__(NW * 64, L2 ? 1 : 4) tiled_col_pass_kernel(const TiledArgs a) {
+__global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD, L2>())) tiled_col_pass_kernel(const TiledArgs a) {
   constexpr int KP = G * R, NGW = 64 / G, SPB = NW * NGW, PSTRIDE = KP + 2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
