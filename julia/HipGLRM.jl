@@ -10,6 +10,7 @@
 #   HipGLRMDescriptors.jl  loss / regularizer types -> (kind, dim, scale, p0, p1) / (kind, wrap, scale); which models the engine takes
 #   HipGLRMExtras.jl       init_svd! / error_metric / impute / subset / sum_order on the same cached handle
 #   HipGLRMRegVec.jl       fixed_latent_features / fixed_last_latent_features / RemQuadReg: glrm_hip_set_regularizers_vec
+#   HipGLRMTopK.jl         precision_at_k's `sort(XY[:])` and double loop on the device: glrm_hip_xy_select / glrm_hip_precision_scan
 # Omega at north-star scale (1e9 observations): a `SparseMatrixCSC` whose lists are the constructor's (`findall(!iszero, A)`,
 # src/glrm.jl:46-48) IS the column view -- colptr / rowval / nzval are handed over after one index shift and NOTHING ELSE: the row view
 # (ascending columns per row = the order sort_observations pushes them in, src/modify_glrm.jl:8-12) is derived by the engine on the

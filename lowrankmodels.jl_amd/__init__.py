@@ -9,7 +9,7 @@ from ._capi import GLRMError
 from .convergence import ConvergenceHistory, update_ch
 from .fit import ShardedFit, fit, fit_b, objective, partition
 from .crossval import (cross_validate, cv_by_iter, flatten_observations, get_train_and_test, getfolds, loss_fn,
-                             regularization_path)
+                             precision_at_k, regularization_path)
 from .initialize import init_kmeanspp_, init_svd_
 from .scaling import equilibrate_variance_, prob_scale_
 from .domains import (BoolDomain, CategoricalDomain, CountDomain, Domain, OrdinalDomain, PeriodicDomain, RealDomain, default_domain,

@@ -165,6 +165,10 @@ STORAGE_SYMBOLS = ("storage",)
 #: the vector-carrying regularizers, include/glrm_hip_regvec.h: outside the boundary, bound only where the library has them
 REGVEC_SYMBOLS = ("set_regularizers_vec", "multi_set_regularizers_vec")
 
+#: the top-k extension, include/glrm_hip_topk.h (the rank-th largest entry of X'Y, the ordered scan of precision_at_k): outside the boundary,
+#: bound only where the library has it
+TOPK_SYMBOLS = ("xy_select", "xy_select_info", "precision_scan")
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -261,8 +265,12 @@ class Api:
             "storage": (C.c_int, [H]),
             "set_regularizers_vec": (C.c_int, [H, C.c_void_p, C.c_int64, C.POINTER(CRegVec), C.c_void_p, C.c_int64, C.POINTER(CRegVec)]),
             "multi_set_regularizers_vec": (C.c_int, [H, C.c_void_p, C.c_int64, C.POINTER(CRegVec), C.c_void_p, C.c_int64, C.POINTER(CRegVec)]),
+            "xy_select": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+            "xy_select_info": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+            "precision_scan": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -577,6 +585,61 @@ class Api:
             weights = np.full((k - 1, int(m)), np.nan)
         self._ck(fn(h, _ptr(Y), int(first), _ptr(u) if k > 1 else None, _ptr(centers), _ptr(weights) if k > 1 else None))
         return centers, weights
+
+    # -- top-k extension (include/glrm_hip_topk.h) -------------------------------------------
+    def _topk(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the top-k extension "
+                                             "(include/glrm_hip_topk.h is implemented by the HIP engine only)")
+        return fn
+
+    @staticmethod
+    def _factor_pair(X, Y):
+        """Host factors as Fortran-ordered float64 arrays (k x m, k x n), or (None, None) for the handle's resident factors."""
+        if (X is None) != (Y is None):
+            raise ValueError("X and Y must both be given or both be None (None = the factors resident in the handle)")
+        if X is None:
+            return None, None
+        return np.asfortranarray(X, dtype=np.float64), np.asfortranarray(Y, dtype=np.float64)
+
+    def xy_select(self, h, X, Y, rank):
+        """glrm_hip_xy_select: (q, n_gt, n_eq) with q the ``rank``-th largest (1-based) of all u_ij = the ascending fma chain of
+        <x_i, y_j> -- ``sort(XY[:], rev=true)[rank]`` -- under Julia's isless (NaN greatest, -0.0 < +0.0), n_gt the entries above q and
+        n_eq the entries equal to it.  ``X``, ``Y``: k x m and k x n, or both None for the handle's resident factors."""
+        fn = self._topk("xy_select")
+        X, Y = self._factor_pair(X, Y)
+        q, gt, eq = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+        self._ck(fn(h, _ptr(X), _ptr(Y), int(rank), C.byref(q), C.byref(gt), C.byref(eq)))
+        return q.value, gt.value, eq.value
+
+    def xy_select_info(self):
+        """(passes over X'Y, keys sorted by the early finish) of this thread's last xy_select."""
+        fn = self._topk("xy_select_info")
+        p, s = C.c_int32(0), C.c_int64(0)
+        self._ck(fn(C.byref(p), C.byref(s)))
+        return p.value, s.value
+
+    def precision_scan(self, h, X, Y, q, test_rowptr, test_colidx, kprec, block_rows=0, want_hits=True):
+        """glrm_hip_precision_scan on the TRAIN model's handle: the loop of src/cross_validate.jl:275-297.  ``test_rowptr`` / ``test_colidx``:
+        the test lists as 0-based CSR (m + 1 offsets, column indices).  Returns (true_pos, false_pos, hits, rows_scanned) with hits =
+        (rows, cols, is_true) of the entries that counted, in the order of the walk (None without ``want_hits``)."""
+        fn = self._topk("precision_scan")
+        X, Y = self._factor_pair(X, Y)
+        ptr = np.ascontiguousarray(test_rowptr, dtype=np.int64)
+        idx = np.ascontiguousarray(test_colidx, dtype=np.int32)
+        tp, fp, rows = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        cap = max(int(kprec), 0)
+        hr = hc = ht = None
+        if want_hits:
+            hr, hc, ht = np.full(max(cap, 1), -1, dtype=np.int64), np.full(max(cap, 1), -1, dtype=np.int64), np.zeros(max(cap, 1), dtype=np.uint8)
+        self._ck(fn(h, _ptr(X), _ptr(Y), float(q), _ptr(ptr), _ptr(idx) if len(idx) else None, int(kprec), int(block_rows),
+                    C.byref(tp), C.byref(fp), _ptr(hr), _ptr(hc), _ptr(ht), C.byref(rows)))
+        hits = None
+        if want_hits:
+            cnt = tp.value + fp.value
+            hits = (hr[:cnt].copy(), hc[:cnt].copy(), ht[:cnt].astype(bool))
+        return tp.value, fp.value, hits, rows.value
 
 
 class ProblemArrays:

@@ -1,4 +1,4 @@
-"""cross_validate / cv_by_iter / regularization_path / get_train_and_test (reference: src/cross_validate.jl:1-240) on the
+"""cross_validate / cv_by_iter / regularization_path / get_train_and_test / precision_at_k (reference: src/cross_validate.jl:1-304) on the
 MI355X engine, with the driver-level fusion of SURVEY.md section 8(f) rank 2: the data matrix is uploaded once; every
 train / test model of a fold is a ``glrm_hip_subset`` of the resident parent handle (one tag byte per observation crosses
 PCIe instead of 12 bytes per observation and view), the regularization path re-fits on one handle through
@@ -16,7 +16,7 @@ import numpy as np
 from . import _capi
 from .convergence import ConvergenceHistory
 from .fit import _ensure_handle, fit_b, objective
-from .glrm import copy_estimate, parameter_estimate, scale_regularizer_
+from .glrm import GLRM, _flatten, copy_estimate, parameter_estimate, scale_regularizer_
 from .params import Params, ProxGradParams
 
 
@@ -228,3 +228,73 @@ def regularization_path(glrm, test_glrm=None, params=None, reg_params=None, hold
         if verbose:
             print(f"computing mean train and test error for reg_param {reg_param}:\n\ttrain error: {train_error[ip]}\n\ttest error:  {test_error[ip]}")
     return train_error, test_error, train_time, reg_params
+
+
+def precision_at_k(train_glrm, test_observed_features, params=None, reg_params=None, verbose=True, ch=None, kprec=10, rng=None, engine=None):
+    """precision_at_k(train_glrm, test_observed_features; params, reg_params, verbose, ch, kprec) -> (train_error, test_error, prec_at_k,
+    train_time, reg_params, solution) (src/cross_validate.jl:243-304).  For every reg_param: fit the train model from a fresh random start,
+    take q = the ntrain-th largest entry of X'Y, walk X'Y row by row for the first ``kprec`` entries >= q that are either in the test set
+    (true positives) or in neither set (false positives), and report true_pos / (true_pos + false_pos).
+
+    The reference forms the dense m x n matrix XY and sorts all of it (:273-274); here q comes from ``glrm_hip_xy_select`` and the walk from
+    ``glrm_hip_precision_scan`` (include/glrm_hip_topk.h) on the train model's resident handle: nothing m x n exists, on the host or on the
+    device.  The model needs one vector of Y per column (scalar losses) and observation lists (``HipProxGradParams(dense=False)`` for a
+    fully observed QuadLoss model, whose handle would otherwise be the dense one, which the engine refuses here).
+
+    The control flow is the reference's, quirks included:
+      * the regularizer scales are SET to reg_param, not multiplied: ``mul!(train_glrm.rx, reg_param)`` assigns (src/regularizers.jl:38,
+        called at src/cross_validate.jl:262-263) -- ``scale_regularizer_``;
+      * X and Y are re-drawn as randn before every fit (:264), from ``rng`` (a numpy Generator; Julia's stream is not reproduced, as
+        elsewhere in this file), so no fit is warm-started; the fits run on ONE resident handle for the whole path;
+      * test_error is divided by ntrain, not ntest (:270);
+      * test_error is evaluated on a model built with ``observed_features = test`` only (:255-257), whose column view -- what objective()
+        sums over -- is therefore EVERY row of every column (src/glrm.jl:33-34);
+      * prec_at_k = true_pos / (true_pos + false_pos) is NaN for 0 / 0 (:298);
+      * solution[i] = (sum(X) + sum(Y), sum|X| + sum|Y|) (:300), returned as an array with one row per reg_param;
+      * defaults: reg_params = 10 .^ range(2, -2, length=5), Params() (:243-245; ``holdout_proportion`` is accepted and unused there).
+    """
+    params = Params() if params is None else params
+    reg_params = np.power(10.0, np.linspace(2, -2, 5)) if reg_params is None else np.asarray(reg_params, dtype=float)
+    ch = ConvergenceHistory("reg_path") if ch is None else ch
+    rng = np.random.default_rng() if rng is None else rng
+    api = engine if engine is not None else _capi.hip_api()
+    m, n, k = train_glrm.m, train_glrm.n, train_glrm.k
+    if len(test_observed_features) != m:
+        raise ValueError("test_observed_features must have one list per row")
+    ntrain = int(train_glrm._rowptr[-1])                                                                   # :247
+    test_ptr, test_idx = _flatten(test_observed_features, n)
+    nparams = len(reg_params)
+    train_error, test_error, prec_at_k_, train_time = (np.full(nparams, np.nan) for _ in range(4))
+    solution = np.full((nparams, 2), np.nan)
+    test_glrm = GLRM(train_glrm.A, train_glrm.losses, train_glrm.rx, train_glrm.ry, k, X=train_glrm.X.copy(), Y=train_glrm.Y.copy(),
+                     observed_features=test_observed_features)                                             # :255-257
+    try:
+        for ip, reg_param in enumerate(reg_params):
+            if verbose:
+                print(f"fitting train GLRM for reg_param {reg_param}")
+            scale_regularizer_(train_glrm, reg_param)                                                      # :262-263
+            train_glrm.X[...] = rng.standard_normal((k, m))                                                # :264
+            train_glrm.Y[...] = rng.standard_normal(train_glrm.Y.shape)
+            X, Y, ch = fit_b(train_glrm, params, ch=ch, verbose=verbose, engine=engine)                    # same handle: only the descriptors are replaced
+            train_time[ip] = ch.times[-1]
+            if verbose:
+                print(f"computing train error and precision at k for reg_param {reg_param}:")
+            train_error[ip] = objective(train_glrm, X, Y, include_regularization=False, engine=engine) / ntrain
+            if verbose:
+                print(f"\ttrain error: {train_error[ip]}")
+            test_error[ip] = objective(test_glrm, X, Y, include_regularization=False, engine=engine) / ntrain   # :270
+            if verbose:
+                print(f"\ttest error: {test_error[ip]}")
+            h = _ensure_handle(train_glrm, api, params)[0]
+            q, _, _ = api.xy_select(h, X, Y, ntrain)                                                       # :273-274
+            true_pos, false_pos, _, _ = api.precision_scan(h, None, None, q, test_ptr, test_idx, kprec, want_hits=False)   # :275-297, on the factors just uploaded
+            with np.errstate(divide="ignore", invalid="ignore"):
+                prec_at_k_[ip] = np.float64(true_pos) / np.float64(true_pos + false_pos)                   # :298
+            if verbose:
+                print(f"\tprec_at_k:  {prec_at_k_[ip]}")
+            solution[ip] = (np.sum(X) + np.sum(Y), np.sum(np.abs(X)) + np.sum(np.abs(Y)))                  # :300
+            if verbose:
+                print(f"\tsum of solution, one norm of solution:  {tuple(solution[ip])}")
+    finally:
+        test_glrm.close()
+    return train_error, test_error, prec_at_k_, train_time, reg_params, solution
