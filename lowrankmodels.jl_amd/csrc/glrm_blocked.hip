@@ -69,7 +69,7 @@ static int build_suppos(glrm_handle* h, int side) {
   const bool build = mode != 0 && cells > 0 && (fits || mode >= 2);
   if (build) {
     unsigned int too_long = 0;
-    HIPCK(hipMalloc((void**)&b.suppos, (size_t)cells * 4));
+    if (const int rc = h->mem.alloc(&b.suppos, (size_t)cells)) return rc;
     HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
     hipLaunchKernelGGL(suppos_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, side == 0 ? h->rowptr : h->colptr,
                        side == 0 ? h->colidx : h->rowidx, nseg, b.nsup, (int64_t)b.tiles_per_sup * glrm_tile_rows(h->kp), b.suppos, h->nactive);

@@ -27,16 +27,10 @@ static int pack_view(glrm_handle* h, const double* dsrc, int64_t ldsrc, int colm
                      int64_t nseg, int64_t nother, double** dst, int64_t* lda) {
   const int64_t nseg_pad = round_up(nseg > 0 ? nseg : 1, 256); // whole 16-wave workgroups stay in bounds
   *lda = round_up(nother, 64);
-  HIPCK(hipMalloc((void**)dst, (size_t)nseg_pad * (size_t)*lda * 8));
+  if (const int rc = h->mem.alloc(dst, (size_t)nseg_pad * (size_t)*lda)) return rc;
   const dim3 grid((unsigned)(*lda / 32), (unsigned)(nseg_pad / 32));
   hipLaunchKernelGGL(dense_pack_kernel, grid, dim3(256), 0, h->stream, dsrc, ldsrc, colmajor, transpose, seg0, nseg, nother, *dst, *lda);
   HIPCK(hipGetLastError());
-  return GLRM_OK;
-}
-
-template <typename T>
-static int alloc_arr(T** p, int64_t count) {
-  HIPCK(hipMalloc((void**)p, (size_t)(count > 0 ? count : 1) * sizeof(T)));
   return GLRM_OK;
 }
 
@@ -81,6 +75,7 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
     if (bad) return fail(GLRM_ERR_NONFINITE, "Observed value in entry (%lld, %lld) is NaN.", (long long)bi, (long long)bj);
   }
   int rc = GLRM_OK;
+  DevArena scratch; // the staged upload of the caller's host matrix
   if (on_dev) {
     rc = pack_view(h, p->dense_A, ld, cm, 0, h->rb, h->ml, h->n, &h->Arow, &h->lda_r);
     if (!rc) rc = pack_view(h, p->dense_A, ld, cm, 1, h->cb, h->nl, h->m, &h->Acol, &h->lda_c);
@@ -88,13 +83,13 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   } else if (whole) {
     double* tmp = nullptr;
     const size_t runs = cm ? (size_t)p->n : (size_t)p->m, run = cm ? (size_t)p->m : (size_t)p->n; // contiguous runs and their length
-    HIPCK(hipMalloc((void**)&tmp, runs * run * 8));
+    if ((rc = scratch.alloc(&tmp, runs * run))) return rc;
     if (hipMemcpy2DAsync(tmp, run * 8, p->dense_A, (size_t)ld * 8, run * 8, runs, hipMemcpyHostToDevice, h->stream) != hipSuccess)
       rc = fail(GLRM_ERR_HIP, "upload of the dense matrix failed");
     if (!rc) rc = pack_view(h, tmp, (int64_t)run, cm, 0, 0, h->ml, h->n, &h->Arow, &h->lda_r);
     if (!rc) rc = pack_view(h, tmp, (int64_t)run, cm, 1, 0, h->nl, h->m, &h->Acol, &h->lda_c);
     if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GLRM_ERR_HIP, "dense pack failed");
-    (void)hipFree(tmp);
+    scratch.release(&tmp);
   } else {
     // (which, first segment, segments, extent of the other dimension) for the row block and the column block
     for (int which = 0; which < 2 && !rc; ++which) {
@@ -105,13 +100,13 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
       const size_t width = (size_t)(seg_is_run ? other : ns) * 8, height = (size_t)(seg_is_run ? ns : other);
       const double* src = p->dense_A + (seg_is_run ? s0 * ld : s0);
       double* tmp = nullptr;
-      HIPCK(hipMalloc((void**)&tmp, width * height));
+      if ((rc = scratch.alloc(&tmp, width / 8 * height))) return rc;
       if (hipMemcpy2DAsync(tmp, width, src, (size_t)ld * 8, width, height, hipMemcpyHostToDevice, h->stream) != hipSuccess)
         rc = fail(GLRM_ERR_HIP, "upload of the dense block failed");
       // inside tmp the block starts at segment 0 and has leading dimension width / 8
       if (!rc) rc = pack_view(h, tmp, (int64_t)(width / 8), cm, which, 0, ns, other, which ? &h->Acol : &h->Arow, which ? &h->lda_c : &h->lda_r);
       if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GLRM_ERR_HIP, "dense pack failed");
-      (void)hipFree(tmp);
+      scratch.release(&tmp);
     }
   }
   if (rc) return rc;
@@ -123,10 +118,10 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   // glrm_options.quad_gram: line-search trials from the quadratic form, no pass over A per trial
   h->dense_gram = h->opts.quad_gram != 0;
   if (h->dense_gram) {
-    if ((rc = alloc_arr(&h->gramH, (int64_t)h->kp * h->kp))) return rc;
-    if ((rc = alloc_arr(&h->gram_part, (int64_t)GRAM_BLOCKS * h->kp * h->kp))) return rc;
-    if ((rc = alloc_arr(&h->jloss_r, ml1))) return rc;
-    if ((rc = alloc_arr(&h->jloss_c, nl1))) return rc;
+    if ((rc = h->mem.alloc(&h->gramH, (size_t)h->kp * h->kp))) return rc;
+    if ((rc = h->mem.alloc(&h->gram_part, (size_t)GRAM_BLOCKS * h->kp * h->kp))) return rc;
+    if ((rc = h->mem.alloc(&h->jloss_r, (size_t)ml1))) return rc;
+    if ((rc = h->mem.alloc(&h->jloss_c, (size_t)nl1))) return rc;
   }
   return GLRM_OK;
 }

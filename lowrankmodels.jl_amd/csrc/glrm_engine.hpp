@@ -11,6 +11,7 @@
 //   glrm_cached_f32.hip fp32 storage: the float instantiations of the cached row sweep's register variant (glrm_cached.hpp)
 //   glrm_regvec.hip     regularizers that carry a vector (include/glrm_hip_regvec.h): checks, the handle's tables, the two entry points
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
+//   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 #pragma once
 
@@ -54,8 +55,11 @@ inline int fail(int code, const char* fmt, ...) {
                   hipGetErrorString(e_), __FILE__, __LINE__);                                         \
   } while (0)
 
+#include "glrm_devmem.hpp"
+
 struct glrm_handle {
   int device = 0;
+  DevArena mem;                       // every device allocation the handle keeps (borrowed arrays never enter it); glrm_hip_destroy releases it
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int64_t m = 0, n = 0;
@@ -130,8 +134,8 @@ struct glrm_handle {
   int64_t *rowptr = nullptr, *colptr = nullptr;
   int32_t *colidx = nullptr, *rowidx = nullptr;
   double *rowvals = nullptr, *colvals = nullptr;
-  // GLRM_PROBLEM_BORROW_DEVICE_ARRAYS: false = the array above is the caller's (never freed, never written by the engine)
-  bool own_ptrs = true, own_rowview = true, own_colview = true;
+  // (GLRM_PROBLEM_BORROW_DEVICE_ARRAYS: the arrays above are the caller's -- not in `mem`, never freed, never written by the engine -- until
+  // a view has to be reordered: the private copy then replaces the borrowed pointer)
   glrm_loss* losses = nullptr;
   int64_t n_losses = 0;
   bool loss_quad_uniform = false;
@@ -203,6 +207,11 @@ struct glrm_handle {
 };
 
 
+// refusals shared by the entry points (the single-shard message is the entry point's own)
+#define GLRM_NEED_FINALIZED(h) \
+  do { if (!(h)->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first"); } while (0)
+inline bool glrm_single_shard(const glrm_handle* h) { return h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n; }
+
 inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return (v && *v) ? atoi(v) : dflt;
@@ -245,7 +254,7 @@ int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi);
 int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch);
 
 // stable segmented sort of a view by tile index (glrm_tilesort.hip)
-int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, bool free_old);
+int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, DevArena& owner);
 
 // reference-order validation sweeps (glrm_reforder.hip; glrm_options.sum_order = 1)
 // test hooks (csrc/glrm_testhooks.hip): constant in the product library, environment-driven in the test build (-DGLRM_HIP_TESTING)

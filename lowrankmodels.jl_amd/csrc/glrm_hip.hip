@@ -112,19 +112,6 @@ __global__ void seg_stats_kernel(const int64_t* ptr, int64_t nseg, int forced_cl
 
 thread_local char g_err[768];
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) ok = false;
-    if (ok && prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-  }
-  ~DeviceGuard() {
-    int cur;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
 extern "C" int glrm_hip_version(void) { return GLRM_HIP_ABI_VERSION; }
 extern "C" const char* glrm_hip_last_error(void) { return g_err; }
 
@@ -142,10 +129,8 @@ static int pick_layout(int k, int& G, int& R) {
 }
 
 template <typename T>
-static int dev_copy_in(T** dst, const T* src, int64_t count, bool src_on_device, hipStream_t st) {
-  *dst = nullptr;
-  const size_t bytes = (size_t)(count > 0 ? count : 1) * sizeof(T);
-  HIPCK(hipMalloc((void**)dst, bytes));
+static int dev_copy_in(glrm_handle* h, T** dst, const T* src, int64_t count, bool src_on_device, hipStream_t st) {
+  if (const int rc = h->mem.alloc(dst, (size_t)std::max<int64_t>(0, count))) return rc;
   if (count > 0)
     HIPCK(hipMemcpyAsync(*dst, src, (size_t)count * sizeof(T), src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   return GLRM_OK;
@@ -260,23 +245,9 @@ static int check_desc(const glrm_problem* p) {
 
 extern "C" void glrm_hip_destroy(glrm_handle* h) {
   if (!h) return;
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   (void)hipStreamSynchronize(h->stream);
-  if (!h->own_ptrs) h->rowptr = h->colptr = nullptr;        // borrowed arrays are the caller's
-  if (!h->own_rowview) { h->colidx = nullptr; h->rowvals = nullptr; }
-  if (!h->own_colview) { h->rowidx = nullptr; h->colvals = nullptr; }
-  void* ptrs[] = {h->rowptr, h->colptr, h->colidx, h->rowidx, h->rowvals, h->colvals, h->losses, h->rx, h->ry,
-                  h->alpharow, h->alphacol, h->oX, h->oY, h->oobjcol, h->oobjrow, h->partials, h->dscalar, h->dcount,
-                  h->trials_r, h->accepts_r, h->trials_c, h->accepts_c, h->pass[0].part, h->pass[0].gsum, h->pass[0].trial,
-                  h->pass[0].jold, h->pass[0].active, h->pass[0].ntrial, h->pass[1].part, h->pass[1].gsum, h->pass[1].trial, h->pass[1].jold,
-                  h->pass[1].active, h->pass[1].ntrial, h->pass[0].suppos, h->pass[1].suppos, h->nactive, h->dflag, h->Arow, h->Acol, h->ystart, h->mtrial, h->mpart_loss, h->mpart_G, h->mgtot,
-                  h->mobjold, h->mactive, h->mnactive, h->colperm, h->rowperm, h->seglist_r, h->seglist_c, h->rowdescid, h->udesc,
-                  h->gramH, h->gram_part, h->jloss_r, h->jloss_c, h->actlist, h->blk_perm_c, h->blk_long_c,
-                  h->lane_bptr[0], h->lane_bptr[1], h->lane_off[0], h->lane_off[1], h->lane_val[0], h->lane_val[1],
-                  h->lane_inv[0], h->lane_inv[1], h->lane_off16[0], h->lane_off16[1], h->lane_vptr[0], h->lane_vptr[1], h->lane_sval[0], h->lane_sval[1], h->lane_gcnt, h->lane_gbase, h->lane_gtotal, h->lane_glist};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  glrm_regvec_drop(h);
+  h->mem.free_all(); // every device allocation of the handle; what follows is not device memory
   if (h->iter_exec) (void)hipGraphExecDestroy(h->iter_exec);
   if (h->iter_graph) (void)hipGraphDestroy(h->iter_graph);
   if (h->pinned_obj) (void)hipHostFree(h->pinned_obj);
@@ -294,14 +265,14 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
 int glrm_alloc_pass_buffers(glrm_handle* h, int side) {
   glrm_handle::PassBuffers& b = h->pass[side];
   const size_t nseg1 = (size_t)std::max<int64_t>(1, side == 0 ? h->ml : h->nl);
-  HIPCK(hipMalloc((void**)&b.part, nseg1 * b.nsup * (h->kp + 2) * 8));
-  HIPCK(hipMalloc((void**)&b.gsum, nseg1 * h->kp * 8));
-  HIPCK(hipMalloc((void**)&b.trial, nseg1 * h->kp * 8));
-  HIPCK(hipMalloc((void**)&b.jold, nseg1 * 8));
-  HIPCK(hipMalloc((void**)&b.active, nseg1 * 4));
-  HIPCK(hipMalloc((void**)&b.ntrial, nseg1 * 4));
-  if (!h->nactive) HIPCK(hipMalloc((void**)&h->nactive, 4));
-  return GLRM_OK;
+  int rc;
+  if ((rc = h->mem.alloc(&b.part, nseg1 * b.nsup * (h->kp + 2)))) return rc;
+  if ((rc = h->mem.alloc(&b.gsum, nseg1 * h->kp))) return rc;
+  if ((rc = h->mem.alloc(&b.trial, nseg1 * h->kp))) return rc;
+  if ((rc = h->mem.alloc(&b.jold, nseg1))) return rc;
+  if ((rc = h->mem.alloc(&b.active, nseg1))) return rc;
+  if ((rc = h->mem.alloc(&b.ntrial, nseg1))) return rc;
+  return h->nactive ? GLRM_OK : h->mem.alloc(&h->nactive, 1);
 }
 
 int glrm_ensure_side_stream(glrm_handle* h) {
@@ -336,7 +307,7 @@ int glrm_host_ptr(glrm_handle* h, bool rows, std::vector<int64_t>& ptr) {
 }
 
 int glrm_upload_list(glrm_handle* h, const std::vector<int32_t>& list, int32_t** out) {
-  HIPCK(hipMalloc((void**)out, std::max<size_t>(1, list.size()) * 4));
+  if (const int rc = h->mem.alloc(out, list.size())) return rc;
   HIPCK(hipMemcpyAsync(*out, list.data(), list.size() * 4, hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return GLRM_OK;
@@ -360,8 +331,9 @@ static int view_stats(glrm_handle* h, bool rows, int forced_cls, int64_t cache_m
   for (auto& v : st) v = 0;
   const int64_t nseg = rows ? h->ml : h->nl;
   if (nseg <= 0) return GLRM_OK;
+  DevArena scratch;
   unsigned long long* d = nullptr;
-  HIPCK(hipMalloc((void**)&d, sizeof st));
+  if (const int rc = scratch.alloc(&d, 6)) return rc;
   hipError_t e = hipMemsetAsync(d, 0, sizeof st, h->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(seg_stats_kernel, dim3(1024), dim3(256), 0, h->stream, rows ? h->rowptr : h->colptr, nseg, forced_cls, cache_maxlen, d);
@@ -369,7 +341,6 @@ static int view_stats(glrm_handle* h, bool rows, int forced_cls, int64_t cache_m
   }
   if (e == hipSuccess) e = hipMemcpyAsync(st, d, sizeof st, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "segment statistics failed: %s", hipGetErrorString(e));
   return GLRM_OK;
 }
@@ -443,7 +414,6 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
   // (a float handle narrows the values into arrays of its own: it copies what it may borrow)
   const bool borrow = on_dev && (p->flags & GLRM_PROBLEM_BORROW_DEVICE_ARRAYS) != 0 && h->storage == GLRM_STORAGE_F64;
   if (!p->dense_A && borrow) { // the caller's device arrays, read in place
-    h->own_ptrs = h->own_rowview = h->own_colview = false;
     h->rowptr = const_cast<int64_t*>(p->rowptr); h->colptr = const_cast<int64_t*>(p->colptr);
     h->colidx = const_cast<int32_t*>(p->colidx); h->rowvals = const_cast<double*>(p->rowvals);
     h->rowidx = const_cast<int32_t*>(p->rowidx); h->colvals = const_cast<double*>(p->colvals);
@@ -453,7 +423,7 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
     if ((h->nnz_r > 0 && (!h->colidx || !h->rowvals)) || (h->nnz_c > 0 && (!h->rowidx || !h->colvals)))
       return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
   } else if (!p->dense_A && (p->flags & GLRM_PROBLEM_ROWS_FROM_COLS)) { // the column view only; the row view is derived on the device
-    if ((rc = dev_copy_in(&h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
     if (on_dev) {
       HIPCK(hipMemcpyAsync(&h->nnz_c, p->colptr + h->nl, 8, hipMemcpyDeviceToHost, st));
       HIPCK(hipStreamSynchronize(st));
@@ -461,12 +431,12 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
       h->nnz_c = p->colptr[h->nl];
     }
     if (h->nnz_c > 0 && (!p->rowidx || !p->colvals)) return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
-    if ((rc = dev_copy_in(&h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(&h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
     if ((rc = glrm_rows_from_cols(h))) return rc;
   } else if (!p->dense_A) {
-    if ((rc = dev_copy_in(&h->rowptr, p->rowptr, h->ml + 1, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(&h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->rowptr, p->rowptr, h->ml + 1, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
     if (on_dev) {
       HIPCK(hipMemcpyAsync(&h->nnz_r, p->rowptr + h->ml, 8, hipMemcpyDeviceToHost, st));
       HIPCK(hipMemcpyAsync(&h->nnz_c, p->colptr + h->nl, 8, hipMemcpyDeviceToHost, st));
@@ -475,28 +445,28 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
       h->nnz_r = p->rowptr[h->ml];
       h->nnz_c = p->colptr[h->nl];
     }
-    if ((rc = dev_copy_in(&h->colidx, p->colidx, h->nnz_r, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(&h->rowvals, p->rowvals, h->nnz_r, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(&h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(&h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->colidx, p->colidx, h->nnz_r, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->rowvals, p->rowvals, h->nnz_r, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
+    if ((rc = dev_copy_in(h, &h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
   }
   h->n_losses = p->n_losses; h->n_rx = p->n_rx; h->n_ry = p->n_ry;
-  if ((rc = dev_copy_in(&h->losses, p->losses, p->n_losses, false, st))) return rc;
-  if ((rc = dev_copy_in(&h->rx, p->rx, p->n_rx, false, st))) return rc;
-  if ((rc = dev_copy_in(&h->ry, p->ry, p->n_ry, false, st))) return rc;
+  if ((rc = dev_copy_in(h, &h->losses, p->losses, p->n_losses, false, st))) return rc;
+  if ((rc = dev_copy_in(h, &h->rx, p->rx, p->n_rx, false, st))) return rc;
+  if ((rc = dev_copy_in(h, &h->ry, p->ry, p->n_ry, false, st))) return rc;
   h->loss_quad_uniform = p->n_losses == 1 && p->losses[0].kind == GLRM_LOSS_QUAD;
   h->has_trig = false;
   for (int64_t i = 0; i < p->n_losses; ++i) h->has_trig = h->has_trig || p->losses[i].kind == GLRM_LOSS_PERIODIC;
   const int64_t ml1 = h->ml > 0 ? h->ml : 1, nl1 = h->nl > 0 ? h->nl : 1;
-  HIPCK(hipMalloc((void**)&h->alpharow, ml1 * 8));
-  HIPCK(hipMalloc((void**)&h->alphacol, nl1 * 8));
-  HIPCK(hipMalloc((void**)&h->partials, SUM_BLOCKS * 8));
-  HIPCK(hipMalloc((void**)&h->dscalar, 8));
-  HIPCK(hipMalloc((void**)&h->dcount, 8));
-  HIPCK(hipMalloc((void**)&h->trials_r, ml1 * 4));
-  HIPCK(hipMalloc((void**)&h->accepts_r, ml1 * 4));
-  HIPCK(hipMalloc((void**)&h->trials_c, nl1 * 4));
-  HIPCK(hipMalloc((void**)&h->accepts_c, nl1 * 4));
+  if ((rc = h->mem.alloc(&h->alpharow, ml1))) return rc;
+  if ((rc = h->mem.alloc(&h->alphacol, nl1))) return rc;
+  if ((rc = h->mem.alloc(&h->partials, SUM_BLOCKS))) return rc;
+  if ((rc = h->mem.alloc(&h->dscalar, 1))) return rc;
+  if ((rc = h->mem.alloc(&h->dcount, 1))) return rc;
+  if ((rc = h->mem.alloc(&h->trials_r, ml1))) return rc;
+  if ((rc = h->mem.alloc(&h->accepts_r, ml1))) return rc;
+  if ((rc = h->mem.alloc(&h->trials_c, nl1))) return rc;
+  if ((rc = h->mem.alloc(&h->accepts_c, nl1))) return rc;
   HIPCK(hipMemsetAsync(h->trials_r, 0, ml1 * 4, st));
   HIPCK(hipMemsetAsync(h->accepts_r, 0, ml1 * 4, st));
   HIPCK(hipMemsetAsync(h->trials_c, 0, nl1 * 4, st));
@@ -602,7 +572,7 @@ extern "C" int glrm_hip_create(glrm_handle** out, const glrm_problem* p, const g
   int dev = o ? o->device_id : -1;
   if (dev < 0) HIPCK(hipGetDevice(&dev));
   if (dev >= ndev) return fail(GLRM_ERR_INVALID, "device_id %d out of range (%d devices)", dev, ndev);
-  DeviceGuard dg(dev);
+  DeviceScope dg(dev);
   if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", dev);
   glrm_handle* h = new (std::nothrow) glrm_handle();
   if (!h) return fail(GLRM_ERR_OOM, "out of host memory");
@@ -631,43 +601,39 @@ extern "C" int glrm_hip_finalize(glrm_handle* h, const glrm_signature* whole) {
   if (h->finalized) return fail(GLRM_ERR_INVALID, "the handle is already set up (glrm_hip_finalize follows a GLRM_PROBLEM_DEFER_SETUP create, once)");
   if (h->finalize_failed)  // a set-up that failed half way (out of memory in a family's buffers) has re-ordered private views and partial buffers
     return fail(GLRM_ERR_INVALID, "an earlier glrm_hip_finalize on this handle failed: destroy it and create the shard again");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return finalize_impl(h, whole);
 }
-
-#define GLRM_NEED_FINALIZED(h) \
-  do { if (!(h)->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first"); } while (0)
 
 // ------------------------------------------------------------------ buffers and factors
 
 static size_t factor_elem(const glrm_handle* h) { return h->storage == GLRM_STORAGE_F32 ? sizeof(float) : sizeof(double); }
 
+// the handle's own buffer behind a factor / objective slot the caller has not bound: bytes, zeroed, allocated once
+static int ensure_one(glrm_handle* h, double** used, double** own, size_t bytes) {
+  if (*used) return GLRM_OK;
+  if (!*own) {
+    if (const int rc = h->mem.alloc(own, (bytes + 7) / 8)) return rc;
+    HIPCK(hipMemsetAsync(*own, 0, bytes, h->stream));
+  }
+  *used = *own;
+  return GLRM_OK;
+}
+
 static int ensure_owned(glrm_handle* h) {
   const size_t fe = factor_elem(h);
-  if (!h->X) {
-    if (!h->oX) { HIPCK(hipMalloc((void**)&h->oX, (size_t)h->kp * h->m * fe)); HIPCK(hipMemsetAsync(h->oX, 0, (size_t)h->kp * h->m * fe, h->stream)); }
-    h->X = h->oX;
-  }
-  if (!h->Y) {
-    if (!h->oY) { HIPCK(hipMalloc((void**)&h->oY, (size_t)h->kp * h->d * fe)); HIPCK(hipMemsetAsync(h->oY, 0, (size_t)h->kp * h->d * fe, h->stream)); }
-    h->Y = h->oY;
-  }
-  if (!h->objcol) {
-    if (!h->oobjcol) { HIPCK(hipMalloc((void**)&h->oobjcol, (size_t)h->n * 8)); HIPCK(hipMemsetAsync(h->oobjcol, 0, (size_t)h->n * 8, h->stream)); }
-    h->objcol = h->oobjcol;
-  }
-  if (!h->objrow) {
-    if (!h->oobjrow) { HIPCK(hipMalloc((void**)&h->oobjrow, (size_t)h->m * 8)); HIPCK(hipMemsetAsync(h->oobjrow, 0, (size_t)h->m * 8, h->stream)); }
-    h->objrow = h->oobjrow;
-  }
-  return GLRM_OK;
+  int rc;
+  if ((rc = ensure_one(h, &h->X, &h->oX, (size_t)h->kp * h->m * fe))) return rc;
+  if ((rc = ensure_one(h, &h->Y, &h->oY, (size_t)h->kp * h->d * fe))) return rc;
+  if ((rc = ensure_one(h, &h->objcol, &h->oobjcol, (size_t)h->n * 8))) return rc;
+  return ensure_one(h, &h->objrow, &h->oobjrow, (size_t)h->m * 8);
 }
 
 extern "C" int glrm_hip_factor_ld(glrm_handle* h) { return h ? h->kp : fail(GLRM_ERR_INVALID, "NULL handle"); }
 
 extern "C" int glrm_hip_bind_buffers(glrm_handle* h, void* dX, void* dY, void* dObjCol, void* dObjRow) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   h->X = (double*)dX; h->Y = (double*)dY; h->objcol = (double*)dObjCol; h->objrow = (double*)dObjRow;
   if (h->iter_exec) { (void)hipGraphExecDestroy(h->iter_exec); h->iter_exec = nullptr; } // the captured launches hold the old pointers
   return ensure_owned(h);
@@ -679,7 +645,7 @@ extern "C" int glrm_hip_set_factors(glrm_handle* h, const double* X, const doubl
     if (const int rcx = glrm_check_narrowable("X", X, (int64_t)h->k * h->m)) return rcx;
     if (const int rcy = glrm_check_narrowable("Y", Y, (int64_t)h->k * h->d)) return rcy;
   }
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   int rc = ensure_owned(h);
   if (rc) return rc;
   if (h->storage == GLRM_STORAGE_F32) {
@@ -700,7 +666,7 @@ extern "C" int glrm_hip_set_factors(glrm_handle* h, const double* X, const doubl
 extern "C" int glrm_hip_get_factors(glrm_handle* h, double* X, double* Y) {
   if (!h || !X || !Y) return fail(GLRM_ERR_INVALID, "NULL argument");
   if (!h->X || !h->Y) return fail(GLRM_ERR_INVALID, "no factors on the device yet");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   if (h->storage == GLRM_STORAGE_F32) {
     if (const int rc = glrm_widen_factor(h, h->X, X, h->m)) return rc;
     return glrm_widen_factor(h, h->Y, Y, h->d);
@@ -714,7 +680,7 @@ extern "C" int glrm_hip_get_factors(glrm_handle* h, double* X, double* Y) {
 
 extern "C" int glrm_hip_reset_stepsizes(glrm_handle* h, double stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   if (h->ml > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->ml + 255) / 256)), dim3(256), 0, h->stream, h->alpharow, h->ml, stepsize);
   if (h->nl > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->nl + 255) / 256)), dim3(256), 0, h->stream, h->alphacol, h->nl, stepsize);
   HIPCK(hipGetLastError());
@@ -746,7 +712,7 @@ int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_
 extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
   if (const int rc = glrm_check_regularizers(h, rx, n_rx, ry, n_ry)) return rc;
   if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry)) h->multi = true; // checked above: this handle can run the general sweeps
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   h->rx_h.assign(rx, rx + n_rx);
   h->ry_h.assign(ry, ry + n_ry);
   const bool vx = any_vector_reg(h->rx_h), vy = any_vector_reg(h->ry_h);
@@ -768,7 +734,7 @@ extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int
 
 extern "C" int glrm_hip_synchronize(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   HIPCK(hipStreamSynchronize(h->stream));
   return GLRM_OK;
 }
@@ -928,7 +894,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
 
 extern "C" int glrm_hip_step_x(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return run_sweep(h, 0, min_stepsize, 0);
 }
 
@@ -937,7 +903,7 @@ extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t 
   GLRM_REFUSE_F32(h, "glrm_hip_step_x_range");
   if (seg_begin < 0 || seg_end > h->ml || seg_begin > seg_end) return fail(GLRM_ERR_INVALID, "row range out of bounds");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "step_x_range is not available on the dense path");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   h->rng_b = seg_begin;
   h->rng_e = seg_end;
   const int rc = run_sweep(h, 0, min_stepsize, 0);
@@ -948,7 +914,7 @@ extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t 
 
 extern "C" int glrm_hip_step_y(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return run_sweep(h, 1, min_stepsize, 0);
 }
 
@@ -1024,7 +990,7 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
     if (at != h->m) return fail(GLRM_ERR_INVALID, "arrival blocks must tile the rows [0, m) of X (they end at row %lld of %lld)", (long long)at, (long long)h->m);
   }
   GLRM_NEED_FINALIZED(h);
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   h->arrival = blocks;
   h->n_arrival = n_blocks;
   h->arrival_waited.assign((size_t)n_blocks, 0);
@@ -1046,7 +1012,7 @@ static int gradstep(glrm_handle* h, int which, double alpha) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   GLRM_REFUSE_F32(h, "glrm_hip_gradstep_x / glrm_hip_gradstep_y");
   if (!(alpha > 0.0)) return fail(GLRM_ERR_INVALID, "the step size must be positive");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   h->fixed_alpha = alpha;
   const int rc = run_sweep(h, which, 0.0, 0);
   h->fixed_alpha = 0.0;
@@ -1057,7 +1023,7 @@ extern "C" int glrm_hip_gradstep_y(glrm_handle* h, double alpha) { return gradst
 
 extern "C" int glrm_hip_col_losses(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return run_sweep(h, 1, 0.0, 1);
 }
 
@@ -1077,19 +1043,19 @@ static int run_penalty(glrm_handle* h, bool rows) {
 
 extern "C" int glrm_hip_row_penalties(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return run_penalty(h, true);
 }
 
 extern "C" int glrm_hip_col_penalties(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   return run_penalty(h, false);
 }
 
 extern "C" int glrm_hip_sum(glrm_handle* h, const void* dvec, int64_t n, double* out) {
   if (!h || !out || (n > 0 && !dvec)) return fail(GLRM_ERR_INVALID, "NULL argument");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   if (h->sum_order_opt) return glrm_reforder_sum(h, dvec, n, out); // sum(::Vector{Float64}) as Julia adds it (proxgrad.jl:205)
   hipLaunchKernelGGL(sum_stage1, dim3(SUM_BLOCKS), dim3(SUM_THREADS), 0, h->stream, (const double*)dvec, n, h->partials);
   hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(SUM_THREADS), 0, h->stream, h->partials, h->dscalar);
@@ -1114,7 +1080,7 @@ static int count_sum(glrm_handle* h, const int32_t* v, int64_t n, int64_t* out) 
 
 extern "C" int glrm_hip_kernel_stats(glrm_handle* h, glrm_kernel_stats* out, int reset) {
   if (!h || !out) return fail(GLRM_ERR_INVALID, "NULL argument");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   int rc = drain_events(h);
   if (rc) return rc;
   memset(out, 0, sizeof *out);
@@ -1209,8 +1175,6 @@ extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order*
 
 // ------------------------------------------------------------------ whole-fit API
 
-static bool single_shard(const glrm_handle* h) { return h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n; }
-
 static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -1237,8 +1201,8 @@ static int device_objective(glrm_handle* h, int include_reg, double* out) {
 
 extern "C" int glrm_hip_objective(glrm_handle* h, const double* X, const double* Y, int include_reg, double* out) {
   if (!h || !X || !Y || !out) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (!single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_objective needs a single-shard handle");
-  DeviceGuard dg(h->device);
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_objective needs a single-shard handle");
+  DeviceScope dg(h->device);
   int rc = glrm_hip_set_factors(h, X, Y);
   if (rc) return rc;
   return device_objective(h, include_reg, out);
@@ -1285,13 +1249,13 @@ static int build_iteration_graph(glrm_handle* h, const glrm_params* prm) {
 extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, double* Y, double* objective,
                             double* seconds, int64_t cap, int64_t* n_recorded) {
   if (!h || !prm || !X || !Y || !objective || !seconds || !n_recorded) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (!single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit needs a single-shard handle (use the step-level API per shard)");
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit needs a single-shard handle (use the step-level API per shard)");
   if (prm->max_iter < 0 || cap < prm->max_iter + 1) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+1");
   if (prm->inner_iter_X < 1 || prm->inner_iter_Y < 1) return fail(GLRM_ERR_INVALID, "inner iteration counts must be >= 1");
   double ynorm = 0.0; // norm(Y)==0 guard, proxgrad.jl:45-48 (the reference would hit an UndefVarError)
   for (int64_t i = 0; i < (int64_t)h->k * h->d; ++i) ynorm += Y[i] * Y[i];
   if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros (the reference cannot start from Y == 0)");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   int rc;
   if ((rc = glrm_hip_set_factors(h, X, Y))) return rc;                 // X = glrm.X; Y = glrm.Y (:43)
   if ((rc = glrm_hip_reset_stepsizes(h, prm->stepsize))) return rc;   // :69-70
@@ -1338,36 +1302,35 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
                                    double* seconds, int64_t cap, int64_t* n_recorded) {
   if (!h || !prm || !X || !Y || !objective || !seconds || !n_recorded) return fail(GLRM_ERR_INVALID, "NULL argument");
   GLRM_REFUSE_F32(h, "glrm_hip_fit_sparse");
-  if (!single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit_sparse needs a single-shard handle");
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit_sparse needs a single-shard handle");
   if (prm->max_iter < 0 || cap < prm->max_iter + 2) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+2");
   if (prm->inner_iter < 1) return fail(GLRM_ERR_INVALID, "inner_iter must be >= 1");
   double ynorm = 0.0; // norm(Y)==0 would be re-randomised by the reference (:41-43); not reproducible -> error
   for (int64_t i = 0; i < (int64_t)h->k * h->d; ++i) ynorm += Y[i] * Y[i];
   if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros");
-  DeviceGuard dg(h->device);
+  DeviceScope dg(h->device);
   int rc;
   if ((rc = glrm_hip_set_factors(h, X, Y))) return rc; // working copies X, Y (:33); glrm.X / glrm.Y = best so far
   const size_t xb = (size_t)h->kp * h->m * 8, yb = (size_t)h->kp * h->d * 8;
+  DevArena scratch;
   double *bestX = nullptr, *bestY = nullptr;
-  HIPCK(hipMalloc((void**)&bestX, xb));
-  if (hipMalloc((void**)&bestY, yb) != hipSuccess) { (void)hipFree(bestX); return fail(GLRM_ERR_OOM, "out of device memory"); }
-  auto cleanup = [&](int code) { (void)hipFree(bestX); (void)hipFree(bestY); return code; };
+  if ((rc = scratch.alloc(&bestX, xb / 8)) || (rc = scratch.alloc(&bestY, yb / 8))) return rc;
   if (hipMemcpyAsync(bestX, h->X, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(bestY, h->Y, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_HIP, "device copy failed"));
+    return fail(GLRM_ERR_HIP, "device copy failed");
   double alpha = prm->stepsize;                              // :46
   const double tol = prm->abs_tol * (double)h->nnz_r;        // :48
   int64_t nrec = 0;
-  if ((rc = device_objective(h, 1, &objective[0]))) return cleanup(rc); // update_ch!(ch, 0, objective(glrm; sparse=true)) :52
+  if ((rc = device_objective(h, 1, &objective[0]))) return rc; // update_ch!(ch, 0, objective(glrm; sparse=true)) :52
   seconds[0] = 0.0;
   nrec = 1;
   double t = now_s();
   int64_t steps_in_a_row = 0;
   for (int64_t i = 1; i <= prm->max_iter; ++i) {
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 0, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return cleanup(rc); }
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 1, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return cleanup(rc); }
+    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 0, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
+    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 1, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
     double obj = 0.0;
-    if ((rc = device_objective(h, 1, &obj))) return cleanup(rc); // :102
+    if ((rc = device_objective(h, 1, &obj))) return rc; // :102
     if (obj < objective[nrec - 1]) {                              // :104-110
       const double dt = now_s() - t;
       objective[nrec] = obj;
@@ -1375,7 +1338,7 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
       ++nrec;
       if (hipMemcpyAsync(bestX, h->X, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(bestY, h->Y, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return cleanup(fail(GLRM_ERR_HIP, "device copy failed"));
+        return fail(GLRM_ERR_HIP, "device copy failed");
       alpha = alpha * 1.05;
       steps_in_a_row = steps_in_a_row + 1 > 1 ? steps_in_a_row + 1 : 1;
       t = now_s();
@@ -1384,7 +1347,7 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
       alpha = alpha / div;
       if (hipMemcpyAsync(h->X, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
           hipMemcpyAsync(h->Y, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return cleanup(fail(GLRM_ERR_HIP, "device copy failed"));
+        return fail(GLRM_ERR_HIP, "device copy failed");
       steps_in_a_row = steps_in_a_row - 1 < 0 ? steps_in_a_row - 1 : 0;
     }
     // :119  i>10 && (steps_in_a_row > 3 && ch.objective[end-1] - obj < tol) || alpha <= params.min_stepsize
@@ -1397,8 +1360,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   // glrm.X, glrm.Y are the best model found
   if (hipMemcpyAsync(h->X, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(h->Y, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_HIP, "device copy failed"));
+    return fail(GLRM_ERR_HIP, "device copy failed");
   rc = glrm_hip_get_factors(h, X, Y);
   *n_recorded = nrec;
-  return cleanup(rc);
+  return rc;
 }

@@ -110,22 +110,22 @@ __global__ void __launch_bounds__(ET) impute_kernel(const EvalArgs a) {
   if (bad) atomicOr(a.bad, 1);
 }
 
-int prepare(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, EvalArgs& a, glrm_domain** ddom, int** dbad) {
-  if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "needs a single-shard handle");
+int prepare(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, EvalArgs& a, DevArena& scratch) {
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "needs a single-shard handle");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "post-fit evaluation works on list handles (create the handle without dense_A)");
-  if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
+  GLRM_NEED_FINALIZED(h);
   for (int64_t f = 0; f < h->n; ++f)
     if (domains[f].kind < 0 || domains[f].kind >= GLRM_DOMAIN_KIND_COUNT || domains[f].reserved != 0)
       return fail(GLRM_ERR_INVALID, "domain descriptor %lld is invalid", (long long)f);
   int rc = glrm_hip_set_factors(h, X, Y);
   if (rc) return rc;
-  HIPCK(hipMalloc((void**)ddom, (size_t)h->n * sizeof(glrm_domain)));
-  HIPCK(hipMalloc((void**)dbad, sizeof(int)));
-  HIPCK(hipMemcpyAsync(*ddom, domains, (size_t)h->n * sizeof(glrm_domain), hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipMemsetAsync(*dbad, 0, sizeof(int), h->stream));
+  glrm_domain* ddom = nullptr;
+  if ((rc = scratch.alloc(&ddom, (size_t)h->n)) || (rc = scratch.alloc(&a.bad, 1))) return rc;
+  HIPCK(hipMemcpyAsync(ddom, domains, (size_t)h->n * sizeof(glrm_domain), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemsetAsync(a.bad, 0, sizeof(int), h->stream));
   a.colptr = h->colptr; a.rowidx = h->rowidx; a.colvals = h->colvals;
-  a.losses = h->losses; a.loss_single = h->n_losses == 1 ? 1 : 0; a.ystart = h->ystart; a.domains = *ddom;
-  a.X = h->X; a.Y = h->Y; a.k = h->k; a.kp = h->kp; a.dmax = h->dmax; a.m = h->m; a.bad = *dbad;
+  a.losses = h->losses; a.loss_single = h->n_losses == 1 ? 1 : 0; a.ystart = h->ystart; a.domains = ddom;
+  a.X = h->X; a.Y = h->Y; a.k = h->k; a.kp = h->kp; a.dmax = h->dmax; a.m = h->m;
   return GLRM_OK;
 }
 
@@ -134,64 +134,55 @@ int prepare(glrm_handle* h, const double* X, const double* Y, const glrm_domain*
 extern "C" int glrm_hip_error_metric(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, int32_t standardize, double* out) {
   if (!h || !X || !Y || !domains || !out) return fail(GLRM_ERR_INVALID, "NULL argument");
   GLRM_REFUSE_F32(h, "glrm_hip_error_metric");
-  if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   EvalArgs a{};
-  glrm_domain* ddom = nullptr;
-  int* dbad = nullptr;
+  DevArena scratch;
   double *part = nullptr, *colerr = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)ddom, (void*)dbad, (void*)part, (void*)colerr}) if (p) (void)hipFree(p);
-    return rc;
-  };
-  int rc = prepare(h, X, Y, domains, a, &ddom, &dbad);
-  if (rc) return cleanup(rc);
+  int rc = prepare(h, X, Y, domains, a, scratch);
+  if (rc) return rc;
   std::vector<int64_t> cp((size_t)h->n + 1);
   if (hipMemcpyAsync(cp.data(), h->colptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "copy failed"));
+      hipStreamSynchronize(h->stream) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
   int64_t longest = 0;
   for (int64_t f = 0; f < h->n; ++f) longest = cp[f + 1] - cp[f] > longest ? cp[f + 1] - cp[f] : longest;
   a.chunk = 65536;
   while ((longest + a.chunk - 1) / a.chunk > 65535) a.chunk *= 2; // gridDim.y
   a.nsplit = (int)((longest + a.chunk - 1) / a.chunk);
   if (a.nsplit < 1) a.nsplit = 1;
-  if (hipMalloc((void**)&part, (size_t)h->n * a.nsplit * 16) != hipSuccess || hipMalloc((void**)&colerr, (size_t)h->n * 8) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
+  if ((rc = scratch.alloc(&part, (size_t)h->n * a.nsplit * 2)) || (rc = scratch.alloc(&colerr, (size_t)h->n))) return rc;
   a.part = part;
   const size_t lds = (size_t)h->dmax * ET * 8;
   hipLaunchKernelGGL(error_metric_kernel, dim3((unsigned)h->n, (unsigned)a.nsplit), dim3(ET), lds, h->stream, a);
   hipLaunchKernelGGL(error_metric_cols_kernel, dim3(64), dim3(256), 0, h->stream, a, h->n, standardize, colerr);
-  if (hipGetLastError() != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "error_metric kernels failed to launch"));
-  if ((rc = glrm_hip_sum(h, colerr, h->n, out))) return cleanup(rc);
+  if (hipGetLastError() != hipSuccess) return fail(GLRM_ERR_HIP, "error_metric kernels failed to launch");
+  if ((rc = glrm_hip_sum(h, colerr, h->n, out))) return rc;
   int bad = 0;
-  if (hipMemcpy(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "copy failed"));
-  if (bad) return cleanup(fail(GLRM_ERR_UNSUPPORTED, "a column's (domain, loss) pair has no imputation rule in the reference (src/impute_and_err.jl)"));
-  return cleanup(GLRM_OK);
+  if (hipMemcpy(&bad, a.bad, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
+  if (bad) return fail(GLRM_ERR_UNSUPPORTED, "a column's (domain, loss) pair has no imputation rule in the reference (src/impute_and_err.jl)");
+  return GLRM_OK;
 }
 
 extern "C" int glrm_hip_impute(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, double* Ahat) {
   if (!h || !X || !Y || !domains || !Ahat) return fail(GLRM_ERR_INVALID, "NULL argument");
   GLRM_REFUSE_F32(h, "glrm_hip_impute");
-  if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   EvalArgs a{};
-  glrm_domain* ddom = nullptr;
-  int* dbad = nullptr;
+  DevArena scratch;
   double* dA = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)ddom, (void*)dbad, (void*)dA}) if (p) (void)hipFree(p);
-    return rc;
-  };
-  int rc = prepare(h, X, Y, domains, a, &ddom, &dbad);
-  if (rc) return cleanup(rc);
-  if (hipMalloc((void**)&dA, (size_t)h->m * h->n * 8) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the m x n imputed matrix"));
+  int rc = prepare(h, X, Y, domains, a, scratch);
+  if (rc) return rc;
+  if ((rc = scratch.alloc(&dA, (size_t)h->m * h->n, "out of device memory for the m x n imputed matrix"))) return rc;
   a.Ahat = dA;
   const size_t lds = (size_t)h->dmax * ET * 8;
-  if ((h->m + ET - 1) / ET * h->n > 2147483647ll) return cleanup(fail(GLRM_ERR_UNSUPPORTED, "m x n too large for one impute launch"));
+  if ((h->m + ET - 1) / ET * h->n > 2147483647ll) return fail(GLRM_ERR_UNSUPPORTED, "m x n too large for one impute launch");
   hipLaunchKernelGGL(impute_kernel, dim3((unsigned)((h->m + ET - 1) / ET * h->n)), dim3(ET), lds, h->stream, a);
-  if (hipGetLastError() != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "impute kernel failed to launch"));
+  if (hipGetLastError() != hipSuccess) return fail(GLRM_ERR_HIP, "impute kernel failed to launch");
   if (hipMemcpyAsync(Ahat, dA, (size_t)h->m * h->n * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "copy failed"));
+      hipStreamSynchronize(h->stream) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
   int bad = 0;
-  if (hipMemcpy(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "copy failed"));
-  if (bad) return cleanup(fail(GLRM_ERR_UNSUPPORTED, "a column's (domain, loss) pair has no imputation rule in the reference (src/impute_and_err.jl)"));
-  return cleanup(GLRM_OK);
+  if (hipMemcpy(&bad, a.bad, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
+  if (bad) return fail(GLRM_ERR_UNSUPPORTED, "a column's (domain, loss) pair has no imputation rule in the reference (src/impute_and_err.jl)");
+  return GLRM_OK;
 }

@@ -229,10 +229,6 @@ struct KmWork {
   double *Y = nullptr, *c = nullptr, *best = nullptr, *w = nullptr, *u = nullptr, *chunksum = nullptr;
   int64_t* centers = nullptr;
   unsigned long long* lastpos = nullptr;
-  ~KmWork() {
-    for (void* p : {(void*)Y, (void*)c, (void*)best, (void*)w, (void*)u, (void*)chunksum, (void*)centers, (void*)lastpos})
-      if (p) (void)hipFree(p);
-  }
 };
 
 } // namespace
@@ -241,8 +237,8 @@ extern "C" int glrm_hip_init_kmeanspp(glrm_handle* h, double* Y, int64_t first_c
   if (!h) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp: NULL handle");
   GLRM_REFUSE_F32(h, "glrm_hip_init_kmeanspp");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_init_kmeanspp works on the observation lists (create the handle without dense_A)");
-  if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp needs a single-shard handle");
-  if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp needs a single-shard handle");
+  GLRM_NEED_FINALIZED(h);
   for (size_t j = 0; j < h->losses_h.size(); ++j)
     if (h->losses_h[j].dim > 1)
       return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_init_kmeanspp: column %lld has a multi-dimensional loss (kind %d, dim %d); the reference's "
@@ -255,21 +251,20 @@ extern "C" int glrm_hip_init_kmeanspp(glrm_handle* h, double* Y, int64_t first_c
     return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp: first_center %lld outside [0, %lld)", (long long)first_center, (long long)m);
   for (int l = 0; l + 1 < k; ++l)
     if (!(u[l] >= 0.0 && u[l] < 1.0)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_kmeanspp: u[%d] = %g outside [0, 1)", l, u[l]);
-  if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   hipStream_t st = h->stream;
   const int rounds = k - 1;
   const int64_t nchunks = (m + KM_CHUNK - 1) / KM_CHUNK;
   const size_t wrounds = weights && rounds > 0 ? (size_t)rounds : 1;
 
   KmWork w;
-  HIPCK(hipMalloc((void**)&w.Y, (size_t)k * n * 8));
-  HIPCK(hipMalloc((void**)&w.c, (size_t)n * 8));
-  HIPCK(hipMalloc((void**)&w.best, (size_t)m * 8));
-  HIPCK(hipMalloc((void**)&w.w, wrounds * (size_t)m * 8));
-  HIPCK(hipMalloc((void**)&w.u, (size_t)(rounds > 0 ? rounds : 1) * 8));
-  HIPCK(hipMalloc((void**)&w.chunksum, (size_t)nchunks * 8));
-  HIPCK(hipMalloc((void**)&w.centers, (size_t)k * 8));
-  HIPCK(hipMalloc((void**)&w.lastpos, (size_t)n * 8));
+  DevArena scratch;
+  int rc;
+  if ((rc = scratch.alloc(&w.Y, (size_t)k * n)) || (rc = scratch.alloc(&w.c, (size_t)n)) || (rc = scratch.alloc(&w.best, (size_t)m)) ||
+      (rc = scratch.alloc(&w.w, wrounds * (size_t)m)) || (rc = scratch.alloc(&w.u, (size_t)std::max(rounds, 0))) || (rc = scratch.alloc(&w.chunksum, (size_t)nchunks)) ||
+      (rc = scratch.alloc(&w.centers, (size_t)k)) || (rc = scratch.alloc(&w.lastpos, (size_t)n)))
+    return rc;
   HIPCK(hipMemcpyAsync(w.Y, Y, (size_t)k * n * 8, hipMemcpyHostToDevice, st));
   if (rounds > 0) HIPCK(hipMemcpyAsync(w.u, u, (size_t)rounds * 8, hipMemcpyHostToDevice, st));
   HIPCK(hipMemcpyAsync(w.centers, &first_center, 8, hipMemcpyHostToDevice, st));

@@ -149,59 +149,56 @@ int glrm_setup_lane(glrm_handle* h) {
     const bool compact = !(rows && h->n_losses > 1) && (cmode == 1 || (cmode == 2 && (rows ? h->sig.nnz_rows : h->sig.nnz_cols) > 2000000000ll)) &&
                          64 * (rows ? h->sig.max_row_len : h->sig.max_col_len) < ((int64_t)1 << 31); // (a wave block's values are counted in 31 bits: LaneArgs::sval)
     int64_t *cnt = nullptr, *scan = nullptr, *vcnt = nullptr;
-    void* tmp = nullptr;
-    auto cleanup = [&](int rc) { (void)hipFree(cnt); (void)hipFree(scan); (void)hipFree(vcnt); (void)hipFree(tmp); return rc; };
-    HIPCK(hipMalloc((void**)&cnt, (size_t)ncell * 8));
-    if (hipMalloc((void**)&scan, (size_t)ncell * 8) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
-    if (compact && hipMalloc((void**)&vcnt, (size_t)ncell * 8) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
+    char* tmp = nullptr;
+    DevArena scratch; // the counts and scans of this side's build
+    int rc;
+    if ((rc = scratch.alloc(&cnt, (size_t)ncell)) || (rc = scratch.alloc(&scan, (size_t)ncell)) || (compact && (rc = scratch.alloc(&vcnt, (size_t)ncell)))) return rc;
     hipLaunchKernelGGL(lane_count_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, perm, nslots, T, ntiles, cnt, vcnt);
     size_t bytes = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "scan (size query) failed"));
-    if (hipMalloc(&tmp, bytes ? bytes : 1) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "scan failed"));
-    if (hipMalloc((void**)&h->lane_bptr[side], (size_t)nwb * (ntiles + 1) * 8) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan (size query) failed");
+    if ((rc = scratch.alloc(&tmp, bytes))) return rc;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
     const int64_t nb = nwb * (ntiles + 1);
+    if ((rc = h->mem.alloc(&h->lane_bptr[side], (size_t)nb))) return rc;
     hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, cnt, nwb, ntiles, h->lane_bptr[side]);
     int64_t last[2] = {0, 0};
     if (hipMemcpyAsync(&last[0], scan + ncell - 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(&last[1], cnt + ncell - 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_HIP, "lane layout: copy failed"));
+      return fail(GLRM_ERR_HIP, "lane layout: copy failed");
     const int64_t steps = last[0] + last[1];
     h->lane_steps[side] = steps;
     const int64_t s1 = steps > 0 ? steps : 1;
     if (compact) {
       // values before every (wave block, tile): the same scan over the observation counts (the step scan's scratch serves again)
-      if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, vcnt, scan, (int)ncell, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "scan failed"));
-      if (hipMalloc((void**)&h->lane_vptr[side], (size_t)nwb * (ntiles + 1) * 8) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory"));
+      if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, vcnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
+      if ((rc = h->mem.alloc(&h->lane_vptr[side], (size_t)nb))) return rc;
       hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, vcnt, nwb, ntiles, h->lane_vptr[side]);
       const int64_t nv = std::max<int64_t>(1, rows ? h->nnz_r : h->nnz_c);
-      const bool ok = hipMalloc((void**)&h->lane_off16[side], (size_t)s1 * 64 * 2) == hipSuccess && hipMalloc((void**)&h->lane_sval[side], (size_t)s1 * 4) == hipSuccess &&
-                      hipMalloc((void**)&h->lane_val[side], (size_t)nv * 8) == hipSuccess;
+      const bool ok = !h->mem.alloc(&h->lane_off16[side], (size_t)s1 * 64) && !h->mem.alloc(&h->lane_sval[side], (size_t)s1) && !h->mem.alloc(&h->lane_val[side], (size_t)nv);
       if (!ok) {
         // No room for the stream beside the lists: the side stays on the four-lane kernels.  (The only family choice that can depend on
         // the device rather than on the problem; glrm_hip_sum_order reports what runs, and the super-tile geometry is already fixed.)
         (void)hipGetLastError();
-        (void)hipFree(h->lane_off16[side]); (void)hipFree(h->lane_sval[side]); (void)hipFree(h->lane_val[side]); (void)hipFree(h->lane_vptr[side]); (void)hipFree(h->lane_bptr[side]);
-        h->lane_off16[side] = nullptr; h->lane_sval[side] = nullptr; h->lane_val[side] = nullptr; h->lane_vptr[side] = nullptr; h->lane_bptr[side] = nullptr;
+        h->mem.release(&h->lane_off16[side]); h->mem.release(&h->lane_sval[side]); h->mem.release(&h->lane_val[side]); h->mem.release(&h->lane_vptr[side]); h->mem.release(&h->lane_bptr[side]);
         h->lane[side] = 0;
         h->lane_steps[side] = 0;
         fprintf(stderr, "[glrm lane] no device memory for the compact stream of the %s view (%.1f GB): the view stays on the four-lane LDS-tiled kernels\n", rows ? "row" : "column",
                 ((double)s1 * 128 + (double)nv * 8) / 1e9);
-        cleanup(0);
         continue;
       }
       hipLaunchKernelGGL(lane_fill_compact_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, vals, perm, nslots, T, ntiles, h->lane_bptr[side], h->lane_vptr[side],
                          h->lane_off16[side], h->lane_sval[side], h->lane_val[side]);
     } else {
-      if (hipMalloc((void**)&h->lane_off[side], (size_t)s1 * 64 * 4) != hipSuccess || hipMalloc((void**)&h->lane_val[side], (size_t)s1 * 64 * 8) != hipSuccess)
-        return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the lane-per-segment stream of the %s view (%lld steps of 64 entries)", rows ? "row" : "column", (long long)steps));
+      char oom[160];
+      snprintf(oom, sizeof oom, "out of device memory for the lane-per-segment stream of the %s view (%lld steps of 64 entries)", rows ? "row" : "column", (long long)steps);
+      if ((rc = h->mem.alloc(&h->lane_off[side], (size_t)s1 * 64, oom)) || (rc = h->mem.alloc(&h->lane_val[side], (size_t)s1 * 64, oom))) return rc;
       hipLaunchKernelGGL(lane_fill_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, vals, (rows && h->n_losses > 1) ? h->rowdescid : nullptr, perm, nslots, T, ntiles,
                          h->kp * 8, h->lane_bptr[side], h->lane_off[side], h->lane_val[side]);
     }
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "lane layout: build failed"));
-    cleanup(0);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "lane layout: build failed");
+    scratch.free_all();
     if (perm) { // FORM 2 of the rounds finds a segment's slot through the inverse of the slot permutation
-      HIPCK(hipMalloc((void**)&h->lane_inv[side], (size_t)nseg * 4));
+      if ((rc = h->mem.alloc(&h->lane_inv[side], (size_t)nseg))) return rc;
       HIPCK(hipMemsetAsync(h->lane_inv[side], 0xFF, (size_t)nseg * 4, st));
       hipLaunchKernelGGL(lane_inv_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, perm, nslots, h->lane_inv[side]);
       HIPCK(hipGetLastError());
@@ -215,10 +212,10 @@ int glrm_setup_lane(glrm_handle* h) {
   if (gseg_max > 0 && !h->lane_glist) { // the wave lists of the rounds (one set serves both sides: a half-step at a time)
     h->lane_gchunks = (gseg_max + LANE_CC - 1) / LANE_CC;
     h->lane_gcap = h->lane_gchunks * 16; // waves: a chunk holds at most 64 segments of a class
-    HIPCK(hipMalloc((void**)&h->lane_gcnt, (size_t)h->lane_gchunks * 4));
-    HIPCK(hipMalloc((void**)&h->lane_gbase, (size_t)h->lane_gchunks * 4));
-    HIPCK(hipMalloc((void**)&h->lane_gtotal, 4));
-    HIPCK(hipMalloc((void**)&h->lane_glist, (size_t)h->lane_gcap * 64 * 4));
+    int rc;
+    if ((rc = h->mem.alloc(&h->lane_gcnt, (size_t)h->lane_gchunks)) || (rc = h->mem.alloc(&h->lane_gbase, (size_t)h->lane_gchunks)) || (rc = h->mem.alloc(&h->lane_gtotal, 1)) ||
+        (rc = h->mem.alloc(&h->lane_glist, (size_t)h->lane_gcap * 64)))
+      return rc;
   }
   return GLRM_OK;
 }

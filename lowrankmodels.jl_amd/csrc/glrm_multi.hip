@@ -45,7 +45,7 @@ int glrm_setup_multi(glrm_handle* h, const glrm_problem* p) {
     return fail(GLRM_ERR_UNSUPPORTED, "multi-dimensional losses / wrapped regularizers need k <= 64 (got %d)", h->k);
   if (multi && p->dense_A)
     return fail(GLRM_ERR_UNSUPPORTED, "the dense hand-over covers scalar QuadLoss with unwrapped regularizers only");
-  HIPCK(hipMalloc((void**)&h->ystart, ((size_t)p->n + 1) * 8));
+  if (const int rc = h->mem.alloc(&h->ystart, (size_t)p->n + 1)) return rc;
   HIPCK(hipMemcpyAsync(h->ystart, ys.data(), ((size_t)p->n + 1) * 8, hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream)); // ys is a local
   h->ys_cb = ys[p->col_begin];
@@ -65,14 +65,12 @@ static int setup_split(glrm_handle* h) {
   if (nsplit <= 1 || nsplit > 65535 || (size_t)h->n * nsplit * blk * 8 > ((size_t)2 << 30)) { h->col_nsplit = -1; return GLRM_OK; }
   h->col_chunk = chunk;
   h->col_nsplit = (int)nsplit;
-  HIPCK(hipMalloc((void**)&h->mtrial, (size_t)h->d * h->kp * 8));
-  HIPCK(hipMalloc((void**)&h->mpart_loss, (size_t)h->nl * nsplit * 8));
-  HIPCK(hipMalloc((void**)&h->mpart_G, (size_t)h->nl * nsplit * blk * 8));
-  HIPCK(hipMalloc((void**)&h->mgtot, (size_t)h->nl * blk * 8));
-  HIPCK(hipMalloc((void**)&h->mobjold, (size_t)h->nl * 8));
-  HIPCK(hipMalloc((void**)&h->mactive, (size_t)h->nl * 4));
-  HIPCK(hipMalloc((void**)&h->mnactive, 4));
-  return GLRM_OK;
+  int rc;
+  if ((rc = h->mem.alloc(&h->mtrial, (size_t)h->d * h->kp)) || (rc = h->mem.alloc(&h->mpart_loss, (size_t)h->nl * nsplit)) ||
+      (rc = h->mem.alloc(&h->mpart_G, (size_t)h->nl * nsplit * blk)) || (rc = h->mem.alloc(&h->mgtot, (size_t)h->nl * blk)) ||
+      (rc = h->mem.alloc(&h->mobjold, (size_t)h->nl)) || (rc = h->mem.alloc(&h->mactive, (size_t)h->nl)))
+    return rc;
+  return h->mem.alloc(&h->mnactive, 1);
 }
 
 // GDC = 8 when no embedding is wider (gradient registers per lane: 8 instead of 32); TRIG: see LOSS_*_NOTRIG in glrm_engine.hpp

@@ -441,8 +441,7 @@ int multi_objective(glrm_multi* mh, double* out) {
 
 extern "C" void glrm_hip_multi_destroy(glrm_multi* mh) {
   if (!mh) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
+  DeviceScope dg; // the loops below select every shard's device in turn
 #ifdef GLRM_HIP_TESTING
   if (mh->emu.timer.joinable()) { // nothing may be left waiting for a release on the device
     mh->emu.release_all();
@@ -478,7 +477,6 @@ extern "C" void glrm_hip_multi_destroy(glrm_multi* mh) {
     if (s < (int)mh->ev_ready.size() && mh->ev_ready[s]) (void)hipEventDestroy(mh->ev_ready[s]);
     if (s < (int)mh->st.size() && mh->st[s]) (void)hipStreamDestroy(mh->st[s]);
   }
-  (void)hipSetDevice(prev);
   delete mh;
 }
 
@@ -717,8 +715,7 @@ extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, co
     for (int64_t s = 0; s < p->m; ++s) if (p->rowptr[s + 1] < p->rowptr[s]) return fail(GLRM_ERR_INVALID, "rowptr is not monotone at %lld", (long long)s);
     for (int64_t s = 0; s < p->n; ++s) if (p->colptr[s + 1] < p->colptr[s]) return fail(GLRM_ERR_INVALID, "colptr is not monotone at %lld", (long long)s);
   }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
+  DeviceScope dg;
   glrm_multi* mh = new (std::nothrow) glrm_multi();
   if (!mh) return fail(GLRM_ERR_OOM, "out of host memory");
   mh->n = mo->n_shards;
@@ -729,10 +726,8 @@ extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, co
     memcpy(keep, g_err, sizeof keep);
     glrm_hip_multi_destroy(mh);
     memcpy(g_err, keep, sizeof keep);
-    (void)hipSetDevice(prev);
     return rc;
   }
-  (void)hipSetDevice(prev);
   *out = mh;
   return GLRM_OK;
 }
@@ -757,9 +752,6 @@ extern "C" int glrm_hip_multi_set_regularizers_vec(glrm_multi* mh, const glrm_re
   if (!mh || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
   if (n_rx != mh->n_rx || n_ry != mh->n_ry) return fail(GLRM_ERR_INVALID, "regularizer counts must match the create call");
   if ((vx && (!vx->vec || !vx->len)) || (vy && (!vy->vec || !vy->len))) return fail(GLRM_ERR_INVALID, "glrm_regvec.vec / len are NULL");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
   for (int pass = 0; pass < 2; ++pass) // every shard's slice is checked before any shard is changed: a refusal leaves the model as it was
     for (int s = 0; s < mh->n; ++s) {
       const int64_t ox = n_rx == 1 ? 0 : mh->rbs[s], oy = n_ry == 1 ? 0 : mh->cbs[s];
@@ -789,9 +781,7 @@ extern "C" int glrm_hip_multi_fit(glrm_multi* mh, const glrm_params* prm, double
   double ynorm = 0.0; // norm(Y)==0 guard, proxgrad.jl:45-48
   for (int64_t i = 0; i < (int64_t)mh->k * mh->d; ++i) ynorm += Y[i] * Y[i];
   if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros (the reference cannot start from Y == 0)");
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
+  DeviceScope dg;
   int rc;
   mh->exchange_ms = 0.0;
   if ((rc = run_all(mh, [&](int s) {                                    // X = glrm.X; Y = glrm.Y (:43), alpharow / alphacol (:69-70)

@@ -386,10 +386,11 @@ int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out) {
     a.own = h->Y; a.own_offset = h->cb; a.other = h->X;
     a.losses = h->losses; a.n_losses = h->n_losses; a.k = h->k;
     const int64_t chunk = std::min<int64_t>(h->nnz_c, (int64_t)1 << 25); // 256 MB of terms at a time
+    DevArena scratch;
     double* dterms = nullptr;
-    HIPCK(hipMalloc((void**)&dterms, (size_t)chunk * 8));
+    if (const int rc = scratch.alloc(&dterms, (size_t)chunk)) return rc;
     std::vector<double> host;
-    try { host.resize((size_t)chunk); } catch (const std::exception&) { (void)hipFree(dterms); return fail(GLRM_ERR_OOM, "out of host memory"); }
+    try { host.resize((size_t)chunk); } catch (const std::exception&) { return fail(GLRM_ERR_OOM, "out of host memory"); }
     for (int64_t t0 = 0; t0 < h->nnz_c; t0 += chunk) {
       const int64_t t1 = std::min(h->nnz_c, t0 + chunk);
       const int rc = glrm_dispatch<8, 16, 32, 64>(
@@ -397,14 +398,10 @@ int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out) {
           [&] { return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp); });
       hipError_t e = rc ? hipSuccess : hipMemcpyAsync(host.data(), dterms, (size_t)(t1 - t0) * 8, hipMemcpyDeviceToHost, h->stream);
       if (!rc && e == hipSuccess) e = hipStreamSynchronize(h->stream);
-      if (rc || e != hipSuccess) {
-        (void)hipFree(dterms);
-        return rc ? rc : fail(GLRM_ERR_HIP, "reference-order objective: %s", hipGetErrorString(e));
-      }
+      if (rc || e != hipSuccess) return rc ? rc : fail(GLRM_ERR_HIP, "reference-order objective: %s", hipGetErrorString(e));
       const double* v = host.data();
       for (int64_t i = 0, ne = t1 - t0; i < ne; ++i) err += v[i]; // err += evaluate(...), one accumulator (src/evaluate_fit.jl:15)
     }
-    (void)hipFree(dterms);
   }
   if (include_reg) {
     double penalty = 0.0; // calc_penalty: rows then columns into one accumulator (src/evaluate_fit.jl:96-102)

@@ -12,17 +12,6 @@ namespace {
 
 constexpr int FIXED = GLRM_WRAP_FIXED_FIRST | GLRM_WRAP_FIXED_LAST;
 
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 bool side_carries(const glrm_reg* r, int64_t cnt) {
   for (int64_t i = 0; i < cnt; ++i)
     if (glrm_regvec_carries(r[i])) return true;
@@ -106,10 +95,8 @@ void glrm_regvec_placeholders(const std::vector<glrm_reg>& in, std::vector<glrm_
 
 void glrm_regvec_drop(glrm_handle* h) {
   for (int s = 0; s < 2; ++s) {
-    if (h->regvec[s]) (void)hipFree(h->regvec[s]);
-    if (h->reglen[s]) (void)hipFree(h->reglen[s]);
-    h->regvec[s] = nullptr;
-    h->reglen[s] = nullptr;
+    h->mem.release(&h->regvec[s]);
+    h->mem.release(&h->reglen[s]);
     h->regvec_h[s].clear();
     h->reglen_h[s].clear();
   }
@@ -152,7 +139,7 @@ extern "C" int glrm_hip_set_regularizers_vec(glrm_handle* h, const glrm_reg* rx,
   // Neither a vector-carrying descriptor nor a table: the plain call (it drops the tables of an earlier call).  A table whose lengths are
   // all 0 still moves the handle to the general sweeps: how the shards of one problem stay on ONE family when only some hold a vector.
   if (!carries[0] && !carries[1] && !vx && !vy) return glrm_hip_set_regularizers(h, rx, n_rx, ry, n_ry);
-  DevGuard dg(h->device);
+  DeviceScope dg(h->device);
   const int k = h->k;
   std::vector<double> tv[2];
   std::vector<int32_t> tl[2];
@@ -169,31 +156,28 @@ extern "C" int glrm_hip_set_regularizers_vec(glrm_handle* h, const glrm_reg* rx,
   } catch (const std::bad_alloc&) {
     return fail(GLRM_ERR_OOM, "out of host memory for the regularizer vectors");
   }
-  // the new device tables first: until they are complete the handle is untouched
+  // the new device tables first, in an arena of their own: until they are complete the handle is untouched
+  DevArena fresh;
   double* dv[2] = {nullptr, nullptr};
   int32_t* dl[2] = {nullptr, nullptr};
   hipError_t e = hipSuccess;
   for (int s = 0; s < 2 && e == hipSuccess; ++s) {
     if (!carries[s]) continue;
-    e = hipMalloc((void**)&dv[s], tv[s].size() * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&dl[s], tl[s].size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(dv[s], tv[s].data(), tv[s].size() * 8, hipMemcpyHostToDevice, h->stream);
+    if (const int rc = fresh.alloc(&dv[s], tv[s].size())) return rc;
+    if (const int rc = fresh.alloc(&dl[s], tl[s].size())) return rc;
+    e = hipMemcpyAsync(dv[s], tv[s].data(), tv[s].size() * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dl[s], tl[s].data(), tl[s].size() * 4, hipMemcpyHostToDevice, h->stream);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h->rx, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(h->ry, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) {
-    for (int s = 0; s < 2; ++s) {
-      if (dv[s]) (void)hipFree(dv[s]);
-      if (dl[s]) (void)hipFree(dl[s]);
-    }
-    return fail(e == hipErrorOutOfMemory ? GLRM_ERR_OOM : GLRM_ERR_HIP, "installing the regularizer vectors failed: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(GLRM_ERR_HIP, "installing the regularizer vectors failed: %s", hipGetErrorString(e));
   glrm_regvec_drop(h); // the previous call's tables (the stream is idle)
   for (int s = 0; s < 2; ++s) {
     h->regvec[s] = dv[s];
     h->reglen[s] = dl[s];
+    fresh.move_to(h->mem, dv[s]);
+    fresh.move_to(h->mem, dl[s]);
     h->regvec_h[s].swap(tv[s]);
     h->reglen_h[s].swap(tl[s]);
   }

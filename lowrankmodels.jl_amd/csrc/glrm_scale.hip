@@ -266,13 +266,6 @@ struct ScaleWork {
   double* colvals = nullptr;
   glrm_loss* losses = nullptr;
   double* stats = nullptr;
-  int prev = -1;
-  ~ScaleWork() {
-    for (void* p : {(void*)colptr, (void*)colvals, (void*)losses, (void*)stats})
-      if (p) (void)hipFree(p);
-    int cur;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
 };
 
 } // namespace
@@ -311,11 +304,13 @@ extern "C" int glrm_hip_scale_columns(const glrm_problem* p, const glrm_options*
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(GLRM_ERR_HIP, "no HIP device is visible (this engine has no CPU fallback)");
   int dev = o ? o->device_id : -1;
-  ScaleWork w;
-  HIPCK(hipGetDevice(&w.prev));
-  if (dev < 0) dev = w.prev;
+  if (dev < 0) HIPCK(hipGetDevice(&dev));
   if (dev >= ndev) return fail(GLRM_ERR_INVALID, "device_id %d out of range (%d devices)", dev, ndev);
-  if (dev != w.prev && hipSetDevice(dev) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", dev);
+  DeviceScope dg(dev);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", dev);
+  ScaleWork w;
+  DevArena scratch;
+  int rc;
   hipStream_t st = o ? (hipStream_t)o->stream : nullptr;
 
   ScaleArgs a{};
@@ -327,17 +322,15 @@ extern "C" int glrm_hip_scale_columns(const glrm_problem* p, const glrm_options*
     for (int64_t j = 0; j < nl; ++j)
       if (p->colptr[j + 1] < p->colptr[j]) return fail(GLRM_ERR_INVALID, "glrm_hip_scale_columns: colptr decreases at column %lld", (long long)j);
     const int64_t nnz = p->colptr[nl];
-    HIPCK(hipMalloc((void**)&w.colptr, (size_t)(nl + 1) * 8));
-    HIPCK(hipMalloc((void**)&w.colvals, (size_t)(nnz > 0 ? nnz : 1) * 8));
+    if ((rc = scratch.alloc(&w.colptr, (size_t)nl + 1)) || (rc = scratch.alloc(&w.colvals, (size_t)std::max<int64_t>(nnz, 0)))) return rc;
     HIPCK(hipMemcpyAsync(w.colptr, p->colptr, (size_t)(nl + 1) * 8, hipMemcpyHostToDevice, st));
     if (nnz > 0) HIPCK(hipMemcpyAsync(w.colvals, p->colvals, (size_t)nnz * 8, hipMemcpyHostToDevice, st));
     a.colptr = w.colptr;
     a.colvals = w.colvals;
   }
   const int64_t nd = single ? 1 : nl;
-  HIPCK(hipMalloc((void**)&w.losses, (size_t)nd * sizeof(glrm_loss)));
+  if ((rc = scratch.alloc(&w.losses, (size_t)nd)) || (rc = scratch.alloc(&w.stats, (size_t)nl * 4))) return rc;
   HIPCK(hipMemcpyAsync(w.losses, lh, (size_t)nd * sizeof(glrm_loss), hipMemcpyHostToDevice, st));
-  HIPCK(hipMalloc((void**)&w.stats, (size_t)nl * 4 * 8));
   a.losses = w.losses;
   a.loss_single = single ? 1 : 0;
   a.mode = mode;

@@ -44,14 +44,14 @@ __global__ void widen_factor_kernel(const float* __restrict__ src, double* __res
 
 static unsigned copy_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 4096); }
 
-// One view's values: a float array of the handle's own replaces the double one (released when the handle owned it).
-static int narrow_values(glrm_handle* h, double** vals, int64_t nnz, bool owned, int* dflag) {
+// One view's values: a float array of the handle's own replaces the double one, which is released.
+static int narrow_values(glrm_handle* h, double** vals, int64_t nnz, int* dflag) {
   float* f = nullptr;
-  HIPCK(hipMalloc((void**)&f, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
+  if (const int rc = h->mem.alloc(&f, (size_t)std::max<int64_t>(nnz, 0))) return rc;
   if (nnz > 0) hipLaunchKernelGGL(narrow_kernel, dim3(copy_grid(nnz)), dim3(256), 0, h->stream, *vals, f, nnz, dflag);
   const hipError_t e = nnz > 0 ? hipGetLastError() : hipSuccess;
   const hipError_t e2 = hipStreamSynchronize(h->stream);
-  if (owned && *vals) (void)hipFree(*vals);
+  h->mem.release(vals);
   *vals = reinterpret_cast<double*>(f); // glrm_handle::storage: floats behind the double* field
   HIPCK(e);
   HIPCK(e2);
@@ -59,18 +59,19 @@ static int narrow_values(glrm_handle* h, double** vals, int64_t nnz, bool owned,
 }
 
 int glrm_narrow_views(glrm_handle* h) {
+  DevArena scratch;
   int* dflag = nullptr;
-  HIPCK(hipMalloc((void**)&dflag, sizeof(int)));
+  int rc = scratch.alloc(&dflag, 1);
+  if (rc) return rc;
   int flag = 0;
   hipError_t e = hipMemsetAsync(dflag, 0, sizeof(int), h->stream);
-  int rc = e == hipSuccess ? GLRM_OK : fail(GLRM_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-  if (!rc) rc = narrow_values(h, &h->rowvals, h->nnz_r, h->own_rowview, dflag);
-  if (!rc) rc = narrow_values(h, &h->colvals, h->nnz_c, h->own_colview, dflag);
+  rc = e == hipSuccess ? GLRM_OK : fail(GLRM_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+  if (!rc) rc = narrow_values(h, &h->rowvals, h->nnz_r, dflag);
+  if (!rc) rc = narrow_values(h, &h->colvals, h->nnz_c, dflag);
   if (!rc) {
     e = hipMemcpy(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(GLRM_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
   }
-  (void)hipFree(dflag);
   if (rc) return rc;
   if (flag) return fail(GLRM_ERR_NONFINITE, "storage = f32: an observed value is finite as a double and +-Inf as a float");
   return GLRM_OK;
@@ -86,16 +87,16 @@ int glrm_check_narrowable(const char* name, const double* v, int64_t n) {
 
 int glrm_narrow_factor(glrm_handle* h, const double* host, void* dev, int64_t nvec) {
   if (nvec <= 0) return GLRM_OK;
+  DevArena scratch;
   double* stage = nullptr;
   const size_t bytes = (size_t)h->k * nvec * sizeof(double);
-  HIPCK(hipMalloc((void**)&stage, bytes));
+  if (const int rc = scratch.alloc(&stage, (size_t)h->k * nvec)) return rc;
   hipError_t e = hipMemcpyAsync(stage, host, bytes, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(narrow_factor_kernel, dim3(copy_grid(nvec * h->kp)), dim3(256), 0, h->stream, stage, (float*)dev, h->k, h->kp, nvec);
     e = hipGetLastError();
   }
   const hipError_t e2 = hipStreamSynchronize(h->stream);
-  (void)hipFree(stage);
   HIPCK(e);
   HIPCK(e2);
   return GLRM_OK;
@@ -103,14 +104,14 @@ int glrm_narrow_factor(glrm_handle* h, const double* host, void* dev, int64_t nv
 
 int glrm_widen_factor(glrm_handle* h, const void* dev, double* host, int64_t nvec) {
   if (nvec <= 0) return GLRM_OK;
+  DevArena scratch;
   double* stage = nullptr;
   const size_t bytes = (size_t)h->k * nvec * sizeof(double);
-  HIPCK(hipMalloc((void**)&stage, bytes));
+  if (const int rc = scratch.alloc(&stage, (size_t)h->k * nvec)) return rc;
   hipLaunchKernelGGL(widen_factor_kernel, dim3(copy_grid(nvec * h->k)), dim3(256), 0, h->stream, (const float*)dev, stage, h->k, h->kp, nvec);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(host, stage, bytes, hipMemcpyDeviceToHost, h->stream);
   const hipError_t e2 = hipStreamSynchronize(h->stream);
-  (void)hipFree(stage);
   HIPCK(e);
   HIPCK(e2);
   return GLRM_OK;

@@ -103,54 +103,47 @@ __global__ void newptr_kernel(const int64_t* ptr, int64_t nseg, int64_t nnz, con
   }
 }
 
-struct View {
+struct View { // a compacted view; `mem` frees it
   int64_t* ptr = nullptr;
   int32_t* idx = nullptr;
   double* vals = nullptr;
-  ~View() {
-    if (ptr) (void)hipFree(ptr);
-    if (idx) (void)hipFree(idx);
-    if (vals) (void)hipFree(vals);
-  }
+  DevArena mem;
 };
 
 int compact_view(hipStream_t st, const int64_t* ptr, const int32_t* idx, const double* vals, int64_t nseg, int64_t nnz,
                  const uint8_t* host_tags, int match, int invert, View& out) {
   uint8_t* dtags = nullptr;
   int64_t *blockcount = nullptr, *pos = nullptr, *dtotal = nullptr;
-  auto cleanup = [&](int rc) {
-    if (dtags) (void)hipFree(dtags);
-    if (blockcount) (void)hipFree(blockcount);
-    if (pos) (void)hipFree(pos);
-    if (dtotal) (void)hipFree(dtotal);
-    return rc;
-  };
+  DevArena scratch;
+  int rc;
   const int64_t nb = (nnz + CB - 1) / CB;
   int64_t total = 0;
-  HIPCK(hipMalloc((void**)&out.ptr, (size_t)(nseg + 1) * 8));
+  if ((rc = out.mem.alloc(&out.ptr, (size_t)nseg + 1))) return rc;
   if (nnz > 0) {
-    if (hipMalloc((void**)&dtags, (size_t)nnz) != hipSuccess || hipMalloc((void**)&blockcount, (size_t)nb * 8) != hipSuccess ||
-        hipMalloc((void**)&pos, (size_t)nnz * 8) != hipSuccess || hipMalloc((void**)&dtotal, 8) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_OOM, "out of device memory while compacting %lld observations", (long long)nnz));
+    char oom[96];
+    snprintf(oom, sizeof oom, "out of device memory while compacting %lld observations", (long long)nnz);
+    if ((rc = scratch.alloc(&dtags, (size_t)nnz, oom)) || (rc = scratch.alloc(&blockcount, (size_t)nb, oom)) || (rc = scratch.alloc(&pos, (size_t)nnz, oom)) ||
+        (rc = scratch.alloc(&dtotal, 1, oom)))
+      return rc;
     if (hipMemcpyAsync(dtags, host_tags, (size_t)nnz, hipMemcpyHostToDevice, st) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_HIP, "tag upload failed"));
+      return fail(GLRM_ERR_HIP, "tag upload failed");
     hipLaunchKernelGGL(count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, dtags, nnz, match, invert, blockcount);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockcount, nb, dtotal);
     hipLaunchKernelGGL(position_kernel, dim3((unsigned)nb), dim3(CT), 0, st, dtags, nnz, match, invert, blockcount, pos);
     if (hipMemcpyAsync(&total, dtotal, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_HIP, "compaction failed: %s", hipGetErrorString(hipGetLastError())));
+      return fail(GLRM_ERR_HIP, "compaction failed: %s", hipGetErrorString(hipGetLastError()));
   }
-  const size_t t1 = (size_t)(total > 0 ? total : 1);
-  if (hipMalloc((void**)&out.idx, t1 * 4) != hipSuccess || hipMalloc((void**)&out.vals, t1 * 8) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the subset (%lld observations)", (long long)total));
+  char oom[96];
+  snprintf(oom, sizeof oom, "out of device memory for the subset (%lld observations)", (long long)total);
+  if ((rc = out.mem.alloc(&out.idx, (size_t)total, oom)) || (rc = out.mem.alloc(&out.vals, (size_t)total, oom))) return rc;
   if (nnz > 0) {
     hipLaunchKernelGGL(scatter_kernel, dim3(4096), dim3(256), 0, st, dtags, nnz, match, invert, pos, idx, vals, out.idx, out.vals);
     hipLaunchKernelGGL(newptr_kernel, dim3(1024), dim3(256), 0, st, ptr, nseg, nnz, pos, dtotal, out.ptr);
   } else {
-    if (hipMemsetAsync(out.ptr, 0, (size_t)(nseg + 1) * 8, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "memset failed"));
+    if (hipMemsetAsync(out.ptr, 0, (size_t)(nseg + 1) * 8, st) != hipSuccess) return fail(GLRM_ERR_HIP, "memset failed");
   }
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "compaction kernels failed"));
-  return cleanup(GLRM_OK);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "compaction kernels failed");
+  return GLRM_OK;
 }
 
 } // namespace
@@ -161,9 +154,10 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   *out = nullptr;
   GLRM_REFUSE_F32(parent, "glrm_hip_subset");
   if (parent->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_subset needs a list (not dense) parent handle");
-  if (!parent->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
+  GLRM_NEED_FINALIZED(parent);
   if ((parent->nnz_r > 0 && !row_tags) || (parent->nnz_c > 0 && !col_tags)) return fail(GLRM_ERR_INVALID, "NULL tag array");
-  if (hipSetDevice(parent->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", parent->device);
+  DeviceScope dg(parent->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", parent->device);
   View rv, cv;
   int rc = compact_view(parent->stream, parent->rowptr, parent->colidx, parent->rowvals, parent->ml, parent->nnz_r, row_tags, match, invert, rv);
   if (rc) return rc;
@@ -193,8 +187,7 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   // signature of the WHOLE (subset) problem, so it is created deferred and the host finalizes it with the combined signature of the
   // shards' children (glrm_hip_signature on each child, sum / max, glrm_hip_finalize) -- the protocol of the parents.  A single-shard
   // parent's child is set up here.
-  const bool shard = !(parent->rb == 0 && parent->re == parent->m && parent->cb == 0 && parent->ce == parent->n);
-  if (shard) p.flags |= GLRM_PROBLEM_DEFER_SETUP;
+  if (!glrm_single_shard(parent)) p.flags |= GLRM_PROBLEM_DEFER_SETUP;
   rc = glrm_hip_create(out, &p, &o); // copies the compacted views; rv / cv are released on return
   if (!rc && (rc = glrm_regvec_inherit(*out, parent))) {
     char keep[sizeof g_err];

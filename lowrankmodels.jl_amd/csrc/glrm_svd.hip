@@ -291,10 +291,6 @@ struct Work {
   double *V = nullptr, *U = nullptr, *means = nullptr, *stds = nullptr, *gpart = nullptr, *G = nullptr, *M = nullptr, *cpart = nullptr,
          *sq = nullptr, *dX = nullptr, *dY = nullptr;
   int nblk_max = 1024;
-  ~Work() {
-    for (double* p : {V, U, means, stds, gpart, G, M, cpart, sq, dX, dY})
-      if (p) (void)hipFree(p);
-  }
 };
 
 // G = Z'Z -> eigenpairs on the host.  Returns descending eigenvalues w and eigenvectors E (row-major, columns).
@@ -357,13 +353,14 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
                                  int32_t* iters_done) {
   if (!h || !X || !Y) return fail(GLRM_ERR_INVALID, "NULL argument");
   GLRM_REFUSE_F32(h, "glrm_hip_init_svd");
-  if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_svd needs a single-shard handle");
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_init_svd needs a single-shard handle");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_init_svd works on the observation lists (create the handle without dense_A)");
-  if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
+  GLRM_NEED_FINALIZED(h);
   const int k = h->k;
   const int64_t m = h->m, d = h->d;
   if (k > m || k > d) return fail(GLRM_ERR_INVALID, "k = %d exceeds min(m, d): no k singular triplets", k);
-  if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   if (max_iter <= 0) max_iter = 60;
   if (!(tol > 0)) tol = 1e-12;
   int l = k + 8;
@@ -374,14 +371,12 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
   Work w;
   w.h = h; w.st = h->stream; w.l = l;
   hipStream_t st = w.st;
-  HIPCK(hipMalloc((void**)&w.V, (size_t)d * l * 8));
-  HIPCK(hipMalloc((void**)&w.U, (size_t)m * l * 8));
-  HIPCK(hipMalloc((void**)&w.means, (size_t)d * 8));
-  HIPCK(hipMalloc((void**)&w.stds, (size_t)d * 8));
-  HIPCK(hipMalloc((void**)&w.gpart, (size_t)w.nblk_max * l * l * 8));
-  HIPCK(hipMalloc((void**)&w.G, (size_t)l * l * 8));
-  HIPCK(hipMalloc((void**)&w.M, (size_t)l * l * 8));
-  HIPCK(hipMalloc((void**)&w.sq, (size_t)l * 8));
+  DevArena scratch;
+  int rc;
+  if ((rc = scratch.alloc(&w.V, (size_t)d * l)) || (rc = scratch.alloc(&w.U, (size_t)m * l)) || (rc = scratch.alloc(&w.means, (size_t)d)) ||
+      (rc = scratch.alloc(&w.stds, (size_t)d)) || (rc = scratch.alloc(&w.gpart, (size_t)w.nblk_max * l * l)) || (rc = scratch.alloc(&w.G, (size_t)l * l)) ||
+      (rc = scratch.alloc(&w.M, (size_t)l * l)) || (rc = scratch.alloc(&w.sq, (size_t)l)))
+    return rc;
   // column statistics
   hipLaunchKernelGGL(svd_stats_kernel, dim3((unsigned)h->n), dim3(256), 0, st, h->colptr, h->colvals, h->losses, h->n_losses == 1 ? 1 : 0,
                      h->ystart, h->n, 1e-10, w.means, w.stds);
@@ -403,7 +398,7 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
     while ((longest + ca.chunk - 1) / ca.chunk > 65535) ca.chunk *= 2; // gridDim.y
     ca.nsplit = (int)std::max<int64_t>(1, (longest + ca.chunk - 1) / ca.chunk);
     if (ca.nsplit > 1) {
-      HIPCK(hipMalloc((void**)&w.cpart, (size_t)h->n * ca.nsplit * h->dmax * l * 8));
+      if ((rc = scratch.alloc(&w.cpart, (size_t)h->n * ca.nsplit * h->dmax * l))) return rc;
       ca.partial = w.cpart;
     } else ca.chunk = longest > 0 ? longest : 1;
   }
@@ -415,8 +410,7 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
     if (ca.nsplit > 1) hipLaunchKernelGGL(svd_cols_reduce_kernel, dim3((unsigned)h->n), dim3(256), 0, st, ca);
   };
   hipLaunchKernelGGL(randn_kernel, dim3(1024), dim3(256), 0, st, w.V, d * l, seed);
-  int rc = orthonormalize(w, w.V, d);
-  if (rc) return rc;
+  if ((rc = orthonormalize(w, w.V, d))) return rc;
   std::vector<double> ritz, prev, E;
   int it = 0;
   for (it = 1; it <= max_iter; ++it) {
@@ -439,8 +433,7 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
   std::vector<double> sq((size_t)l);
   for (int c = 0; c < l; ++c) sq[c] = std::sqrt(std::sqrt(std::max(ritz[c], 0.0))); // sqrt of the singular value
   HIPCK(hipMemcpyAsync(w.sq, sq.data(), (size_t)l * 8, hipMemcpyHostToDevice, st));
-  HIPCK(hipMalloc((void**)&w.dX, (size_t)m * k * 8));
-  HIPCK(hipMalloc((void**)&w.dY, (size_t)d * k * 8));
+  if ((rc = scratch.alloc(&w.dX, (size_t)m * k)) || (rc = scratch.alloc(&w.dY, (size_t)d * k))) return rc;
   hipLaunchKernelGGL(factors_kernel, dim3(1024), dim3(256), 0, st, w.U, m, l, k, w.sq, (const double*)nullptr, w.dX);
   hipLaunchKernelGGL(factors_kernel, dim3(1024), dim3(256), 0, st, w.V, d, l, k, w.sq, w.stds, w.dY);
   HIPCK(hipGetLastError());

@@ -4,6 +4,7 @@
 //   libglrm_hip_testing.so   the same objects with this file and csrc/glrm_multigpu.hip rebuilt under -DGLRM_HIP_TESTING: GLRM_HIP_TEST_FAIL_FINALIZE,
 //                            GLRM_HIP_RCCL_LIB / GLRM_HIP_RCCL_ALLOW_SHARED (tests/stubs/rccl_stub.cpp) and the link emulator
 //                            (GLRM_EXCHANGE_EMULATE_*) exist only there; tests and `bench.py --emulate-link-gbps` load it by name.
+#include <atomic>
 #include <cstdlib>
 
 #include "glrm_engine.hpp"
@@ -23,6 +24,37 @@ int glrm_test_fail_finalize() {
   return v && *v && atoi(v) != 0;
 #else
   return 0;
+#endif
+}
+
+// ------------------------------------------------------------------ DevArena's allocator (csrc/glrm_devmem.hpp): the engine's only hipMalloc / hipFree.
+// The test build counts the live allocations (tests/test_gpu_devmem.py: every handle and every extension call gives back what it took).
+#ifdef GLRM_HIP_TESTING
+static std::atomic<long long> g_live_allocations{0};
+#endif
+
+hipError_t glrm_device_alloc(void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+#ifdef GLRM_HIP_TESTING
+  if (e == hipSuccess) ++g_live_allocations;
+#endif
+  return e;
+}
+
+void glrm_device_free(void* p) {
+  if (!p) return;
+  (void)hipFree(p);
+#ifdef GLRM_HIP_TESTING
+  --g_live_allocations;
+#endif
+}
+
+// live device allocations of this library's arenas; -1 in the product library, which does not count
+extern "C" long long glrm_test_live_device_allocations(void) {
+#ifdef GLRM_HIP_TESTING
+  return g_live_allocations.load();
+#else
+  return -1;
 #endif
 }
 
@@ -135,9 +167,10 @@ extern "C" int glrm_test_reg_prox_eval(const glrm_reg* reg, int32_t k, double al
   std::vector<double> padded((size_t)nvec * kp, 0.0);
   for (int64_t v = 0; v < nvec; ++v)
     for (int c = 0; c < k; ++c) padded[(size_t)v * kp + c] = u[(size_t)v * k + c];
+  DevArena scratch;
   double* d = nullptr;
   const size_t nb = (size_t)nvec * kp * 8, ne = (size_t)nvec * 8;
-  HIPCK(hipMalloc((void**)&d, nb + 2 * ne));
+  if (const int rca = scratch.alloc(&d, (nb + 2 * ne) / 8)) return rca;
   RegHookArgs a{*reg, k, kp, alpha, nvec, d, d + (size_t)nvec * kp, d + (size_t)nvec * kp + nvec};
   hipError_t e = hipMemcpy(d, padded.data(), nb, hipMemcpyHostToDevice);
   int rc = GLRM_OK;
@@ -147,7 +180,6 @@ extern "C" int glrm_test_reg_prox_eval(const glrm_reg* reg, int32_t k, double al
   if (e == hipSuccess && !rc) e = hipMemcpy(prox_out, d, nb, hipMemcpyDeviceToHost);
   if (e == hipSuccess && !rc) e = hipMemcpy(eval_in, a.ein, ne, hipMemcpyDeviceToHost);
   if (e == hipSuccess && !rc) e = hipMemcpy(eval_out, a.eout, ne, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (rc) return rc;
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_reg_prox_eval: %s", hipGetErrorString(e));
   return GLRM_OK;
@@ -191,9 +223,10 @@ extern "C" int glrm_test_regvec_prox_eval(const glrm_reg* reg, const double* rve
   std::vector<double> padded((size_t)nvec * kp, 0.0);
   for (int64_t v = 0; v < nvec; ++v)
     for (int c = 0; c < k; ++c) padded[(size_t)v * kp + c] = u[(size_t)v * k + c];
+  DevArena scratch;
   double* d = nullptr;
   const size_t nb = (size_t)nvec * kp * 8, ne = (size_t)nvec * 8;
-  HIPCK(hipMalloc((void**)&d, nb + 2 * ne + (size_t)k * 8));
+  if (const int rca = scratch.alloc(&d, (nb + 2 * ne) / 8 + (size_t)k)) return rca;
   double* drv = d + (size_t)nvec * kp + 2 * nvec;
   RegVecHookArgs h{RegHookArgs{*reg, k, kp, alpha, nvec, d, d + (size_t)nvec * kp, d + (size_t)nvec * kp + nvec}, drv, rlen};
   std::vector<double> rvk((size_t)k, 0.0);
@@ -208,7 +241,6 @@ extern "C" int glrm_test_regvec_prox_eval(const glrm_reg* reg, const double* rve
   if (e == hipSuccess) e = hipMemcpy(prox_out, d, nb, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(eval_in, h.a.ein, ne, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(eval_out, h.a.eout, ne, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_regvec_prox_eval: %s", hipGetErrorString(e));
   return GLRM_OK;
 }

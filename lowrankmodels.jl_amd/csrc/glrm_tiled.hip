@@ -91,7 +91,7 @@ int glrm_prepare_tiled(glrm_handle* h) {
   h->tG = h->G;
   h->tR = h->R;
   const int T = glrm_tile_rows(h->kp);
-  HIPCK(hipMalloc((void**)&h->dflag, 2 * sizeof(int)));
+  if (const int rc = h->mem.alloc(&h->dflag, 2)) return rc;
   HIPCK(hipMemsetAsync(h->dflag, 0, 2 * sizeof(int), st));
   if (h->ml > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->ml, T, h->dflag);
   if (h->nl > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->nl), dim3(256), 0, st, h->colptr, h->rowidx, h->nl, T, h->dflag + 1);
@@ -139,17 +139,15 @@ int glrm_setup_tiled(glrm_handle* h) {
   const int64_t sort_limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0) > 0 ? env_int("GLRM_HIP_TILE_SORT_BATCH", 0) : 1500000000ll;
   if (want_row && !h->rows_sorted && may_sort && h->sig.max_row_len <= sort_limit) {
     if (h->sig_local.rows_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->rowptr, h->ml, h->nnz_r, T, h->n, &h->colidx, &h->rowvals, h->own_rowview);
+      const int rc = glrm_tile_sort_view(st, h->rowptr, h->ml, h->nnz_r, T, h->n, &h->colidx, &h->rowvals, h->mem);
       if (rc) return rc;
-      h->own_rowview = true;
     }
     h->rows_sorted = true;
   }
   if (want_col && !h->cols_sorted && may_sort && h->sig.max_col_len <= sort_limit) {
     if (h->sig_local.cols_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->colptr, h->nl, h->nnz_c, T, h->m, &h->rowidx, &h->colvals, h->own_colview);
+      const int rc = glrm_tile_sort_view(st, h->colptr, h->nl, h->nnz_c, T, h->m, &h->rowidx, &h->colvals, h->mem);
       if (rc) return rc;
-      h->own_colview = true;
     }
     h->cols_sorted = true;
   }
@@ -159,20 +157,19 @@ int glrm_setup_tiled(glrm_handle* h) {
   // there is no wave-wide formula to align, and the grouped copy would cost 12 B per observation beside the SELL stream)
   const bool lane_rows = h->tiled_row && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && glrm_lane_wants(h, true);
   if (h->tiled_row && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !lane_rows) {
+    DevArena scratch;
     int32_t* oidx = nullptr;
     double* ovals = nullptr;
-    HIPCK(hipMalloc((void**)&oidx, (size_t)h->nnz_r * 4));
-    if (hipMalloc((void**)&ovals, (size_t)h->nnz_r * 8) != hipSuccess) { (void)hipFree(oidx); return fail(GLRM_ERR_OOM, "out of device memory"); }
+    if ((rc0 = scratch.alloc(&oidx, (size_t)h->nnz_r)) || (rc0 = scratch.alloc(&ovals, (size_t)h->nnz_r))) return rc0;
     hipLaunchKernelGGL(group_rows_by_kind_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->rowvals, h->ml, T, h->losses, oidx, ovals);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(st));
-    if (h->own_rowview) {
-      (void)hipFree(h->colidx);
-      (void)hipFree(h->rowvals);
-    }
+    h->mem.release(&h->colidx); // (a borrowed view is not the arena's: it stays the caller's)
+    h->mem.release(&h->rowvals);
     h->colidx = oidx;
     h->rowvals = ovals;
-    h->own_rowview = true;
+    scratch.move_to(h->mem, oidx);
+    scratch.move_to(h->mem, ovals);
   }
   if (h->tiled_row && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_UDESC", 1)) {
     // distinct loss descriptors of the model; with at most 256 of them every entry of the row view carries a one-byte id and the
@@ -192,16 +189,14 @@ int glrm_setup_tiled(glrm_handle* h) {
       colid[(size_t)f] = (uint8_t)u;
     }
     if (ok) {
+      DevArena scratch;
       uint8_t* dcolid = nullptr;
-      HIPCK(hipMalloc((void**)&dcolid, (size_t)h->n));
-      HIPCK(hipMalloc((void**)&h->udesc, uniq.size() * sizeof(glrm_loss)));
-      HIPCK(hipMalloc((void**)&h->rowdescid, (size_t)h->nnz_r));
+      if ((rc0 = scratch.alloc(&dcolid, (size_t)h->n)) || (rc0 = h->mem.alloc(&h->udesc, uniq.size())) || (rc0 = h->mem.alloc(&h->rowdescid, (size_t)h->nnz_r))) return rc0;
       HIPCK(hipMemcpyAsync(dcolid, colid.data(), (size_t)h->n, hipMemcpyHostToDevice, st));
       HIPCK(hipMemcpyAsync(h->udesc, uniq.data(), uniq.size() * sizeof(glrm_loss), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(entry_descid_kernel, dim3(4096), dim3(256), 0, st, h->colidx, h->nnz_r, dcolid, h->rowdescid);
       HIPCK(hipGetLastError());
       HIPCK(hipStreamSynchronize(st)); // colid / uniq are locals
-      (void)hipFree(dcolid);
       h->n_udesc = (int)uniq.size();
     }
   }
@@ -252,7 +247,7 @@ int glrm_setup_tiled(glrm_handle* h) {
   h->tile_rounds = env_int("GLRM_HIP_TILE_ROUNDS", 3);
   if ((h->tiled_row && (h->tile_rounds & 1)) || (h->tiled_col && (h->tile_rounds & 2))) {
     const int64_t cap = std::max<int64_t>(1, std::max(h->tiled_row ? h->ml : 0, h->tiled_col ? h->nl : 0));
-    HIPCK(hipMalloc((void**)&h->actlist, (size_t)cap * 2 * sizeof(int32_t)));
+    if ((rc0 = h->mem.alloc(&h->actlist, (size_t)cap * 2))) return rc0;
     h->actlist_cap = cap;
   }
   // the pass buffers of the row rounds: ONE super-tile (nothing is re-added: the bits of the one-kernel sweep)

@@ -37,8 +37,9 @@ struct MinusBase { // segment offsets relative to the batch's first entry
 // hipCUB counts items and segments in int, so a view is sorted in batches of whole segments with at most `limit` entries each
 // (1.5e9; GLRM_HIP_TILE_SORT_BATCH overrides, the tests use it to exercise the batching on small inputs); the scratch arrays are
 // sized for one batch.  A single segment longer than the limit cannot be sorted this way (GLRM_ERR_UNSUPPORTED: gather sweeps).
-// free_old = false: the old arrays are the caller's (GLRM_PROBLEM_BORROW_DEVICE_ARRAYS) and stay untouched.
-int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, bool free_old) {
+// owner: the arena that gets the new arrays and frees the old ones -- unless they are not its own (GLRM_PROBLEM_BORROW_DEVICE_ARRAYS: the
+// caller's, which stay untouched).
+int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, DevArena& owner) {
   if (nnz <= 0 || nseg <= 0) return GLRM_OK;
   int64_t limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0);
   if (limit <= 0) limit = 1500000000ll;
@@ -59,18 +60,15 @@ int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_
   int64_t *p0 = nullptr, *p1 = nullptr;
   int32_t* oidx = nullptr;
   double* ovals = nullptr;
-  void* tmp = nullptr;
+  char* tmp = nullptr;
+  DevArena scratch;
+  const char* oom = "out of device memory for the tile sort";
   size_t tmp_bytes = 0;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)k0, (void*)k1, (void*)p0, (void*)p1, tmp}) if (p) (void)hipFree(p);
-    if (rc) { if (oidx) (void)hipFree(oidx); if (ovals) (void)hipFree(ovals); }
-    return rc;
-  };
   const size_t cap1 = (size_t)(cap > 0 ? cap : 1);
-  if (hipMalloc((void**)&k0, cap1 * 4) != hipSuccess || hipMalloc((void**)&k1, cap1 * 4) != hipSuccess ||
-      hipMalloc((void**)&p0, cap1 * 8) != hipSuccess || hipMalloc((void**)&p1, cap1 * 8) != hipSuccess ||
-      hipMalloc((void**)&oidx, (size_t)nnz * 4) != hipSuccess || hipMalloc((void**)&ovals, (size_t)nnz * 8) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the tile sort"));
+  int rc;
+  if ((rc = scratch.alloc(&k0, cap1, oom)) || (rc = scratch.alloc(&k1, cap1, oom)) || (rc = scratch.alloc(&p0, cap1, oom)) || (rc = scratch.alloc(&p1, cap1, oom)) ||
+      (rc = scratch.alloc(&oidx, (size_t)nnz, oom)) || (rc = scratch.alloc(&ovals, (size_t)nnz, oom)))
+    return rc;
   int bits = 1;
   while (((int64_t)1 << bits) < (n_other + tile - 1) / tile) ++bits;
   for (size_t b = 0; b + 1 < cuts.size(); ++b) {
@@ -80,23 +78,22 @@ int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_
     hipcub::TransformInputIterator<int, MinusBase, const int64_t*> beg(ptr + s0, MinusBase{base}), end(ptr + s0 + 1, MinusBase{base});
     size_t bytes = 0;
     if (hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, bytes, k0, k1, p0, p1, (int)cnt, (int)(s1 - s0), beg, end, 0, bits, st) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_HIP, "segmented sort (size query) failed"));
+      return fail(GLRM_ERR_HIP, "segmented sort (size query) failed");
     if (bytes > tmp_bytes) {
-      if (tmp) (void)hipFree(tmp);
-      tmp = nullptr;
-      if (hipMalloc(&tmp, bytes) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the tile sort"));
+      scratch.release(&tmp);
+      if ((rc = scratch.alloc(&tmp, bytes, oom))) return rc;
       tmp_bytes = bytes;
     }
     if (hipcub::DeviceSegmentedRadixSort::SortPairs(tmp, bytes, k0, k1, p0, p1, (int)cnt, (int)(s1 - s0), beg, end, 0, bits, st) != hipSuccess)
-      return cleanup(fail(GLRM_ERR_HIP, "segmented sort failed"));
+      return fail(GLRM_ERR_HIP, "segmented sort failed");
     hipLaunchKernelGGL(apply_perm_kernel, dim3(4096), dim3(256), 0, st, p1, cnt, *idx + base, *vals + base, oidx + base, ovals + base);
   }
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "tile sort kernels failed"));
-  if (free_old) {
-    (void)hipFree(*idx);
-    (void)hipFree(*vals);
-  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "tile sort kernels failed");
+  owner.release(idx);
+  owner.release(vals);
   *idx = oidx;
   *vals = ovals;
-  return cleanup(GLRM_OK);
+  scratch.move_to(owner, oidx);
+  scratch.move_to(owner, ovals);
+  return GLRM_OK;
 }

@@ -349,20 +349,6 @@ __global__ void __launch_bounds__(TK_THREADS) topk_compact_kernel(int64_t rows, 
   }
 }
 
-struct TkWork {
-  std::vector<void*> ptrs;
-  template <class T> hipError_t alloc(T** p, size_t count) {
-    hipError_t e = hipMalloc((void**)p, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back((void*)*p);
-    return e;
-  }
-  void release() {
-    for (void* p : ptrs) (void)hipFree(p);
-    ptrs.clear();
-  }
-  ~TkWork() { release(); }
-};
-
 thread_local int32_t g_select_passes = 0;
 thread_local int64_t g_select_sorted = 0;
 
@@ -371,8 +357,8 @@ int tk_check(glrm_handle* h, const double* X, const double* Y, const char* what)
   if (!h) return fail(GLRM_ERR_INVALID, "%s: NULL handle", what);
   GLRM_REFUSE_F32(h, what);
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "%s works on the observation lists (create the handle without dense_A)", what);
-  if (!(h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n)) return fail(GLRM_ERR_INVALID, "%s needs a single-shard handle", what);
-  if (!h->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first");
+  if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "%s needs a single-shard handle", what);
+  GLRM_NEED_FINALIZED(h);
   for (size_t j = 0; j < h->losses_h.size(); ++j)
     if (h->losses_h[j].dim > 1)
       return fail(GLRM_ERR_UNSUPPORTED, "%s: column %lld has a multi-dimensional loss (kind %d, dim %d); XY[i,j] with j in 1:n needs one vector "
@@ -383,9 +369,8 @@ int tk_check(glrm_handle* h, const double* X, const double* Y, const char* what)
   return GLRM_OK;
 }
 
-// after every argument check: the factors, uploaded like glrm_hip_impute does it
+// after every argument check, inside the entry point's device scope: the factors, uploaded like glrm_hip_impute does it
 int tk_factors(glrm_handle* h, const double* X, const double* Y, TkFactors& f) {
-  if (hipSetDevice(h->device) != hipSuccess) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   if (X) {
     const int rc = glrm_hip_set_factors(h, X, Y);
     if (rc) return rc;
@@ -411,6 +396,8 @@ extern "C" int glrm_hip_xy_select(glrm_handle* h, const double* X, const double*
     return fail(GLRM_ERR_INVALID, "glrm_hip_xy_select: rank %lld outside [1, m n = %lld x %lld] (the reference raises a BoundsError)",
                 (long long)rank, (long long)m, (long long)n);
   TkFactors f{};
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   if ((rc = tk_factors(h, X, Y, f))) return rc;
   hipStream_t st = h->stream;
   const int64_t tiles_m = (m + TK_TILE - 1) / TK_TILE, tiles_n = (n + TK_TILE - 1) / TK_TILE, ntiles = tiles_m * tiles_n;
@@ -422,13 +409,13 @@ extern "C" int glrm_hip_xy_select(glrm_handle* h, const double* X, const double*
   const int grid = (int)grid64;
   const int64_t finish = (int64_t)env_int("GLRM_HIP_TOPK_FINISH", (int)TK_FINISH);
 
-  TkWork w;
+  DevArena w;
   unsigned long long *slots = nullptr, *totals = nullptr, *woff = nullptr, *keys = nullptr, *sorted = nullptr, *picked = nullptr;
-  void* tmp = nullptr;
-  HIPCK(w.alloc(&slots, (size_t)grid * TK_DIGITS));
-  HIPCK(w.alloc(&totals, (size_t)TK_DIGITS));
-  HIPCK(w.alloc(&woff, (size_t)grid + 1));
-  HIPCK(w.alloc(&picked, 3));
+  char* tmp = nullptr;
+  if ((rc = w.alloc(&slots, (size_t)grid * TK_DIGITS))) return rc;
+  if ((rc = w.alloc(&totals, (size_t)TK_DIGITS))) return rc;
+  if ((rc = w.alloc(&woff, (size_t)grid + 1))) return rc;
+  if ((rc = w.alloc(&picked, 3))) return rc;
 
   unsigned long long prefix = 0, above = 0, equal = 0, key = 0;
   unsigned long long r = (unsigned long long)rank; // the rank inside the entries that still match the prefix
@@ -458,16 +445,15 @@ extern "C" int glrm_hip_xy_select(glrm_handle* h, const double* X, const double*
     if (finish > 0 && (int64_t)tot[d] <= finish && tot[d] <= 0x7fffffffull) {
       // one more pass writes the bucket's keys out; sort, pick
       const size_t cnt = (size_t)tot[d];
-      HIPCK(w.alloc(&keys, cnt));
-      HIPCK(w.alloc(&sorted, cnt));
+      if ((rc = w.alloc(&keys, cnt))) return rc;
+      if ((rc = w.alloc(&sorted, cnt))) return rc;
       hipLaunchKernelGGL(topk_offsets_kernel, dim3(1), dim3(TK_THREADS), 0, st, (const unsigned long long*)slots, grid, d, woff);
       hipLaunchKernelGGL(topk_collect_kernel, dim3((unsigned)grid), dim3(TK_THREADS), 0, st, f, tiles_n, ntiles, prefix, shift,
                          (const unsigned long long*)woff, keys);
       HIPCK(hipGetLastError());
       size_t bytes = 0;
       HIPCK(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, bytes, (const unsigned long long*)keys, sorted, (int)cnt, 0, shift, st));
-      HIPCK(hipMalloc(&tmp, bytes ? bytes : 1));
-      w.ptrs.push_back(tmp);
+      if ((rc = w.alloc(&tmp, bytes))) return rc;
       HIPCK(hipcub::DeviceRadixSort::SortKeysDescending(tmp, bytes, (const unsigned long long*)keys, sorted, (int)cnt, 0, shift, st));
       hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)sorted, (long long)cnt, (long long)r, picked);
       HIPCK(hipGetLastError());
@@ -515,14 +501,16 @@ extern "C" int glrm_hip_precision_scan(glrm_handle* h, const double* X, const do
   if (q != q || m <= 0 || n <= 0) return GLRM_OK; // a NaN threshold matches nothing: the walk runs to the end
 
   TkFactors f{};
+  DeviceScope dg(h->device);
+  if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
   if ((rc = tk_factors(h, X, Y, f))) return rc;
   hipStream_t st = h->stream;
-  TkWork lists;
+  DevArena lists;
   TkLists l{};
   int64_t* d_tptr = nullptr;
   int32_t* d_tidx = nullptr;
-  HIPCK(lists.alloc(&d_tptr, (size_t)m + 1));
-  HIPCK(lists.alloc(&d_tidx, (size_t)ntest));
+  if ((rc = lists.alloc(&d_tptr, (size_t)m + 1))) return rc;
+  if ((rc = lists.alloc(&d_tidx, (size_t)ntest))) return rc;
   HIPCK(hipMemcpyAsync(d_tptr, test_rowptr, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
   if (ntest > 0) HIPCK(hipMemcpyAsync(d_tidx, test_colidx, (size_t)ntest * 4, hipMemcpyHostToDevice, st));
   l.train_ptr = h->rowptr; l.train_idx = h->colidx; l.test_ptr = d_tptr; l.test_idx = d_tidx;
@@ -536,16 +524,16 @@ extern "C" int glrm_hip_precision_scan(glrm_handle* h, const double* X, const do
   for (int64_t r0 = 0; r0 < m;) {
     const int64_t r1 = std::min(m, r0 + rows), nr = r1 - r0;
     const int64_t need = kprec - found, cap = std::min(need, nr * n);
-    TkWork w;
+    DevArena w;
     uint8_t *codes = nullptr, *d_ht = nullptr;
     int64_t *rowcount = nullptr, *rowoff = nullptr;
     int32_t *d_hr = nullptr, *d_hc = nullptr;
-    HIPCK(w.alloc(&codes, (size_t)(nr * n)));
-    HIPCK(w.alloc(&rowcount, (size_t)nr));
-    HIPCK(w.alloc(&rowoff, (size_t)nr + 1));
-    HIPCK(w.alloc(&d_hr, (size_t)cap));
-    HIPCK(w.alloc(&d_hc, (size_t)cap));
-    HIPCK(w.alloc(&d_ht, (size_t)cap));
+    if ((rc = w.alloc(&codes, (size_t)(nr * n)))) return rc;
+    if ((rc = w.alloc(&rowcount, (size_t)nr))) return rc;
+    if ((rc = w.alloc(&rowoff, (size_t)nr + 1))) return rc;
+    if ((rc = w.alloc(&d_hr, (size_t)cap))) return rc;
+    if ((rc = w.alloc(&d_hc, (size_t)cap))) return rc;
+    if ((rc = w.alloc(&d_ht, (size_t)cap))) return rc;
     HIPCK(hipMemsetAsync(codes, 0, (size_t)(nr * n), st));
     const int64_t ntiles = ((nr + TK_TILE - 1) / TK_TILE) * tiles_n;
     if (ntiles > 0x7fffffffll) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_precision_scan: block too large");

@@ -93,9 +93,8 @@ int glrm_rows_from_cols(glrm_handle* h) {
   const int64_t nnz = h->nnz_c, m = h->m, n = h->n;
   hipStream_t st = h->stream;
   h->nnz_r = nnz;
-  HIPCK(hipMalloc((void**)&h->rowptr, ((size_t)m + 1) * 8));
-  HIPCK(hipMalloc((void**)&h->colidx, (size_t)(nnz > 0 ? nnz : 1) * 4));
-  HIPCK(hipMalloc((void**)&h->rowvals, (size_t)(nnz > 0 ? nnz : 1) * 8));
+  int rc;
+  if ((rc = h->mem.alloc(&h->rowptr, (size_t)m + 1)) || (rc = h->mem.alloc(&h->colidx, (size_t)nnz)) || (rc = h->mem.alloc(&h->rowvals, (size_t)nnz))) return rc;
   HIPCK(hipMemsetAsync(h->rowptr, 0, ((size_t)m + 1) * 8, st));
   if (nnz == 0) return GLRM_OK;
   if (m + 1 > (int64_t)INT32_MAX) return fail(GLRM_ERR_UNSUPPORTED, "GLRM_PROBLEM_ROWS_FROM_COLS: %lld rows", (long long)m);
@@ -113,35 +112,32 @@ int glrm_rows_from_cols(glrm_handle* h) {
   uint32_t *k0 = nullptr, *k1 = nullptr, *p0 = nullptr, *p1 = nullptr;
   int64_t* gpos = nullptr;
   unsigned long long* blk = nullptr;
-  void* tmp = nullptr;
+  char* tmp = nullptr;
   int* flag = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)k0, (void*)k1, (void*)p0, (void*)p1, (void*)gpos, (void*)blk, tmp, (void*)flag}) if (p) (void)hipFree(p);
-    return rc;
-  };
+  DevArena scratch;
+  const char* oom = "out of device memory for the row view (GLRM_PROBLEM_ROWS_FROM_COLS)";
   // 1. indices in range; 2. row pointers = inclusive scan of the per-row counts
-  if (hipMalloc((void**)&flag, 4) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the row view (GLRM_PROBLEM_ROWS_FROM_COLS)"));
-  if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "memset failed"));
+  if ((rc = scratch.alloc(&flag, 1, oom))) return rc;
+  if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return fail(GLRM_ERR_HIP, "memset failed");
   hipLaunchKernelGGL(check_rowidx_kernel, dim3(4096), dim3(256), 0, st, h->rowidx, nnz, m, flag);
   int bad = 0;
   if (hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_HIP, "row index check failed"));
-  if (bad) return cleanup(fail(GLRM_ERR_INVALID, "rowidx holds an index outside [0, m)"));
+    return fail(GLRM_ERR_HIP, "row index check failed");
+  if (bad) return fail(GLRM_ERR_INVALID, "rowidx holds an index outside [0, m)");
   lap("index check");
   hipLaunchKernelGGL(row_count_kernel, dim3(8192), dim3(256), 0, st, h->rowidx, nnz, reinterpret_cast<unsigned long long*>(h->rowptr));
   size_t bytes = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "scan (size query) failed"));
-  if (hipMalloc(&tmp, bytes > 0 ? bytes : 1) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the row view (scan scratch)"));
-  if (hipcub::DeviceScan::InclusiveSum(tmp, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "scan failed"));
+  if (hipcub::DeviceScan::InclusiveSum(nullptr, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan (size query) failed");
+  if ((rc = scratch.alloc(&tmp, bytes, "out of device memory for the row view (scan scratch)"))) return rc;
+  if (hipcub::DeviceScan::InclusiveSum(tmp, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
   std::vector<int64_t> rp;
   const bool whole = nnz <= cap;
   if (!whole) {
     rp.resize((size_t)m + 1);
-    if (hipMemcpyAsync(rp.data(), h->rowptr, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "row pointer read-back failed"));
+    if (hipMemcpyAsync(rp.data(), h->rowptr, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(GLRM_ERR_HIP, "row pointer read-back failed");
   }
-  if (hipStreamSynchronize(st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "row pointers failed"));
-  (void)hipFree(tmp);
-  tmp = nullptr;
+  if (hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "row pointers failed");
+  scratch.release(&tmp);
   lap("row counts + scan");
   // 3. row ranges of at most `cap` entries (one row at least); the whole stream when it fits
   std::vector<int64_t> cuts{0};
@@ -155,19 +151,18 @@ int glrm_rows_from_cols(glrm_handle* h) {
     cuts.push_back(r1);
     maxcnt = std::max(maxcnt, rp[(size_t)r1] - rp[(size_t)r0]);
   }
-  if (maxcnt > (int64_t)INT32_MAX - 1) return cleanup(fail(GLRM_ERR_UNSUPPORTED, "GLRM_PROBLEM_ROWS_FROM_COLS: a row of %lld observations", (long long)maxcnt));
+  if (maxcnt > (int64_t)INT32_MAX - 1) return fail(GLRM_ERR_UNSUPPORTED, "GLRM_PROBLEM_ROWS_FROM_COLS: a row of %lld observations", (long long)maxcnt);
   const size_t cnt1 = (size_t)(maxcnt > 0 ? maxcnt : 1);
   const int64_t span = 1 << 20;
   const int64_t nblk = (nnz + span - 1) / span;
-  bool oom = hipMalloc((void**)&k1, cnt1 * 4) != hipSuccess || hipMalloc((void**)&p0, cnt1 * 4) != hipSuccess || hipMalloc((void**)&p1, cnt1 * 4) != hipSuccess;
-  if (!whole) oom = oom || hipMalloc((void**)&k0, cnt1 * 4) != hipSuccess || hipMalloc((void**)&gpos, cnt1 * 8) != hipSuccess || hipMalloc((void**)&blk, (size_t)nblk * 8) != hipSuccess;
-  if (oom) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the row view (GLRM_PROBLEM_ROWS_FROM_COLS)"));
+  if ((rc = scratch.alloc(&k1, cnt1, oom)) || (rc = scratch.alloc(&p0, cnt1, oom)) || (rc = scratch.alloc(&p1, cnt1, oom))) return rc;
+  if (!whole && ((rc = scratch.alloc(&k0, cnt1, oom)) || (rc = scratch.alloc(&gpos, cnt1, oom)) || (rc = scratch.alloc(&blk, (size_t)nblk, oom)))) return rc;
   int bits = 1;
   while (((int64_t)1 << bits) < m) ++bits;
   bytes = 0;
   if (hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const uint32_t*)k1, k1, p0, p1, (int)cnt1, 0, bits, st) != hipSuccess)
-    return cleanup(fail(GLRM_ERR_HIP, "radix sort (size query) failed"));
-  if (hipMalloc(&tmp, bytes > 0 ? bytes : 1) != hipSuccess) return cleanup(fail(GLRM_ERR_OOM, "out of device memory for the row view (sort scratch)"));
+    return fail(GLRM_ERR_HIP, "radix sort (size query) failed");
+  if ((rc = scratch.alloc(&tmp, bytes, "out of device memory for the row view (sort scratch)"))) return rc;
   std::vector<unsigned long long> cnts((size_t)nblk);
   lap("scratch allocation");
   for (size_t c = 0; c + 1 < cuts.size(); ++c) {
@@ -178,11 +173,11 @@ int glrm_rows_from_cols(glrm_handle* h) {
     if (!whole) {
       hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, h->rowidx, nnz, span, (int32_t)r0, (int32_t)r1, blk);
       if (hipMemcpyAsync(cnts.data(), blk, (size_t)nblk * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return cleanup(fail(GLRM_ERR_HIP, "row-range count failed"));
+        return fail(GLRM_ERR_HIP, "row-range count failed");
       unsigned long long run = 0;
       for (auto& v : cnts) { const unsigned long long x = v; v = run; run += x; }
-      if ((int64_t)run != cnt) return cleanup(fail(GLRM_ERR_HIP, "row-range count disagrees with the row pointers (%llu vs %lld)", run, (long long)cnt));
-      if (hipMemcpyAsync(blk, cnts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "row-range offsets failed"));
+      if ((int64_t)run != cnt) return fail(GLRM_ERR_HIP, "row-range count disagrees with the row pointers (%llu vs %lld)", run, (long long)cnt);
+      if (hipMemcpyAsync(blk, cnts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, st) != hipSuccess) return fail(GLRM_ERR_HIP, "row-range offsets failed");
       lap("range count");
       hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, h->rowidx, nnz, span, (int32_t)r0, (int32_t)r1, blk, k0, gpos);
       keys = k0;
@@ -191,11 +186,11 @@ int glrm_rows_from_cols(glrm_handle* h) {
     hipLaunchKernelGGL(iota_u32_kernel, dim3(4096), dim3(256), 0, st, p0, cnt);
     size_t b2 = bytes;
     if (hipcub::DeviceRadixSort::SortPairs(tmp, b2, keys, k1, p0, p1, (int)cnt, 0, bits, st) != hipSuccess) // stable: a row's entries keep their column order
-      return cleanup(fail(GLRM_ERR_HIP, "radix sort failed"));
+      return fail(GLRM_ERR_HIP, "radix sort failed");
     lap("sort");
     hipLaunchKernelGGL(gather_rows_kernel, dim3(8192), dim3(256), 0, st, p1, whole ? nullptr : gpos, cnt, h->colptr, n, h->colvals, h->colidx + at, h->rowvals + at);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return cleanup(fail(GLRM_ERR_HIP, "row view kernels failed")); // cnts is reused
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "row view kernels failed"); // cnts is reused
     lap("gather");
   }
-  return cleanup(GLRM_OK);
+  return GLRM_OK;
 }
