@@ -62,47 +62,47 @@ static __global__ void __launch_bounds__(256) suppos_kernel(const int64_t* ptr, 
 // the last one 38.8 -> 33.9 us), Y half-step 118.0 -> 114.1 ms, iteration 192.9 -> 188.8 ms; the L2 hit rate hardly moves (0.29 -> 0.29 / 0.30
 // -> 0.31).  Changes no sum.
 static int build_suppos(glrm_handle* h, int side) {
-  glrm_handle::PassBuffers& b = h->pass[side];
+  const glrm_handle::Side& v = h->side[side];
+  glrm_handle::PassBuffers& b = h->side[side].pass;
   const int mode = env_int("GLRM_HIP_BLOCKED_SUPPOS", 1);
-  const int64_t nseg = side == 0 ? h->ml : h->nl, nnz = side == 0 ? h->nnz_r : h->nnz_c, cells = nseg * b.nsup;
+  const int64_t nseg = v.nseg, nnz = v.nnz, cells = nseg * b.nsup;
   const bool fits = (double)cells * 4.0 * 16.0 <= 12.0 * (double)nnz;
   const bool build = mode != 0 && cells > 0 && (fits || mode >= 2);
   if (build) {
     unsigned int too_long = 0;
     if (const int rc = h->mem.alloc(&b.suppos, (size_t)cells)) return rc;
     HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-    hipLaunchKernelGGL(suppos_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, side == 0 ? h->rowptr : h->colptr,
-                       side == 0 ? h->colidx : h->rowidx, nseg, b.nsup, (int64_t)b.tiles_per_sup * glrm_tile_rows(h->kp), b.suppos, h->nactive);
+    hipLaunchKernelGGL(suppos_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, v.ptr, v.idx, nseg, b.nsup, (int64_t)b.tiles_per_sup * glrm_tile_rows(h->kp), b.suppos, h->nactive);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(&too_long, h->nactive, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    if (too_long) return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: a %s holds 2^31 observations or more", side == 0 ? "row" : "column");
+    if (too_long) return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: a %s holds 2^31 observations or more", side == GLRM_ROWS ? "row" : "column");
   }
   if (env_int("GLRM_HIP_BLOCKED_TRACE", 0))
-    fprintf(stderr, "[glrm blocked] %s view: %d super-tiles x %lld segments, start table %s (%.1f MB, lists %.1f MB)\n", side == 0 ? "row" : "column", b.nsup,
+    fprintf(stderr, "[glrm blocked] %s view: %d super-tiles x %lld segments, start table %s (%.1f MB, lists %.1f MB)\n", side == GLRM_ROWS ? "row" : "column", b.nsup,
             (long long)nseg, build ? "built" : (mode == 0 ? "off: the passes search" : "over 1/16 of the lists: the passes search"), (double)cells * 4e-6, 12e-6 * (double)nnz);
   return GLRM_OK;
 }
 
 int glrm_setup_blocked(glrm_handle* h) {
-  h->blocked_row = h->blocked_col = 0;
+  for (glrm_handle::Side& v : h->side) v.blocked = 0;
   const int want = env_int("GLRM_HIP_BLOCKED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
   if (want == 0 || h->kp < 8) return GLRM_OK;
   hipDeviceProp_t prop;
   HIPCK(hipGetDeviceProperties(&prop, h->device));
   const int64_t cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   const int T = glrm_tile_rows(h->kp);
-  auto decide = [&](bool rows) -> bool {
+  auto decide = [&](int side) -> bool {
     // Everything below is read from the WHOLE problem (m, n, k, glrm_signature, options), never from the shard, so that every
     // shard count runs the same family (the families differ in summation order).
-    if (rows ? h->tiled_row : h->tiled_col) return false;          // the LDS-tiled sweep already owns this view
-    if (rows && h->cached_want) return false;                      // the short rows run on the cached sweep (glrm_cached.hip)
-    if (!(rows ? h->rows_sorted : h->cols_sorted)) return false;   // a group must meet the opposing factor front to back
-    const int64_t nnz = rows ? h->sig.nnz_rows : h->sig.nnz_cols, nopp = rows ? h->n : h->m;
+    if (h->side[side].tiled) return false;         // the LDS-tiled sweep already owns this view
+    if (side == GLRM_ROWS && h->cached_want) return false;                      // the short rows run on the cached sweep (glrm_cached.hip)
+    if (!h->side[side].sorted) return false;   // a group must meet the opposing factor front to back
+    const int64_t nnz = side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols, nopp = h->side[side ^ 1].nglob;
     if (nnz <= 0) return false;
-    if (want > 0) return ((want >> (rows ? 0 : 1)) & 1) != 0;
+    if (want > 0) return ((want >> side) & 1) != 0;
     const double opp_bytes = (double)nopp * h->kp * 8;
-    const int64_t nseg_glob = rows ? h->m : h->n;
+    const int64_t nseg_glob = h->side[side].nglob;
     const double mean_len = (double)nnz / (double)nseg_glob;
     if (opp_bytes <= 32.0 * 1024 * 1024 || mean_len * (double)nseg_glob < 2e8) return false; // small factor: LDS tiles or plain L2 hits do better
     // observations that meet one vector of the opposing factor while the groups the chip holds (4 waves per SIMD) walk past it, per XCD
@@ -110,29 +110,28 @@ int glrm_setup_blocked(glrm_handle* h) {
     const double reuse = resident * mean_len / (double)nopp / 8.0;
     return reuse >= 2.0;
   };
-  const bool br = decide(true), bc = decide(false);
+  const bool blocked[2] = {decide(GLRM_ROWS), decide(GLRM_COLS)};
   int rc;
-  auto buffers = [&](int side, int64_t nopp) { // super-tile geometry and pass buffers of one side
+  auto buffers = [&](int side) { // super-tile geometry and pass buffers of one side
+    const int64_t nopp = h->side[side ^ 1].nglob;
     const int64_t ntiles = (nopp + T - 1) / T;
     int64_t t = ((int64_t)128 * 1024 * 1024) / ((int64_t)T * h->kp * 8); // ~128 MB of the opposing factor per super-tile
     t = env_int("GLRM_HIP_BLOCKED_TPS", (int)(t < 1 ? 1 : t));
     // the passes address an observation's vector by a 32-bit byte offset from the first row of its super-tile (tiled_pass, L2 = true)
     if ((double)std::min<int64_t>(t * T, nopp) * h->kp * 8 >= 4294967296.0)
       return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: GLRM_HIP_BLOCKED_TPS=%lld makes a super-tile of 4 GiB or more of the opposing factor", (long long)t);
-    h->pass[side].tiles_per_sup = (int)t;
-    h->pass[side].nsup = (int)((ntiles + t - 1) / t);
+    h->side[side].pass.tiles_per_sup = (int)t;
+    h->side[side].pass.nsup = (int)((ntiles + t - 1) / t);
     return glrm_alloc_pass_buffers(h, side);
   };
-  if (br) {
-    if ((rc = buffers(0, h->n))) return rc;
-    if ((rc = build_suppos(h, 0))) return rc;
-    h->blocked_row = 1;
+  for (int s = 0; s < 2; ++s) {
+    if (!blocked[s]) continue;
+    if ((rc = buffers(s))) return rc;
+    if ((rc = build_suppos(h, s))) return rc;
+    h->side[s].blocked = 1;
   }
-  if (bc) {
-    if ((rc = buffers(1, h->m))) return rc;
-    if ((rc = build_suppos(h, 1))) return rc;
-    HIPCK(hipMemsetAsync(h->pass[1].active, 0, (size_t)(h->nl > 0 ? h->nl : 1) * 4, h->stream)); // diverted columns are never touched by col_reduce: they must read "not searching"
-    h->blocked_col = 1;
+  if (blocked[GLRM_COLS]) { // columns only: the diverted long columns
+    HIPCK(hipMemsetAsync(h->side[GLRM_COLS].pass.active, 0, (size_t)(h->side[GLRM_COLS].nseg > 0 ? h->side[GLRM_COLS].nseg : 1) * 4, h->stream)); // diverted columns are never touched by col_reduce: they must read "not searching"
     // Skewed column lengths (power-law Omega; round 5).  A launch covers one super-tile x a slice of the columns, one lane group per column:
     // a column 100 x the mean keeps its group walking 100 x longer than the others of its launch, alone and latency bound (C4 recipe with
     // Zipf degrees: Y half-step 2.6 s against 0.13 s).  (i) The passes hand the columns out LONGEST FIRST, so the groups of a slice walk
@@ -146,10 +145,10 @@ int glrm_setup_blocked(glrm_handle* h) {
     const int64_t mean_len = h->sig.nnz_cols / (h->n > 0 ? h->n : 1);
     h->blk_long_from = env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0) > 0 ? env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0)
                                                                      : std::max<int64_t>(4096, 2 * mean_len);
-    if (h->nl > 0 && h->blk_long_from > 0) {
+    if (h->side[GLRM_COLS].nseg > 0 && h->blk_long_from > 0) {
       std::vector<int64_t> ptr;
       std::vector<int32_t> shortl, longl;
-      if ((rc = glrm_host_ptr(h, false, ptr))) return rc;
+      if ((rc = glrm_host_ptr(h, GLRM_COLS, ptr))) return rc;
       glrm_split_by_length(ptr, h->blk_long_from, shortl, longl);
       h->blk_nshort_c = (int64_t)shortl.size();
       if ((rc = glrm_upload_list(h, shortl, &h->blk_perm_c))) return rc;
@@ -179,13 +178,13 @@ static int64_t slice_capacity(K kernel, int device, int spb) {
 }
 
 template <int G, int R, int LOSS, bool GRAD>
-static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
+static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
   constexpr int KP = G * R, T = glrm_tile_rows(KP), SPB = BNW * (64 / G);
   auto kernel = tiled_col_pass_kernel<G, R, BNW, T, LOSS, GRAD, true>;
   // per handle, view and pass kind: the row passes (LOSS_PER_OBS* instantiations of a heterogeneous model) and the column passes
   // (LOSS_SEGMENT*) of one handle are different kernels with their own occupancy; the CU count is the handle's device's, the fill
   // percentage the environment's at the handle's first sweep
-  int64_t& cap_slot = h->blocked_cap[rows ? 0 : 1][GRAD ? 0 : 1];
+  int64_t& cap_slot = h->side[side].blocked_cap[GRAD ? 0 : 1];
   if (cap_slot == 0) cap_slot = slice_capacity(kernel, h->device, SPB);
   const int64_t cap = cap_slot;
   // phase gate in rows of the opposing factor (tiled_pass, L2 = true): read at every pass, so that one handle can be timed under several
@@ -200,7 +199,7 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
   // glrm_hip_step_y_arrival: the gradient pass of the column view walks the super-tiles in the order their rows of X arrive, each behind
   // the events of the blocks it touches (h->sup_order, glrm_run_blocked); the partial sums are per (segment, super-tile) and col_reduce
   // adds them in super-tile order, so the launch order changes no bit
-  const bool ordered = GRAD && !rows && h->n_arrival > 0 && (int)h->sup_order.size() == a.nsup;
+  const bool ordered = GRAD && side == GLRM_COLS && h->n_arrival > 0 && (int)h->sup_order.size() == a.nsup;
   const int64_t rows_per_sup = (int64_t)a.tiles_per_sup * T;
   auto launch_sup = [&](int sup) -> int { // one super-tile: behind the events of the blocks it touches (ordered), slice by slice
     if (ordered) {
@@ -273,12 +272,12 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, bool rows) {
 }
 
 
-static int launch_blocked(glrm_handle* h, int loss, bool grad, const TiledArgs& a, bool rows) {
+static int launch_blocked(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side) {
   auto by_layout = [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     auto by_loss = [&](auto LOSS) {
       constexpr int L = decltype(LOSS)::value;
-      return grad ? launch_blocked_inst<G, R, L, true>(h, a, rows) : launch_blocked_inst<G, R, L, false>(h, a, rows);
+      return grad ? launch_blocked_inst<G, R, L, true>(h, a, side) : launch_blocked_inst<G, R, L, false>(h, a, side);
     };
     return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
   };
@@ -286,13 +285,13 @@ static int launch_blocked(glrm_handle* h, int loss, bool grad, const TiledArgs& 
                                                   [&] { return fail(GLRM_ERR_UNSUPPORTED, "no phase-aligned pass kernel for lane layout G=%d R=%d", h->G, h->R); });
 }
 
-int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
+int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
   TiledArgs a{};
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
   a.loss_by_segment = loss_by_segment;
-  const bool range = rows && h->rng_e >= 0; // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-  glrm_bind_pass_buffers(a, h, rows ? 0 : 1, range ? h->rng_b : 0);
-  if (!rows && h->blk_perm_c) { // length-sorted slots; the columns at or above long_from run on the gather sweep (run_sweep, glrm_hip.hip)
+  const bool range = side == GLRM_ROWS && h->rng_e >= 0; // glrm_hip_step_x_range: local rows [rng_b, rng_e)
+  glrm_bind_pass_buffers(a, h, side, range ? h->rng_b : 0);
+  if (side == GLRM_COLS && h->blk_perm_c) { // length-sorted slots; the columns at or above long_from run on the gather sweep (run_sweep, glrm_hip.hip)
     a.segperm = h->blk_perm_c;
     a.npass = h->blk_nshort_c;
     a.long_from = h->blk_long_from;
@@ -308,7 +307,7 @@ int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, d
   int rc;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   h->sup_order.clear();
-  if (!rows && h->n_arrival > 0 && !eval_only) {
+  if (side == GLRM_COLS && h->n_arrival > 0 && !eval_only) {
     // a super-tile can run once the LAST (in the host's order) of the blocks it touches is there: sort the super-tiles by that position
     const int64_t rows_per_sup = (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp);
     std::vector<std::pair<int, int>> key((size_t)a.nsup);
@@ -322,12 +321,12 @@ int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, d
     std::sort(key.begin(), key.end());
     for (auto& kv : key) h->sup_order.push_back(kv.second);
   }
-  if ((rc = launch_blocked(h, loss, true, a, rows))) return rc;  // gradient + loss partials, super-tile by super-tile
+  if ((rc = launch_blocked(h, loss, true, a, side))) return rc;  // gradient + loss partials, super-tile by super-tile
   glrm_launch_col_small(h->kp, 0, a, h->stream);                 // reduce in super-tile order, J_old, first trial point
   HIPCK(hipGetLastError());
   if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
   return glrm_run_rounds(
       h, a, min_stepsize, glrm_act_lists{},
-      [&](int, unsigned int, int32_t*) { return launch_blocked(h, loss, false, a, rows); },  // loss partials at the trial points of the searching segments
+      [&](int, unsigned int, int32_t*) { return launch_blocked(h, loss, false, a, side); },  // loss partials at the trial points of the searching segments
       [&](const TiledArgs& d) { glrm_launch_col_small(h->kp, 1, d, h->stream); });           // accept / shrink / give up, next trial point
 }

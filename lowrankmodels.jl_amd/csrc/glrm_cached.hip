@@ -236,7 +236,7 @@ int launch_inst(const CachedArgs& a, hipStream_t st) {
 int glrm_setup_cached(glrm_handle* h) {
   h->cached_row = h->cached_want = 0;
   const int want = env_int("GLRM_HIP_CACHED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, 0 off, 1 wherever the rows fit
-  if (want == 0 || h->tiled_row || h->sig.nnz_rows <= 0) return GLRM_OK;
+  if (want == 0 || h->side[GLRM_ROWS].tiled || h->sig.nnz_rows <= 0) return GLRM_OK;
   if (!((h->G == 4 || h->G == 8) && h->R == 8)) return GLRM_OK;
   if (want < 0) {
     if (h->storage == GLRM_STORAGE_F32 && !GLRM_CACHED_F32_AUTO) return GLRM_OK;
@@ -258,8 +258,8 @@ int glrm_cached_variant(const glrm_handle* h) {
 int glrm_cached_waves(const glrm_handle* h) { return h->storage == GLRM_STORAGE_F32 ? 2 : env_int("GLRM_HIP_CACHED_WAVES", 2); }
 
 // longest row the cached sweep takes
-int64_t glrm_cached_maxlen(const glrm_handle* h) {
-  if (h->cached_row == 2) return glrm_cached_reg_maxlen(h->G);
+int64_t glrm_cached_maxlen(const glrm_handle* h, int variant) {
+  if (variant == 2) return glrm_cached_reg_maxlen(h->G);
   const int vpi = 64 / (h->kp * 8 / 16);
   const int64_t budget = env_int("GLRM_HIP_CACHED", -1) > 0 ? 160 * 1024 : 53 * 1024; // auto: three waves per CU
   return budget / (h->kp * 8 + 12) / vpi * vpi;
@@ -280,10 +280,10 @@ void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen) {
 // seglist == nullptr: every local row (restricted to the range of glrm_hip_step_x_range, if one is set); otherwise the rows listed
 int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st) {
   CachedArgs a{};
-  glrm_fill_side(a, h, true, min_stepsize, 0);
+  glrm_fill_side(a, h, GLRM_ROWS, min_stepsize, 0);
   a.cap = h->cached_cap;
   a.seg_lo = 0;
-  a.seg_hi = h->ml;
+  a.seg_hi = h->side[GLRM_ROWS].nseg;
   if (seglist) {
     a.seglist = seglist;
     a.nseg = nlist;

@@ -46,14 +46,14 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   if (p->dense_ld < need_ld) return fail(GLRM_ERR_INVALID, "dense_ld is smaller than the matrix dimension");
   h->dense = true;
   h->dense_scale = p->losses[0].scale;
-  h->nnz_r = h->ml * h->n;
-  h->nnz_c = h->nl * h->m;
+  h->side[GLRM_ROWS].nnz = h->side[GLRM_ROWS].nseg * h->n;
+  h->side[GLRM_COLS].nnz = h->side[GLRM_COLS].nseg * h->m;
   // Bring the caller's matrix to the device if needed.  Whole problem on this handle: one upload, both packed views come from it.
   // A shard of a multi-GPU fit only needs its row block (for the X half-step) and its column block (for the Y half-step): those
   // two sub-matrices are uploaded one after the other (2D copies), never the whole matrix -- at C3 on 8 GPUs 10 + 10 GB per
   // device instead of 80 GB.  The NaN check (src/glrm.jl:63-71) covers the shard's row block; the row blocks partition A.
   const bool on_dev = (p->flags & GLRM_PROBLEM_DEVICE_ARRAYS) != 0;
-  const bool whole = h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n;
+  const bool whole = h->side[GLRM_ROWS].begin == 0 && h->side[GLRM_ROWS].end == h->m && h->side[GLRM_COLS].begin == 0 && h->side[GLRM_COLS].end == h->n;
   const int cm = p->dense_colmajor ? 1 : 0;
   const int64_t ld = p->dense_ld;
   if (!on_dev) { // walk along the contiguous dimension of the caller's storage order (column-major: what the Julia shim passes)
@@ -62,11 +62,11 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
     if (cm) {
       for (int64_t j = 0; j < h->n && !bad; ++j) {
         const double* col = p->dense_A + j * ld;
-        for (int64_t i = h->rb; i < h->re; ++i)
+        for (int64_t i = h->side[GLRM_ROWS].begin; i < h->side[GLRM_ROWS].end; ++i)
           if (std::isnan(col[i])) { bad = true; bi = i; bj = j; break; }
       }
     } else {
-      for (int64_t i = h->rb; i < h->re && !bad; ++i) {
+      for (int64_t i = h->side[GLRM_ROWS].begin; i < h->side[GLRM_ROWS].end && !bad; ++i) {
         const double* row = p->dense_A + i * ld;
         for (int64_t j = 0; j < h->n; ++j)
           if (std::isnan(row[j])) { bad = true; bi = i; bj = j; break; }
@@ -77,8 +77,7 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
   int rc = GLRM_OK;
   DevArena scratch; // the staged upload of the caller's host matrix
   if (on_dev) {
-    rc = pack_view(h, p->dense_A, ld, cm, 0, h->rb, h->ml, h->n, &h->Arow, &h->lda_r);
-    if (!rc) rc = pack_view(h, p->dense_A, ld, cm, 1, h->cb, h->nl, h->m, &h->Acol, &h->lda_c);
+    for (int s = 0; s < 2 && !rc; ++s) rc = pack_view(h, p->dense_A, ld, cm, s, h->side[s].begin, h->side[s].nseg, h->side[s ^ 1].nglob, &h->side[s].A, &h->side[s].lda);
     if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GLRM_ERR_HIP, "dense pack failed");
   } else if (whole) {
     double* tmp = nullptr;
@@ -86,17 +85,17 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
     if ((rc = scratch.alloc(&tmp, runs * run))) return rc;
     if (hipMemcpy2DAsync(tmp, run * 8, p->dense_A, (size_t)ld * 8, run * 8, runs, hipMemcpyHostToDevice, h->stream) != hipSuccess)
       rc = fail(GLRM_ERR_HIP, "upload of the dense matrix failed");
-    if (!rc) rc = pack_view(h, tmp, (int64_t)run, cm, 0, 0, h->ml, h->n, &h->Arow, &h->lda_r);
-    if (!rc) rc = pack_view(h, tmp, (int64_t)run, cm, 1, 0, h->nl, h->m, &h->Acol, &h->lda_c);
+    for (int s = 0; s < 2 && !rc; ++s) rc = pack_view(h, tmp, (int64_t)run, cm, s, 0, h->side[s].nseg, h->side[s ^ 1].nglob, &h->side[s].A, &h->side[s].lda);
     if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GLRM_ERR_HIP, "dense pack failed");
     scratch.release(&tmp);
   } else {
-    // (which, first segment, segments, extent of the other dimension) for the row block and the column block
-    for (int which = 0; which < 2 && !rc; ++which) {
-      const int64_t s0 = which ? h->cb : h->rb, ns = which ? h->nl : h->ml, other = which ? h->m : h->n;
-      if (ns <= 0) { rc = pack_view(h, p->dense_A, ld, cm, which, 0, 0, other, which ? &h->Acol : &h->Arow, which ? &h->lda_c : &h->lda_r); continue; }
-      // the block as a dense sub-matrix in the caller's own storage order: segments run along the caller's rows (which = 0) / columns
-      const bool seg_is_run = (which == 0) != (cm != 0); // are whole segments contiguous runs of the source?
+    // (first segment, segments, extent of the other dimension) of the row block and of the column block
+    for (int side = 0; side < 2 && !rc; ++side) {
+      glrm_handle::Side& v = h->side[side];
+      const int64_t s0 = v.begin, ns = v.nseg, other = h->side[side ^ 1].nglob;
+      if (ns <= 0) { rc = pack_view(h, p->dense_A, ld, cm, side, 0, 0, other, &v.A, &v.lda); continue; }
+      // the block as a dense sub-matrix in the caller's own storage order: segments run along the caller's rows (row block) / columns
+      const bool seg_is_run = (side == GLRM_ROWS) != (cm != 0); // are whole segments contiguous runs of the source?
       const size_t width = (size_t)(seg_is_run ? other : ns) * 8, height = (size_t)(seg_is_run ? ns : other);
       const double* src = p->dense_A + (seg_is_run ? s0 * ld : s0);
       double* tmp = nullptr;
@@ -104,33 +103,31 @@ int glrm_setup_dense(glrm_handle* h, const glrm_problem* p) {
       if (hipMemcpy2DAsync(tmp, width, src, (size_t)ld * 8, width, height, hipMemcpyHostToDevice, h->stream) != hipSuccess)
         rc = fail(GLRM_ERR_HIP, "upload of the dense block failed");
       // inside tmp the block starts at segment 0 and has leading dimension width / 8
-      if (!rc) rc = pack_view(h, tmp, (int64_t)(width / 8), cm, which, 0, ns, other, which ? &h->Acol : &h->Arow, which ? &h->lda_c : &h->lda_r);
+      if (!rc) rc = pack_view(h, tmp, (int64_t)(width / 8), cm, side, 0, ns, other, &v.A, &v.lda);
       if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GLRM_ERR_HIP, "dense pack failed");
       scratch.release(&tmp);
     }
   }
   if (rc) return rc;
-  pick_sup(h->n, h->pass[0].nsup, h->vps_r);
-  pick_sup(h->m, h->pass[1].nsup, h->vps_c);
-  const int64_t ml1 = h->ml > 0 ? h->ml : 1, nl1 = h->nl > 0 ? h->nl : 1;
-  if ((rc = glrm_alloc_pass_buffers(h, 0))) return rc;
-  if ((rc = glrm_alloc_pass_buffers(h, 1))) return rc;
+  for (int s = 0; s < 2; ++s) pick_sup(h->side[s ^ 1].nglob, h->side[s].pass.nsup, h->side[s].vps);
+  for (int s = 0; s < 2; ++s)
+    if ((rc = glrm_alloc_pass_buffers(h, s))) return rc;
   // glrm_options.quad_gram: line-search trials from the quadratic form, no pass over A per trial
   h->dense_gram = h->opts.quad_gram != 0;
   if (h->dense_gram) {
     if ((rc = h->mem.alloc(&h->gramH, (size_t)h->kp * h->kp))) return rc;
     if ((rc = h->mem.alloc(&h->gram_part, (size_t)GRAM_BLOCKS * h->kp * h->kp))) return rc;
-    if ((rc = h->mem.alloc(&h->jloss_r, (size_t)ml1))) return rc;
-    if ((rc = h->mem.alloc(&h->jloss_c, (size_t)nl1))) return rc;
+    for (glrm_handle::Side& v : h->side)
+      if ((rc = h->mem.alloc(&v.jloss, (size_t)(v.nseg > 0 ? v.nseg : 1)))) return rc;
   }
   return GLRM_OK;
 }
 
-// which = 0: H = other other' (kp x kp); which = 1: the trial objectives of the active segments from the quadratic form
-static void launch_gram(int kp, int which, const TiledArgs& a, const double* other, int64_t n_other, double* part, double* H, double scale, hipStream_t st) {
+// stage 0: H = other other' (kp x kp); stage 1: the trial objectives of the active segments from the quadratic form
+static void launch_gram(int kp, int stage, const TiledArgs& a, const double* other, int64_t n_other, double* part, double* H, double scale, hipStream_t st) {
   auto by_kp = [&](auto kpc) {
     constexpr int KP = decltype(kpc)::value;
-    if (which == 0) {
+    if (stage == 0) {
       hipLaunchKernelGGL((dense_gram_partial_kernel<KP>), dim3(GRAM_BLOCKS), dim3(256), 0, st, other, n_other, part);
       hipLaunchKernelGGL((dense_gram_final_kernel<KP>), dim3((KP * KP + 255) / 256), dim3(256), 0, st, part, H);
     } else {
@@ -161,29 +158,24 @@ static void launch_dense_any(int kp, bool grad, const DenseArgs& a, hipStream_t 
 
 // One half-step on the dense path: pass 1 (residuals, objective, gradient on the matrix cores) -> per-segment
 // reduce + first trial point -> rounds of (trial objective pass, decide) until no segment is still searching.
-int glrm_run_dense(glrm_handle* h, bool rows, double min_stepsize, int eval_only) {
-  const int64_t nseg = rows ? h->ml : h->nl;
-  if (nseg <= 0) return GLRM_OK;
-  DenseArgs d{};
-  d.nseg = nseg;
-  d.xsrc = rows ? h->X : h->Y;
-  d.own_offset = rows ? h->rb : h->cb;
-  d.other = rows ? h->Y : h->X;
-  d.n_other = rows ? h->n : h->m;
-  d.A = rows ? h->Arow : h->Acol;
-  d.lda = rows ? h->lda_r : h->lda_c;
-  d.scale = h->dense_scale;
-  d.vec_per_sup = rows ? h->vps_r : h->vps_c;
+int glrm_run_dense(glrm_handle* h, int side, double min_stepsize, int eval_only) {
+  const glrm_handle::Side& v = h->side[side];
+  if (v.nseg <= 0) return GLRM_OK;
   TiledArgs a{};
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
+  DenseArgs d{}; // the side as the MFMA kernels read it: what `a` says, plus the packed matrix
+  d.nseg = a.nseg; d.xsrc = a.own; d.own_offset = a.own_offset; d.other = a.other;
+  d.n_other = h->side[side ^ 1].nglob;
+  d.A = v.A; d.lda = v.lda; d.vec_per_sup = v.vps;
+  d.scale = h->dense_scale;
   a.ptr = nullptr; // no view: every segment has dense_len observations
   a.dense_len = d.n_other;
-  glrm_bind_pass_buffers(a, h, rows ? 0 : 1);
+  glrm_bind_pass_buffers(a, h, side);
   d.nsup = a.nsup;
   d.part = a.part;
   d.active = a.active;
   const bool gram = h->dense_gram && !eval_only && a.fixed_alpha <= 0.0;
-  a.jloss = gram ? (rows ? h->jloss_r : h->jloss_c) : nullptr;
+  a.jloss = gram ? v.jloss : nullptr;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   if (gram) launch_gram(h->kp, 0, a, d.other, d.n_other, h->gram_part, h->gramH, d.scale, h->stream);
   launch_dense_any(h->kp, true, d, h->stream);

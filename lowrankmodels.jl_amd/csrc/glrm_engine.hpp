@@ -13,6 +13,8 @@
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
+// Below: glrm_handle keeps what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`, the opposing
+// side is side ^ 1); glrm_side_family is the one place that says which kernel family runs a side.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -57,6 +59,9 @@ inline int fail(int code, const char* fmt, ...) {
 
 #include "glrm_devmem.hpp"
 
+// which side of the factorization: glrm_handle::side[] and every `int side` argument are indexed by it; the opposing side is side ^ 1
+enum { GLRM_ROWS = 0, GLRM_COLS = 1 }; // rows = row view, X half-step; columns = column view, Y half-step
+
 struct glrm_handle {
   int device = 0;
   DevArena mem;                       // every device allocation the handle keeps (borrowed arrays never enter it); glrm_hip_destroy releases it
@@ -64,18 +69,14 @@ struct glrm_handle {
   bool own_stream = false;
   int64_t m = 0, n = 0;
   int k = 0, kp = 0, G = 4, R = 2;
-  // LDS-tiled sweeps (glrm_tiled.hpp)
-  bool rows_sorted = false, cols_sorted = false;
   double fixed_alpha = 0.0;           // > 0 while a SparseProxGradParams step (no line search) is being launched
   int64_t rng_b = 0, rng_e = -1;      // row sub-range of the next X sweep (glrm_hip_step_x_range); rng_e < 0 = all
   int tiled_opt = 0;                  // glrm_options.tiled
-  int tiled_row = 0, tiled_col = 0;   // 0 = gather sweep, 1 = tiled
   int tG = 4, tR = 2;                 // lane layout of the tiled kernels (kp = tG*tR)
-  int blocked_row = 0, blocked_col = 0; // phase-aligned gather passes (glrm_blocked.hip) instead of the one-kernel gather sweep
   int tile_rounds = 0;                // LDS-tiled sweeps: line-search rounds over the still-searching segments only (bit0 rows, bit1 columns)
   int32_t* actlist = nullptr;         // two lists of actlist_cap segment ids (glrm_tiled.hpp: TiledArgs::actlist_out / actlist_in)
   int64_t actlist_cap = 0;
-  // per-segment buffers of the multi-pass families (LDS-tiled, lane, phase-aligned, dense), [0] rows, [1] columns: TiledArgs::part ... ntrial
+  // per-segment buffers of the multi-pass families (LDS-tiled, lane, phase-aligned, dense): TiledArgs::part ... ntrial
   // and the super-tile geometry they were sized for (glrm_alloc_pass_buffers / glrm_bind_pass_buffers)
   struct PassBuffers {
     double *part = nullptr, *gsum = nullptr, *trial = nullptr, *jold = nullptr;
@@ -84,35 +85,72 @@ struct glrm_handle {
     // phase-aligned passes (glrm_blocked.hip).  suppos[seg * nsup + sup]: offset inside segment seg's list of its first entry of super-tile
     // sup (what the pass kernel's search would find; nullptr = the kernel searches)
     int32_t* suppos = nullptr;
-  } pass[2];
+  };
+  // Everything that exists once per view: side[GLRM_ROWS] is the row view and the X half-step, side[GLRM_COLS] the column view and the Y
+  // half-step.  A "segment" is a row of the one and a column of the other.
+  struct Side {
+    // range and size: global segments [begin, end) of nglob (= m / n) are this shard's, nseg = end - begin, nnz observations
+    int64_t begin = 0, end = 0, nseg = 0, nglob = 0, nnz = 0;
+    // the view: segment offsets, opposing index and value of every observation
+    // (GLRM_PROBLEM_BORROW_DEVICE_ARRAYS: these arrays are the caller's -- not in `mem`, never freed, never written by the engine -- until
+    // a view has to be reordered: the private copy then replaces the borrowed pointer)
+    int64_t* ptr = nullptr; int32_t* idx = nullptr; double* vals = nullptr;
+    bool sorted = false;              // LDS-tiled sweeps (glrm_tiled.hpp): every list is in tile order
+    int32_t* perm = nullptr;          // tiled sweeps: segments sorted by length (columns: by (loss kind, length))
+    // regularizer descriptors (rx / ry): device, count, host copy (what glrm_hip_subset needs to build a child handle)
+    glrm_reg* regs = nullptr; int64_t n_regs = 0; std::vector<glrm_reg> regs_h;
+    bool vecreg = false;              // some descriptor of this side is a vector regularizer (kind >= GLRM_REG_QUAD_CONSTRAINT): VR kernels
+    // regularizers that carry a vector (include/glrm_hip_regvec.h, glrm_regvec.hip): nullptr / empty while the side has none.
+    // regvec: k x count doubles (ld k), reglen: count lengths, indexed like regs; regs_h then holds the descriptors WITH the new codes
+    double* regvec = nullptr; int32_t* reglen = nullptr;
+    std::vector<double> regvec_h; std::vector<int32_t> reglen_h;
+    // per-segment state.  factor / obj are in use (bound or owned), own_factor / own_obj owned; factor is X / Y (GLRM_STORAGE_F32: it, like
+    // vals, holds FLOATS behind the double* type, see glrm_handle::storage), obj is obj_by_row / obj_by_col
+    double* alpha = nullptr;
+    int32_t *trials = nullptr, *accepts = nullptr;
+    double *factor = nullptr, *own_factor = nullptr, *obj = nullptr, *own_obj = nullptr;
+    // family state
+    int tiled = 0;                    // 0 = gather sweep, 1 = LDS-tiled
+    int blocked = 0;                  // phase-aligned gather passes (glrm_blocked.hip) instead of the one-kernel gather sweep
+    // lane-per-segment LDS-tiled passes (glrm_lane.hpp): family flag and the SELL layout of the view
+    int lane = 0;
+    int64_t* lane_bptr = nullptr; int32_t* lane_off = nullptr; double* lane_val = nullptr;
+    int64_t lane_nwb = 0, lane_steps = 0; int lane_ntiles = 0;
+    uint16_t* lane_off16 = nullptr; int64_t* lane_vptr = nullptr; int32_t* lane_sval = nullptr; // the compact form of the stream (glrm_lane.hpp: LaneArgs::off16 / vptr) of the sides that run it
+    int lane_dealt = 0;               // the side's sorted slot permutation was dealt out by class (make_segperm): slot s holds a segment of class s & 15
+    int32_t* lane_inv = nullptr;      // local segment -> slot of the layout (sides whose slots are permuted); -1 = not in the layout
+    PassBuffers pass;
+    int64_t blocked_cap[2] = {0, 0};  // phase-aligned passes: segments per launch slice, [gradient / trial instantiation]
+    // Gather sweeps: the waves that share a segment are a function of the segment's OWN length (1 below 1536 observations, 4 below
+    // 98304, else 8; glrm_options.waves_* pins one count for all), so the order of a segment's sums never depends on which shard
+    // holds it.  Class 0 = rows the cached sweep holds on chip.  ncls counts the local segments per class; when more than one class
+    // is populated seglist lists the segments class by class (ascending ids inside a class) and each class gets its own launch.
+    int waves = 1;                    // the class most local segments fall into (reported by glrm_hip_kernel_stats); columns start at 4
+    int32_t* seglist = nullptr; int64_t ncls[4] = {0, 0, 0, 0};
+    // dense MFMA path (glrm_dense.hip)
+    double* A = nullptr; int64_t lda = 0; // packed, zero padded: [nseg_pad][lda]
+    int64_t vps = 0;                  // opposing vectors per super-tile
+    double* jloss = nullptr;          // loss sum at the current point, per local segment
+    int64_t launches = 0; double ms = 0; // counters of glrm_hip_kernel_stats
+  } side[2];
+  glrm_handle() { side[GLRM_COLS].waves = 4; }
   unsigned int* nactive = nullptr;    // segments still searching (one counter: a half-step at a time)
   int* dflag = nullptr;
-  uint8_t* rowdescid = nullptr;       // heterogeneous tiled row sweep: id of the loss descriptor of every entry of the row view
+  // rows only: the heterogeneous tiled row sweep
+  uint8_t* rowdescid = nullptr;       // id of the loss descriptor of every entry of the row view
   glrm_loss* udesc = nullptr;         // the model's distinct loss descriptors (<= 256), device
   int n_udesc = 0;
-  int32_t *colperm = nullptr, *rowperm = nullptr; // tiled sweeps: segments sorted by (loss kind, length) / by length
-  // lane-per-segment LDS-tiled passes (glrm_lane.hpp), [0] rows, [1] columns: family flag and the SELL layout of the view
-  int lane[2] = {0, 0};
-  int64_t* lane_bptr[2] = {nullptr, nullptr};
-  int32_t* lane_off[2] = {nullptr, nullptr};
-  double* lane_val[2] = {nullptr, nullptr};
-  int64_t lane_nwb[2] = {0, 0}, lane_steps[2] = {0, 0};
-  int lane_ntiles[2] = {0, 0};
-  uint16_t* lane_off16[2] = {nullptr, nullptr}; // the compact form of the stream (glrm_lane.hpp: LaneArgs::off16 / vptr) of the sides that run it
-  int64_t* lane_vptr[2] = {nullptr, nullptr};
-  int32_t* lane_sval[2] = {nullptr, nullptr};
-  int lane_dealt[2] = {0, 0};                    // the side's sorted slot permutation was dealt out by class (make_segperm): slot s holds a segment of class s & 15
-  int32_t* lane_inv[2] = {nullptr, nullptr};   // local segment -> slot of the layout (sides whose slots are permuted); -1 = not in the layout
   // trial rounds read out of the SELL layout (lane_pass_kernel FORM 2): the still-searching segments class by class, rebuilt every round
   int32_t *lane_gcnt = nullptr, *lane_gbase = nullptr, *lane_gtotal = nullptr, *lane_glist = nullptr;
   int64_t lane_gcap = 0, lane_gchunks = 0;
   // general sweeps: multi-dimensional losses / wrapped regularizers (glrm_multi.hip)
   bool multi = false;
+  // columns only: the embedding of Y and the split Y half-step of the general sweeps
   int64_t d = 0;                      // vectors of Y = sum of embedding dimensions (= n for scalar losses)
   int dmax = 1;
   int multi_kmask = 0;                // loss kinds of the model: bit `kind` per multi-dimensional kind, bit 0 = some scalar loss (glrm_multi.hpp: MULTI_KM_*)
   int64_t* ystart = nullptr;          // device, n+1
-  int64_t ys_cb = 0;                  // ystart[cb]: first vector of the shard's column block
+  int64_t ys_cb = 0;                  // ystart[side[GLRM_COLS].begin]: first vector of the shard's column block
   int col_nsplit = 1;                 // > 1: the Y half-step runs as split passes + decide rounds
   int64_t col_chunk = 0;
   double *mtrial = nullptr, *mpart_loss = nullptr, *mpart_G = nullptr, *mgtot = nullptr, *mobjold = nullptr;
@@ -120,57 +158,34 @@ struct glrm_handle {
   unsigned int* mnactive = nullptr;
   // dense MFMA path (glrm_dense.hip)
   bool dense = false;
-  double *Arow = nullptr, *Acol = nullptr; // packed, zero padded: [ml_pad][lda_r], [nl_pad][lda_c]
-  int64_t lda_r = 0, lda_c = 0;
   double dense_scale = 1.0;
-  int64_t vps_r = 0, vps_c = 0;           // opposing vectors per super-tile
+  // rows only: the cached gather row sweep
   int cached_row = 0, cached_cap = 0; // cached gather row sweep (glrm_cached.hip): 0 off, 1 LDS, 2 registers; trips / vectors a row may have
   int cached_want = 0;                // the whole problem runs its short rows on the cached sweep (decided from glrm_signature, never from the shard)
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]
-  double *jloss_r = nullptr, *jloss_c = nullptr; // loss sum at the current point, per local segment
-  int64_t rb = 0, re = 0, cb = 0, ce = 0, ml = 0, nl = 0, nnz_r = 0, nnz_c = 0;
-  int64_t *rowptr = nullptr, *colptr = nullptr;
-  int32_t *colidx = nullptr, *rowidx = nullptr;
-  double *rowvals = nullptr, *colvals = nullptr;
-  // (GLRM_PROBLEM_BORROW_DEVICE_ARRAYS: the arrays above are the caller's -- not in `mem`, never freed, never written by the engine -- until
-  // a view has to be reordered: the private copy then replaces the borrowed pointer)
   glrm_loss* losses = nullptr;
   int64_t n_losses = 0;
   bool loss_quad_uniform = false;
   bool has_trig = false; // some column carries a PeriodicLoss
-  glrm_reg *rx = nullptr, *ry = nullptr;
-  int64_t n_rx = 0, n_ry = 0;
-  double *alpharow = nullptr, *alphacol = nullptr;
-  double *X = nullptr, *Y = nullptr, *objcol = nullptr, *objrow = nullptr;             // in use (bound or owned)
-  double *oX = nullptr, *oY = nullptr, *oobjcol = nullptr, *oobjrow = nullptr;         // owned
   double *partials = nullptr, *dscalar = nullptr;
   unsigned long long* dcount = nullptr;
-  int32_t *trials_r = nullptr, *accepts_r = nullptr, *trials_c = nullptr, *accepts_c = nullptr;
-  // Gather sweeps: the waves that share a segment are a function of the segment's OWN length (1 below 1536 observations, 4 below
-  // 98304, else 8; glrm_options.waves_* pins one count for all), so the order of a segment's sums never depends on which shard
-  // holds it.  Class 0 = rows the cached sweep holds on chip.  ncls_* counts the local segments per class; when more than one class
-  // is populated seglist_* lists the segments class by class (ascending ids inside a class) and each class gets its own launch.
-  int waves_row = 1, waves_col = 4;   // the class most local segments fall into (reported by glrm_hip_kernel_stats)
-  int32_t *seglist_r = nullptr, *seglist_c = nullptr;
-  int64_t ncls_r[4] = {0, 0, 0, 0}, ncls_c[4] = {0, 0, 0, 0};
   bool finalized = false;             // false between a GLRM_PROBLEM_DEFER_SETUP create and glrm_hip_finalize
   bool finalize_failed = false;       // glrm_hip_finalize ran and failed half way: the handle can only be destroyed
-  // launch geometry of the persistent / sliced kernels, per handle (device and fill percentage at finalize; a process may drive devices
-  // with different CU counts, and the knobs are read per handle): 0 = not computed yet
-  // phase-aligned column passes on skewed data: slot -> column for the passes (columns below blk_long_from observations, longest
-  // first), the columns at or above it (8-wave gather sweep on the side stream), and the threshold (from the WHOLE problem's mean)
+  // columns only.  Phase-aligned column passes on skewed data: slot -> column for the passes (columns below blk_long_from observations,
+  // longest first), the columns at or above it (8-wave gather sweep on the side stream), and the threshold (from the WHOLE problem's mean)
   int32_t *blk_perm_c = nullptr, *blk_long_c = nullptr;
   int64_t blk_nshort_c = 0, blk_nlong_c = 0, blk_long_from = 0;
-  int64_t blocked_cap[2][2] = {{0, 0}, {0, 0}}; // phase-aligned passes: segments per launch slice, [row / column view][gradient / trial instantiation]
+  // launch geometry of the persistent / sliced kernels, per handle (device and fill percentage at finalize; a process may drive devices
+  // with different CU counts, and the knobs are read per handle): 0 = not computed yet
   int cached_grid[6] = {0, 0, 0, 0, 0, 0}; // persistent cached row sweep: resident workgroups of the MAXT = 7 / 4 instantiation; [2], [3]: of their VR = true twins; [4], [5]: of the float ones
   glrm_signature sig_local{}, sig{};  // this shard's contribution / the whole problem's
   hipStream_t side_stream = nullptr;  // the launches of the minority classes run beside the main launch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int profile = 0;
-  // glrm_hip_step_y_arrival: the blocks of X that are still arriving (valid during that call only), which of them the launch stream has
-  // already been made to wait for, and -- phase-aligned column passes -- the order in which the gradient pass walks the super-tiles
+  // columns only.  glrm_hip_step_y_arrival: the blocks of X that are still arriving (valid during that call only), which of them the launch
+  // stream has already been made to wait for, and -- phase-aligned column passes -- the order in which the gradient pass walks the super-tiles
   const glrm_arrival* arrival = nullptr;
   int n_arrival = 0;
   std::vector<char> arrival_waited;
@@ -178,7 +193,7 @@ struct glrm_handle {
   std::vector<int> sup_order;
   double ms_wait = 0;                 // profile: time the launch stream stood in those waits
   int sum_order_opt = 0;              // glrm_options.sum_order (1: reference-order validation sweeps, glrm_reforder.hip)
-  // glrm_options.storage.  GLRM_STORAGE_F32: rowvals / colvals / X / Y / oX / oY below hold FLOATS behind their double* type (the same
+  // glrm_options.storage.  GLRM_STORAGE_F32: Side::vals / factor / own_factor hold FLOATS behind their double* type (the same
   // element counts); only the float gather sweeps, the float cached row sweep (glrm_cached_f32.hip) and the copy kernels of
   // glrm_storage.hip read them, every other family is refused.
   int storage = 0;
@@ -188,29 +203,33 @@ struct glrm_handle {
   double* pinned_obj = nullptr;       // host-pinned scalar the graph copies sum(obj_by_col) into
   int64_t graph_ix = 0, graph_iy = 0; // inner iteration counts the graph was captured for
   double graph_min = 0.0, graph_step = 0.0;
-  // what glrm_hip_subset needs to build a child handle: the options and host copies of the descriptors
+  // what glrm_hip_subset needs to build a child handle: the options and host copies of the descriptors (Side::regs_h)
   glrm_options opts{};
-  int wr_opt = 0, wc_opt = 0;
   std::vector<glrm_loss> losses_h;
-  std::vector<glrm_reg> rx_h, ry_h;
-  bool vecreg_x = false, vecreg_y = false; // some rx / ry of this handle is a vector regularizer (kind >= GLRM_REG_QUAD_CONSTRAINT): VR kernels
-  // regularizers that carry a vector (include/glrm_hip_regvec.h, glrm_regvec.hip), [0] rx, [1] ry: nullptr / empty while the side has none.
-  // regvec: k x count doubles (ld k), reglen: count lengths, indexed like rx / ry; rx_h / ry_h then hold the descriptors WITH the new codes
-  double* regvec[2] = {nullptr, nullptr};
-  int32_t* reglen[2] = {nullptr, nullptr};
-  std::vector<double> regvec_h[2];
-  std::vector<int32_t> reglen_h[2];
-  struct Ev { hipEvent_t a, b; int which; };
+  struct Ev { hipEvent_t a, b; int slot; }; // slot: the side whose half-step the pair times, 2 = a wait for arriving blocks (ms_wait)
   std::vector<Ev> pending, pool;
-  int64_t launches_x = 0, launches_y = 0;
-  double ms_x = 0, ms_y = 0;
 };
 
+// The kernel family that runs a side's half-step (eval_only: the loss evaluation of glrm_hip_col_losses / the objective).  The ONE statement
+// of the precedence among families: run_sweep dispatches on it, glrm_hip_sum_order describes it, the arrival and graph decisions ask it.
+// The raw flags are not exclusive -- glrm_hip_set_regularizers can move a finalized tiled handle to multi while tiled stays set -- so the
+// precedence is spelled nowhere else.  The flags are still read by the set-up functions (they run before the flags are final), for the
+// lane refinement of TILED and the cached class of GATHER (decided where those families run) and by glrm_hip_kernel_stats.
+enum glrm_family { GLRM_FAM_REFERENCE, GLRM_FAM_GENERAL, GLRM_FAM_DENSE, GLRM_FAM_TILED, GLRM_FAM_BLOCKED, GLRM_FAM_GATHER };
+inline glrm_family glrm_side_family(const glrm_handle* h, int side, bool eval_only) {
+  if (h->sum_order_opt) return GLRM_FAM_REFERENCE;
+  if (h->multi) return GLRM_FAM_GENERAL;
+  if (h->dense) return GLRM_FAM_DENSE;
+  const bool passes = side == GLRM_COLS || !eval_only; // the row passes have no evaluation form: the gather sweep evaluates
+  if (h->side[side].tiled && passes) return GLRM_FAM_TILED;
+  if (h->side[side].blocked && passes) return GLRM_FAM_BLOCKED;
+  return GLRM_FAM_GATHER;
+}
 
 // refusals shared by the entry points (the single-shard message is the entry point's own)
 #define GLRM_NEED_FINALIZED(h) \
   do { if (!(h)->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first"); } while (0)
-inline bool glrm_single_shard(const glrm_handle* h) { return h->rb == 0 && h->re == h->m && h->cb == 0 && h->ce == h->n; }
+inline bool glrm_single_shard(const glrm_handle* h) { return h->side[GLRM_ROWS].begin == 0 && h->side[GLRM_ROWS].end == h->m && h->side[GLRM_COLS].begin == 0 && h->side[GLRM_COLS].end == h->n; }
 
 inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -220,7 +239,7 @@ inline int env_int(const char* name, int dflt) {
 namespace glrm { struct TiledArgs; }
 
 
-// per-segment class of the gather sweeps (see glrm_handle::seglist_r)
+// per-segment class of the gather sweeps (see glrm_handle::Side::seglist)
 constexpr int64_t GLRM_WAVES4_FROM = 1536, GLRM_WAVES8_FROM = 98304;
 __host__ __device__ inline int glrm_wave_class(int64_t len) { return len < GLRM_WAVES4_FROM ? 1 : (len < GLRM_WAVES8_FROM ? 2 : 3); }
 constexpr int glrm_class_waves(int cls) { return cls <= 1 ? 1 : (cls == 2 ? 4 : 8); }
@@ -231,19 +250,19 @@ inline int64_t glrm_cached_reg_maxlen(int G) { return (int64_t)13 * (64 / G); }
 // setup: family choice from h->sig and buffers (finalize)
 int glrm_prepare_tiled(glrm_handle* h);
 int glrm_setup_tiled(glrm_handle* h);
-int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only);
+int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only);
 
 // lane-per-segment LDS-tiled passes (glrm_lane.hip): setup decides lane[] from the whole problem's signature and builds the SELL layouts;
 // run takes the TiledArgs glrm_run_tiled prepared (glrm_tiled.hpp)
-bool glrm_lane_wants(const glrm_handle* h, bool rows);   // the whole problem's shape / losses / options admit the family on that side (given that the side runs the LDS tiles)
+bool glrm_lane_wants(const glrm_handle* h, int side);   // the whole problem's shape / losses / options admit the family on that side (given that the side runs the LDS tiles)
 int glrm_setup_lane(glrm_handle* h);
 bool glrm_lane_loss_ok(const glrm_handle* h, int loss);
 bool glrm_lane_few_descriptors(const glrm_handle* h);
-int glrm_run_lane(glrm_handle* h, bool rows, int loss, const glrm::TiledArgs& a, double min_stepsize, int eval_only);
+int glrm_run_lane(glrm_handle* h, int side, int loss, const glrm::TiledArgs& a, double min_stepsize, int eval_only);
 
-// phase-aligned gather passes (glrm_blocked.hip): setup decides blocked_row / blocked_col and allocates the pass buffers
+// phase-aligned gather passes (glrm_blocked.hip): setup decides Side::blocked and allocates the pass buffers
 int glrm_setup_blocked(glrm_handle* h);
-int glrm_run_blocked(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only);
+int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only);
 
 // glrm_hip_step_y_arrival (glrm_hip.hip): make h->stream wait for every block of h->arrival that intersects rows [lo, hi) of X and has
 // not been waited for yet
@@ -269,7 +288,7 @@ void glrm_regvec_placeholders(const std::vector<glrm_reg>& in, std::vector<glrm_
 int glrm_regvec_inherit(glrm_handle* child, const glrm_handle* parent);
 void glrm_regvec_drop(glrm_handle* h);
 int glrm_setup_reforder(glrm_handle* h);               // finalize: refuses what the mode does not cover
-int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
+int glrm_run_reforder(glrm_handle* h, int side, double min_stepsize, int eval_only);
 int glrm_reforder_sum(glrm_handle* h, const void* dvec, int64_t n, double* out); // Julia's pairwise sum(::Vector{Float64})
 int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out);       // objective(): ONE accumulator over all observations, then the penalties
 
@@ -279,19 +298,19 @@ int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out);      
 namespace glrm { struct SweepArgs; }
 int glrm_check_storage(const glrm_problem* p, const glrm_options* o);   // create: the option's range and everything a float handle refuses
 int glrm_check_storage_regs(const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry); // wrapped / vector regularizers
-int glrm_narrow_views(glrm_handle* h);                                  // end of create: rowvals / colvals double -> float arrays of the handle's own
+int glrm_narrow_views(glrm_handle* h);                                  // end of create: both views' vals double -> float arrays of the handle's own
 int glrm_narrow_factor(glrm_handle* h, const double* host, void* dev, int64_t nvec); // host k x nvec doubles -> device floats, ld kp, zero padded
 int glrm_widen_factor(glrm_handle* h, const void* dev, double* host, int64_t nvec);  // and back
 int glrm_check_narrowable(const char* name, const double* v, int64_t n);             // GLRM_ERR_NONFINITE for a finite value beyond float's range
-void glrm_launch_sweep_f32(int G, int R, int waves, int loss, bool rows, const glrm::SweepArgs& a, hipStream_t st);
-void glrm_launch_penalty_f32(glrm_handle* h, bool rows);
+void glrm_launch_sweep_f32(int G, int R, int waves, int loss, int side, const glrm::SweepArgs& a, hipStream_t st);
+void glrm_launch_penalty_f32(glrm_handle* h, int side);
 
 // GLRM_PROBLEM_ROWS_FROM_COLS (glrm_transpose.hip): the row view derived on the device from the uploaded column view
 int glrm_rows_from_cols(glrm_handle* h);
 
 // cached gather row sweep (glrm_cached.hip)
 int glrm_setup_cached(glrm_handle* h);                 // finalize: cached_want / cached_row from h->sig
-int64_t glrm_cached_maxlen(const glrm_handle* h);      // longest row the cached sweep takes (a function of k and the variant)
+int64_t glrm_cached_maxlen(const glrm_handle* h, int variant); // longest row the cached sweep takes: a function of k and the variant (a cached_row value)
 int glrm_cached_variant(const glrm_handle* h);         // cached_row of a handle on the family: 2 registers (always, for float storage), 1 LDS
 int glrm_cached_waves(const glrm_handle* h);           // waves per row of the register variant
 // float storage, GLRM_HIP_CACHED unset: 1 = the fp64 auto rule applies, 0 = the family stays behind GLRM_HIP_CACHED=1
@@ -300,25 +319,25 @@ void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
 int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)
 int glrm_setup_dense(glrm_handle* h, const glrm_problem* p);
-int glrm_run_dense(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
+int glrm_run_dense(glrm_handle* h, int side, double min_stepsize, int eval_only);
 
 // general sweeps (glrm_multi.hip)
 int glrm_setup_multi(glrm_handle* h, const glrm_problem* p);
-int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only);
-int glrm_run_multi_penalty(glrm_handle* h, bool rows);
+int glrm_run_multi(glrm_handle* h, int side, double min_stepsize, int eval_only);
+int glrm_run_multi_penalty(glrm_handle* h, int side);
 
-// per-segment reduce (which = 0) / decide (which = 1) kernels of glrm_tiled.hpp for a kp-wide factor
-void glrm_launch_col_small(int kp, int which, const glrm::TiledArgs& a, hipStream_t st);
+// per-segment reduce (stage = 0) / decide (stage = 1) kernels of glrm_tiled.hpp for a kp-wide factor
+void glrm_launch_col_small(int kp, int stage, const glrm::TiledArgs& a, hipStream_t st);
 
 // ---- shared host helpers (glrm_hip.hip)
-// the pass buffers of one side ([0] rows, [1] columns) for the local segments and pass[side].nsup super-tiles, and nactive
+// the pass buffers of one side for the local segments and side[side].pass.nsup super-tiles, and nactive
 int glrm_alloc_pass_buffers(glrm_handle* h, int side);
 // side stream + fork / join events (created once): launches that run beside the main stream's
 int glrm_ensure_side_stream(glrm_handle* h);
 int glrm_fork_side_stream(glrm_handle* h);        // the side stream continues behind what h->stream holds
 hipError_t glrm_join_side_stream(glrm_handle* h); // h->stream continues behind the side stream; g_err is left as it was (joins also run on error paths)
 // host copy of a view's segment offsets (nseg + 1)
-int glrm_host_ptr(glrm_handle* h, bool rows, std::vector<int64_t>& ptr);
+int glrm_host_ptr(glrm_handle* h, int side, std::vector<int64_t>& ptr);
 // a host list as a device array of its own (at least one element is allocated); synchronizes, so the list may be a local
 int glrm_upload_list(glrm_handle* h, const std::vector<int32_t>& list, int32_t** out);
 // segments split at long_from observations (<= 0: none is long): the short ones by descending length (stable), the long ones by id

@@ -262,9 +262,19 @@ extern "C" void glrm_hip_destroy(glrm_handle* h) {
 
 // ------------------------------------------------------------------ host helpers shared by the families (glrm_engine.hpp)
 
+// the line-search counters of both sides back to zero (create, glrm_hip_kernel_stats with reset)
+static int zero_counters(glrm_handle* h) {
+  for (glrm_handle::Side& v : h->side) {
+    const size_t bytes = (size_t)(v.nseg > 0 ? v.nseg : 1) * 4;
+    HIPCK(hipMemsetAsync(v.trials, 0, bytes, h->stream));
+    HIPCK(hipMemsetAsync(v.accepts, 0, bytes, h->stream));
+  }
+  return GLRM_OK;
+}
+
 int glrm_alloc_pass_buffers(glrm_handle* h, int side) {
-  glrm_handle::PassBuffers& b = h->pass[side];
-  const size_t nseg1 = (size_t)std::max<int64_t>(1, side == 0 ? h->ml : h->nl);
+  glrm_handle::PassBuffers& b = h->side[side].pass;
+  const size_t nseg1 = (size_t)std::max<int64_t>(1, h->side[side].nseg);
   int rc;
   if ((rc = h->mem.alloc(&b.part, nseg1 * b.nsup * (h->kp + 2)))) return rc;
   if ((rc = h->mem.alloc(&b.gsum, nseg1 * h->kp))) return rc;
@@ -298,10 +308,10 @@ hipError_t glrm_join_side_stream(glrm_handle* h) {
   return e_rec != hipSuccess ? e_rec : e_wait;
 }
 
-int glrm_host_ptr(glrm_handle* h, bool rows, std::vector<int64_t>& ptr) {
-  const size_t nseg = (size_t)(rows ? h->ml : h->nl);
+int glrm_host_ptr(glrm_handle* h, int side, std::vector<int64_t>& ptr) {
+  const size_t nseg = (size_t)h->side[side].nseg;
   ptr.resize(nseg + 1);
-  HIPCK(hipMemcpyAsync(ptr.data(), rows ? h->rowptr : h->colptr, (nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpyAsync(ptr.data(), h->side[side].ptr, (nseg + 1) * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return GLRM_OK;
 }
@@ -327,16 +337,16 @@ int glrm_set_long_columns(glrm_handle* h, const std::vector<int32_t>& longs) {
   return rc ? rc : glrm_ensure_side_stream(h);
 }
 
-static int view_stats(glrm_handle* h, bool rows, int forced_cls, int64_t cache_maxlen, unsigned long long (&st)[6]) {
+static int view_stats(glrm_handle* h, int side, int forced_cls, int64_t cache_maxlen, unsigned long long (&st)[6]) {
   for (auto& v : st) v = 0;
-  const int64_t nseg = rows ? h->ml : h->nl;
+  const int64_t nseg = h->side[side].nseg;
   if (nseg <= 0) return GLRM_OK;
   DevArena scratch;
   unsigned long long* d = nullptr;
   if (const int rc = scratch.alloc(&d, 6)) return rc;
   hipError_t e = hipMemsetAsync(d, 0, sizeof st, h->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(seg_stats_kernel, dim3(1024), dim3(256), 0, h->stream, rows ? h->rowptr : h->colptr, nseg, forced_cls, cache_maxlen, d);
+    hipLaunchKernelGGL(seg_stats_kernel, dim3(1024), dim3(256), 0, h->stream, h->side[side].ptr, nseg, forced_cls, cache_maxlen, d);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(st, d, sizeof st, hipMemcpyDeviceToHost, h->stream);
@@ -352,14 +362,14 @@ static int forced_class(int waves_opt) { return waves_opt == 1 ? 1 : (waves_opt 
 // one -- so a segment is summed in the same order whichever shard holds it.  One populated class: one launch over all local segments.
 // Several (skewed lengths: a few very popular columns / very active rows next to many short ones): seglist = the segments class by
 // class, one launch per class, the minority classes on a side stream beside the main launch.
-static int build_class_plan(glrm_handle* h, bool rows) {
-  int64_t* ncls = rows ? h->ncls_r : h->ncls_c;
-  const int64_t nseg = rows ? h->ml : h->nl;
-  const int forced = forced_class(rows ? h->opts.waves_row : h->opts.waves_col);
-  const bool cached = rows && h->cached_row != 0;
-  const int64_t cmax = cached ? glrm_cached_maxlen(h) : -1;
+static int build_class_plan(glrm_handle* h, int side) {
+  glrm_handle::Side& v = h->side[side];
+  int64_t* ncls = v.ncls;
+  const int forced = forced_class(side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col);
+  const bool cached = side == GLRM_ROWS && h->cached_row != 0; // only rows have a cached sweep
+  const int64_t cmax = cached ? glrm_cached_maxlen(h, h->cached_row) : -1;
   unsigned long long st[6];
-  int rc = view_stats(h, rows, forced, cmax, st);
+  int rc = view_stats(h, side, forced, cmax, st);
   if (rc) return rc;
   ncls[0] = (int64_t)st[4]; ncls[1] = (int64_t)st[1]; ncls[2] = (int64_t)st[2]; ncls[3] = (int64_t)st[3];
   if (cached) {
@@ -369,26 +379,28 @@ static int build_class_plan(glrm_handle* h, bool rows) {
   int best = 1, populated = 0;
   for (int c = 0; c < 4; ++c) populated += ncls[c] > 0;
   for (int c = 2; c < 4; ++c) if (ncls[c] > ncls[best]) best = c;
-  (rows ? h->waves_row : h->waves_col) = forced ? glrm_class_waves(forced) : glrm_class_waves(best);
+  v.waves = forced ? glrm_class_waves(forced) : glrm_class_waves(best);
   if (populated <= 1) return GLRM_OK;
   std::vector<int64_t> ptr;
-  if ((rc = glrm_host_ptr(h, rows, ptr))) return rc;
-  std::vector<int32_t> lst((size_t)nseg);
+  if ((rc = glrm_host_ptr(h, side, ptr))) return rc;
+  std::vector<int32_t> lst((size_t)v.nseg);
   int64_t pos[4] = {0, ncls[0], ncls[0] + ncls[1], ncls[0] + ncls[1] + ncls[2]};
-  for (int64_t s = 0; s < nseg; ++s) {
+  for (int64_t s = 0; s < v.nseg; ++s) {
     const int64_t len = ptr[s + 1] - ptr[s];
     const int c = (cmax >= 0 && len <= cmax) ? 0 : (forced ? forced : glrm_wave_class(len));
     lst[(size_t)pos[c]++] = (int32_t)s;
   }
-  if ((rc = glrm_upload_list(h, lst, rows ? &h->seglist_r : &h->seglist_c))) return rc;
+  if ((rc = glrm_upload_list(h, lst, &v.seglist))) return rc;
   return glrm_ensure_side_stream(h);
 }
 
 static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options* o) {
   const bool on_dev = (p->flags & GLRM_PROBLEM_DEVICE_ARRAYS) != 0;
   h->m = p->m; h->n = p->n; h->k = p->k;
-  h->rb = p->row_begin; h->re = p->row_end; h->cb = p->col_begin; h->ce = p->col_end;
-  h->ml = h->re - h->rb; h->nl = h->ce - h->cb;
+  glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
+  rows.begin = p->row_begin; rows.end = p->row_end; rows.nglob = p->m;
+  cols.begin = p->col_begin; cols.end = p->col_end; cols.nglob = p->n;
+  for (glrm_handle::Side& v : h->side) v.nseg = v.end - v.begin;
   pick_layout(p->k, h->G, h->R);
   h->kp = h->G * h->R;
   h->profile = o ? o->profile : 0;
@@ -399,10 +411,9 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
   if (o && (o->sum_order < 0 || o->sum_order > 1)) return fail(GLRM_ERR_INVALID, "glrm_options.sum_order must be 0 (engine orders) or 1 (reference order)");
   if (o) h->opts = *o; else { h->opts = glrm_options{}; h->opts.device_id = -1; }
   h->losses_h.assign(p->losses, p->losses + p->n_losses);
-  h->rx_h.assign(p->rx, p->rx + p->n_rx);
-  h->ry_h.assign(p->ry, p->ry + p->n_ry);
-  h->vecreg_x = any_vector_reg(h->rx_h);
-  h->vecreg_y = any_vector_reg(h->ry_h);
+  rows.regs_h.assign(p->rx, p->rx + p->n_rx);
+  cols.regs_h.assign(p->ry, p->ry + p->n_ry);
+  for (glrm_handle::Side& v : h->side) v.vecreg = any_vector_reg(v.regs_h);
   if (o && (o->stream || o->caller_stream)) {
     h->stream = (hipStream_t)o->stream; // may be NULL = the legacy default stream (caller_stream)
   } else {
@@ -413,83 +424,71 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
   int rc;
   // (a float handle narrows the values into arrays of its own: it copies what it may borrow)
   const bool borrow = on_dev && (p->flags & GLRM_PROBLEM_BORROW_DEVICE_ARRAYS) != 0 && h->storage == GLRM_STORAGE_F64;
+  const struct { const int64_t* ptr; const int32_t* idx; const double* vals; } pv[2] = {{p->rowptr, p->colidx, p->rowvals}, {p->colptr, p->rowidx, p->colvals}};
   if (!p->dense_A && borrow) { // the caller's device arrays, read in place
-    h->rowptr = const_cast<int64_t*>(p->rowptr); h->colptr = const_cast<int64_t*>(p->colptr);
-    h->colidx = const_cast<int32_t*>(p->colidx); h->rowvals = const_cast<double*>(p->rowvals);
-    h->rowidx = const_cast<int32_t*>(p->rowidx); h->colvals = const_cast<double*>(p->colvals);
-    HIPCK(hipMemcpyAsync(&h->nnz_r, p->rowptr + h->ml, 8, hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(&h->nnz_c, p->colptr + h->nl, 8, hipMemcpyDeviceToHost, st));
+    for (int s = 0; s < 2; ++s) {
+      glrm_handle::Side& v = h->side[s];
+      v.ptr = const_cast<int64_t*>(pv[s].ptr); v.idx = const_cast<int32_t*>(pv[s].idx); v.vals = const_cast<double*>(pv[s].vals);
+      HIPCK(hipMemcpyAsync(&v.nnz, v.ptr + v.nseg, 8, hipMemcpyDeviceToHost, st));
+    }
     HIPCK(hipStreamSynchronize(st));
-    if ((h->nnz_r > 0 && (!h->colidx || !h->rowvals)) || (h->nnz_c > 0 && (!h->rowidx || !h->colvals)))
+    if ((rows.nnz > 0 && (!rows.idx || !rows.vals)) || (cols.nnz > 0 && (!cols.idx || !cols.vals)))
       return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
-  } else if (!p->dense_A && (p->flags & GLRM_PROBLEM_ROWS_FROM_COLS)) { // the column view only; the row view is derived on the device
-    if ((rc = dev_copy_in(h, &h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
-    if (on_dev) {
-      HIPCK(hipMemcpyAsync(&h->nnz_c, p->colptr + h->nl, 8, hipMemcpyDeviceToHost, st));
-      HIPCK(hipStreamSynchronize(st));
-    } else {
-      h->nnz_c = p->colptr[h->nl];
-    }
-    if (h->nnz_c > 0 && (!p->rowidx || !p->colvals)) return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
-    if ((rc = dev_copy_in(h, &h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(h, &h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
-    if ((rc = glrm_rows_from_cols(h))) return rc;
   } else if (!p->dense_A) {
-    if ((rc = dev_copy_in(h, &h->rowptr, p->rowptr, h->ml + 1, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(h, &h->colptr, p->colptr, h->nl + 1, on_dev, st))) return rc;
-    if (on_dev) {
-      HIPCK(hipMemcpyAsync(&h->nnz_r, p->rowptr + h->ml, 8, hipMemcpyDeviceToHost, st));
-      HIPCK(hipMemcpyAsync(&h->nnz_c, p->colptr + h->nl, 8, hipMemcpyDeviceToHost, st));
-      HIPCK(hipStreamSynchronize(st));
-    } else {
-      h->nnz_r = p->rowptr[h->ml];
-      h->nnz_c = p->colptr[h->nl];
+    // GLRM_PROBLEM_ROWS_FROM_COLS: the column view only; the row view is derived on the device
+    const bool from_cols = (p->flags & GLRM_PROBLEM_ROWS_FROM_COLS) != 0;
+    const int first = from_cols ? GLRM_COLS : GLRM_ROWS;
+    for (int s = first; s < 2; ++s)
+      if ((rc = dev_copy_in(h, &h->side[s].ptr, pv[s].ptr, h->side[s].nseg + 1, on_dev, st))) return rc;
+    for (int s = first; s < 2; ++s) {
+      if (on_dev) HIPCK(hipMemcpyAsync(&h->side[s].nnz, pv[s].ptr + h->side[s].nseg, 8, hipMemcpyDeviceToHost, st));
+      else h->side[s].nnz = pv[s].ptr[h->side[s].nseg];
     }
-    if ((rc = dev_copy_in(h, &h->colidx, p->colidx, h->nnz_r, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(h, &h->rowvals, p->rowvals, h->nnz_r, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(h, &h->rowidx, p->rowidx, h->nnz_c, on_dev, st))) return rc;
-    if ((rc = dev_copy_in(h, &h->colvals, p->colvals, h->nnz_c, on_dev, st))) return rc;
+    if (on_dev) HIPCK(hipStreamSynchronize(st));
+    if (from_cols && cols.nnz > 0 && (!p->rowidx || !p->colvals)) return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
+    for (int s = first; s < 2; ++s) {
+      if ((rc = dev_copy_in(h, &h->side[s].idx, pv[s].idx, h->side[s].nnz, on_dev, st))) return rc;
+      if ((rc = dev_copy_in(h, &h->side[s].vals, pv[s].vals, h->side[s].nnz, on_dev, st))) return rc;
+    }
+    if (from_cols && (rc = glrm_rows_from_cols(h))) return rc;
   }
-  h->n_losses = p->n_losses; h->n_rx = p->n_rx; h->n_ry = p->n_ry;
+  h->n_losses = p->n_losses; rows.n_regs = p->n_rx; cols.n_regs = p->n_ry;
   if ((rc = dev_copy_in(h, &h->losses, p->losses, p->n_losses, false, st))) return rc;
-  if ((rc = dev_copy_in(h, &h->rx, p->rx, p->n_rx, false, st))) return rc;
-  if ((rc = dev_copy_in(h, &h->ry, p->ry, p->n_ry, false, st))) return rc;
+  if ((rc = dev_copy_in(h, &rows.regs, p->rx, p->n_rx, false, st))) return rc;
+  if ((rc = dev_copy_in(h, &cols.regs, p->ry, p->n_ry, false, st))) return rc;
   h->loss_quad_uniform = p->n_losses == 1 && p->losses[0].kind == GLRM_LOSS_QUAD;
   h->has_trig = false;
   for (int64_t i = 0; i < p->n_losses; ++i) h->has_trig = h->has_trig || p->losses[i].kind == GLRM_LOSS_PERIODIC;
-  const int64_t ml1 = h->ml > 0 ? h->ml : 1, nl1 = h->nl > 0 ? h->nl : 1;
-  if ((rc = h->mem.alloc(&h->alpharow, ml1))) return rc;
-  if ((rc = h->mem.alloc(&h->alphacol, nl1))) return rc;
   if ((rc = h->mem.alloc(&h->partials, SUM_BLOCKS))) return rc;
   if ((rc = h->mem.alloc(&h->dscalar, 1))) return rc;
   if ((rc = h->mem.alloc(&h->dcount, 1))) return rc;
-  if ((rc = h->mem.alloc(&h->trials_r, ml1))) return rc;
-  if ((rc = h->mem.alloc(&h->accepts_r, ml1))) return rc;
-  if ((rc = h->mem.alloc(&h->trials_c, nl1))) return rc;
-  if ((rc = h->mem.alloc(&h->accepts_c, nl1))) return rc;
-  HIPCK(hipMemsetAsync(h->trials_r, 0, ml1 * 4, st));
-  HIPCK(hipMemsetAsync(h->accepts_r, 0, ml1 * 4, st));
-  HIPCK(hipMemsetAsync(h->trials_c, 0, nl1 * 4, st));
-  HIPCK(hipMemsetAsync(h->accepts_c, 0, nl1 * 4, st));
+  for (glrm_handle::Side& v : h->side) {
+    const int64_t nseg1 = v.nseg > 0 ? v.nseg : 1;
+    if ((rc = h->mem.alloc(&v.alpha, nseg1))) return rc;
+    if ((rc = h->mem.alloc(&v.trials, nseg1))) return rc;
+    if ((rc = h->mem.alloc(&v.accepts, nseg1))) return rc;
+  }
+  if ((rc = zero_counters(h))) return rc;
   int rc2 = glrm_setup_multi(h, p);
   if (rc2) return rc2;
   // this shard's contribution to the signature of the whole problem (include/glrm_hip.h: glrm_signature)
   h->sig_local = glrm_signature{};
   if (p->dense_A) {
-    h->sig_local.nnz_rows = h->ml * h->n; h->sig_local.nnz_cols = h->nl * h->m;
-    h->sig_local.max_row_len = h->ml > 0 ? h->n : 0; h->sig_local.max_col_len = h->nl > 0 ? h->m : 0;
+    h->sig_local.nnz_rows = rows.nseg * h->n; h->sig_local.nnz_cols = cols.nseg * h->m;
+    h->sig_local.max_row_len = rows.nseg > 0 ? h->n : 0; h->sig_local.max_col_len = cols.nseg > 0 ? h->m : 0;
     if ((rc2 = glrm_setup_dense(h, p))) return rc2;
   } else {
-    unsigned long long st6[6];
-    if ((rc = view_stats(h, true, 0, -1, st6))) return rc;
-    h->sig_local.max_row_len = (int64_t)st6[0];
-    if ((rc = view_stats(h, false, 0, -1, st6))) return rc;
-    h->sig_local.max_col_len = (int64_t)st6[0];
-    h->sig_local.nnz_rows = h->nnz_r; h->sig_local.nnz_cols = h->nnz_c;
+    int64_t* const max_len[2] = {&h->sig_local.max_row_len, &h->sig_local.max_col_len};
+    for (int s = 0; s < 2; ++s) {
+      unsigned long long st6[6];
+      if ((rc = view_stats(h, s, 0, -1, st6))) return rc;
+      *max_len[s] = (int64_t)st6[0];
+    }
+    h->sig_local.nnz_rows = h->side[GLRM_ROWS].nnz; h->sig_local.nnz_cols = h->side[GLRM_COLS].nnz;
     if (!h->multi && (rc2 = glrm_prepare_tiled(h))) return rc2;
   }
   HIPCK(hipStreamSynchronize(st)); // host descriptor / index arrays may be released by the caller now
-  if (h->storage == GLRM_STORAGE_F32 && (rc = glrm_narrow_views(h))) return rc; // from here on rowvals / colvals are floats
+  if (h->storage == GLRM_STORAGE_F32 && (rc = glrm_narrow_views(h))) return rc; // from here on both views' vals are floats
   return GLRM_OK;
 }
 
@@ -501,19 +500,22 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
       h->sig.cols_unordered < h->sig_local.cols_unordered)
     return fail(GLRM_ERR_INVALID, "the signature of the whole problem cannot be smaller than this shard's (sum the counts, max the rest)");
   int rc;
+  const int opt_waves[2] = {h->opts.waves_row, h->opts.waves_col};
   if ((rc = glrm_setup_reforder(h))) return rc; // glrm_options.sum_order = 1: refuses models the validation sweeps do not cover
   if (h->sum_order_opt) {
     // reference-order validation sweeps: one lane per segment in list order, no family to choose and no view to re-order
-    h->tiled_row = h->tiled_col = h->blocked_row = h->blocked_col = h->cached_row = h->cached_want = 0;
-    h->waves_row = h->waves_col = 1;
+    for (int s = 0; s < 2; ++s) { h->side[s].tiled = h->side[s].blocked = 0; h->side[s].waves = 1; }
+    h->cached_row = h->cached_want = 0;
   } else if (h->storage == GLRM_STORAGE_F32) {
     // float storage: gather sweeps on both views; rows of at most glrm_cached_maxlen observations on the cached row sweep where
     // glrm_setup_cached says so, otherwise on the one-wave sweep (the other families have no float form)
-    h->tiled_row = h->tiled_col = h->blocked_row = h->blocked_col = 0;
+    for (int s = 0; s < 2; ++s) h->side[s].tiled = h->side[s].blocked = 0;
     if ((rc = glrm_setup_cached(h))) return rc;
-    if ((rc = build_class_plan(h, true))) return rc;
-    if ((rc = build_class_plan(h, false))) return rc;
-  } else if (!h->multi && !h->dense) {
+    for (int s = 0; s < 2; ++s)
+      if ((rc = build_class_plan(h, s))) return rc;
+  } else if (h->multi || h->dense) {
+    for (int s = 0; s < 2; ++s) h->side[s].waves = opt_waves[s] ? opt_waves[s] : (s == GLRM_ROWS ? 1 : 4);
+  } else {
     // a failure from here on leaves re-ordered private views and partial buffers behind: the handle can then only be destroyed
     h->finalize_failed = true;
     if (glrm_test_fail_finalize())  // csrc/glrm_testhooks.hip: always 0 in the product library; the test build injects a failure on request
@@ -521,12 +523,9 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     if ((rc = glrm_setup_tiled(h))) return rc;
     if ((rc = glrm_setup_cached(h))) return rc;
     if ((rc = glrm_setup_blocked(h))) return rc;
-    if (!h->tiled_row && !h->blocked_row && (rc = build_class_plan(h, true))) return rc;
-    if (!h->tiled_col && !h->blocked_col && (rc = build_class_plan(h, false))) return rc;
+    for (int s = 0; s < 2; ++s)
+      if (!h->side[s].tiled && !h->side[s].blocked && (rc = build_class_plan(h, s))) return rc;
     h->finalize_failed = false;
-  } else {
-    h->waves_row = h->opts.waves_row ? h->opts.waves_row : 1;
-    h->waves_col = h->opts.waves_col ? h->opts.waves_col : 4;
   }
   HIPCK(hipStreamSynchronize(h->stream));
   h->finalized = true;
@@ -622,11 +621,12 @@ static int ensure_one(glrm_handle* h, double** used, double** own, size_t bytes)
 
 static int ensure_owned(glrm_handle* h) {
   const size_t fe = factor_elem(h);
+  glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
   int rc;
-  if ((rc = ensure_one(h, &h->X, &h->oX, (size_t)h->kp * h->m * fe))) return rc;
-  if ((rc = ensure_one(h, &h->Y, &h->oY, (size_t)h->kp * h->d * fe))) return rc;
-  if ((rc = ensure_one(h, &h->objcol, &h->oobjcol, (size_t)h->n * 8))) return rc;
-  return ensure_one(h, &h->objrow, &h->oobjrow, (size_t)h->m * 8);
+  if ((rc = ensure_one(h, &rows.factor, &rows.own_factor, (size_t)h->kp * h->m * fe))) return rc;
+  if ((rc = ensure_one(h, &cols.factor, &cols.own_factor, (size_t)h->kp * h->d * fe))) return rc; // (d vectors: the embedding dimensions of the columns)
+  if ((rc = ensure_one(h, &cols.obj, &cols.own_obj, (size_t)h->n * 8))) return rc;
+  return ensure_one(h, &rows.obj, &rows.own_obj, (size_t)h->m * 8);
 }
 
 extern "C" int glrm_hip_factor_ld(glrm_handle* h) { return h ? h->kp : fail(GLRM_ERR_INVALID, "NULL handle"); }
@@ -634,7 +634,7 @@ extern "C" int glrm_hip_factor_ld(glrm_handle* h) { return h ? h->kp : fail(GLRM
 extern "C" int glrm_hip_bind_buffers(glrm_handle* h, void* dX, void* dY, void* dObjCol, void* dObjRow) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  h->X = (double*)dX; h->Y = (double*)dY; h->objcol = (double*)dObjCol; h->objrow = (double*)dObjRow;
+  h->side[GLRM_ROWS].factor = (double*)dX; h->side[GLRM_COLS].factor = (double*)dY; h->side[GLRM_COLS].obj = (double*)dObjCol; h->side[GLRM_ROWS].obj = (double*)dObjRow;
   if (h->iter_exec) { (void)hipGraphExecDestroy(h->iter_exec); h->iter_exec = nullptr; } // the captured launches hold the old pointers
   return ensure_owned(h);
 }
@@ -648,32 +648,34 @@ extern "C" int glrm_hip_set_factors(glrm_handle* h, const double* X, const doubl
   DeviceScope dg(h->device);
   int rc = ensure_owned(h);
   if (rc) return rc;
+  double *dX = h->side[GLRM_ROWS].factor, *dY = h->side[GLRM_COLS].factor;
   if (h->storage == GLRM_STORAGE_F32) {
-    if ((rc = glrm_narrow_factor(h, X, h->X, h->m))) return rc;
-    return glrm_narrow_factor(h, Y, h->Y, h->d);
+    if ((rc = glrm_narrow_factor(h, X, dX, h->m))) return rc;
+    return glrm_narrow_factor(h, Y, dY, h->d);
   }
   const size_t kb = (size_t)h->k * 8, pb = (size_t)h->kp * 8;
   if (h->kp != h->k) {
-    HIPCK(hipMemsetAsync(h->X, 0, pb * h->m, h->stream));
-    HIPCK(hipMemsetAsync(h->Y, 0, pb * h->d, h->stream));
+    HIPCK(hipMemsetAsync(dX, 0, pb * h->m, h->stream));
+    HIPCK(hipMemsetAsync(dY, 0, pb * h->d, h->stream));
   }
-  HIPCK(hipMemcpy2DAsync(h->X, pb, X, kb, kb, (size_t)h->m, hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipMemcpy2DAsync(h->Y, pb, Y, kb, kb, (size_t)h->d, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpy2DAsync(dX, pb, X, kb, kb, (size_t)h->m, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpy2DAsync(dY, pb, Y, kb, kb, (size_t)h->d, hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return GLRM_OK;
 }
 
 extern "C" int glrm_hip_get_factors(glrm_handle* h, double* X, double* Y) {
   if (!h || !X || !Y) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (!h->X || !h->Y) return fail(GLRM_ERR_INVALID, "no factors on the device yet");
+  const double *dX = h->side[GLRM_ROWS].factor, *dY = h->side[GLRM_COLS].factor;
+  if (!dX || !dY) return fail(GLRM_ERR_INVALID, "no factors on the device yet");
   DeviceScope dg(h->device);
   if (h->storage == GLRM_STORAGE_F32) {
-    if (const int rc = glrm_widen_factor(h, h->X, X, h->m)) return rc;
-    return glrm_widen_factor(h, h->Y, Y, h->d);
+    if (const int rc = glrm_widen_factor(h, dX, X, h->m)) return rc;
+    return glrm_widen_factor(h, dY, Y, h->d);
   }
   const size_t kb = (size_t)h->k * 8, pb = (size_t)h->kp * 8;
-  HIPCK(hipMemcpy2DAsync(X, kb, h->X, pb, kb, (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
-  HIPCK(hipMemcpy2DAsync(Y, kb, h->Y, pb, kb, (size_t)h->d, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpy2DAsync(X, kb, dX, pb, kb, (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpy2DAsync(Y, kb, dY, pb, kb, (size_t)h->d, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   return GLRM_OK;
 }
@@ -681,8 +683,8 @@ extern "C" int glrm_hip_get_factors(glrm_handle* h, double* X, double* Y) {
 extern "C" int glrm_hip_reset_stepsizes(glrm_handle* h, double stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  if (h->ml > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->ml + 255) / 256)), dim3(256), 0, h->stream, h->alpharow, h->ml, stepsize);
-  if (h->nl > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->nl + 255) / 256)), dim3(256), 0, h->stream, h->alphacol, h->nl, stepsize);
+  for (const glrm_handle::Side& v : h->side)
+    if (v.nseg > 0) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((v.nseg + 255) / 256)), dim3(256), 0, h->stream, v.alpha, v.nseg, stepsize);
   HIPCK(hipGetLastError());
   return GLRM_OK;
 }
@@ -697,12 +699,12 @@ static bool any_wrapped(const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, in
 // with it before it replaces any (csrc/glrm_multigpu.hip).
 int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
   if (!h || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (n_rx != h->n_rx || n_ry != h->n_ry)
-    return fail(GLRM_ERR_INVALID, "regularizer counts must match the handle (rx %lld, ry %lld)", (long long)h->n_rx, (long long)h->n_ry);
+  if (n_rx != h->side[GLRM_ROWS].n_regs || n_ry != h->side[GLRM_COLS].n_regs)
+    return fail(GLRM_ERR_INVALID, "regularizer counts must match the handle (rx %lld, ry %lld)", (long long)h->side[GLRM_ROWS].n_regs, (long long)h->side[GLRM_COLS].n_regs);
   if (h->storage == GLRM_STORAGE_F32)
     if (const int rc = glrm_check_storage_regs(rx, n_rx, ry, n_ry)) return rc;
   if (const int rc = check_regs("rx", rx, n_rx, h->k, nullptr, 0, 0, 0)) return rc;
-  if (const int rc = check_regs("ry", ry, n_ry, h->k, h->losses_h.data(), (int64_t)h->losses_h.size(), h->cb, h->nl)) return rc;
+  if (const int rc = check_regs("ry", ry, n_ry, h->k, h->losses_h.data(), (int64_t)h->losses_h.size(), h->side[GLRM_COLS].begin, h->side[GLRM_COLS].nseg)) return rc;
   // a handle created on the scalar fast paths moves to the general sweeps when a wrapper appears
   if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry) && (h->dense || h->kp > 64))
     return fail(GLRM_ERR_UNSUPPORTED, "wrapped regularizers need a sparse-view handle with k <= 64");
@@ -713,19 +715,20 @@ extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int
   if (const int rc = glrm_check_regularizers(h, rx, n_rx, ry, n_ry)) return rc;
   if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry)) h->multi = true; // checked above: this handle can run the general sweeps
   DeviceScope dg(h->device);
-  h->rx_h.assign(rx, rx + n_rx);
-  h->ry_h.assign(ry, ry + n_ry);
-  const bool vx = any_vector_reg(h->rx_h), vy = any_vector_reg(h->ry_h);
-  if ((vx != h->vecreg_x || vy != h->vecreg_y) && h->iter_exec) { // the captured iteration holds the other instantiation's launches
+  glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
+  rows.regs_h.assign(rx, rx + n_rx);
+  cols.regs_h.assign(ry, ry + n_ry);
+  const bool vx = any_vector_reg(rows.regs_h), vy = any_vector_reg(cols.regs_h);
+  if ((vx != rows.vecreg || vy != cols.vecreg) && h->iter_exec) { // the captured iteration holds the other instantiation's launches
     (void)hipGraphExecDestroy(h->iter_exec);
     h->iter_exec = nullptr;
   }
-  h->vecreg_x = vx;
-  h->vecreg_y = vy;
-  HIPCK(hipMemcpyAsync(h->rx, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipMemcpyAsync(h->ry, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
+  rows.vecreg = vx;
+  cols.vecreg = vy;
+  HIPCK(hipMemcpyAsync(rows.regs, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpyAsync(cols.regs, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
-  if (h->regvec[0] || h->regvec[1]) { // the vectors of an earlier glrm_hip_set_regularizers_vec go with its descriptors (include/glrm_hip_regvec.h)
+  if (rows.regvec || cols.regvec) { // the vectors of an earlier glrm_hip_set_regularizers_vec go with its descriptors (include/glrm_hip_regvec.h)
     glrm_regvec_drop(h);
     if (h->iter_exec) { (void)hipGraphExecDestroy(h->iter_exec); h->iter_exec = nullptr; }
   }
@@ -741,9 +744,9 @@ extern "C" int glrm_hip_synchronize(glrm_handle* h) {
 
 // ------------------------------------------------------------------ sweep launch (glrm_sweep.hpp)
 
-static void launch_sweep(int G, int R, int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
-  if (a.storage == GLRM_STORAGE_F32) glrm_launch_sweep_f32(G, R, waves, loss, rows, a, st);
-  else launch_sweep_st<double>(G, R, waves, loss, rows, a, st);
+static void launch_sweep(int G, int R, int waves, int loss, int side, const SweepArgs& a, hipStream_t st) {
+  if (a.storage == GLRM_STORAGE_F32) glrm_launch_sweep_f32(G, R, waves, loss, side, a, st);
+  else launch_sweep_st<double>(G, R, waves, loss, side, a, st);
 }
 
 
@@ -752,7 +755,7 @@ static int drain_events(glrm_handle* h) {
     HIPCK(hipEventSynchronize(e.b));
     float ms = 0;
     HIPCK(hipEventElapsedTime(&ms, e.a, e.b));
-    (e.which == 0 ? h->ms_x : e.which == 1 ? h->ms_y : h->ms_wait) += ms;
+    (e.slot < 2 ? h->side[e.slot].ms : h->ms_wait) += ms;
     h->pool.push_back(e);
   }
   h->pending.clear();
@@ -781,23 +784,23 @@ struct RoctxRange {
   ~RoctxRange() { if (api().pop) api().pop(); }
 };
 
-// which: 0 = row sweep (X half-step), 1 = column sweep (Y half-step)
-static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_only) {
-  RoctxRange range(eval_only ? "glrm col_losses" : (which == 0 ? "glrm step_x" : "glrm step_y"));
+// One half-step of a side, or with eval_only its loss evaluation.  glrm_side_family names the family; this is the dispatch on it.
+static int run_sweep(glrm_handle* h, int side, double min_stepsize, int eval_only) {
+  RoctxRange range(eval_only ? "glrm col_losses" : (side == GLRM_ROWS ? "glrm step_x" : "glrm step_y"));
   GLRM_NEED_FINALIZED(h);
   int rc = ensure_owned(h);
   if (rc) return rc;
   SweepArgs a{};
-  const bool rows = which == 0;
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_handle::Side& v = h->side[side];
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
   a.storage = h->storage;
   if (a.nseg <= 0) return GLRM_OK;
   if (eval_only) a.trials = nullptr;
   a.seg_lo = 0;
   a.seg_hi = a.nseg;
-  if (rows && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
+  if (side == GLRM_ROWS && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
     if (h->rng_e - h->rng_b <= 0) return GLRM_OK;
-    if (h->seglist_r) { // several classes: the class launches filter their lists by the range
+    if (v.seglist) { // several classes: the class launches filter their lists by the range
       a.seg_lo = h->rng_b; a.seg_hi = h->rng_e;
     } else {
       glrm_apply_row_range(a, h->rng_b, h->rng_e);
@@ -807,7 +810,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
   int loss;
   if (h->loss_quad_uniform) { loss = LOSS_QUAD_UNIFORM; a.loss_by_segment = 0; }
   else if (h->n_losses == 1) { loss = LOSS_SEGMENT; a.loss_by_segment = 0; }
-  else if (rows) { loss = LOSS_PER_OBS; a.loss_by_segment = 0; }
+  else if (side == GLRM_ROWS) { loss = LOSS_PER_OBS; a.loss_by_segment = 0; }
   else { loss = LOSS_SEGMENT; a.loss_by_segment = 1; }
   if (!h->has_trig && loss != LOSS_QUAD_UNIFORM) loss += 2; // LOSS_*_NOTRIG: kernels compiled without the PeriodicLoss case
   glrm_handle::Ev ev{};
@@ -815,21 +818,18 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
   if (timed) {
     if (!h->pool.empty()) { ev = h->pool.back(); h->pool.pop_back(); }
     else { HIPCK(hipEventCreate(&ev.a)); HIPCK(hipEventCreate(&ev.b)); }
-    ev.which = which;
+    ev.slot = side;
     HIPCK(hipEventRecord(ev.a, h->stream));
   }
-  const bool tiled = rows ? (h->tiled_row && !eval_only) : h->tiled_col;
-  if (h->sum_order_opt) {
-    rc = glrm_run_reforder(h, rows, min_stepsize, eval_only);
-    if (rc) return rc;
-  } else if (h->multi) {
-    rc = glrm_run_multi(h, rows, min_stepsize, eval_only);
-    if (rc) return rc;
-  } else if (h->dense) {
-    rc = glrm_run_dense(h, rows, min_stepsize, eval_only);
-    if (rc) return rc;
-  } else if (tiled || (rows ? (h->blocked_row && !eval_only) : h->blocked_col)) {
-    const bool divert = !rows && h->blk_nlong_c > 0; // the very long columns: 8-wave gather sweep on the side stream, beside the passes
+  const glrm_family fam = glrm_side_family(h, side, eval_only != 0);
+  if (fam == GLRM_FAM_REFERENCE) {
+    rc = glrm_run_reforder(h, side, min_stepsize, eval_only);
+  } else if (fam == GLRM_FAM_GENERAL) {
+    rc = glrm_run_multi(h, side, min_stepsize, eval_only);
+  } else if (fam == GLRM_FAM_DENSE) {
+    rc = glrm_run_dense(h, side, min_stepsize, eval_only);
+  } else if (fam == GLRM_FAM_TILED || fam == GLRM_FAM_BLOCKED) {
+    const bool divert = side == GLRM_COLS && h->blk_nlong_c > 0; // the very long columns: 8-wave gather sweep on the side stream, beside the passes
     if (divert) {
       // the gather sweep reads all of X: behind the sweeps already queued (fork) and, while X is still arriving
       // (glrm_hip_step_y_arrival), behind every block -- without holding up the passes on the main stream
@@ -839,23 +839,22 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
       SweepArgs b = a;
       b.seglist = h->blk_long_c;
       b.nseg = h->blk_nlong_c;
-      launch_sweep(h->G, h->R, 8, loss, false, b, h->side_stream);
+      launch_sweep(h->G, h->R, 8, loss, GLRM_COLS, b, h->side_stream);
     }
-    rc = tiled ? glrm_run_tiled(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only)
-               : glrm_run_blocked(h, rows, loss, a.loss_by_segment, min_stepsize, eval_only);
+    rc = fam == GLRM_FAM_TILED ? glrm_run_tiled(h, side, loss, a.loss_by_segment, min_stepsize, eval_only)
+                               : glrm_run_blocked(h, side, loss, a.loss_by_segment, min_stepsize, eval_only);
     if (divert) (void)glrm_join_side_stream(h); // join before anything else (also before reporting an error: later work on the stream stays ordered)
-    if (rc) return rc;
   } else {
     // gather sweeps (and the cached row sweep), class by class -- see build_class_plan
-    const int64_t* ncls = rows ? h->ncls_r : h->ncls_c;
-    const int32_t* lst = rows ? h->seglist_r : h->seglist_c;
+    const int64_t* ncls = v.ncls;
+    const int32_t* lst = v.seglist;
     if (!lst) { // one class holds every local segment
       int cls = 1;
       for (int c = 0; c < 4; ++c) if (ncls[c] > 0) cls = c;
       if (cls == 0 && !eval_only) {
         if ((rc = glrm_run_cached(h, loss, min_stepsize, nullptr, 0, h->stream))) return rc;
       } else {
-        launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, rows, a, h->stream);
+        launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, side, a, h->stream);
       }
     } else {
       // fork: the minority classes on the side stream, beside the majority class on the main stream; join
@@ -873,7 +872,7 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
           SweepArgs b = a;
           b.seglist = lst + off;
           b.nseg = ncls[c];
-          launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, rows, b, st);
+          launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, side, b, st);
         }
       }
       // join also before reporting an error: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
@@ -882,31 +881,32 @@ static int run_sweep(glrm_handle* h, int which, double min_stepsize, int eval_on
       HIPCK(e_join);
     }
   }
+  if (rc) return rc;
   HIPCK(hipGetLastError());
   if (timed) {
     HIPCK(hipEventRecord(ev.b, h->stream));
     h->pending.push_back(ev);
     if (h->pending.size() >= 4096) { rc = drain_events(h); if (rc) return rc; }
   }
-  if (!eval_only) (rows ? h->launches_x : h->launches_y) += 1;
+  if (!eval_only) v.launches += 1;
   return GLRM_OK;
 }
 
 extern "C" int glrm_hip_step_x(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, 0, min_stepsize, 0);
+  return run_sweep(h, GLRM_ROWS, min_stepsize, 0);
 }
 
 extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t seg_end, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   GLRM_REFUSE_F32(h, "glrm_hip_step_x_range");
-  if (seg_begin < 0 || seg_end > h->ml || seg_begin > seg_end) return fail(GLRM_ERR_INVALID, "row range out of bounds");
+  if (seg_begin < 0 || seg_end > h->side[GLRM_ROWS].nseg || seg_begin > seg_end) return fail(GLRM_ERR_INVALID, "row range out of bounds");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "step_x_range is not available on the dense path");
   DeviceScope dg(h->device);
   h->rng_b = seg_begin;
   h->rng_e = seg_end;
-  const int rc = run_sweep(h, 0, min_stepsize, 0);
+  const int rc = run_sweep(h, GLRM_ROWS, min_stepsize, 0);
   h->rng_b = 0;
   h->rng_e = -1;
   return rc;
@@ -915,7 +915,13 @@ extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t 
 extern "C" int glrm_hip_step_y(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, 1, min_stepsize, 0);
+  return run_sweep(h, GLRM_COLS, min_stepsize, 0);
+}
+
+// the Y half-step runs as passes over super-tiles (LDS-tiled, lane or phase-aligned)
+static bool col_passes(const glrm_handle* h) {
+  const glrm_family fam = glrm_side_family(h, GLRM_COLS, false);
+  return fam == GLRM_FAM_TILED || fam == GLRM_FAM_BLOCKED;
 }
 
 // ---- the Y half-step while X is still arriving (include/glrm_hip.h: glrm_hip_step_y_arrival) ----------------------------------------
@@ -929,7 +935,7 @@ int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi) {
     if (h->profile) { // what the launch stream spends in front of a block that is not there yet (ms_wait_y)
       if (!h->pool.empty()) { ev = h->pool.back(); h->pool.pop_back(); }
       else { HIPCK(hipEventCreate(&ev.a)); HIPCK(hipEventCreate(&ev.b)); }
-      ev.which = 2;
+      ev.slot = 2;
       HIPCK(hipEventRecord(ev.a, h->stream));
     }
     HIPCK(hipStreamWaitEvent(h->stream, (hipEvent_t)blk.event, 0));
@@ -997,9 +1003,9 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
   int rc = GLRM_OK;
   // the pass families of the column view can start on a part of X (the phase-aligned passes super-tile by super-tile in true arrival order,
   // the LDS-tiled / lane passes in runs of super-tiles in the announced order: round 6); everything else needs all of it
-  const bool by_super_tile = (h->blocked_col || h->tiled_col) && !h->multi && !h->dense && !h->sum_order_opt && env_int("GLRM_HIP_ARRIVAL", 1);
+  const bool by_super_tile = col_passes(h) && env_int("GLRM_HIP_ARRIVAL", 1);
   if (!by_super_tile) rc = glrm_arrival_wait(h, 0, h->m);
-  if (!rc) rc = run_sweep(h, 1, min_stepsize, 0);
+  if (!rc) rc = run_sweep(h, GLRM_COLS, min_stepsize, 0);
   if (!rc) rc = glrm_arrival_wait(h, 0, h->m); // (a shard without columns launches nothing: later work on the stream still follows the arrivals)
   h->arrival = nullptr;
   h->n_arrival = 0;
@@ -1008,35 +1014,32 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
 }
 
 // One prox-gradient step with a global step size and no line search (src/algorithms/sparse_proxgrad.jl:59-77, :81-99).
-static int gradstep(glrm_handle* h, int which, double alpha) {
+static int gradstep(glrm_handle* h, int side, double alpha) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   GLRM_REFUSE_F32(h, "glrm_hip_gradstep_x / glrm_hip_gradstep_y");
   if (!(alpha > 0.0)) return fail(GLRM_ERR_INVALID, "the step size must be positive");
   DeviceScope dg(h->device);
   h->fixed_alpha = alpha;
-  const int rc = run_sweep(h, which, 0.0, 0);
+  const int rc = run_sweep(h, side, 0.0, 0);
   h->fixed_alpha = 0.0;
   return rc;
 }
-extern "C" int glrm_hip_gradstep_x(glrm_handle* h, double alpha) { return gradstep(h, 0, alpha); }
-extern "C" int glrm_hip_gradstep_y(glrm_handle* h, double alpha) { return gradstep(h, 1, alpha); }
+extern "C" int glrm_hip_gradstep_x(glrm_handle* h, double alpha) { return gradstep(h, GLRM_ROWS, alpha); }
+extern "C" int glrm_hip_gradstep_y(glrm_handle* h, double alpha) { return gradstep(h, GLRM_COLS, alpha); }
 
 extern "C" int glrm_hip_col_losses(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, 1, 0.0, 1);
+  return run_sweep(h, GLRM_COLS, 0.0, 1);
 }
 
-static int run_penalty(glrm_handle* h, bool rows) {
+static int run_penalty(glrm_handle* h, int side) {
   int rc = ensure_owned(h);
   if (rc) return rc;
-  const int64_t nseg = rows ? h->ml : h->nl;
-  if (nseg <= 0) return GLRM_OK;
-  if (h->multi) return glrm_run_multi_penalty(h, rows);
-  if (h->storage == GLRM_STORAGE_F32) glrm_launch_penalty_f32(h, rows);
-  else hipLaunchKernelGGL(penalty_kernel<double>, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, h->stream, rows ? h->X : h->Y, h->kp,
-                     h->k, rows ? h->rb : h->cb, nseg, rows ? h->rx : h->ry, (rows ? h->n_rx : h->n_ry) == 1 ? 1 : 0,
-                     rows ? h->objrow : h->objcol);
+  if (h->side[side].nseg <= 0) return GLRM_OK;
+  if (h->multi) return glrm_run_multi_penalty(h, side);
+  if (h->storage == GLRM_STORAGE_F32) glrm_launch_penalty_f32(h, side);
+  else launch_penalty_st<double>(h, side);
   HIPCK(hipGetLastError());
   return GLRM_OK;
 }
@@ -1044,13 +1047,13 @@ static int run_penalty(glrm_handle* h, bool rows) {
 extern "C" int glrm_hip_row_penalties(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_penalty(h, true);
+  return run_penalty(h, GLRM_ROWS);
 }
 
 extern "C" int glrm_hip_col_penalties(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_penalty(h, false);
+  return run_penalty(h, GLRM_COLS);
 }
 
 extern "C" int glrm_hip_sum(glrm_handle* h, const void* dvec, int64_t n, double* out) {
@@ -1084,24 +1087,22 @@ extern "C" int glrm_hip_kernel_stats(glrm_handle* h, glrm_kernel_stats* out, int
   int rc = drain_events(h);
   if (rc) return rc;
   memset(out, 0, sizeof *out);
-  out->launches_x = h->launches_x; out->launches_y = h->launches_y;
-  out->ms_x = h->ms_x; out->ms_y = h->ms_y; out->ms_wait_y = h->ms_wait;
-  if ((rc = count_sum(h, h->trials_r, h->ml, &out->trials_x))) return rc;
-  if ((rc = count_sum(h, h->accepts_r, h->ml, &out->accepts_x))) return rc;
-  if ((rc = count_sum(h, h->trials_c, h->nl, &out->trials_y))) return rc;
-  if ((rc = count_sum(h, h->accepts_c, h->nl, &out->accepts_y))) return rc;
-  out->nnz_rows = h->nnz_r; out->nnz_cols = h->nnz_c;
-  out->waves_row = h->waves_row; out->waves_col = h->waves_col; out->ld = h->kp;
-  out->tiled = h->multi ? 8 : (h->tiled_row ? 1 : 0) | (h->tiled_col ? 2 : 0) | (h->dense ? 4 : 0) | (h->cached_row ? 64 : 0) | (h->blocked_row ? 16 : 0) |
-               (h->blocked_col ? 32 : 0) | (h->sum_order_opt ? 128 : 0) | (h->lane[0] ? 256 : 0) | (h->lane[1] ? 512 : 0); // bit8 / bit9: lane-per-segment form of the LDS-tiled row / column passes; bit0 / bit1: LDS-tiled row / column sweep, bit4 / bit5: phase-aligned gather passes, bit7: reference order
+  out->launches_x = h->side[GLRM_ROWS].launches; out->launches_y = h->side[GLRM_COLS].launches;
+  out->ms_x = h->side[GLRM_ROWS].ms; out->ms_y = h->side[GLRM_COLS].ms; out->ms_wait_y = h->ms_wait;
+  int64_t* const n_trials[2] = {&out->trials_x, &out->trials_y};
+  int64_t* const n_accepts[2] = {&out->accepts_x, &out->accepts_y};
+  for (int s = 0; s < 2; ++s) {
+    if ((rc = count_sum(h, h->side[s].trials, h->side[s].nseg, n_trials[s]))) return rc;
+    if ((rc = count_sum(h, h->side[s].accepts, h->side[s].nseg, n_accepts[s]))) return rc;
+  }
+  out->nnz_rows = h->side[GLRM_ROWS].nnz; out->nnz_cols = h->side[GLRM_COLS].nnz;
+  out->waves_row = h->side[GLRM_ROWS].waves; out->waves_col = h->side[GLRM_COLS].waves; out->ld = h->kp;
+  out->tiled = h->multi ? 8 : (h->side[GLRM_ROWS].tiled ? 1 : 0) | (h->side[GLRM_COLS].tiled ? 2 : 0) | (h->dense ? 4 : 0) | (h->cached_row ? 64 : 0) | (h->side[GLRM_ROWS].blocked ? 16 : 0) |
+               (h->side[GLRM_COLS].blocked ? 32 : 0) | (h->sum_order_opt ? 128 : 0) | (h->side[GLRM_ROWS].lane ? 256 : 0) | (h->side[GLRM_COLS].lane ? 512 : 0); // bit8 / bit9: lane-per-segment form of the LDS-tiled row / column passes; bit0 / bit1: LDS-tiled row / column sweep, bit4 / bit5: phase-aligned gather passes, bit7: reference order
   if (reset) {
-    h->launches_x = h->launches_y = 0;
-    h->ms_x = h->ms_y = h->ms_wait = 0;
-    const int64_t ml1 = h->ml > 0 ? h->ml : 1, nl1 = h->nl > 0 ? h->nl : 1;
-    HIPCK(hipMemsetAsync(h->trials_r, 0, ml1 * 4, h->stream));
-    HIPCK(hipMemsetAsync(h->accepts_r, 0, ml1 * 4, h->stream));
-    HIPCK(hipMemsetAsync(h->trials_c, 0, nl1 * 4, h->stream));
-    HIPCK(hipMemsetAsync(h->accepts_c, 0, nl1 * 4, h->stream));
+    for (glrm_handle::Side& v : h->side) { v.launches = 0; v.ms = 0; }
+    h->ms_wait = 0;
+    if ((rc = zero_counters(h))) return rc;
   }
   return GLRM_OK;
 }
@@ -1109,60 +1110,57 @@ extern "C" int glrm_hip_kernel_stats(glrm_handle* h, glrm_kernel_stats* out, int
 // The order in which this handle adds a segment's terms (include/glrm_hip.h: glrm_sum_order) -- a description of what the kernels of
 // the family that run_sweep dispatches do, read from the same handle fields.  The CPU oracle adopts it (glrm_cpu_set_sum_order) and then
 // lands on this engine's factors bit for bit: tests/test_gpu_sum_order.py.
-extern "C" int glrm_hip_sum_order(glrm_handle* h, int32_t which, glrm_sum_order* out) {
-  if (!h || !out || (which != 0 && which != 1)) return fail(GLRM_ERR_INVALID, "bad argument");
+extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_order* out) {
+  const glrm_handle* h = handle; // a query: nothing is written
+  if (!h || !out || (side != GLRM_ROWS && side != GLRM_COLS)) return fail(GLRM_ERR_INVALID, "bad argument");
   GLRM_NEED_FINALIZED(h);
-  const bool rows = which == 0;
+  const glrm_family fam = glrm_side_family(h, side, false);
   glrm_sum_order o{};
   o.cached_maxlen = -1;
   o.waves4_from = GLRM_WAVES4_FROM;
   o.waves8_from = GLRM_WAVES8_FROM;
   // the loss variant run_sweep instantiates: 0 = one QuadLoss, segment = one descriptor per segment, per-observation = rows of a heterogeneous model
-  const bool quad = h->loss_quad_uniform, per_obs = !quad && h->n_losses > 1 && rows;
-  const bool tiled = rows ? h->tiled_row != 0 : h->tiled_col != 0;
-  const bool blocked = rows ? h->blocked_row != 0 : h->blocked_col != 0;
-  if (!rows && (h->blocked_col || h->tiled_col) && !h->sum_order_opt && !h->multi && !h->dense) o.long_from = (int32_t)std::min<int64_t>(h->blk_long_from, INT32_MAX);
-  if (h->sum_order_opt) {
+  const bool quad = h->loss_quad_uniform, per_obs = !quad && h->n_losses > 1 && side == GLRM_ROWS;
+  if (side == GLRM_COLS && col_passes(h)) o.long_from = (int32_t)std::min<int64_t>(h->blk_long_from, INT32_MAX);
+  if (fam == GLRM_FAM_REFERENCE) {
     o.family = GLRM_ORDER_REFERENCE; // glrm_reforder.hip: one lane per segment, list order, one accumulator per sum
     o.lanes = 1; o.comps = h->kp;
-  } else if (h->multi || h->dense) {
+  } else if (fam == GLRM_FAM_GENERAL || fam == GLRM_FAM_DENSE) {
     o.family = GLRM_ORDER_OTHER;
-  } else if (tiled) {
+  } else if (fam == GLRM_FAM_TILED) {
     const int T = glrm_tile_rows(h->kp); // vectors per staged tile
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->tG; o.comps = h->tR;
     o.window = T;
-    o.windows_per_sup = rows ? 0 : h->pass[1].tiles_per_sup; // (rows: one super-tile, nothing re-added = 0)
+    o.windows_per_sup = side == GLRM_ROWS ? 0 : h->side[side].pass.tiles_per_sup; // (rows: one super-tile, nothing re-added = 0)
     o.batch = (!quad && (h->tG == 4 || h->tG == 8)) ? h->tG : 2;
-    o.rotate = (!rows && !quad && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
+    o.rotate = (side == GLRM_COLS && !quad && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
     // a private copy in another order: lists the engine tile-sorted, rows regrouped by loss kind inside the tile windows
-    const bool sorted_here = rows ? h->sig_local.rows_unordered != 0 : h->sig_local.cols_unordered != 0;
-    const bool grouped = rows && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !h->lane[0]; // glrm_tiled.hpp: group_rows_by_kind_kernel (lane rows keep the caller's order)
+    const bool sorted_here = side == GLRM_ROWS ? h->sig_local.rows_unordered != 0 : h->sig_local.cols_unordered != 0;
+    const bool grouped = side == GLRM_ROWS && h->n_losses > 1 && h->side[GLRM_ROWS].nnz > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !h->side[GLRM_ROWS].lane; // glrm_tiled.hpp: group_rows_by_kind_kernel (lane rows keep the caller's order)
     o.private_order = sorted_here ? 1 : grouped ? 2 : 0; // (2: stable grouping by ascending loss kind inside every window -- the oracle restates it)
-    if (h->lane[rows ? 0 : 1]) { // lane-per-segment passes (glrm_lane.hpp): two fma chains over the even / odd chunks = the two-lane layout, rotated walk
+    if (h->side[side].lane) { // lane-per-segment passes (glrm_lane.hpp): two fma chains over the even / odd chunks = the two-lane layout, rotated walk
       o.lanes = 2; o.comps = h->kp / 2;
       o.batch = 2;
       o.rotate = 2;
       o.window = T;
-      o.windows_per_sup = rows ? 0 : h->pass[1].tiles_per_sup;
+      o.windows_per_sup = side == GLRM_ROWS ? 0 : h->side[side].pass.tiles_per_sup;
     }
-  } else if (blocked) {
+  } else if (fam == GLRM_FAM_BLOCKED) {
     o.family = GLRM_ORDER_WINDOWED;
     o.lanes = h->G; o.comps = h->R;
-    o.window = (int64_t)glrm_tile_rows(h->kp) * h->pass[rows ? 0 : 1].tiles_per_sup; // one walk per super-tile: the super-tile is the window
+    o.window = (int64_t)glrm_tile_rows(h->kp) * h->side[side].pass.tiles_per_sup; // one walk per super-tile: the super-tile is the window
     o.windows_per_sup = 1;
     o.batch = (!quad && (h->G == 4 || h->G == 8)) ? h->G : 2;
   } else {
     o.family = GLRM_ORDER_STRIDED;
     o.lanes = h->G; o.comps = h->R;
-    const int forced = rows ? h->opts.waves_row : h->opts.waves_col;
+    const int forced = side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col;
     o.waves = (forced == 1 || forced == 4 || forced == 8) ? forced : 0;
-    if (rows && h->cached_want) { // which rows the cached sweep takes is a function of the row's own length
-      const int keep = h->cached_row;   // 0 on a shard that holds no such row: the variant is still the whole problem's
-      if (!keep) h->cached_row = glrm_cached_variant(h);
-      o.cached_maxlen = glrm_cached_maxlen(h);
-      o.cached_waves = h->cached_row == 2 ? glrm_cached_waves(h) : 1;
-      h->cached_row = keep;
+    if (side == GLRM_ROWS && h->cached_want) { // which rows the cached sweep takes is a function of the row's own length
+      const int variant = h->cached_row ? h->cached_row : glrm_cached_variant(h); // 0 on a shard that holds no such row: the variant is still the whole problem's
+      o.cached_maxlen = glrm_cached_maxlen(h, variant);
+      o.cached_waves = variant == 2 ? glrm_cached_waves(h) : 1;
     }
     // four observations per trip with one loss evaluation per lane (sweep_pass: SCATTER): G == 4 and not the uniform QuadLoss kernel;
     // the per-segment variant only on one-wave segments (launch_sweep_loss)
@@ -1187,13 +1185,13 @@ static int device_objective(glrm_handle* h, int include_reg, double* out) {
     if ((rc = ensure_owned(h))) return rc;
     return glrm_reforder_objective(h, include_reg, out);
   }
-  if ((rc = run_sweep(h, 1, 0.0, 1))) return rc;
-  if ((rc = glrm_hip_sum(h, h->objcol, h->n, &loss))) return rc;
+  if ((rc = run_sweep(h, GLRM_COLS, 0.0, 1))) return rc;
+  if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &loss))) return rc;
   if (include_reg) {
-    if ((rc = run_penalty(h, true))) return rc;
-    if ((rc = glrm_hip_sum(h, h->objrow, h->m, &px))) return rc;
-    if ((rc = run_penalty(h, false))) return rc;
-    if ((rc = glrm_hip_sum(h, h->objcol, h->n, &py))) return rc;
+    if ((rc = run_penalty(h, GLRM_ROWS))) return rc;
+    if ((rc = glrm_hip_sum(h, h->side[GLRM_ROWS].obj, h->m, &px))) return rc;
+    if ((rc = run_penalty(h, GLRM_COLS))) return rc;
+    if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &py))) return rc;
   }
   *out = loss + (px + py);
   return GLRM_OK;
@@ -1211,8 +1209,8 @@ extern "C" int glrm_hip_objective(glrm_handle* h, const double* X, const double*
 // One outer iteration as a hipGraph.  Eligible: gather sweeps (fixed launch sequence, no host round trips inside a half-step) on
 // the handle's private stream (the legacy default stream cannot be captured), no per-launch event timing.
 static bool graph_eligible(const glrm_handle* h) {
-  return h->own_stream && !h->profile && !h->multi && !h->dense && !h->sum_order_opt && !h->tiled_row && !h->tiled_col && !h->blocked_row && !h->blocked_col && !h->cached_row &&
-         env_int("GLRM_HIP_GRAPH", 1) != 0;
+  return h->own_stream && !h->profile && glrm_side_family(h, GLRM_ROWS, false) == GLRM_FAM_GATHER && glrm_side_family(h, GLRM_COLS, false) == GLRM_FAM_GATHER &&
+         !h->cached_row && env_int("GLRM_HIP_GRAPH", 1) != 0;
 }
 
 static int build_iteration_graph(glrm_handle* h, const glrm_params* prm) {
@@ -1227,16 +1225,16 @@ static int build_iteration_graph(glrm_handle* h, const glrm_params* prm) {
   HIPCK(hipStreamSynchronize(h->stream));
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return GLRM_OK; } // no graph: plain launches
   bool ok = true;
-  const int64_t lx = h->launches_x, ly = h->launches_y;
+  const int64_t lx = h->side[GLRM_ROWS].launches, ly = h->side[GLRM_COLS].launches;
   if (prm->inner_iter_X > 1 || prm->inner_iter_Y > 1) ok = ok && glrm_hip_reset_stepsizes(h, prm->stepsize) == GLRM_OK;
-  for (int64_t in = 0; ok && in < prm->inner_iter_X; ++in) ok = run_sweep(h, 0, prm->min_stepsize, 0) == GLRM_OK;
-  for (int64_t in = 0; ok && in < prm->inner_iter_Y; ++in) ok = run_sweep(h, 1, prm->min_stepsize, 0) == GLRM_OK;
+  for (int64_t in = 0; ok && in < prm->inner_iter_X; ++in) ok = run_sweep(h, GLRM_ROWS, prm->min_stepsize, 0) == GLRM_OK;
+  for (int64_t in = 0; ok && in < prm->inner_iter_Y; ++in) ok = run_sweep(h, GLRM_COLS, prm->min_stepsize, 0) == GLRM_OK;
   if (ok) {
-    hipLaunchKernelGGL(sum_stage1, dim3(SUM_BLOCKS), dim3(SUM_THREADS), 0, h->stream, (const double*)h->objcol, h->n, h->partials);
+    hipLaunchKernelGGL(sum_stage1, dim3(SUM_BLOCKS), dim3(SUM_THREADS), 0, h->stream, (const double*)h->side[GLRM_COLS].obj, h->n, h->partials);
     hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(SUM_THREADS), 0, h->stream, h->partials, h->dscalar);
     ok = hipMemcpyAsync(h->pinned_obj, h->dscalar, 8, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
   }
-  h->launches_x = lx; h->launches_y = ly; // capturing is not launching
+  h->side[GLRM_ROWS].launches = lx; h->side[GLRM_COLS].launches = ly; // capturing is not launching
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(h->stream, &g);
   if (!ok || ec != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return GLRM_OK; }
@@ -1259,7 +1257,7 @@ extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, d
   int rc;
   if ((rc = glrm_hip_set_factors(h, X, Y))) return rc;                 // X = glrm.X; Y = glrm.Y (:43)
   if ((rc = glrm_hip_reset_stepsizes(h, prm->stepsize))) return rc;   // :69-70
-  const double scaled_abs_tol = prm->abs_tol * (double)h->nnz_r;       // :72 (observed_features)
+  const double scaled_abs_tol = prm->abs_tol * (double)h->side[GLRM_ROWS].nnz;       // :72 (observed_features)
   int64_t nrec = 0;
   if ((rc = device_objective(h, 1, &objective[0]))) return rc;        // update_ch!(ch, 0, objective(...)) :76
   seconds[0] = 0.0;
@@ -1273,15 +1271,15 @@ extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, d
       HIPCK(hipGraphLaunch(h->iter_exec, h->stream));
       HIPCK(hipStreamSynchronize(h->stream));
       obj = *h->pinned_obj;
-      h->launches_x += prm->inner_iter_X; h->launches_y += prm->inner_iter_Y;
+      h->side[GLRM_ROWS].launches += prm->inner_iter_X; h->side[GLRM_COLS].launches += prm->inner_iter_Y;
     } else {
       if (prm->inner_iter_X > 1 || prm->inner_iter_Y > 1)
         if ((rc = glrm_hip_reset_stepsizes(h, prm->stepsize))) return rc; // :112-115
       for (int64_t in = 0; in < prm->inner_iter_X; ++in)
-        if ((rc = run_sweep(h, 0, prm->min_stepsize, 0))) return rc;    // :117-158
+        if ((rc = run_sweep(h, GLRM_ROWS, prm->min_stepsize, 0))) return rc;    // :117-158
       for (int64_t in = 0; in < prm->inner_iter_Y; ++in)
-        if ((rc = run_sweep(h, 1, prm->min_stepsize, 0))) return rc;    // :160-203
-      if ((rc = glrm_hip_sum(h, h->objcol, h->n, &obj))) return rc;     // obj = sum(obj_by_col) :205
+        if ((rc = run_sweep(h, GLRM_COLS, prm->min_stepsize, 0))) return rc;    // :160-203
+      if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &obj))) return rc;     // obj = sum(obj_by_col) :205
     }
     const double dt = now_s() - t;
     objective[nrec] = obj;
@@ -1315,11 +1313,11 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   DevArena scratch;
   double *bestX = nullptr, *bestY = nullptr;
   if ((rc = scratch.alloc(&bestX, xb / 8)) || (rc = scratch.alloc(&bestY, yb / 8))) return rc;
-  if (hipMemcpyAsync(bestX, h->X, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(bestY, h->Y, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+  if (hipMemcpyAsync(bestX, h->side[GLRM_ROWS].factor, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(bestY, h->side[GLRM_COLS].factor, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
     return fail(GLRM_ERR_HIP, "device copy failed");
   double alpha = prm->stepsize;                              // :46
-  const double tol = prm->abs_tol * (double)h->nnz_r;        // :48
+  const double tol = prm->abs_tol * (double)h->side[GLRM_ROWS].nnz;        // :48
   int64_t nrec = 0;
   if ((rc = device_objective(h, 1, &objective[0]))) return rc; // update_ch!(ch, 0, objective(glrm; sparse=true)) :52
   seconds[0] = 0.0;
@@ -1327,8 +1325,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   double t = now_s();
   int64_t steps_in_a_row = 0;
   for (int64_t i = 1; i <= prm->max_iter; ++i) {
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 0, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, 1, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
+    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, GLRM_ROWS, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
+    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, GLRM_COLS, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
     double obj = 0.0;
     if ((rc = device_objective(h, 1, &obj))) return rc; // :102
     if (obj < objective[nrec - 1]) {                              // :104-110
@@ -1336,8 +1334,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
       objective[nrec] = obj;
       seconds[nrec] = seconds[nrec - 1] + dt;
       ++nrec;
-      if (hipMemcpyAsync(bestX, h->X, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(bestY, h->Y, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+      if (hipMemcpyAsync(bestX, h->side[GLRM_ROWS].factor, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+          hipMemcpyAsync(bestY, h->side[GLRM_COLS].factor, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
         return fail(GLRM_ERR_HIP, "device copy failed");
       alpha = alpha * 1.05;
       steps_in_a_row = steps_in_a_row + 1 > 1 ? steps_in_a_row + 1 : 1;
@@ -1345,8 +1343,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
     } else {                                                      // :111-117
       const double div = -(double)steps_in_a_row > 1.5 ? -(double)steps_in_a_row : 1.5;
       alpha = alpha / div;
-      if (hipMemcpyAsync(h->X, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(h->Y, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+      if (hipMemcpyAsync(h->side[GLRM_ROWS].factor, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+          hipMemcpyAsync(h->side[GLRM_COLS].factor, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
         return fail(GLRM_ERR_HIP, "device copy failed");
       steps_in_a_row = steps_in_a_row - 1 < 0 ? steps_in_a_row - 1 : 0;
     }
@@ -1358,8 +1356,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   seconds[nrec] = seconds[nrec - 1] + (now_s() - t);
   ++nrec;
   // glrm.X, glrm.Y are the best model found
-  if (hipMemcpyAsync(h->X, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(h->Y, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+  if (hipMemcpyAsync(h->side[GLRM_ROWS].factor, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(h->side[GLRM_COLS].factor, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
     return fail(GLRM_ERR_HIP, "device copy failed");
   rc = glrm_hip_get_factors(h, X, Y);
   *n_recorded = nrec;

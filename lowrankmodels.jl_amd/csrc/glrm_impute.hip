@@ -123,9 +123,9 @@ int prepare(glrm_handle* h, const double* X, const double* Y, const glrm_domain*
   if ((rc = scratch.alloc(&ddom, (size_t)h->n)) || (rc = scratch.alloc(&a.bad, 1))) return rc;
   HIPCK(hipMemcpyAsync(ddom, domains, (size_t)h->n * sizeof(glrm_domain), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemsetAsync(a.bad, 0, sizeof(int), h->stream));
-  a.colptr = h->colptr; a.rowidx = h->rowidx; a.colvals = h->colvals;
+  a.colptr = h->side[GLRM_COLS].ptr; a.rowidx = h->side[GLRM_COLS].idx; a.colvals = h->side[GLRM_COLS].vals;
   a.losses = h->losses; a.loss_single = h->n_losses == 1 ? 1 : 0; a.ystart = h->ystart; a.domains = ddom;
-  a.X = h->X; a.Y = h->Y; a.k = h->k; a.kp = h->kp; a.dmax = h->dmax; a.m = h->m;
+  a.X = h->side[GLRM_ROWS].factor; a.Y = h->side[GLRM_COLS].factor; a.k = h->k; a.kp = h->kp; a.dmax = h->dmax; a.m = h->m;
   return GLRM_OK;
 }
 
@@ -142,7 +142,7 @@ extern "C" int glrm_hip_error_metric(glrm_handle* h, const double* X, const doub
   int rc = prepare(h, X, Y, domains, a, scratch);
   if (rc) return rc;
   std::vector<int64_t> cp((size_t)h->n + 1);
-  if (hipMemcpyAsync(cp.data(), h->colptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+  if (hipMemcpyAsync(cp.data(), h->side[GLRM_COLS].ptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
       hipStreamSynchronize(h->stream) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
   int64_t longest = 0;
   for (int64_t f = 0; f < h->n; ++f) longest = cp[f + 1] - cp[f] > longest ? cp[f + 1] - cp[f] : longest;

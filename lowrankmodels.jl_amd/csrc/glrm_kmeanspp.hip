@@ -271,7 +271,7 @@ extern "C" int glrm_hip_init_kmeanspp(glrm_handle* h, double* Y, int64_t first_c
   HIPCK(hipMemsetAsync(w.lastpos, 0, (size_t)n * 8, st));
 
   KmArgs a{};
-  a.rowptr = h->rowptr; a.colidx = h->colidx; a.rowvals = h->rowvals;
+  a.rowptr = h->side[GLRM_ROWS].ptr; a.colidx = h->side[GLRM_ROWS].idx; a.rowvals = h->side[GLRM_ROWS].vals;
   a.losses = h->losses; a.loss_single = h->n_losses == 1 ? 1 : 0;
   a.m = m; a.n = n; a.k = k;
   a.Y = w.Y; a.c = w.c; a.best = w.best; a.centers = w.centers; a.lastpos = w.lastpos;

@@ -69,11 +69,11 @@ int launch_lane_tail(int loss, const TiledArgs& a, const int32_t* list, int64_t 
 }
 
 // the small kernels of the pass machinery in the two-lane layout the family's sums are reported in
-void launch_small(int which, const TiledArgs& a, hipStream_t st) {
+void launch_small(int stage, const TiledArgs& a, hipStream_t st) {
   constexpr int G = 2, R = 16;
   const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
-  if (which == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
-  else if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+  if (stage == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
+  else if (stage == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
   else if (a.vecreg) hipLaunchKernelGGL((col_decide_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
 }
@@ -102,112 +102,108 @@ bool glrm_lane_few_descriptors(const glrm_handle* h) {
 }
 
 // what does not depend on the buffers: padded rank, losses, view size -- all of the WHOLE problem
-bool glrm_lane_wants(const glrm_handle* h, bool rows) {
+bool glrm_lane_wants(const glrm_handle* h, int side) {
   const int want = env_int("GLRM_HIP_LANE", 3); // bit0 rows, bit1 columns
-  if (!((want >> (rows ? 0 : 1)) & 1) || h->kp != 32 || h->multi || h->dense || h->sum_order_opt) return false;
+  if (!((want >> side) & 1) || h->kp != 32 || h->multi || h->dense || h->sum_order_opt) return false;
   // a loss per column: the row view meets a descriptor per observation -- through one-byte ids, i.e. at most 256 distinct descriptors.
   // Default since session r6_33 (GLRM_HIP_LANE_PER_OBS=0 keeps such rows on the four-lane kernels): with the trial rounds read out of the
   // SELL layout (glrm_run_lane) the C5 recipe's X half-step is 42.5 against 46.6 ms at 1M rows and 194 against 215 ms at its stated size.
   // (Session r6_19/20, rounds on the CSR form: 64.4 against 45.8 ms -- opt-in then.)
-  if (rows && h->n_losses > 1 && (!env_int("GLRM_HIP_UDESC", 1) || !env_int("GLRM_HIP_LANE_PER_OBS", 1) || !glrm_lane_few_descriptors(h))) return false;
+  if (side == GLRM_ROWS && h->n_losses > 1 && (!env_int("GLRM_HIP_UDESC", 1) || !env_int("GLRM_HIP_LANE_PER_OBS", 1) || !glrm_lane_few_descriptors(h))) return false;
   // the SELL copy is 12 B x its padding per observation on top of the lists: a memory policy per view (rows: the copy REPLACES the kind-grouped
   // private row view of such models, and rows pad little; columns pad x 1.5-1.8).  C5 at its stated size: 5e9 observations per view
   // (columns beyond 2e9 observations: the COMPACT form of the stream -- 2-byte offsets, unpadded values, 11.5 instead of 21 B per observation at
   // x 1.76 padding; GLRM_HIP_LANE_COMPACT = 0 never, 1 every side it serves, 2 (default) views beyond 2e9 observations)
-  const int64_t max_nnz = (int64_t)env_int(rows ? "GLRM_HIP_LANE_MAX_NNZ_ROWS_M" : "GLRM_HIP_LANE_MAX_NNZ_M", rows || env_int("GLRM_HIP_LANE_COMPACT", 2) ? 6000 : 2000) * 1000000ll;
-  return (rows ? h->sig.nnz_rows : h->sig.nnz_cols) <= max_nnz;
+  const int64_t max_nnz = (int64_t)env_int(side == GLRM_ROWS ? "GLRM_HIP_LANE_MAX_NNZ_ROWS_M" : "GLRM_HIP_LANE_MAX_NNZ_M", side == GLRM_ROWS || env_int("GLRM_HIP_LANE_COMPACT", 2) ? 6000 : 2000) * 1000000ll;
+  return (side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols) <= max_nnz;
 }
 
 // finalize, after glrm_setup_tiled has chosen the LDS tiles and built the slot permutations: decide the family per side and build its SELL layout
 int glrm_setup_lane(glrm_handle* h) {
-  h->lane[0] = h->lane[1] = 0;
+  for (glrm_handle::Side& v : h->side) v.lane = 0;
   int64_t gseg_max = 0;
   const int T = glrm_tile_rows(h->kp);
   hipStream_t st = h->stream;
   for (int side = 0; side < 2; ++side) {
-    const bool rows = side == 0;
-    if (!glrm_lane_wants(h, rows)) continue;
-    if (rows ? !(h->tiled_row && (h->tile_rounds & 1) && h->actlist && h->pass[0].part) : !h->tiled_col) continue;
-    if (rows && h->n_losses > 1 && !(h->rowdescid && h->n_udesc > 0)) continue;
-    h->lane[side] = 1;
-    const int64_t nseg = rows ? h->ml : h->nl;
-    const int64_t nslots = rows ? nseg : (h->blk_nlong_c > 0 ? h->blk_nshort_c : nseg);
-    const int64_t nother = rows ? h->n : h->m;
+    glrm_handle::Side& v = h->side[side];
+    if (!glrm_lane_wants(h, side)) continue;
+    if (side == GLRM_ROWS ? !(v.tiled && (h->tile_rounds & 1) && h->actlist && v.pass.part) : !v.tiled) continue;
+    if (side == GLRM_ROWS && h->n_losses > 1 && !(h->rowdescid && h->n_udesc > 0)) continue;
+    v.lane = 1;
+    const int64_t nseg = v.nseg;
+    const int64_t nslots = side == GLRM_ROWS ? nseg : (h->blk_nlong_c > 0 ? h->blk_nshort_c : nseg);
+    const int64_t nother = h->side[side ^ 1].nglob;
     const int ntiles = (int)((nother + T - 1) / T);
     const int64_t nwb = (nslots + 63) / 64;
-    h->lane_nwb[side] = nwb;
-    h->lane_ntiles[side] = ntiles;
+    v.lane_nwb = nwb;
+    v.lane_ntiles = ntiles;
     if (nwb == 0 || ntiles == 0) continue;
-    const int64_t* ptr = rows ? h->rowptr : h->colptr;
-    const int32_t* idx = rows ? h->colidx : h->rowidx;
-    const double* vals = rows ? h->rowvals : h->colvals;
-    const int32_t* perm = rows ? h->rowperm : h->colperm;
     const int64_t ncell = nwb * ntiles;
-    if (ncell > (int64_t)1 << 30) { h->lane[side] = 0; continue; } // (cannot happen at shapes the LDS tiles are chosen for)
+    if (ncell > (int64_t)1 << 30) { v.lane = 0; continue; } // (cannot happen at shapes the LDS tiles are chosen for)
     // the compact form of the stream for this side?  A function of the whole problem (view size, losses, options), like the family itself
     const int cmode = env_int("GLRM_HIP_LANE_COMPACT", 2);
-    const bool compact = !(rows && h->n_losses > 1) && (cmode == 1 || (cmode == 2 && (rows ? h->sig.nnz_rows : h->sig.nnz_cols) > 2000000000ll)) &&
-                         64 * (rows ? h->sig.max_row_len : h->sig.max_col_len) < ((int64_t)1 << 31); // (a wave block's values are counted in 31 bits: LaneArgs::sval)
+    const bool compact = !(side == GLRM_ROWS && h->n_losses > 1) && (cmode == 1 || (cmode == 2 && (side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols) > 2000000000ll)) &&
+                         64 * (side == GLRM_ROWS ? h->sig.max_row_len : h->sig.max_col_len) < ((int64_t)1 << 31); // (a wave block's values are counted in 31 bits: LaneArgs::sval)
     int64_t *cnt = nullptr, *scan = nullptr, *vcnt = nullptr;
     char* tmp = nullptr;
     DevArena scratch; // the counts and scans of this side's build
     int rc;
     if ((rc = scratch.alloc(&cnt, (size_t)ncell)) || (rc = scratch.alloc(&scan, (size_t)ncell)) || (compact && (rc = scratch.alloc(&vcnt, (size_t)ncell)))) return rc;
-    hipLaunchKernelGGL(lane_count_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, perm, nslots, T, ntiles, cnt, vcnt);
+    hipLaunchKernelGGL(lane_count_kernel, dim3((unsigned)nwb), dim3(64), 0, st, v.ptr, v.idx, v.perm, nslots, T, ntiles, cnt, vcnt);
     size_t bytes = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan (size query) failed");
     if ((rc = scratch.alloc(&tmp, bytes))) return rc;
     if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
     const int64_t nb = nwb * (ntiles + 1);
-    if ((rc = h->mem.alloc(&h->lane_bptr[side], (size_t)nb))) return rc;
-    hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, cnt, nwb, ntiles, h->lane_bptr[side]);
+    if ((rc = h->mem.alloc(&v.lane_bptr, (size_t)nb))) return rc;
+    hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, cnt, nwb, ntiles, v.lane_bptr);
     int64_t last[2] = {0, 0};
     if (hipMemcpyAsync(&last[0], scan + ncell - 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(&last[1], cnt + ncell - 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       return fail(GLRM_ERR_HIP, "lane layout: copy failed");
     const int64_t steps = last[0] + last[1];
-    h->lane_steps[side] = steps;
+    v.lane_steps = steps;
     const int64_t s1 = steps > 0 ? steps : 1;
     if (compact) {
       // values before every (wave block, tile): the same scan over the observation counts (the step scan's scratch serves again)
       if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, vcnt, scan, (int)ncell, st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
-      if ((rc = h->mem.alloc(&h->lane_vptr[side], (size_t)nb))) return rc;
-      hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, vcnt, nwb, ntiles, h->lane_vptr[side]);
-      const int64_t nv = std::max<int64_t>(1, rows ? h->nnz_r : h->nnz_c);
-      const bool ok = !h->mem.alloc(&h->lane_off16[side], (size_t)s1 * 64) && !h->mem.alloc(&h->lane_sval[side], (size_t)s1) && !h->mem.alloc(&h->lane_val[side], (size_t)nv);
+      if ((rc = h->mem.alloc(&v.lane_vptr, (size_t)nb))) return rc;
+      hipLaunchKernelGGL(lane_bptr_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, scan, vcnt, nwb, ntiles, v.lane_vptr);
+      const int64_t nv = std::max<int64_t>(1, v.nnz);
+      const bool ok = !h->mem.alloc(&v.lane_off16, (size_t)s1 * 64) && !h->mem.alloc(&v.lane_sval, (size_t)s1) && !h->mem.alloc(&v.lane_val, (size_t)nv);
       if (!ok) {
         // No room for the stream beside the lists: the side stays on the four-lane kernels.  (The only family choice that can depend on
         // the device rather than on the problem; glrm_hip_sum_order reports what runs, and the super-tile geometry is already fixed.)
         (void)hipGetLastError();
-        h->mem.release(&h->lane_off16[side]); h->mem.release(&h->lane_sval[side]); h->mem.release(&h->lane_val[side]); h->mem.release(&h->lane_vptr[side]); h->mem.release(&h->lane_bptr[side]);
-        h->lane[side] = 0;
-        h->lane_steps[side] = 0;
-        fprintf(stderr, "[glrm lane] no device memory for the compact stream of the %s view (%.1f GB): the view stays on the four-lane LDS-tiled kernels\n", rows ? "row" : "column",
+        h->mem.release(&v.lane_off16); h->mem.release(&v.lane_sval); h->mem.release(&v.lane_val); h->mem.release(&v.lane_vptr); h->mem.release(&v.lane_bptr);
+        v.lane = 0;
+        v.lane_steps = 0;
+        fprintf(stderr, "[glrm lane] no device memory for the compact stream of the %s view (%.1f GB): the view stays on the four-lane LDS-tiled kernels\n", side == GLRM_ROWS ? "row" : "column",
                 ((double)s1 * 128 + (double)nv * 8) / 1e9);
         continue;
       }
-      hipLaunchKernelGGL(lane_fill_compact_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, vals, perm, nslots, T, ntiles, h->lane_bptr[side], h->lane_vptr[side],
-                         h->lane_off16[side], h->lane_sval[side], h->lane_val[side]);
+      hipLaunchKernelGGL(lane_fill_compact_kernel, dim3((unsigned)nwb), dim3(64), 0, st, v.ptr, v.idx, v.vals, v.perm, nslots, T, ntiles, v.lane_bptr, v.lane_vptr,
+                         v.lane_off16, v.lane_sval, v.lane_val);
     } else {
       char oom[160];
-      snprintf(oom, sizeof oom, "out of device memory for the lane-per-segment stream of the %s view (%lld steps of 64 entries)", rows ? "row" : "column", (long long)steps);
-      if ((rc = h->mem.alloc(&h->lane_off[side], (size_t)s1 * 64, oom)) || (rc = h->mem.alloc(&h->lane_val[side], (size_t)s1 * 64, oom))) return rc;
-      hipLaunchKernelGGL(lane_fill_kernel, dim3((unsigned)nwb), dim3(64), 0, st, ptr, idx, vals, (rows && h->n_losses > 1) ? h->rowdescid : nullptr, perm, nslots, T, ntiles,
-                         h->kp * 8, h->lane_bptr[side], h->lane_off[side], h->lane_val[side]);
+      snprintf(oom, sizeof oom, "out of device memory for the lane-per-segment stream of the %s view (%lld steps of 64 entries)", side == GLRM_ROWS ? "row" : "column", (long long)steps);
+      if ((rc = h->mem.alloc(&v.lane_off, (size_t)s1 * 64, oom)) || (rc = h->mem.alloc(&v.lane_val, (size_t)s1 * 64, oom))) return rc;
+      hipLaunchKernelGGL(lane_fill_kernel, dim3((unsigned)nwb), dim3(64), 0, st, v.ptr, v.idx, v.vals, (side == GLRM_ROWS && h->n_losses > 1) ? h->rowdescid : nullptr, v.perm, nslots, T, ntiles,
+                         h->kp * 8, v.lane_bptr, v.lane_off, v.lane_val);
     }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "lane layout: build failed");
     scratch.free_all();
-    if (perm) { // FORM 2 of the rounds finds a segment's slot through the inverse of the slot permutation
-      if ((rc = h->mem.alloc(&h->lane_inv[side], (size_t)nseg))) return rc;
-      HIPCK(hipMemsetAsync(h->lane_inv[side], 0xFF, (size_t)nseg * 4, st));
-      hipLaunchKernelGGL(lane_inv_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, perm, nslots, h->lane_inv[side]);
+    if (v.perm) { // FORM 2 of the rounds finds a segment's slot through the inverse of the slot permutation
+      if ((rc = h->mem.alloc(&v.lane_inv, (size_t)nseg))) return rc;
+      HIPCK(hipMemsetAsync(v.lane_inv, 0xFF, (size_t)nseg * 4, st));
+      hipLaunchKernelGGL(lane_inv_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, v.perm, nslots, v.lane_inv);
       HIPCK(hipGetLastError());
     }
     if (nseg > gseg_max) gseg_max = nseg;
     if (env_int("GLRM_HIP_LANE_TRACE", 0))
-      fprintf(stderr, "[glrm lane] %s view: %lld slots in %lld wave blocks x %d tiles, %lld steps of 64 = %.3f x the %lld observations%s\n", rows ? "row" : "column",
-              (long long)nslots, (long long)nwb, ntiles, (long long)steps, (double)steps * 64.0 / (double)std::max<int64_t>(1, rows ? h->nnz_r : h->nnz_c),
-              (long long)(rows ? h->nnz_r : h->nnz_c), compact ? " (compact stream: 2-byte offsets padded, values unpadded)" : "");
+      fprintf(stderr, "[glrm lane] %s view: %lld slots in %lld wave blocks x %d tiles, %lld steps of 64 = %.3f x the %lld observations%s\n", side == GLRM_ROWS ? "row" : "column",
+              (long long)nslots, (long long)nwb, ntiles, (long long)steps, (double)steps * 64.0 / (double)std::max<int64_t>(1, v.nnz),
+              (long long)v.nnz, compact ? " (compact stream: 2-byte offsets padded, values unpadded)" : "");
   }
   if (gseg_max > 0 && !h->lane_glist) { // the wave lists of the rounds (one set serves both sides: a half-step at a time)
     h->lane_gchunks = (gseg_max + LANE_CC - 1) / LANE_CC;
@@ -222,33 +218,28 @@ int glrm_setup_lane(glrm_handle* h) {
 
 // One half-step (or the evaluation pass of the column view) on the lane-per-segment passes.  `a` comes prepared by glrm_run_tiled: the side's
 // views, factors, pass buffers, slot permutation and -- rows of a sub-range sweep -- everything offset to the range's first row.
-int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, double min_stepsize, int eval_only) {
+int glrm_run_lane(glrm_handle* h, int side, int loss, const TiledArgs& a_in, double min_stepsize, int eval_only) {
   TiledArgs a = a_in;
-  const int side = rows ? 0 : 1;
   hipStream_t st = h->stream;
   LaneArgs la{};
-  la.bptr = h->lane_bptr[side];
-  la.off = h->lane_off[side];
-  la.val = h->lane_val[side];
-  la.off16 = h->lane_off16[side];
-  la.vptr = h->lane_vptr[side];
-  la.sval = h->lane_sval[side];
-  la.ntiles = h->lane_ntiles[side];
-  la.nwb = h->lane_nwb[side];
+  const glrm_handle::Side& v = h->side[side];
+  la.bptr = v.lane_bptr; la.off = v.lane_off; la.val = v.lane_val;
+  la.off16 = v.lane_off16; la.vptr = v.lane_vptr; la.sval = v.lane_sval;
+  la.ntiles = v.lane_ntiles; la.nwb = v.lane_nwb;
   la.slot0 = 0;
-  la.inv = h->lane_inv[side];
+  la.inv = v.lane_inv;
   la.glist = h->lane_glist;
   la.gwaves = 0;
   (void)min_stepsize;
   // does the SELL layout cover this launch?  It was built on the side's full slot space (slot permutation included); a row sub-range
   // (glrm_hip_step_x_range) is covered when the slots are the rows themselves: its wave blocks run with the lanes outside the range masked
-  const bool range = rows && h->rng_e >= 0;
-  const bool sell_ok = !range || h->rowperm == nullptr;
+  const bool range = side == GLRM_ROWS && h->rng_e >= 0;
+  const bool sell_ok = !range || v.perm == nullptr;
   if (range) la.slot0 = h->rng_b;
   const int64_t nslots = a.npass > 0 ? a.npass : a.nseg;
   const int64_t blk_lo = la.slot0 / 64, blk_hi = (la.slot0 + nslots + 63) / 64;
   int rc;
-  const glrm_act_lists lists = glrm_active_lists(h, rows, a.nseg);
+  const glrm_act_lists lists = glrm_active_lists(h, side, a.nseg);
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, st));
   a.actlist_out = lists.list[0];
   auto csr_args = [&](const TiledArgs& t) { // the CSR form numbers its slots from 0 over t.nseg (a compact list or a plain range)
@@ -266,13 +257,13 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
     r.npass = 0;
     return launch_lane_loss<true, 1>(loss, r, csr_args(r), (r.nseg + 63) / 64, st);
   };
-  rc = rows ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), grad); // (rows read Y: complete)
+  rc = side == GLRM_ROWS ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), grad); // (rows read Y: complete)
   if (rc) return rc;
   launch_small(0, a, st);
   HIPCK(hipGetLastError());
   if (eval_only) return GLRM_OK;
   const TiledArgs full = a;
-  const bool gather = env_int("GLRM_HIP_LANE_ROUNDS", 1) != 0 && sell_ok && h->lane_glist && la.bptr && h->lane_steps[side] > 0 &&
+  const bool gather = env_int("GLRM_HIP_LANE_ROUNDS", 1) != 0 && sell_ok && h->lane_glist && la.bptr && h->side[side].lane_steps > 0 &&
                       full.nseg <= h->lane_gchunks * (int64_t)LANE_CC;
   // the round's trial pass in whichever form fits the fraction of segments that still searches; `list` holds them (nullptr without lists)
   auto trial = [&](int round, unsigned int nact, int32_t* list) -> int {
@@ -291,13 +282,13 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
     // Tail rounds: a wave per (segment, super-tile) instead of a lane's serial walk through every tile (rows: 1.5-9 ms per round at C5's stated
     // size, eight to ten of them per X half-step) -- below GLRM_HIP_LANE_TAIL / GLRM_HIP_LANE_TAIL_COLS percent of the segments
     if (list && (int64_t)nact * 100 < full.nseg * (int64_t)(full.nsup == 1 ? env_int("GLRM_HIP_LANE_TAIL", 5) : env_int("GLRM_HIP_LANE_TAIL_COLS", 3))) {
-      if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: a wave per segment\n", rows ? "row" : "column", round, nact, (long long)full.nseg);
+      if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: a wave per segment\n", side == GLRM_ROWS ? "row" : "column", round, nact, (long long)full.nseg);
       return launch_lane_tail(loss, full, list, (int64_t)nact, st);
     }
     bool packed = list && (int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_GATHER_PACKED", 4);
     // (sides with permuted slots: chunk lists over the SLOTS, which were dealt out class by class -- make_segperm)
     const int32_t* gperm = la.inv ? full.segperm : nullptr;
-    const bool chunks_ok = !la.inv || (h->lane_dealt[side] && gperm && env_int("GLRM_HIP_LANE_GATHER_SLOTS", 1));
+    const bool chunks_ok = !la.inv || (v.lane_dealt && gperm && env_int("GLRM_HIP_LANE_GATHER_SLOTS", 1));
     bool use_gather = gather && (chunks_ok || packed) && pct >= env_int("GLRM_HIP_LANE_GATHER_FROM", 0) && pct < env_int("GLRM_HIP_LANE_GATHER_TO", 70);
     int32_t gwaves = 0;
     if (use_gather) {
@@ -329,13 +320,13 @@ int glrm_run_lane(glrm_handle* h, bool rows, int loss, const TiledArgs& a_in, do
     }
     if (use_gather) {
       la.gwaves = gwaves;
-      if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: SELL gathered%s, %d waves\n", rows ? "row" : "column", round, nact, (long long)full.nseg, packed ? " (packed)" : "", (int)gwaves);
+      if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: SELL gathered%s, %d waves\n", side == GLRM_ROWS ? "row" : "column", round, nact, (long long)full.nseg, packed ? " (packed)" : "", (int)gwaves);
       t.npass = 0;
       return launch_lane_loss<false, 2>(loss, t, la, (int64_t)gwaves, st);
     }
     // (measured cross-over of the two older forms at about a sixth of the segments, session r6_20)
     const bool compact = list && ((int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_CSR_BELOW", 16) || !sell_ok);
-    if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: %s\n", rows ? "row" : "column", round, nact, (long long)full.nseg, compact ? "CSR" : "SELL full grid");
+    if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: %s\n", side == GLRM_ROWS ? "row" : "column", round, nact, (long long)full.nseg, compact ? "CSR" : "SELL full grid");
     if (compact) {
       // (tried in session r6_45/46 and taken out again: this form over class-aware wave lists -- conflict-free tile reads -- measured the same at
       // full waves and worse spread over the chip; nor did batching its list reads move it.  A CSR round costs 2.8 x the full grid's time

@@ -27,28 +27,30 @@ template <class A, class V> void set_vecreg(A&, V, long) {}
 // The view, factors, step sizes, descriptors and counters of the row (X half-step) or column (Y half-step) side.  What a family does
 // differently (nullable trials, its own mode fields) follows at the call site.
 template <class A>
-void glrm_fill_side(A& a, const glrm_handle* h, bool rows, double min_stepsize, int eval_only) {
-  a.nseg = rows ? h->ml : h->nl;
-  a.ptr = rows ? h->rowptr : h->colptr;
-  a.idx = rows ? h->colidx : h->rowidx;
-  a.vals = rows ? h->rowvals : h->colvals;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.other = rows ? h->Y : h->X;
-  a.alpha = rows ? h->alpharow : h->alphacol;
+void glrm_fill_side(A& a, const glrm_handle* h, int side, double min_stepsize, int eval_only) {
+  const glrm_handle::Side& v = h->side[side];
+  a.nseg = v.nseg;
+  a.ptr = v.ptr;
+  a.idx = v.idx;
+  a.vals = v.vals;
+  a.own = v.factor;
+  a.own_offset = v.begin;
+  a.other = h->side[side ^ 1].factor;
+  a.alpha = v.alpha;
   a.losses = h->losses;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
-  glrm_detail::set_vecreg(a, (rows ? h->vecreg_x : h->vecreg_y) ? 1 : 0, 0);
+  a.regs = v.regs;
+  a.reg_single = v.n_regs == 1;
+  glrm_detail::set_vecreg(a, v.vecreg ? 1 : 0, 0);
   a.k = h->k;
   a.min_stepsize = min_stepsize;
-  a.trials = rows ? h->trials_r : h->trials_c;
-  a.accepts = rows ? h->accepts_r : h->accepts_c;
-  glrm_detail::set_obj(a, rows ? nullptr : h->objcol, 0);
-  glrm_detail::set_n_other(a, rows ? h->n : h->m, 0);
+  a.trials = v.trials;
+  a.accepts = v.accepts;
+  glrm_detail::set_obj(a, side == GLRM_ROWS ? nullptr : v.obj, 0);
+  glrm_detail::set_n_other(a, h->side[side ^ 1].nglob, 0);
   glrm_detail::set_eval_only(a, eval_only, 0);
   glrm_detail::set_fixed_alpha(a, eval_only ? 0.0 : h->fixed_alpha, 0);
 }
+template <class A> void glrm_fill_side(A&, const glrm_handle*, bool, double, int) = delete; // `true` would mean columns.  Guards this function only (it fills kernel arguments); the other `int side` functions convert silently
 
 // glrm_hip_step_x_range: the description restricted to local rows [rng_b, rng_e) (the caller returns when a.nseg <= 0)
 template <class A>
@@ -60,10 +62,10 @@ void glrm_apply_row_range(A& a, int64_t rng_b, int64_t rng_e) {
   if (a.accepts) a.accepts += rng_b;
 }
 
-// points the pass-buffer fields of a TiledArgs at a side's buffers ([0] rows, [1] columns), from local segment s0 on
+// points the pass-buffer fields of a TiledArgs at a side's buffers (GLRM_ROWS / GLRM_COLS), from local segment s0 on
 template <class A>
 void glrm_bind_pass_buffers(A& a, const glrm_handle* h, int side, int64_t s0 = 0) {
-  const glrm_handle::PassBuffers& b = h->pass[side];
+  const glrm_handle::PassBuffers& b = h->side[side].pass;
   a.nsup = b.nsup;
   a.tiles_per_sup = b.tiles_per_sup;
   a.part = b.part + s0 * (int64_t)b.nsup * (h->kp + 2);
@@ -83,9 +85,9 @@ void glrm_bind_pass_buffers(A& a, const glrm_handle* h, int side, int64_t s0 = 0
 struct glrm_act_lists {
   int32_t* list[2] = {nullptr, nullptr};
 };
-inline glrm_act_lists glrm_active_lists(const glrm_handle* h, bool rows, int64_t nseg) {
+inline glrm_act_lists glrm_active_lists(const glrm_handle* h, int side, int64_t nseg) {
   glrm_act_lists l;
-  if (h->actlist && (h->tile_rounds & (rows ? 1 : 2)) && nseg <= h->actlist_cap) {
+  if (h->actlist && (h->tile_rounds & (1 << side)) && nseg <= h->actlist_cap) {
     l.list[0] = h->actlist;
     l.list[1] = h->actlist + h->actlist_cap;
   }

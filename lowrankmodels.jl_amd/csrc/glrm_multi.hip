@@ -8,7 +8,7 @@
 using namespace glrm;
 
 // The kernels that apply a regularizer exist twice: VR = true holds the vector regularizers and is launched when a descriptor of the
-// side names one or carries a vector (glrm_handle::vecreg_x / vecreg_y -> MultiArgs::vecreg; csrc/glrm_device.hpp, DESIGN.md sections
+// side names one or carries a vector (glrm_handle::Side::vecreg -> MultiArgs::vecreg; csrc/glrm_device.hpp, DESIGN.md sections
 // 4.11 and 4.14).
 #define MULTI_SWEEP(threads, ...)                                                                                                        \
   do {                                                                                                                                   \
@@ -66,9 +66,9 @@ static int setup_split(glrm_handle* h) {
   h->col_chunk = chunk;
   h->col_nsplit = (int)nsplit;
   int rc;
-  if ((rc = h->mem.alloc(&h->mtrial, (size_t)h->d * h->kp)) || (rc = h->mem.alloc(&h->mpart_loss, (size_t)h->nl * nsplit)) ||
-      (rc = h->mem.alloc(&h->mpart_G, (size_t)h->nl * nsplit * blk)) || (rc = h->mem.alloc(&h->mgtot, (size_t)h->nl * blk)) ||
-      (rc = h->mem.alloc(&h->mobjold, (size_t)h->nl)) || (rc = h->mem.alloc(&h->mactive, (size_t)h->nl)))
+  if ((rc = h->mem.alloc(&h->mtrial, (size_t)h->d * h->kp)) || (rc = h->mem.alloc(&h->mpart_loss, (size_t)h->side[GLRM_COLS].nseg * nsplit)) ||
+      (rc = h->mem.alloc(&h->mpart_G, (size_t)h->side[GLRM_COLS].nseg * nsplit * blk)) || (rc = h->mem.alloc(&h->mgtot, (size_t)h->side[GLRM_COLS].nseg * blk)) ||
+      (rc = h->mem.alloc(&h->mobjold, (size_t)h->side[GLRM_COLS].nseg)) || (rc = h->mem.alloc(&h->mactive, (size_t)h->side[GLRM_COLS].nseg)))
     return rc;
   return h->mem.alloc(&h->mnactive, 1);
 }
@@ -140,9 +140,9 @@ static int run_split_cols(glrm_handle* h, const MultiArgs& a) {
   return GLRM_OK;
 }
 
-int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only) {
+int glrm_run_multi(glrm_handle* h, int side, double min_stepsize, int eval_only) {
   MultiArgs a{};
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
   a.ystart = h->ystart;
   a.loss_single = h->n_losses == 1;
   a.kp = h->kp; a.dmax = h->dmax;
@@ -151,15 +151,15 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
   a.mode = eval_only ? 1 : (h->fixed_alpha > 0.0 ? 2 : 0);
   if (a.mode != 0) a.trials = a.accepts = nullptr; // the counters belong to the line-search steps
   // the vectors of the side's descriptors (include/glrm_hip_regvec.h), indexed like the descriptors
-  a.regvec = h->regvec[rows ? 0 : 1];
-  a.reglen = h->reglen[rows ? 0 : 1];
+  a.regvec = h->side[side].regvec;
+  a.reglen = h->side[side].reglen;
   a.regvec_single = a.reg_single;
-  if (rows && h->rng_e >= 0) {
+  if (side == GLRM_ROWS && h->rng_e >= 0) {
     glrm_apply_row_range(a, h->rng_b, h->rng_e);
     if (a.regvec && !a.reg_single) { a.regvec += h->rng_b * h->k; a.reglen += h->rng_b; }
   }
   if (a.nseg <= 0) return GLRM_OK;
-  if (rows) {
+  if (side == GLRM_ROWS) {
     const size_t lds = multi_lds_doubles(true, 1, h->kp, h->dmax, a.lgP) * 8;
     // every embedding dimension <= 8: the opposing block of an observation is held in registers (glrm_multi.hpp: multi_pass, RD)
     const bool regs = h->dmax <= 8 && env_int("GLRM_HIP_MULTI_REGS", 1);
@@ -193,22 +193,16 @@ int glrm_run_multi(glrm_handle* h, bool rows, double min_stepsize, int eval_only
   return GLRM_OK;
 }
 
-int glrm_run_multi_penalty(glrm_handle* h, bool rows) {
+int glrm_run_multi_penalty(glrm_handle* h, int side) {
+  const glrm_handle::Side& v = h->side[side];
+  if (v.nseg <= 0) return GLRM_OK;
   PenaltyArgs a{};
-  a.nseg = rows ? h->ml : h->nl;
-  if (a.nseg <= 0) return GLRM_OK;
-  a.own = rows ? h->X : h->Y;
-  a.own_offset = rows ? h->rb : h->cb;
-  a.ystart = rows ? nullptr : h->ystart;
-  a.regs = rows ? h->rx : h->ry;
-  a.reg_single = (rows ? h->n_rx : h->n_ry) == 1;
+  a.nseg = v.nseg; a.own = v.factor; a.own_offset = v.begin; a.out = v.obj;
+  a.ystart = side == GLRM_ROWS ? nullptr : h->ystart; // (a row is one vector, a column its block of Y)
+  a.regs = v.regs; a.reg_single = a.regvec_single = v.n_regs == 1;
   a.k = h->k; a.kp = h->kp;
-  a.out = rows ? h->objrow : h->objcol;
-  const size_t lds = ((size_t)(rows ? 1 : h->dmax) * (h->kp + 1) + 16) * 8;
-  a.vecreg = (rows ? h->vecreg_x : h->vecreg_y) ? 1 : 0;
-  a.regvec = h->regvec[rows ? 0 : 1];
-  a.reglen = h->reglen[rows ? 0 : 1];
-  a.regvec_single = a.reg_single;
+  a.vecreg = v.vecreg ? 1 : 0; a.regvec = v.regvec; a.reglen = v.reglen;
+  const size_t lds = ((size_t)(side == GLRM_ROWS ? 1 : h->dmax) * (h->kp + 1) + 16) * 8;
   if (a.vecreg) hipLaunchKernelGGL(multi_penalty_kernel<true>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
   else hipLaunchKernelGGL(multi_penalty_kernel<false>, dim3((unsigned)a.nseg), dim3(64), lds, h->stream, a);
   HIPCK(hipGetLastError());

@@ -790,7 +790,7 @@ extern "C" int glrm_hip_multi_fit(glrm_multi* mh, const glrm_params* prm, double
        })))
     return rc;
   int64_t nnz_rows = 0;
-  for (int s = 0; s < mh->n; ++s) nnz_rows += mh->sh[s]->nnz_r;
+  for (int s = 0; s < mh->n; ++s) nnz_rows += mh->sh[s]->side[GLRM_ROWS].nnz;
   // arrival order: what shard t's Y half-step is told about the rows of X -- its own block is there, then chunk 0 of every peer (ring
   // order from t: the order the peers push in), chunk 1 of every peer, ...; the events are re-recorded by every iteration's pushes
   const int n = mh->n, C = mh->x_chunks;

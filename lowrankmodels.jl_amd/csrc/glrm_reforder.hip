@@ -317,11 +317,11 @@ int launch_ref_terms(bool trig, const RefArgs& a, int64_t t0, int64_t t1, double
 }
 
 template <int KP>
-int launch_ref(bool rows, bool trig, const RefArgs& a, hipStream_t st) {
+int launch_ref(int side, bool trig, const RefArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)((a.nseg + 63) / 64);
   auto go = [&](auto VR) {
     constexpr bool V = decltype(VR)::value;
-    if (rows) {
+    if (side == GLRM_ROWS) {
       if (trig) hipLaunchKernelGGL((ref_row_kernel<KP, true, V>), dim3(grid), dim3(64), 0, st, a);
       else hipLaunchKernelGGL((ref_row_kernel<KP, false, V>), dim3(grid), dim3(64), 0, st, a);
     } else {
@@ -345,18 +345,18 @@ int glrm_setup_reforder(glrm_handle* h) {
   return GLRM_OK;
 }
 
-int glrm_run_reforder(glrm_handle* h, bool rows, double min_stepsize, int eval_only) {
+int glrm_run_reforder(glrm_handle* h, int side, double min_stepsize, int eval_only) {
   if (h->fixed_alpha > 0.0 && !eval_only)
     return fail(GLRM_ERR_UNSUPPORTED, "glrm_options.sum_order = 1 (reference order) restates the ProxGradParams half-steps only, not the fixed-step sweeps of SparseProxGradParams");
-  if (rows && eval_only) return fail(GLRM_ERR_INVALID, "no evaluation pass over the row view");
+  if (side == GLRM_ROWS && eval_only) return fail(GLRM_ERR_INVALID, "no evaluation pass over the row view");
   RefArgs a{};
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
   a.n_losses = h->n_losses;
   if (eval_only) a.trials = nullptr;
-  if (rows && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e); // glrm_hip_step_x_range
+  if (side == GLRM_ROWS && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e); // glrm_hip_step_x_range
   if (a.nseg <= 0) return GLRM_OK;
   return glrm_dispatch<8, 16, 32, 64>(
-      h->kp, [&](auto KP) { return launch_ref<decltype(KP)::value>(rows, h->has_trig, a, h->stream); },
+      h->kp, [&](auto KP) { return launch_ref<decltype(KP)::value>(side, h->has_trig, a, h->stream); },
       [&] { return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp); });
 }
 
@@ -380,19 +380,19 @@ static double julia_pairwise_host(const double* v, int64_t first, int64_t last) 
 // the recorded objective[0] of the reference-order mode equals the reference-order oracle's to the last bit.
 int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out) {
   double err = 0.0;
-  if (h->nl > 0 && h->nnz_c > 0) {
+  if (h->side[GLRM_COLS].nseg > 0 && h->side[GLRM_COLS].nnz > 0) {
     RefArgs a{};
-    a.nseg = h->nl; a.ptr = h->colptr; a.idx = h->rowidx; a.vals = h->colvals;
-    a.own = h->Y; a.own_offset = h->cb; a.other = h->X;
+    a.nseg = h->side[GLRM_COLS].nseg; a.ptr = h->side[GLRM_COLS].ptr; a.idx = h->side[GLRM_COLS].idx; a.vals = h->side[GLRM_COLS].vals;
+    a.own = h->side[GLRM_COLS].factor; a.own_offset = h->side[GLRM_COLS].begin; a.other = h->side[GLRM_ROWS].factor;
     a.losses = h->losses; a.n_losses = h->n_losses; a.k = h->k;
-    const int64_t chunk = std::min<int64_t>(h->nnz_c, (int64_t)1 << 25); // 256 MB of terms at a time
+    const int64_t chunk = std::min<int64_t>(h->side[GLRM_COLS].nnz, (int64_t)1 << 25); // 256 MB of terms at a time
     DevArena scratch;
     double* dterms = nullptr;
     if (const int rc = scratch.alloc(&dterms, (size_t)chunk)) return rc;
     std::vector<double> host;
     try { host.resize((size_t)chunk); } catch (const std::exception&) { return fail(GLRM_ERR_OOM, "out of host memory"); }
-    for (int64_t t0 = 0; t0 < h->nnz_c; t0 += chunk) {
-      const int64_t t1 = std::min(h->nnz_c, t0 + chunk);
+    for (int64_t t0 = 0; t0 < h->side[GLRM_COLS].nnz; t0 += chunk) {
+      const int64_t t1 = std::min(h->side[GLRM_COLS].nnz, t0 + chunk);
       const int rc = glrm_dispatch<8, 16, 32, 64>(
           h->kp, [&](auto KP) { return launch_ref_terms<decltype(KP)::value>(h->has_trig, a, t0, t1, dterms, h->stream); },
           [&] { return fail(GLRM_ERR_UNSUPPORTED, "no reference-order kernel for a padded rank of %d", h->kp); });
@@ -408,11 +408,11 @@ int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out) {
     int rc;
     std::vector<double> host((size_t)std::max<int64_t>(h->m, h->n));
     if ((rc = glrm_hip_row_penalties(h))) return rc;
-    HIPCK(hipMemcpyAsync(host.data(), h->objrow, (size_t)h->m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipMemcpyAsync(host.data(), h->side[GLRM_ROWS].obj, (size_t)h->m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     for (int64_t i = 0; i < h->m; ++i) penalty += host[(size_t)i];
     if ((rc = glrm_hip_col_penalties(h))) return rc;
-    HIPCK(hipMemcpyAsync(host.data(), h->objcol, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipMemcpyAsync(host.data(), h->side[GLRM_COLS].obj, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     for (int64_t f = 0; f < h->n; ++f) penalty += host[(size_t)f];
     err += penalty;

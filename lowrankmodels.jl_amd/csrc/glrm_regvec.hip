@@ -95,18 +95,18 @@ void glrm_regvec_placeholders(const std::vector<glrm_reg>& in, std::vector<glrm_
 
 void glrm_regvec_drop(glrm_handle* h) {
   for (int s = 0; s < 2; ++s) {
-    h->mem.release(&h->regvec[s]);
-    h->mem.release(&h->reglen[s]);
-    h->regvec_h[s].clear();
-    h->reglen_h[s].clear();
+    h->mem.release(&h->side[s].regvec);
+    h->mem.release(&h->side[s].reglen);
+    h->side[s].regvec_h.clear();
+    h->side[s].reglen_h.clear();
   }
 }
 
 int glrm_check_regularizers_vec(const glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_regvec* vx, const glrm_reg* ry, int64_t n_ry,
                                 const glrm_regvec* vy) {
   if (!h || !rx || !ry) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (n_rx != h->n_rx || n_ry != h->n_ry)
-    return fail(GLRM_ERR_INVALID, "regularizer counts must match the handle (rx %lld, ry %lld)", (long long)h->n_rx, (long long)h->n_ry);
+  if (n_rx != h->side[GLRM_ROWS].n_regs || n_ry != h->side[GLRM_COLS].n_regs)
+    return fail(GLRM_ERR_INVALID, "regularizer counts must match the handle (rx %lld, ry %lld)", (long long)h->side[GLRM_ROWS].n_regs, (long long)h->side[GLRM_COLS].n_regs);
   if (side_carries(rx, n_rx) || side_carries(ry, n_ry) || vx || vy) { // the handle moves to (or stays on) the general sweeps
     if (h->storage == GLRM_STORAGE_F32)
       return fail(GLRM_ERR_UNSUPPORTED, "regularizers that carry a vector are not available with storage = f32 (glrm_options.storage = 1): they run on the general sweeps, which read fp64 factors");
@@ -116,7 +116,7 @@ int glrm_check_regularizers_vec(const glrm_handle* h, const glrm_reg* rx, int64_
       return fail(GLRM_ERR_UNSUPPORTED, "regularizers that carry a vector need a sparse-view handle with k <= 64 (like the wrapped regularizers)");
   }
   if (const int rc = check_side("rx", rx, n_rx, vx, h->k, nullptr, 0, 0, 0)) return rc;
-  if (const int rc = check_side("ry", ry, n_ry, vy, h->k, h->losses_h.data(), (int64_t)h->losses_h.size(), h->cb, h->nl)) return rc;
+  if (const int rc = check_side("ry", ry, n_ry, vy, h->k, h->losses_h.data(), (int64_t)h->losses_h.size(), h->side[GLRM_COLS].begin, h->side[GLRM_COLS].nseg)) return rc;
   try { // the descriptors that carry no vector: everything glrm_hip_set_regularizers refuses
     std::vector<glrm_reg> px, py;
     to_placeholders(rx, n_rx, px);
@@ -168,24 +168,23 @@ extern "C" int glrm_hip_set_regularizers_vec(glrm_handle* h, const glrm_reg* rx,
     e = hipMemcpyAsync(dv[s], tv[s].data(), tv[s].size() * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dl[s], tl[s].data(), tl[s].size() * 4, hipMemcpyHostToDevice, h->stream);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(h->rx, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->ry, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->side[GLRM_ROWS].regs, rx, (size_t)n_rx * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->side[GLRM_COLS].regs, ry, (size_t)n_ry * sizeof(glrm_reg), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "installing the regularizer vectors failed: %s", hipGetErrorString(e));
   glrm_regvec_drop(h); // the previous call's tables (the stream is idle)
   for (int s = 0; s < 2; ++s) {
-    h->regvec[s] = dv[s];
-    h->reglen[s] = dl[s];
+    h->side[s].regvec = dv[s];
+    h->side[s].reglen = dl[s];
     fresh.move_to(h->mem, dv[s]);
     fresh.move_to(h->mem, dl[s]);
-    h->regvec_h[s].swap(tv[s]);
-    h->reglen_h[s].swap(tl[s]);
+    h->side[s].regvec_h.swap(tv[s]);
+    h->side[s].reglen_h.swap(tl[s]);
   }
-  h->rx_h.swap(nr[0]);
-  h->ry_h.swap(nr[1]);
+  for (int s = 0; s < 2; ++s) h->side[s].regs_h.swap(nr[s]);
   h->multi = true; // checked above: this handle can run the general sweeps
-  h->vecreg_x = carries[0] || any_vector_kind(rx, n_rx);
-  h->vecreg_y = carries[1] || any_vector_kind(ry, n_ry);
+  h->side[GLRM_ROWS].vecreg = carries[0] || any_vector_kind(rx, n_rx);
+  h->side[GLRM_COLS].vecreg = carries[1] || any_vector_kind(ry, n_ry);
   if (h->iter_exec) { // a captured iteration holds the launches of the other family and the old table pointers
     (void)hipGraphExecDestroy(h->iter_exec);
     h->iter_exec = nullptr;
@@ -196,8 +195,9 @@ extern "C" int glrm_hip_set_regularizers_vec(glrm_handle* h, const glrm_reg* rx,
 // glrm_hip_subset: the child was created from the parent's descriptors with the vector codes taken out; it now gets the parent's
 // descriptors and vectors (a subset keeps m, n and the shard's ranges, so the tables carry over unchanged).
 int glrm_regvec_inherit(glrm_handle* child, const glrm_handle* parent) {
-  if (!parent->regvec[0] && !parent->regvec[1]) return GLRM_OK;
-  const glrm_regvec vx{parent->regvec_h[0].data(), parent->reglen_h[0].data()}, vy{parent->regvec_h[1].data(), parent->reglen_h[1].data()};
-  return glrm_hip_set_regularizers_vec(child, parent->rx_h.data(), (int64_t)parent->rx_h.size(), parent->regvec[0] ? &vx : nullptr, parent->ry_h.data(),
-                                       (int64_t)parent->ry_h.size(), parent->regvec[1] ? &vy : nullptr);
+  const glrm_handle::Side &rows = parent->side[GLRM_ROWS], &cols = parent->side[GLRM_COLS];
+  if (!rows.regvec && !cols.regvec) return GLRM_OK;
+  const glrm_regvec vx{rows.regvec_h.data(), rows.reglen_h.data()}, vy{cols.regvec_h.data(), cols.reglen_h.data()};
+  return glrm_hip_set_regularizers_vec(child, rows.regs_h.data(), (int64_t)rows.regs_h.size(), rows.regvec ? &vx : nullptr, cols.regs_h.data(),
+                                       (int64_t)cols.regs_h.size(), cols.regvec ? &vy : nullptr);
 }

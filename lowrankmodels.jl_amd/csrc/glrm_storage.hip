@@ -66,8 +66,8 @@ int glrm_narrow_views(glrm_handle* h) {
   int flag = 0;
   hipError_t e = hipMemsetAsync(dflag, 0, sizeof(int), h->stream);
   rc = e == hipSuccess ? GLRM_OK : fail(GLRM_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-  if (!rc) rc = narrow_values(h, &h->rowvals, h->nnz_r, dflag);
-  if (!rc) rc = narrow_values(h, &h->colvals, h->nnz_c, dflag);
+  if (!rc) rc = narrow_values(h, &h->side[GLRM_ROWS].vals, h->side[GLRM_ROWS].nnz, dflag);
+  if (!rc) rc = narrow_values(h, &h->side[GLRM_COLS].vals, h->side[GLRM_COLS].nnz, dflag);
   if (!rc) {
     e = hipMemcpy(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(GLRM_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
@@ -156,13 +156,8 @@ extern "C" int glrm_hip_storage(glrm_handle* h) { return h ? h->storage : fail(G
 
 // ------------------------------------------------------------------ the float instantiations
 
-void glrm_launch_sweep_f32(int G, int R, int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
-  launch_sweep_st<float>(G, R, waves, loss, rows, a, st);
+void glrm_launch_sweep_f32(int G, int R, int waves, int loss, int side, const SweepArgs& a, hipStream_t st) {
+  launch_sweep_st<float>(G, R, waves, loss, side, a, st);
 }
 
-void glrm_launch_penalty_f32(glrm_handle* h, bool rows) {
-  const int64_t nseg = rows ? h->ml : h->nl;
-  hipLaunchKernelGGL(penalty_kernel<float>, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, h->stream,
-                     reinterpret_cast<const float*>(rows ? h->X : h->Y), h->kp, h->k, rows ? h->rb : h->cb, nseg, rows ? h->rx : h->ry,
-                     (rows ? h->n_rx : h->n_ry) == 1 ? 1 : 0, rows ? h->objrow : h->objcol);
-}
+void glrm_launch_penalty_f32(glrm_handle* h, int side) { launch_penalty_st<float>(h, side); }

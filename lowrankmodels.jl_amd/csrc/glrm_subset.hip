@@ -155,18 +155,19 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   GLRM_REFUSE_F32(parent, "glrm_hip_subset");
   if (parent->dense) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_subset needs a list (not dense) parent handle");
   GLRM_NEED_FINALIZED(parent);
-  if ((parent->nnz_r > 0 && !row_tags) || (parent->nnz_c > 0 && !col_tags)) return fail(GLRM_ERR_INVALID, "NULL tag array");
+  const glrm_handle::Side &rows = parent->side[GLRM_ROWS], &cols = parent->side[GLRM_COLS];
+  if ((rows.nnz > 0 && !row_tags) || (cols.nnz > 0 && !col_tags)) return fail(GLRM_ERR_INVALID, "NULL tag array");
   DeviceScope dg(parent->device);
   if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", parent->device);
   View rv, cv;
-  int rc = compact_view(parent->stream, parent->rowptr, parent->colidx, parent->rowvals, parent->ml, parent->nnz_r, row_tags, match, invert, rv);
+  int rc = compact_view(parent->stream, rows.ptr, rows.idx, rows.vals, rows.nseg, rows.nnz, row_tags, match, invert, rv);
   if (rc) return rc;
-  rc = compact_view(parent->stream, parent->colptr, parent->rowidx, parent->colvals, parent->nl, parent->nnz_c, col_tags, match, invert, cv);
+  rc = compact_view(parent->stream, cols.ptr, cols.idx, cols.vals, cols.nseg, cols.nnz, col_tags, match, invert, cv);
   if (rc) return rc;
   glrm_problem p{};
   p.m = parent->m; p.n = parent->n; p.k = parent->k;
   p.flags = GLRM_PROBLEM_DEVICE_ARRAYS;
-  p.row_begin = parent->rb; p.row_end = parent->re; p.col_begin = parent->cb; p.col_end = parent->ce;
+  p.row_begin = rows.begin; p.row_end = rows.end; p.col_begin = cols.begin; p.col_end = cols.end;
   p.rowptr = rv.ptr; p.colidx = rv.idx; p.rowvals = rv.vals;
   p.colptr = cv.ptr; p.rowidx = cv.idx; p.colvals = cv.vals;
   p.losses = parent->losses_h.data(); p.n_losses = (int64_t)parent->losses_h.size();
@@ -174,8 +175,8 @@ extern "C" int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, con
   // taken out and inherits descriptors and vectors afterwards
   std::vector<glrm_reg> prx, pry;
   try {
-    glrm_regvec_placeholders(parent->rx_h, prx);
-    glrm_regvec_placeholders(parent->ry_h, pry);
+    glrm_regvec_placeholders(rows.regs_h, prx);
+    glrm_regvec_placeholders(cols.regs_h, pry);
   } catch (const std::bad_alloc&) {
     return fail(GLRM_ERR_OOM, "out of host memory");
   }

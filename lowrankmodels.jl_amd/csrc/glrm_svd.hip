@@ -378,19 +378,19 @@ extern "C" int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t m
       (rc = scratch.alloc(&w.M, (size_t)l * l)) || (rc = scratch.alloc(&w.sq, (size_t)l)))
     return rc;
   // column statistics
-  hipLaunchKernelGGL(svd_stats_kernel, dim3((unsigned)h->n), dim3(256), 0, st, h->colptr, h->colvals, h->losses, h->n_losses == 1 ? 1 : 0,
+  hipLaunchKernelGGL(svd_stats_kernel, dim3((unsigned)h->n), dim3(256), 0, st, h->side[GLRM_COLS].ptr, h->side[GLRM_COLS].vals, h->losses, h->n_losses == 1 ? 1 : 0,
                      h->ystart, h->n, 1e-10, w.means, w.stds);
   HIPCK(hipGetLastError());
   SvdArgs ra{}, ca{};
-  ra.nseg = m; ra.ptr = h->rowptr; ra.idx = h->colidx; ra.vals = h->rowvals;
+  ra.nseg = m; ra.ptr = h->side[GLRM_ROWS].ptr; ra.idx = h->side[GLRM_ROWS].idx; ra.vals = h->side[GLRM_ROWS].vals;
   ra.losses = h->losses; ra.loss_single = h->n_losses == 1 ? 1 : 0; ra.ystart = h->ystart; ra.means = w.means;
-  ra.cscale = h->nnz_r > 0 ? (double)m * (double)h->n / (double)h->nnz_r : 0.0; // Astd *= m*n/sum(map(length, observed_features)) (:113)
+  ra.cscale = h->side[GLRM_ROWS].nnz > 0 ? (double)m * (double)h->n / (double)h->side[GLRM_ROWS].nnz : 0.0; // Astd *= m*n/sum(map(length, observed_features)) (:113)
   ra.in = w.V; ra.out = w.U; ra.l = l; ra.nsplit = 1; ra.dmax = h->dmax;
   ca = ra;
-  ca.nseg = h->n; ca.ptr = h->colptr; ca.idx = h->rowidx; ca.vals = h->colvals; ca.in = w.U; ca.out = w.V;
+  ca.nseg = h->n; ca.ptr = h->side[GLRM_COLS].ptr; ca.idx = h->side[GLRM_COLS].idx; ca.vals = h->side[GLRM_COLS].vals; ca.in = w.U; ca.out = w.V;
   { // long columns: several workgroups per column, partials added in chunk order
     std::vector<int64_t> cp((size_t)h->n + 1);
-    HIPCK(hipMemcpyAsync(cp.data(), h->colptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(cp.data(), h->side[GLRM_COLS].ptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
     int64_t longest = 0;
     for (int64_t f = 0; f < h->n; ++f) longest = std::max(longest, cp[f + 1] - cp[f]);

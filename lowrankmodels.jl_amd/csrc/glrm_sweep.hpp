@@ -33,7 +33,7 @@ struct SweepArgs {
   int32_t* trials;       // per local segment accumulators (nullable)
   int32_t* accepts;
   const int32_t* seglist; // nullable: the launch covers the local segments seglist[0..nseg) instead of 0..nseg -- the segments of ONE
-                          // wave class when the shard holds several (glrm_handle::seglist_r) -- restricted to [seg_lo, seg_hi)
+                          // wave class when the shard holds several (glrm_handle::Side::seglist) -- restricted to [seg_lo, seg_hi)
   int64_t seg_lo, seg_hi; // (glrm_hip_step_x_range on such a shard; otherwise [0, local segments))
   int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels (csrc/glrm_device.hpp)
   int storage;           // GLRM_STORAGE_*: the type ST behind vals / own / other, i.e. which instantiation the launch takes
@@ -418,7 +418,7 @@ __global__ void penalty_kernel(const ST* fac, int ld, int k, int64_t offset, int
 
 // Observations per lane group in flight (a group adds its observations in ascending order whatever the count: the bits do not depend on it)
 template <class ST, int G, int R, int WAVES>
-void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream_t st) {
+void launch_sweep_loss(int loss, int side, const SweepArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)(WAVES == 1 ? (a.nseg + 3) / 4 : a.nseg);
   const dim3 block(WAVES == 1 ? 256 : WAVES * 64);
   auto launch = [&](auto LOSS, auto U) {
@@ -438,7 +438,7 @@ void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream_t st) 
   auto by_loss = [&](auto LOSS) {
     if constexpr (LOSS == LOSS_QUAD_UNIFORM) {
       if constexpr (WAVES == 1) { // two observations in flight on the row view: -20 % on the L2-latency-bound row sweep
-        return rows ? launch(LOSS, glrm_const<2>{}) : launch(LOSS, glrm_const<1>{});
+        return side == GLRM_ROWS ? launch(LOSS, glrm_const<2>{}) : launch(LOSS, glrm_const<1>{});
       } else {
         return launch(LOSS, glrm_const<(WAVES == 8 ? 8 : 1)>{});
       }
@@ -451,13 +451,21 @@ void launch_sweep_loss(int loss, bool rows, const SweepArgs& a, hipStream_t st) 
 
 // (lanes per observation G, components per lane R) with G*R == kp: the layouts of pick_layout
 template <class ST>
-void launch_sweep_st(int G, int R, int waves, int loss, bool rows, const SweepArgs& a, hipStream_t st) {
+void launch_sweep_st(int G, int R, int waves, int loss, int side, const SweepArgs& a, hipStream_t st) {
   auto by_layout = [&](auto g, auto r) {
     constexpr int GG = decltype(g)::value, RR = decltype(r)::value;
-    auto by_waves = [&](auto W) { launch_sweep_loss<ST, GG, RR, decltype(W)::value>(loss, rows, a, st); return GLRM_OK; };
+    auto by_waves = [&](auto W) { launch_sweep_loss<ST, GG, RR, decltype(W)::value>(loss, side, a, st); return GLRM_OK; };
     return glrm_dispatch<1, 4>(waves, by_waves, [&] { return by_waves(glrm_const<8>{}); });
   };
   glrm_dispatch_layout<8, 16, 32, 64>(G, R, by_layout, [&] { return by_layout(glrm_const<16>{}, glrm_const<8>{}); });
+}
+
+// the penalty kernel over a side's local segments (the caller has checked that there are some)
+template <class ST>
+void launch_penalty_st(const glrm_handle* h, int side) {
+  const glrm_handle::Side& v = h->side[side];
+  hipLaunchKernelGGL(penalty_kernel<ST>, dim3((unsigned)((v.nseg + 255) / 256)), dim3(256), 0, h->stream, reinterpret_cast<const ST*>(v.factor), h->kp, h->k,
+                     v.begin, v.nseg, v.regs, v.n_regs == 1 ? 1 : 0, v.obj);
 }
 
 } // namespace glrm

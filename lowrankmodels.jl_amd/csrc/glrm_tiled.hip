@@ -21,17 +21,17 @@ static bool tile_rot_rt(int G, int R) { return (G == 4 || G == 8) && R == 8; }
 // (one loss kind and lengths within 25 % of each other: the synthetic BASELINE workloads).
 // long_from > 0 (columns): segments of at least that many observations are left out of the slots (they run on the 8-wave gather sweep
 // beside the passes, glrm_hip.hip: run_sweep) and listed in *longs; *nshort = slots handed out
-static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_from = 0, std::vector<int32_t>* longs = nullptr, int64_t* nshort = nullptr) {
+static int make_segperm(glrm_handle* h, int side, int32_t** out, int64_t long_from = 0, std::vector<int32_t>* longs = nullptr, int64_t* nshort = nullptr) {
   *out = nullptr;
-  const int64_t nseg = rows ? h->ml : h->nl;
+  const int64_t nseg = h->side[side].nseg;
   if (nshort) *nshort = nseg;
   if (nseg <= 1 || !env_int("GLRM_HIP_SEGPERM", 1)) return GLRM_OK;
   std::vector<int64_t> ptr;
-  int rc = glrm_host_ptr(h, rows, ptr);
+  int rc = glrm_host_ptr(h, side, ptr);
   if (rc) return rc;
   int64_t lmin = INT64_MAX, lmax = 0;
   for (int64_t s = 0; s < nseg; ++s) { const int64_t l = ptr[s + 1] - ptr[s]; lmin = l < lmin ? l : lmin; lmax = l > lmax ? l : lmax; }
-  const bool kinds = !rows && h->n_losses > 1;
+  const bool kinds = side == GLRM_COLS && h->n_losses > 1;
   const bool divert = long_from > 0 && longs && lmax >= long_from;
   if (!kinds && !divert && lmax * 4 <= lmin * 5) return GLRM_OK;
   std::vector<int32_t> perm, none;
@@ -39,10 +39,10 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
   const int64_t nslots = (int64_t)perm.size();
   if (nshort) *nshort = nslots;
   if (kinds) { // loss kind first (stable: by descending length inside a kind)
-    const glrm_loss* lt = h->losses_h.data() + h->cb;
+    const glrm_loss* lt = h->losses_h.data() + h->side[GLRM_COLS].begin;
     std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return lt[x].kind < lt[y].kind; });
   }
-  const bool lane_side = (rows ? h->tiled_row : h->tiled_col) && glrm_lane_wants(h, rows) && env_int("GLRM_HIP_LANE_DEAL", 1);
+  const bool lane_side = h->side[side].tiled && glrm_lane_wants(h, side) && env_int("GLRM_HIP_LANE_DEAL", 1);
   if (lane_side) {
     // The lane-per-segment passes (glrm_lane.hpp) read their tiles conflict free when the 16 lanes of an LDS cycle hold 16 different
     // classes (global id) & 15 -- true when slot s holds a segment of class s & 15.  In natural order that is given; a sorted list is dealt
@@ -50,8 +50,8 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
     // that runs dry is filled from the longest remaining queue: costs conflicts at the tail, never bits).  Measured before (session r6_35,
     // C5 recipe at 1M rows, columns sorted by kind and length): bank conflicts in 48 % of the column passes' LDS cycles.
     std::vector<int32_t> q[16];
-    const int64_t g0 = rows ? h->rb : h->cb;
-    h->lane_dealt[rows ? 0 : 1] = 1;
+    const int64_t g0 = h->side[side].begin;
+    h->side[side].lane_dealt = 1;
     for (int32_t sgm : perm) q[(g0 + sgm) & 15].push_back(sgm);
     size_t head[16] = {0};
     for (int64_t slot = 0; slot < nslots; ++slot) {
@@ -63,13 +63,13 @@ static int make_segperm(glrm_handle* h, bool rows, int32_t** out, int64_t long_f
       }
       perm[(size_t)slot] = q[c][head[c]++];
     }
-  } else if (!rows && tile_rot_rt(h->G, h->R)) {
+  } else if (side == GLRM_COLS && tile_rot_rt(h->G, h->R)) {
     // the column passes read their tiles conflict-free (glrm_tiled.hpp: tile_rot) when slot s holds a segment of class (s & 7) >> 1,
     // class = ((global id) & 7) >> 1: deal the sorted list out class by class, two per block of eight slots -- the four classes are
     // equally frequent, so every wave still meets segments of one kind and similar length; a class that runs dry is filled from the
     // longest remaining queue (costs bank conflicts at the tail, never bits)
     std::vector<int32_t> q[4];
-    for (int32_t sgm : perm) q[tile_rot_of(h->cb + sgm)].push_back(sgm);
+    for (int32_t sgm : perm) q[tile_rot_of(h->side[GLRM_COLS].begin + sgm)].push_back(sgm);
     size_t head[4] = {0, 0, 0, 0};
     for (int64_t slot = 0; slot < nslots; ++slot) {
       int c = tile_rot_of(slot); // the class the slot's position wants
@@ -93,8 +93,10 @@ int glrm_prepare_tiled(glrm_handle* h) {
   const int T = glrm_tile_rows(h->kp);
   if (const int rc = h->mem.alloc(&h->dflag, 2)) return rc;
   HIPCK(hipMemsetAsync(h->dflag, 0, 2 * sizeof(int), st));
-  if (h->ml > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->ml, T, h->dflag);
-  if (h->nl > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)h->nl), dim3(256), 0, st, h->colptr, h->rowidx, h->nl, T, h->dflag + 1);
+  for (int s = 0; s < 2; ++s) { // a block per segment: 64 threads for a row's list, 256 for a column's (columns are the long ones)
+    const glrm_handle::Side& v = h->side[s];
+    if (v.nseg > 0) hipLaunchKernelGGL(check_sorted_kernel, dim3((unsigned)v.nseg), dim3(s == GLRM_ROWS ? 64 : 256), 0, st, v.ptr, v.idx, v.nseg, T, h->dflag + s);
+  }
   HIPCK(hipGetLastError());
   int flags[2] = {0, 0};
   HIPCK(hipMemcpyAsync(flags, h->dflag, sizeof flags, hipMemcpyDeviceToHost, st));
@@ -109,8 +111,9 @@ int glrm_prepare_tiled(glrm_handle* h) {
 int glrm_setup_tiled(glrm_handle* h) {
   hipStream_t st = h->stream;
   int rc0 = GLRM_OK;
-  h->rows_sorted = !h->sig.rows_unordered;
-  h->cols_sorted = !h->sig.cols_unordered;
+  glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
+  rows.sorted = !h->sig.rows_unordered;
+  cols.sorted = !h->sig.cols_unordered;
 
   const int T = glrm_tile_rows(h->kp);
   // expected observations of one segment inside one tile; the tiled sweeps pay off when a staged
@@ -137,41 +140,38 @@ int glrm_setup_tiled(glrm_handle* h) {
   // (a shard whose own lists are already in tile order gets them back unchanged -- the sort is stable -- so the decision may be
   // taken for the whole problem; a list too long for the segmented sort anywhere keeps every shard on the gather sweeps)
   const int64_t sort_limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0) > 0 ? env_int("GLRM_HIP_TILE_SORT_BATCH", 0) : 1500000000ll;
-  if (want_row && !h->rows_sorted && may_sort && h->sig.max_row_len <= sort_limit) {
-    if (h->sig_local.rows_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->rowptr, h->ml, h->nnz_r, T, h->n, &h->colidx, &h->rowvals, h->mem);
-      if (rc) return rc;
+  const bool want_side[2] = {want_row, want_col}, unordered_here[2] = {h->sig_local.rows_unordered != 0, h->sig_local.cols_unordered != 0};
+  const int64_t max_len[2] = {h->sig.max_row_len, h->sig.max_col_len};
+  for (int s = 0; s < 2; ++s) {
+    glrm_handle::Side& v = h->side[s];
+    if (want_side[s] && !v.sorted && may_sort && max_len[s] <= sort_limit) {
+      if (unordered_here[s]) {
+        const int rc = glrm_tile_sort_view(st, v.ptr, v.nseg, v.nnz, T, h->side[s ^ 1].nglob, &v.idx, &v.vals, h->mem);
+        if (rc) return rc;
+      }
+      v.sorted = true;
     }
-    h->rows_sorted = true;
+    v.tiled = (v.sorted && want_side[s]) ? 1 : 0;
   }
-  if (want_col && !h->cols_sorted && may_sort && h->sig.max_col_len <= sort_limit) {
-    if (h->sig_local.cols_unordered) {
-      const int rc = glrm_tile_sort_view(st, h->colptr, h->nl, h->nnz_c, T, h->m, &h->rowidx, &h->colvals, h->mem);
-      if (rc) return rc;
-    }
-    h->cols_sorted = true;
-  }
-  h->tiled_row = (h->rows_sorted && want_row) ? 1 : 0;
-  h->tiled_col = (h->cols_sorted && want_col) ? 1 : 0;
   // (rows on the lane-per-segment passes -- glrm_lane.hpp -- keep the caller's order: every lane evaluates its own observation's loss, so
   // there is no wave-wide formula to align, and the grouped copy would cost 12 B per observation beside the SELL stream)
-  const bool lane_rows = h->tiled_row && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && glrm_lane_wants(h, true);
-  if (h->tiled_row && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !lane_rows) {
+  const bool lane_rows = rows.tiled && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && glrm_lane_wants(h, GLRM_ROWS);
+  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !lane_rows) {
     DevArena scratch;
     int32_t* oidx = nullptr;
     double* ovals = nullptr;
-    if ((rc0 = scratch.alloc(&oidx, (size_t)h->nnz_r)) || (rc0 = scratch.alloc(&ovals, (size_t)h->nnz_r))) return rc0;
-    hipLaunchKernelGGL(group_rows_by_kind_kernel, dim3((unsigned)h->ml), dim3(64), 0, st, h->rowptr, h->colidx, h->rowvals, h->ml, T, h->losses, oidx, ovals);
+    if ((rc0 = scratch.alloc(&oidx, (size_t)rows.nnz)) || (rc0 = scratch.alloc(&ovals, (size_t)rows.nnz))) return rc0;
+    hipLaunchKernelGGL(group_rows_by_kind_kernel, dim3((unsigned)rows.nseg), dim3(64), 0, st, rows.ptr, rows.idx, rows.vals, rows.nseg, T, h->losses, oidx, ovals);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(st));
-    h->mem.release(&h->colidx); // (a borrowed view is not the arena's: it stays the caller's)
-    h->mem.release(&h->rowvals);
-    h->colidx = oidx;
-    h->rowvals = ovals;
+    h->mem.release(&rows.idx); // (a borrowed view is not the arena's: it stays the caller's)
+    h->mem.release(&rows.vals);
+    rows.idx = oidx;
+    rows.vals = ovals;
     scratch.move_to(h->mem, oidx);
     scratch.move_to(h->mem, ovals);
   }
-  if (h->tiled_row && h->n_losses > 1 && h->nnz_r > 0 && env_int("GLRM_HIP_UDESC", 1)) {
+  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && env_int("GLRM_HIP_UDESC", 1)) {
     // distinct loss descriptors of the model; with at most 256 of them every entry of the row view carries a one-byte id and the
     // row sweep reads descriptors from an LDS table (TiledArgs::descid)
     std::vector<glrm_loss> uniq;
@@ -191,10 +191,10 @@ int glrm_setup_tiled(glrm_handle* h) {
     if (ok) {
       DevArena scratch;
       uint8_t* dcolid = nullptr;
-      if ((rc0 = scratch.alloc(&dcolid, (size_t)h->n)) || (rc0 = h->mem.alloc(&h->udesc, uniq.size())) || (rc0 = h->mem.alloc(&h->rowdescid, (size_t)h->nnz_r))) return rc0;
+      if ((rc0 = scratch.alloc(&dcolid, (size_t)h->n)) || (rc0 = h->mem.alloc(&h->udesc, uniq.size())) || (rc0 = h->mem.alloc(&h->rowdescid, (size_t)rows.nnz))) return rc0;
       HIPCK(hipMemcpyAsync(dcolid, colid.data(), (size_t)h->n, hipMemcpyHostToDevice, st));
       HIPCK(hipMemcpyAsync(h->udesc, uniq.data(), uniq.size() * sizeof(glrm_loss), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(entry_descid_kernel, dim3(4096), dim3(256), 0, st, h->colidx, h->nnz_r, dcolid, h->rowdescid);
+      hipLaunchKernelGGL(entry_descid_kernel, dim3(4096), dim3(256), 0, st, rows.idx, rows.nnz, dcolid, h->rowdescid);
       HIPCK(hipGetLastError());
       HIPCK(hipStreamSynchronize(st)); // colid / uniq are locals
       h->n_udesc = (int)uniq.size();
@@ -210,7 +210,7 @@ int glrm_setup_tiled(glrm_handle* h) {
     // (the lane-per-segment form of the passes holds 512 columns per workgroup and stages its tiles of X at ~3 TB/s with nothing to overlap
     // them: more, shorter super-tiles even the workgroups out -- C2 Y half-step 7.6 -> 7.0 ms at twice the workgroups, session r6_09; the
     // family is a function of the whole problem's signature, so this still is)
-    const bool lane_c = h->tiled_col && glrm_lane_wants(h, false);
+    const bool lane_c = cols.tiled && glrm_lane_wants(h, GLRM_COLS);
     const int spb = lane_c ? 512 : 16 * (64 / h->tG);
     const int64_t groups = (h->n + spb - 1) / spb;
     const int64_t want_wg = env_int("GLRM_HIP_COL_WORKGROUPS", lane_c ? 2048 : 1024);
@@ -220,12 +220,12 @@ int glrm_setup_tiled(glrm_handle* h) {
     const int64_t tps_max = 32768 / T > 1 ? 32768 / T : 1; // at most ~32k rows per super-tile (long columns still spread out)
     if (tps > tps_max) tps = tps_max;
     if (tps < 1) tps = 1;
-    h->pass[1].tiles_per_sup = (int)tps;
+    cols.pass.tiles_per_sup = (int)tps;
   }
-  h->pass[1].nsup = (int)((ntiles + h->pass[1].tiles_per_sup - 1) / h->pass[1].tiles_per_sup);
-  if (h->tiled_col) {
-    if ((rc0 = glrm_alloc_pass_buffers(h, 1))) return rc0;
-    HIPCK(hipMemsetAsync(h->pass[1].active, 0, (size_t)(h->nl > 0 ? h->nl : 1) * 4, st)); // diverted columns are never touched by col_reduce: "not searching"
+  cols.pass.nsup = (int)((ntiles + cols.pass.tiles_per_sup - 1) / cols.pass.tiles_per_sup);
+  if (cols.tiled) {
+    if ((rc0 = glrm_alloc_pass_buffers(h, GLRM_COLS))) return rc0;
+    HIPCK(hipMemsetAsync(cols.pass.active, 0, (size_t)(cols.nseg > 0 ? cols.nseg : 1) * 4, st)); // diverted columns are never touched by col_reduce: "not searching"
     // Skewed column lengths (round 5, like the phase-aligned passes: glrm_blocked.hip).  The columns are already handed out sorted by
     // length; a workgroup's 256 columns walk a tile in lockstep (one barrier per tile), so ONE column many times the others keeps its
     // workgroup on every tile for its own entries alone, and the few workgroups of the head of the sorted list are the makespan (C2
@@ -237,25 +237,25 @@ int glrm_setup_tiled(glrm_handle* h) {
     const int64_t mean_len = h->sig.nnz_cols / (h->n > 0 ? h->n : 1);
     h->blk_long_from = env_int("GLRM_HIP_TILED_LONG_FROM", -1) >= 0 ? env_int("GLRM_HIP_TILED_LONG_FROM", 0) : std::max<int64_t>(4096, 4 * mean_len);
     std::vector<int32_t> longl;
-    if ((rc0 = make_segperm(h, false, &h->colperm, h->blk_long_from, &longl, &h->blk_nshort_c))) return rc0;
+    if ((rc0 = make_segperm(h, GLRM_COLS, &cols.perm, h->blk_long_from, &longl, &h->blk_nshort_c))) return rc0;
     if ((rc0 = glrm_set_long_columns(h, longl))) return rc0;
   }
-  if (h->tiled_row && (rc0 = make_segperm(h, true, &h->rowperm))) return rc0;
+  if (rows.tiled && (rc0 = make_segperm(h, GLRM_ROWS, &rows.perm))) return rc0;
   // Line-search rounds over the still-searching segments only (glrm_tiled.hpp: TiledArgs::actlist_out).  Columns: the passes after the
   // first trial; rows: everything after the first trial, which stays fused with the gradient pass in one kernel (GLRM_HIP_TILE_ROUNDS:
   // bit0 rows, bit1 columns, default 3; 0 = the round-3 forms).  Two lists (the decide kernel reads one and writes the next).
   h->tile_rounds = env_int("GLRM_HIP_TILE_ROUNDS", 3);
-  if ((h->tiled_row && (h->tile_rounds & 1)) || (h->tiled_col && (h->tile_rounds & 2))) {
-    const int64_t cap = std::max<int64_t>(1, std::max(h->tiled_row ? h->ml : 0, h->tiled_col ? h->nl : 0));
+  if ((rows.tiled && (h->tile_rounds & 1)) || (cols.tiled && (h->tile_rounds & 2))) {
+    const int64_t cap = std::max<int64_t>(1, std::max(rows.tiled ? rows.nseg : 0, cols.tiled ? cols.nseg : 0));
     if ((rc0 = h->mem.alloc(&h->actlist, (size_t)cap * 2))) return rc0;
     h->actlist_cap = cap;
   }
   // the pass buffers of the row rounds: ONE super-tile (nothing is re-added: the bits of the one-kernel sweep)
-  if (h->tiled_row && (h->tile_rounds & 1)) {
+  if (rows.tiled && (h->tile_rounds & 1)) {
     const int64_t nt = (h->n + T - 1) / T;
-    h->pass[0].tiles_per_sup = (int)(nt > 0 ? nt : 1);
-    h->pass[0].nsup = 1;
-    if ((rc0 = glrm_alloc_pass_buffers(h, 0))) return rc0;
+    rows.pass.tiles_per_sup = (int)(nt > 0 ? nt : 1);
+    rows.pass.nsup = 1;
+    if ((rc0 = glrm_alloc_pass_buffers(h, GLRM_ROWS))) return rc0;
   }
   return glrm_setup_lane(h); // the lane-per-segment form of the passes where it applies (glrm_lane.hip)
 }
@@ -314,12 +314,12 @@ static int launch_tiled(glrm_handle* h, int loss, int kind, const TiledArgs& a) 
   return glrm_dispatch_layout<8, 16, 32, 64, 128>(h->tG, h->tR, by_layout, [&] { return fail(GLRM_ERR_UNSUPPORTED, "no tiled kernel for lane layout G=%d R=%d", h->tG, h->tR); });
 }
 
-void glrm_launch_col_small(int kp, int which, const TiledArgs& a, hipStream_t st) {
+void glrm_launch_col_small(int kp, int stage, const TiledArgs& a, hipStream_t st) {
   auto by_layout = [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     const unsigned gx = (unsigned)((a.nseg + 4 * (64 / G) - 1) / (4 * (64 / G)));
-    if (which == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
-    else if (which == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
+    if (stage == 0 && a.vecreg) hipLaunchKernelGGL((col_reduce_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
+    else if (stage == 0) hipLaunchKernelGGL((col_reduce_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
     else if (a.vecreg) hipLaunchKernelGGL((col_decide_kernel<G, R, true>), dim3(gx), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((col_decide_kernel<G, R>), dim3(gx), dim3(256), 0, st, a);
     return GLRM_OK;
@@ -329,26 +329,26 @@ void glrm_launch_col_small(int kp, int which, const TiledArgs& a, hipStream_t st
 
 // The tiled variants of run_sweep's launch.  Rows: one kernel.  Columns: pass 1 -> reduce -> rounds of
 // (trial pass, decide) until no column is still searching (the count is read back once per round).
-int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
+int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
   TiledArgs a{};
-  glrm_fill_side(a, h, rows, min_stepsize, eval_only);
+  glrm_fill_side(a, h, side, min_stepsize, eval_only);
   a.loss_by_segment = loss_by_segment;
-  a.descid = rows ? h->rowdescid : nullptr;
+  a.descid = side == GLRM_ROWS ? h->rowdescid : nullptr;
   a.udesc = h->udesc;
   a.n_udesc = h->n_udesc;
-  const bool range = rows && h->rng_e >= 0; // glrm_hip_step_x_range
+  const bool range = side == GLRM_ROWS && h->rng_e >= 0; // glrm_hip_step_x_range
   if (range) {
     glrm_apply_row_range(a, h->rng_b, h->rng_e);
     if (a.nseg <= 0) return GLRM_OK;
   }
-  const glrm_act_lists lists = glrm_active_lists(h, rows, a.nseg);
-  const bool row_rounds = rows && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
+  const glrm_act_lists lists = glrm_active_lists(h, side, a.nseg);
+  const bool row_rounds = side == GLRM_ROWS && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
   // lane-per-segment passes (glrm_lane.hpp): the ProxGradParams half-steps and the evaluation pass of the sides that run that family
-  const bool lane_here = h->lane[rows ? 0 : 1] && glrm_lane_loss_ok(h, loss) && a.fixed_alpha <= 0.0 && (rows ? row_rounds : true);
-  a.segperm = rows ? (range ? nullptr : h->rowperm) : h->colperm; // a sub-range sweep keeps the natural order
-  if (rows && !row_rounds) return launch_tiled(h, loss, 0, a);
-  glrm_bind_pass_buffers(a, h, rows ? 0 : 1, range ? h->rng_b : 0); // (rows: one super-tile, glrm_setup_tiled)
-  if (!rows && h->blk_nlong_c > 0) { // the columns at or above long_from run on the gather sweep beside the passes (run_sweep, glrm_hip.hip)
+  const bool lane_here = h->side[side].lane && glrm_lane_loss_ok(h, loss) && a.fixed_alpha <= 0.0 && (side == GLRM_ROWS ? row_rounds : true);
+  a.segperm = range ? nullptr : h->side[side].perm; // a sub-range sweep keeps the natural order
+  if (side == GLRM_ROWS && !row_rounds) return launch_tiled(h, loss, 0, a);
+  glrm_bind_pass_buffers(a, h, side, range ? h->rng_b : 0); // (rows: one super-tile, glrm_setup_tiled)
+  if (side == GLRM_COLS && h->blk_nlong_c > 0) { // the columns at or above long_from run on the gather sweep beside the passes (run_sweep, glrm_hip.hip)
     a.long_from = h->blk_long_from;
     a.npass = h->blk_nshort_c;
     if (a.npass == 0) { // every local column is diverted
@@ -356,11 +356,11 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
       return GLRM_OK;
     }
   }
-  if (lane_here) return glrm_run_lane(h, rows, loss, a, min_stepsize, eval_only);
+  if (lane_here) return glrm_run_lane(h, side, loss, a, min_stepsize, eval_only);
   int rc;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   a.actlist_out = lists.list[0]; // the list the kernels of this stage append to
-  if (rows) {
+  if (side == GLRM_ROWS) {
     if ((rc = launch_tiled(h, loss, 3, a))) return rc; // gradient pass + first trial; rejected rows are listed
   } else {
     // gradient pass: under glrm_hip_step_y_arrival in runs of super-tiles, each behind the blocks of X it reads (announced order)
@@ -381,12 +381,12 @@ int glrm_run_tiled(glrm_handle* h, bool rows, int loss, int loss_by_segment, dou
         TiledArgs t = a;
         // the trial pass: over the listed segments when they are the minority (a full grid keeps the length / kind order of segperm, which
         // pays while nearly every segment still takes part: the first trial of the columns)
-        if (list && (rows || (int64_t)nact * 4 < a.nseg * 3)) {
+        if (list && (side == GLRM_ROWS || (int64_t)nact * 4 < a.nseg * 3)) {
           t.segperm = list;
           t.nseg = nact;
           t.npass = 0;
         }
-        return launch_tiled(h, loss, rows ? 4 : 2, t);
+        return launch_tiled(h, loss, side == GLRM_ROWS ? 4 : 2, t);
       },
       [&](const TiledArgs& d) { glrm_launch_col_small(h->kp, 1, d, h->stream); });
 }

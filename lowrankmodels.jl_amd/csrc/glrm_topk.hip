@@ -365,7 +365,7 @@ int tk_check(glrm_handle* h, const double* X, const double* Y, const char* what)
                   "of Y per data column (d == n)", what, (long long)j, h->losses_h[j].kind, h->losses_h[j].dim);
   if (h->d != h->n) return fail(GLRM_ERR_UNSUPPORTED, "%s: Y has %lld vectors for %lld columns (d != n)", what, (long long)h->d, (long long)h->n);
   if ((X == nullptr) != (Y == nullptr)) return fail(GLRM_ERR_INVALID, "%s: X and Y must both be given or both be NULL (NULL = the handle's resident factors)", what);
-  if (!X && (!h->X || !h->Y)) return fail(GLRM_ERR_INVALID, "%s: no factors on the device yet (pass X and Y, or fit / glrm_hip_set_factors first)", what);
+  if (!X && (!h->side[GLRM_ROWS].factor || !h->side[GLRM_COLS].factor)) return fail(GLRM_ERR_INVALID, "%s: no factors on the device yet (pass X and Y, or fit / glrm_hip_set_factors first)", what);
   return GLRM_OK;
 }
 
@@ -375,7 +375,7 @@ int tk_factors(glrm_handle* h, const double* X, const double* Y, TkFactors& f) {
     const int rc = glrm_hip_set_factors(h, X, Y);
     if (rc) return rc;
   }
-  f.X = h->X; f.Y = h->Y; f.k = h->k; f.kp = h->kp; f.m = h->m; f.n = h->n;
+  f.X = h->side[GLRM_ROWS].factor; f.Y = h->side[GLRM_COLS].factor; f.k = h->k; f.kp = h->kp; f.m = h->m; f.n = h->n;
   return GLRM_OK;
 }
 
@@ -513,7 +513,7 @@ extern "C" int glrm_hip_precision_scan(glrm_handle* h, const double* X, const do
   if ((rc = lists.alloc(&d_tidx, (size_t)ntest))) return rc;
   HIPCK(hipMemcpyAsync(d_tptr, test_rowptr, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
   if (ntest > 0) HIPCK(hipMemcpyAsync(d_tidx, test_colidx, (size_t)ntest * 4, hipMemcpyHostToDevice, st));
-  l.train_ptr = h->rowptr; l.train_idx = h->colidx; l.test_ptr = d_tptr; l.test_idx = d_tidx;
+  l.train_ptr = h->side[GLRM_ROWS].ptr; l.train_idx = h->side[GLRM_ROWS].idx; l.test_ptr = d_tptr; l.test_idx = d_tidx;
 
   const int64_t tiles_n = (n + TK_TILE - 1) / TK_TILE;
   const int64_t most_rows = std::max<int64_t>(1, std::min<int64_t>(TK_BLOCK_ROWS, TK_BLOCK_ENTRIES / n));

@@ -88,14 +88,15 @@ __global__ void check_rowidx_kernel(const int32_t* rowidx, int64_t nnz, int64_t 
 
 } // namespace
 
-// h holds the uploaded column view (colptr, rowidx, colvals, nnz_c) of the WHOLE problem; fills rowptr, colidx, rowvals, nnz_r.
+// h holds the uploaded column view (side[GLRM_COLS]: ptr, idx, vals, nnz) of the WHOLE problem; fills the same four of side[GLRM_ROWS].
 int glrm_rows_from_cols(glrm_handle* h) {
-  const int64_t nnz = h->nnz_c, m = h->m, n = h->n;
+  glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
+  const int64_t nnz = cols.nnz, m = h->m, n = h->n;
   hipStream_t st = h->stream;
-  h->nnz_r = nnz;
+  rows.nnz = nnz;
   int rc;
-  if ((rc = h->mem.alloc(&h->rowptr, (size_t)m + 1)) || (rc = h->mem.alloc(&h->colidx, (size_t)nnz)) || (rc = h->mem.alloc(&h->rowvals, (size_t)nnz))) return rc;
-  HIPCK(hipMemsetAsync(h->rowptr, 0, ((size_t)m + 1) * 8, st));
+  if ((rc = h->mem.alloc(&rows.ptr, (size_t)m + 1)) || (rc = h->mem.alloc(&rows.idx, (size_t)nnz)) || (rc = h->mem.alloc(&rows.vals, (size_t)nnz))) return rc;
+  HIPCK(hipMemsetAsync(rows.ptr, 0, ((size_t)m + 1) * 8, st));
   if (nnz == 0) return GLRM_OK;
   if (m + 1 > (int64_t)INT32_MAX) return fail(GLRM_ERR_UNSUPPORTED, "GLRM_PROBLEM_ROWS_FROM_COLS: %lld rows", (long long)m);
   const int64_t cap0 = env_int("GLRM_HIP_TRANSPOSE_CHUNK", 1500000000);
@@ -119,22 +120,22 @@ int glrm_rows_from_cols(glrm_handle* h) {
   // 1. indices in range; 2. row pointers = inclusive scan of the per-row counts
   if ((rc = scratch.alloc(&flag, 1, oom))) return rc;
   if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return fail(GLRM_ERR_HIP, "memset failed");
-  hipLaunchKernelGGL(check_rowidx_kernel, dim3(4096), dim3(256), 0, st, h->rowidx, nnz, m, flag);
+  hipLaunchKernelGGL(check_rowidx_kernel, dim3(4096), dim3(256), 0, st, cols.idx, nnz, m, flag);
   int bad = 0;
   if (hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return fail(GLRM_ERR_HIP, "row index check failed");
   if (bad) return fail(GLRM_ERR_INVALID, "rowidx holds an index outside [0, m)");
   lap("index check");
-  hipLaunchKernelGGL(row_count_kernel, dim3(8192), dim3(256), 0, st, h->rowidx, nnz, reinterpret_cast<unsigned long long*>(h->rowptr));
+  hipLaunchKernelGGL(row_count_kernel, dim3(8192), dim3(256), 0, st, cols.idx, nnz, reinterpret_cast<unsigned long long*>(rows.ptr));
   size_t bytes = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan (size query) failed");
+  if (hipcub::DeviceScan::InclusiveSum(nullptr, bytes, rows.ptr, rows.ptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan (size query) failed");
   if ((rc = scratch.alloc(&tmp, bytes, "out of device memory for the row view (scan scratch)"))) return rc;
-  if (hipcub::DeviceScan::InclusiveSum(tmp, bytes, h->rowptr, h->rowptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
+  if (hipcub::DeviceScan::InclusiveSum(tmp, bytes, rows.ptr, rows.ptr, (int)(m + 1), st) != hipSuccess) return fail(GLRM_ERR_HIP, "scan failed");
   std::vector<int64_t> rp;
   const bool whole = nnz <= cap;
   if (!whole) {
     rp.resize((size_t)m + 1);
-    if (hipMemcpyAsync(rp.data(), h->rowptr, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(GLRM_ERR_HIP, "row pointer read-back failed");
+    if (hipMemcpyAsync(rp.data(), rows.ptr, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(GLRM_ERR_HIP, "row pointer read-back failed");
   }
   if (hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "row pointers failed");
   scratch.release(&tmp);
@@ -169,9 +170,9 @@ int glrm_rows_from_cols(glrm_handle* h) {
     const int64_t r0 = cuts[c], r1 = cuts[c + 1];
     const int64_t at = whole ? 0 : rp[(size_t)r0], cnt = whole ? nnz : rp[(size_t)r1] - rp[(size_t)r0];
     if (cnt == 0) continue;
-    const uint32_t* keys = reinterpret_cast<const uint32_t*>(h->rowidx); // non-negative int32: the same bits
+    const uint32_t* keys = reinterpret_cast<const uint32_t*>(cols.idx); // non-negative int32: the same bits
     if (!whole) {
-      hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, h->rowidx, nnz, span, (int32_t)r0, (int32_t)r1, blk);
+      hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, cols.idx, nnz, span, (int32_t)r0, (int32_t)r1, blk);
       if (hipMemcpyAsync(cnts.data(), blk, (size_t)nblk * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return fail(GLRM_ERR_HIP, "row-range count failed");
       unsigned long long run = 0;
@@ -179,7 +180,7 @@ int glrm_rows_from_cols(glrm_handle* h) {
       if ((int64_t)run != cnt) return fail(GLRM_ERR_HIP, "row-range count disagrees with the row pointers (%llu vs %lld)", run, (long long)cnt);
       if (hipMemcpyAsync(blk, cnts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, st) != hipSuccess) return fail(GLRM_ERR_HIP, "row-range offsets failed");
       lap("range count");
-      hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, h->rowidx, nnz, span, (int32_t)r0, (int32_t)r1, blk, k0, gpos);
+      hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nblk), dim3(SEL_THREADS), 0, st, cols.idx, nnz, span, (int32_t)r0, (int32_t)r1, blk, k0, gpos);
       keys = k0;
       lap("range scatter");
     }
@@ -188,7 +189,7 @@ int glrm_rows_from_cols(glrm_handle* h) {
     if (hipcub::DeviceRadixSort::SortPairs(tmp, b2, keys, k1, p0, p1, (int)cnt, 0, bits, st) != hipSuccess) // stable: a row's entries keep their column order
       return fail(GLRM_ERR_HIP, "radix sort failed");
     lap("sort");
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(8192), dim3(256), 0, st, p1, whole ? nullptr : gpos, cnt, h->colptr, n, h->colvals, h->colidx + at, h->rowvals + at);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(8192), dim3(256), 0, st, p1, whole ? nullptr : gpos, cnt, cols.ptr, n, cols.vals, rows.idx + at, rows.vals + at);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GLRM_ERR_HIP, "row view kernels failed"); // cnts is reused
     lap("gather");
   }

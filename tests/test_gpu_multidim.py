@@ -263,6 +263,35 @@ def test_set_regularizers_moves_a_scalar_handle_to_the_general_sweeps():
     assert np.all(X[-1] == 1.0)
 
 
+def test_set_regularizers_moves_a_tiled_handle_to_the_general_sweeps():
+    """The same move on a handle whose LDS-tiled flags are set (tiled = 2): the flags stay, yet the general sweeps run both half-steps and
+    glrm_hip_sum_order says so -- `multi` comes before `tiled` in the family precedence (csrc/glrm_engine.hpp: glrm_side_family).  Rank 5 is
+    padded to 8, the tile holds 1 920 vectors, so a column of the 2 500 rows spans two tiles."""
+    rng = np.random.default_rng(32)
+    m, n, k = 2500, 300, 5
+    A = rng.standard_normal((m, 3)) @ rng.standard_normal((3, n)) + 2.0
+    I, J = np.nonzero(rng.random((m, n)) < 0.4)
+    X0, Y0 = rng.standard_normal((k, m)), rng.standard_normal((k, n))
+    g = L.GLRM(A, L.QuadLoss(), L.QuadReg(0.1), L.QuadReg(0.1), k, obs=(I, J), X=X0, Y=Y0)
+    p = L.ProxGradParams(max_iter=10)
+    api = hip()
+    h = api.create(g.problem_arrays(), tiled=2)
+    try:
+        assert api.kernel_stats(h)["tiled"] & 3 == 3  # bit 0 / bit 1: LDS-tiled row / column sweep
+        L.add_offset_(g)
+        from lowrankmodels.jl_amd.regularizers import pack_regs
+        api.set_regularizers(h, pack_regs(g.rx), pack_regs(g.ry))
+        assert api.kernel_stats(h)["tiled"] == 8
+        assert [api.sum_order(h, w).asdict()["family_name"] for w in (0, 1)] == ["other", "other"]
+        X, Y = np.array(X0, order="F"), np.array(Y0, order="F")
+        obj, _ = api.fit(h, p, X, Y)
+    finally:
+        api.destroy(h)
+    o_c, X_c, Y_c, _ = cases.run_engine(O.oracle_api(), g.problem_arrays(), X0, Y0, p)
+    assert cases.rel_err(obj, o_c) < TOL and cases.fro_err(X, X_c) < TOL and cases.fro_err(Y, Y_c) < TOL
+    assert np.all(X[-1] == 1.0)
+
+
 def test_python_fit_with_offset_and_categoricals():
     """The host-side mirror: GLRM(..., offset=True) + fit! on the HIP engine, warm start continues."""
     kwargs, _ = cases.build_multidim_case("categorical_mix")
