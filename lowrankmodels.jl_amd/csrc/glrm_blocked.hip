@@ -40,7 +40,10 @@ constexpr int BNW = 1;                                                     // wa
 // loop is compiled in either way (134 instead of 118 VGPRs and 3 waves per SIMD when it was built), and C4's Y half-step ran 134.1 ms with
 // the gate off against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).  Since the 32-bit gather offsets the
 // rank-64 QuadLoss gradient kernel is built for 128 VGPRs and 4 waves per SIMD again, gate included (pass_waves_per_simd, glrm_tiled.hpp).
-constexpr int BLOCKED_GATE_DEFAULT = 8192;
+// The default was 8 192 rows (round 7: the 4 MB of an XCD's L2 at rank 64, chosen when both passes ran 3 waves per SIMD).  With both passes
+// at 4 waves per SIMD and 16 384 columns per launch the optimum sits lower -- C4 Y half-step at 4 096 / 5 120 / 5 632 / 6 144 / 6 656 /
+// 7 168 / 8 192 rows: 109.7 / 107.9 / 108.3 / 108.9 / 109.4 / 110.0 / 110.9 ms (profiles/r14_c4_ab.txt).  Changes no sum.
+constexpr int BLOCKED_GATE_DEFAULT = 5120;
 
 // suppos[seg * nsup + sup] = lower_bound_idx(segment seg's list, first row of super-tile sup) - ptr[seg]: the pass kernel's own search, so
 // that lists ordered by tile only get exactly the position the kernel would find.  *too_long is set where a segment does not fit int32.
