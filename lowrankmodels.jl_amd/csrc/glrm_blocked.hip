@@ -26,24 +26,9 @@
 #include <chrono>
 #include <thread>
 
-#include "glrm_engine.hpp"
-#include "glrm_launch.hpp"
-#include "glrm_tiled.hpp"
+#include "glrm_blocked.hpp"
 
 using namespace glrm;
-
-// Waves per workgroup.  ONE: the finest grain the dispatcher can spread over the CUs and retire -- C4 Y half-step, same box, with the
-// half-residency launch slices below: 138.5 (4 waves) / 134.9 (2) / 129.6 ms (1); at full-residency slices 150.7 / 146.3 / 144.4
-// (profiles/r03_c4_blocked_knobs.txt).  Changes no sum (a lane group owns a segment whatever workgroup it sits in).
-constexpr int BNW = 1;                                                     // waves per workgroup
-// GLRM_HIP_BLOCKED_GATE: phase gate of the passes in rows (tiled_pass, L2 = true), 0 = off.  Off is NOT the kernel of round 6: the gated
-// loop is compiled in either way (134 instead of 118 VGPRs and 3 waves per SIMD when it was built), and C4's Y half-step ran 134.1 ms with
-// the gate off against 129.6 on the round-6 kernel and 119.2 at the default (profiles/r07_c4_ab.txt).  Since the 32-bit gather offsets the
-// rank-64 QuadLoss gradient kernel is built for 128 VGPRs and 4 waves per SIMD again, gate included (pass_waves_per_simd, glrm_tiled.hpp).
-// The default was 8 192 rows (round 7: the 4 MB of an XCD's L2 at rank 64, chosen when both passes ran 3 waves per SIMD).  With both passes
-// at 4 waves per SIMD and 16 384 columns per launch the optimum sits lower -- C4 Y half-step at 4 096 / 5 120 / 5 632 / 6 144 / 6 656 /
-// 7 168 / 8 192 rows: 109.7 / 107.9 / 108.3 / 108.9 / 109.4 / 110.0 / 110.9 ms (profiles/r14_c4_ab.txt).  Changes no sum.
-constexpr int BLOCKED_GATE_DEFAULT = 5120;
 
 // suppos[seg * nsup + sup] = lower_bound_idx(segment seg's list, first row of super-tile sup) - ptr[seg]: the pass kernel's own search, so
 // that lists ordered by tile only get exactly the position the kernel would find.  *too_long is set where a segment does not fit int32.
@@ -89,7 +74,16 @@ static int build_suppos(glrm_handle* h, int side) {
 
 int glrm_setup_blocked(glrm_handle* h) {
   for (glrm_handle::Side& v : h->side) v.blocked = 0;
-  const int want = env_int("GLRM_HIP_BLOCKED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
+  int want = env_int("GLRM_HIP_BLOCKED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
+  const bool f32 = h->storage == GLRM_STORAGE_F32;
+  if (f32) {
+    // A float handle takes the family only where GLRM_HIP_BLOCKED asks for it (tiled = 1 handles included: the variable outranks the option
+    // in both storages) until the auto rule is adopted: GLRM_BLOCKED_F32_AUTO.  Its finalize branch runs no glrm_setup_tiled, which is
+    // where an fp64 handle learns whether its lists are in tile order.
+    if (want < 0 && !GLRM_BLOCKED_F32_AUTO) want = 0;
+    h->side[GLRM_ROWS].sorted = !h->sig.rows_unordered;
+    h->side[GLRM_COLS].sorted = !h->sig.cols_unordered;
+  }
   if (want == 0 || h->kp < 8) return GLRM_OK;
   hipDeviceProp_t prop;
   HIPCK(hipGetDeviceProperties(&prop, h->device));
@@ -104,7 +98,7 @@ int glrm_setup_blocked(glrm_handle* h) {
     const int64_t nnz = side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols, nopp = h->side[side ^ 1].nglob;
     if (nnz <= 0) return false;
     if (want > 0) return ((want >> side) & 1) != 0;
-    const double opp_bytes = (double)nopp * h->kp * 8;
+    const double opp_bytes = (double)nopp * h->kp * 8; // (the fp64 rule on the same (nopp, kp, nnz), counted in 8-byte elements, in both storages)
     const int64_t nseg_glob = h->side[side].nglob;
     const double mean_len = (double)nnz / (double)nseg_glob;
     if (opp_bytes <= 32.0 * 1024 * 1024 || mean_len * (double)nseg_glob < 2e8) return false; // small factor: LDS tiles or plain L2 hits do better
@@ -121,7 +115,7 @@ int glrm_setup_blocked(glrm_handle* h) {
     int64_t t = ((int64_t)128 * 1024 * 1024) / ((int64_t)T * h->kp * 8); // ~128 MB of the opposing factor per super-tile
     t = env_int("GLRM_HIP_BLOCKED_TPS", (int)(t < 1 ? 1 : t));
     // the passes address an observation's vector by a 32-bit byte offset from the first row of its super-tile (tiled_pass, L2 = true)
-    if ((double)std::min<int64_t>(t * T, nopp) * h->kp * 8 >= 4294967296.0)
+    if ((double)std::min<int64_t>(t * T, nopp) * h->kp * (f32 ? 4 : 8) >= 4294967296.0) // (the geometry above is the 8-byte one in both storages: one problem, one order)
       return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: GLRM_HIP_BLOCKED_TPS=%lld makes a super-tile of 4 GiB or more of the opposing factor", (long long)t);
     h->side[side].pass.tiles_per_sup = (int)t;
     h->side[side].pass.nsup = (int)((ntiles + t - 1) / t);
@@ -161,133 +155,6 @@ int glrm_setup_blocked(glrm_handle* h) {
   return GLRM_OK;
 }
 
-// segments one launch may cover: what the chip holds at once (every group of the launch then starts its walk together)
-template <typename K>
-static int64_t slice_capacity(K kernel, int device, int spb) {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, BNW * 64, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
-  hipDeviceProp_t prop;
-  int cus = 256;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-  const int64_t cap = (int64_t)nb * cus * spb;
-  // percent of the residency one launch covers.  Half: the next launch's workgroups fill the CUs the current one's stragglers have left
-  // (launches of one stream overlap at their tails), which a slice of exactly the residency cannot do -- C4 Y half-step 143.2 -> 138.4 ms
-  // with four-wave workgroups (25 / 33 / 66 / 100 / 200 %: 149.0 / 148.1 / 141.6 / 143.2 / 144.1), and with one-wave workgroups
-  // 25 / 33 / 40 / 50 / 60 / 75 / 100 %: 139.7 / 137.0 / 135.6 / 131.0 / 133.0 / 136.9 / 144.4 (profiles/r03_c4_blocked_knobs.txt).
-  // With the gradient pass at 4 waves per SIMD (16 384 columns per launch in both passes) 40 / 50 / 60 / 75 %: 116.1 / 110.8 / 117.2 /
-  // 119.7 ms (profiles/r13_c4_ab.txt): half stays.  Changes no sum.
-  const int pct = env_int("GLRM_HIP_BLOCKED_FILL", 50);
-  return std::max<int64_t>(spb, cap * pct / 100 / spb * spb);
-}
-
-template <int G, int R, int LOSS, bool GRAD>
-static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
-  constexpr int KP = G * R, T = glrm_tile_rows(KP), SPB = BNW * (64 / G);
-  auto kernel = tiled_col_pass_kernel<G, R, BNW, T, LOSS, GRAD, true>;
-  // per handle, view and pass kind: the row passes (LOSS_PER_OBS* instantiations of a heterogeneous model) and the column passes
-  // (LOSS_SEGMENT*) of one handle are different kernels with their own occupancy; the CU count is the handle's device's, the fill
-  // percentage the environment's at the handle's first sweep
-  int64_t& cap_slot = h->side[side].blocked_cap[GRAD ? 0 : 1];
-  if (cap_slot == 0) cap_slot = slice_capacity(kernel, h->device, SPB);
-  const int64_t cap = cap_slot;
-  // phase gate in rows of the opposing factor (tiled_pass, L2 = true): read at every pass, so that one handle can be timed under several
-  // settings.  Changes no sum.
-  a.gate = std::max(0, env_int("GLRM_HIP_BLOCKED_GATE", BLOCKED_GATE_DEFAULT));
-  const int64_t nseg = a.npass > 0 ? a.npass : a.nseg;
-  // equal slices: ceil(nseg / cap) launches per super-tile, all of the same size (a last slice of a few percent of the others is a launch
-  // that cannot fill the chip)
-  const int64_t nslices = (nseg + cap - 1) / cap;
-  const int64_t per = nslices > 0 ? ((nseg + nslices - 1) / nslices + SPB - 1) / SPB * SPB : cap;
-  if (!env_int("GLRM_HIP_BLOCKED_SUPPOS", 1)) a.suppos = nullptr;
-  // glrm_hip_step_y_arrival: the gradient pass of the column view walks the super-tiles in the order their rows of X arrive, each behind
-  // the events of the blocks it touches (h->sup_order, glrm_run_blocked); the partial sums are per (segment, super-tile) and col_reduce
-  // adds them in super-tile order, so the launch order changes no bit
-  const bool ordered = GRAD && side == GLRM_COLS && h->n_arrival > 0 && (int)h->sup_order.size() == a.nsup;
-  const int64_t rows_per_sup = (int64_t)a.tiles_per_sup * T;
-  auto launch_sup = [&](int sup) -> int { // one super-tile: behind the events of the blocks it touches (ordered), slice by slice
-    if (ordered) {
-      const int rcw = glrm_arrival_wait(h, sup * rows_per_sup, std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other));
-      if (rcw) return rcw;
-    }
-    for (int64_t s0 = 0; s0 < nseg; s0 += per) {
-      a.sup_fixed = sup;
-      a.seg_begin = s0;
-      a.nseg_slice = std::min(per, nseg - s0);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((a.nseg_slice + SPB - 1) / SPB)), dim3(BNW * 64), 0, h->stream, a);
-    }
-    return GLRM_OK;
-  };
-  std::vector<int> pend;
-  if (ordered) pend = h->sup_order;
-  else for (int si = 0; si < a.nsup; ++si) pend.push_back(si);
-  if (ordered && !h->arrival_static && env_int("GLRM_HIP_ARRIVAL_DYNAMIC", 1)) {
-    // TRUE arrival order.  The fixed order above is the order blocks arrive in when every peer keeps pace; behind a lagging peer the
-    // in-order stream would stand in front of its block while super-tiles further down the list are ready.  So the host enqueues a
-    // super-tile only once the events of ALL its blocks have fired (hipEventQuery), the ready ones in list order, and polls for the
-    // rest: the stream never stands in a wait while work is ready.  An event that cannot be queried (or 5 s without any progress) hands
-    // the remaining super-tiles -- and every later call on this handle -- to the in-stream waits below.  Which order the super-tiles run in changes no bit.
-    std::vector<char> fired((size_t)h->n_arrival, 0);
-    bool unknown = false;
-    auto ready = [&](int sup) {
-      const int64_t lo = sup * rows_per_sup, hi = std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other);
-      for (int b = 0; b < h->n_arrival; ++b) {
-        const glrm_arrival& blk = h->arrival[b];
-        if (fired[b] || !blk.event || blk.end <= lo || blk.begin >= hi) continue;
-        const hipError_t q = hipEventQuery((hipEvent_t)blk.event);
-        if (q == hipSuccess) { fired[b] = 1; continue; }
-        (void)hipGetLastError();
-        if (q != hipErrorNotReady) unknown = true;
-        return false;
-      }
-      return true;
-    };
-    auto t_progress = std::chrono::steady_clock::now();
-    // the host polls where the stream used to wait: with glrm_options.profile the time in which NO super-tile was ready is booked as exposed
-    // exchange time (glrm_kernel_stats.ms_wait_y, ADVICE r5: in true arrival order the in-stream waits are ~0 and this time was counted nowhere).
-    // An upper bound on what the device stood idle for: super-tiles enqueued earlier may still be running while the host finds nothing ready.
-    double idle_s = 0.0;
-    while (!pend.empty() && !unknown) {
-      bool progressed = false;
-      for (size_t i = 0; i < pend.size() && !unknown;) {
-        if (!ready(pend[i])) { ++i; continue; }
-        const int rcl = launch_sup(pend[i]);
-        if (rcl) return rcl;
-        pend.erase(pend.begin() + (long)i);
-        progressed = true;
-      }
-      const auto now = std::chrono::steady_clock::now();
-      if (progressed) t_progress = now;
-      else if (std::chrono::duration<double>(now - t_progress).count() > 5.0) break;
-      else {
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-        idle_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - now).count();
-      }
-    }
-    if (h->profile) h->ms_wait += idle_s * 1e3;
-    if (!pend.empty()) h->arrival_static = true; // gave up: this handle keeps to the in-stream waits (no 5 s stall per iteration)
-  }
-  for (int sup : pend) {
-    const int rcl = launch_sup(sup);
-    if (rcl) return rcl;
-  }
-  HIPCK(hipGetLastError());
-  return GLRM_OK;
-}
-
-
-static int launch_blocked(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side) {
-  auto by_layout = [&](auto g, auto r) {
-    constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    auto by_loss = [&](auto LOSS) {
-      constexpr int L = decltype(LOSS)::value;
-      return grad ? launch_blocked_inst<G, R, L, true>(h, a, side) : launch_blocked_inst<G, R, L, false>(h, a, side);
-    };
-    return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
-  };
-  return glrm_dispatch_layout<8, 16, 32, 64, 128>(h->G, h->R, by_layout,
-                                                  [&] { return fail(GLRM_ERR_UNSUPPORTED, "no phase-aligned pass kernel for lane layout G=%d R=%d", h->G, h->R); });
-}
-
 int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
   TiledArgs a{};
   glrm_fill_side(a, h, side, min_stepsize, eval_only);
@@ -324,12 +191,16 @@ int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, do
     std::sort(key.begin(), key.end());
     for (auto& kv : key) h->sup_order.push_back(kv.second);
   }
-  if ((rc = launch_blocked(h, loss, true, a, side))) return rc;  // gradient + loss partials, super-tile by super-tile
-  glrm_launch_col_small(h->kp, 0, a, h->stream);                 // reduce in super-tile order, J_old, first trial point
+  // a float handle (glrm_options.storage = 1) takes the ST = float kernels of glrm_blocked_f32.hip: the same launches over the same buffers
+  const bool f32 = h->storage == GLRM_STORAGE_F32;
+  auto pass = [&](bool grad) { return f32 ? glrm_launch_blocked_f32(h, loss, grad, a, side) : launch_blocked_st<double>(h, loss, grad, a, side); };
+  auto small = [&](int stage, const TiledArgs& d) { f32 ? glrm_launch_col_small_f32(h->kp, stage, d, h->stream) : glrm_launch_col_small(h->kp, stage, d, h->stream); };
+  if ((rc = pass(true))) return rc;  // gradient + loss partials, super-tile by super-tile
+  small(0, a);                       // reduce in super-tile order, J_old, first trial point
   HIPCK(hipGetLastError());
   if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
   return glrm_run_rounds(
       h, a, min_stepsize, glrm_act_lists{},
-      [&](int, unsigned int, int32_t*) { return launch_blocked(h, loss, false, a, side); },  // loss partials at the trial points of the searching segments
-      [&](const TiledArgs& d) { glrm_launch_col_small(h->kp, 1, d, h->stream); });           // accept / shrink / give up, next trial point
+      [&](int, unsigned int, int32_t*) { return pass(false); },  // loss partials at the trial points of the searching segments
+      [&](const TiledArgs& d) { small(1, d); });                 // accept / shrink / give up, next trial point
 }

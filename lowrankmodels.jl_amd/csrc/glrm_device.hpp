@@ -209,6 +209,25 @@ struct Vec {
 template <int G, int R>
 __device__ __forceinline__ int comp_index(int i, int j, int h) { return i * 2 * G + 2 * j + h; }
 
+// Two adjacent components as the STORAGE type ST holds them (include/glrm_hip_storage.h; the families with a float form are templates
+// over ST: glrm_sweep.hpp, glrm_cached.hpp, the phase-aligned passes of glrm_tiled.hpp).  A lane's chunk i is one 16-byte (double) or one
+// 8-byte (float) load; the gathered chunks stay in their storage type until the fma that uses them, which halves the registers of the
+// float form's gather buffers.
+template <class ST> struct Pair;
+template <> struct Pair<double> { using type = double2; };
+template <> struct Pair<float> { using type = float2; };
+__device__ __forceinline__ double2 widen(double2 v) { return v; }
+__device__ __forceinline__ double2 widen(float2 v) { return make_double2((double)v.x, (double)v.y); }
+// the value the storage will hold for v: C's (float) conversion, round to nearest even, widened again (exact)
+template <class ST> __device__ __forceinline__ double stored(double v) {
+  if constexpr (sizeof(ST) == 4) return (double)(float)v;
+  else return v;
+}
+template <class ST> __device__ __forceinline__ void store_pair(typename Pair<ST>::type* p, double2 v) {
+  if constexpr (sizeof(ST) == 4) *p = make_float2((float)v.x, (float)v.y); // exact: v went through stored<ST>
+  else *p = v;
+}
+
 // One step of an ordered selection on the distributed vector (K-sparse, simplex): among the components c < k
 // that are not taken yet, the one with the largest key -- |u_c| (ABS) or u_c -- and the lowest index among equal keys.  Its owner
 // marks it taken (bit 2 i + h of the lane's mask); every lane of the group returns the same key.  Padding never takes part.  The

@@ -9,6 +9,7 @@
 //   glrm_multigpu.hip   sharded fits                glrm_testhooks.hip  test hooks (constant in the product library)
 //   glrm_storage.hip    fp32 storage: the float gather sweeps, narrowing / widening copies (include/glrm_hip_storage.h)
 //   glrm_cached_f32.hip fp32 storage: the float instantiations of the cached row sweep's register variant (glrm_cached.hpp)
+//   glrm_blocked_f32.hip fp32 storage: the float instantiations of the phase-aligned passes (glrm_blocked.hpp, glrm_tiled.hpp)
 //   glrm_regvec.hip     regularizers that carry a vector (include/glrm_hip_regvec.h): checks, the handle's tables, the two entry points
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
@@ -194,8 +195,8 @@ struct glrm_handle {
   double ms_wait = 0;                 // profile: time the launch stream stood in those waits
   int sum_order_opt = 0;              // glrm_options.sum_order (1: reference-order validation sweeps, glrm_reforder.hip)
   // glrm_options.storage.  GLRM_STORAGE_F32: Side::vals / factor / own_factor hold FLOATS behind their double* type (the same
-  // element counts); only the float gather sweeps, the float cached row sweep (glrm_cached_f32.hip) and the copy kernels of
-  // glrm_storage.hip read them, every other family is refused.
+  // element counts); only the float gather sweeps, the float cached row sweep (glrm_cached_f32.hip), the float phase-aligned passes
+  // (glrm_blocked_f32.hip) and the copy kernels of glrm_storage.hip read them, every other family is refused.
   int storage = 0;
   // hipGraph of one outer iteration (gather sweeps on a private stream): small fits are launch bound
   hipGraph_t iter_graph = nullptr;
@@ -304,6 +305,9 @@ int glrm_widen_factor(glrm_handle* h, const void* dev, double* host, int64_t nve
 int glrm_check_narrowable(const char* name, const double* v, int64_t n);             // GLRM_ERR_NONFINITE for a finite value beyond float's range
 void glrm_launch_sweep_f32(int G, int R, int waves, int loss, int side, const glrm::SweepArgs& a, hipStream_t st);
 void glrm_launch_penalty_f32(glrm_handle* h, int side);
+// the float instantiations of the phase-aligned passes and of their reduce / decide kernels (glrm_blocked_f32.hip)
+int glrm_launch_blocked_f32(glrm_handle* h, int loss, bool grad, const glrm::TiledArgs& a, int side);
+void glrm_launch_col_small_f32(int kp, int stage, const glrm::TiledArgs& a, hipStream_t st);
 
 // GLRM_PROBLEM_ROWS_FROM_COLS (glrm_transpose.hip): the row view derived on the device from the uploaded column view
 int glrm_rows_from_cols(glrm_handle* h);
@@ -315,6 +319,9 @@ int glrm_cached_variant(const glrm_handle* h);         // cached_row of a handle
 int glrm_cached_waves(const glrm_handle* h);           // waves per row of the register variant
 // float storage, GLRM_HIP_CACHED unset: 1 = the fp64 auto rule applies, 0 = the family stays behind GLRM_HIP_CACHED=1
 constexpr int GLRM_CACHED_F32_AUTO = 0;
+// float storage, GLRM_HIP_BLOCKED unset: 1 = the fp64 auto rule of the phase-aligned passes applies, 0 = the family stays behind
+// GLRM_HIP_BLOCKED (turning it on changes which kernels, and which summation order, existing float handles take)
+constexpr int GLRM_BLOCKED_F32_AUTO = 0;
 void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
 int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)

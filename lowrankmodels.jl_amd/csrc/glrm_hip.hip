@@ -508,11 +508,13 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     h->cached_row = h->cached_want = 0;
   } else if (h->storage == GLRM_STORAGE_F32) {
     // float storage: gather sweeps on both views; rows of at most glrm_cached_maxlen observations on the cached row sweep where
-    // glrm_setup_cached says so, otherwise on the one-wave sweep (the other families have no float form)
+    // glrm_setup_cached says so, otherwise on the one-wave sweep; the phase-aligned passes where GLRM_HIP_BLOCKED asks for them
+    // (glrm_setup_blocked; the other families have no float form)
     for (int s = 0; s < 2; ++s) h->side[s].tiled = h->side[s].blocked = 0;
     if ((rc = glrm_setup_cached(h))) return rc;
+    if ((rc = glrm_setup_blocked(h))) return rc;
     for (int s = 0; s < 2; ++s)
-      if ((rc = build_class_plan(h, s))) return rc;
+      if (!h->side[s].blocked && (rc = build_class_plan(h, s))) return rc;
   } else if (h->multi || h->dense) {
     for (int s = 0; s < 2; ++s) h->side[s].waves = opt_waves[s] ? opt_waves[s] : (s == GLRM_ROWS ? 1 : 4);
   } else {

@@ -39,23 +39,7 @@ struct SweepArgs {
   int storage;           // GLRM_STORAGE_*: the type ST behind vals / own / other, i.e. which instantiation the launch takes
 };
 
-// Two adjacent components as the storage holds them.  A lane's chunk i is one 16-byte (double) or one 8-byte (float) load; the gathered
-// chunks stay in their storage type until the fma that uses them, which halves the registers of the float form's y[U][R/2].
-template <class ST> struct Pair;
-template <> struct Pair<double> { using type = double2; };
-template <> struct Pair<float> { using type = float2; };
-__device__ __forceinline__ double2 widen(double2 v) { return v; }
-__device__ __forceinline__ double2 widen(float2 v) { return make_double2((double)v.x, (double)v.y); }
-// the value the storage will hold for v: C's (float) conversion, round to nearest even, widened again (exact)
-template <class ST> __device__ __forceinline__ double stored(double v) {
-  if constexpr (sizeof(ST) == 4) return (double)(float)v;
-  else return v;
-}
-template <class ST> __device__ __forceinline__ void store_pair(typename Pair<ST>::type* p, double2 v) {
-  if constexpr (sizeof(ST) == 4) *p = make_float2((float)v.x, (float)v.y); // exact: v went through stored<ST>
-  else *p = v;
-}
-
+// (Pair, widen, stored, store_pair -- two components as the storage holds them -- are glrm_device.hpp's: the pass kernels use them too.)
 
 // One pass over the segment for one wave: J = sum of losses at u = <xv, other[idx]>, and (GRAD)
 // g = sum of dL * other[idx].  Returns wave-level totals replicated in every lane.

@@ -179,9 +179,9 @@ __device__ __forceinline__ void dma_tile_all(const double* __restrict__ other, i
 
 // chunk held by register i of a lane whose first chunk sits at byte `ro` of the tile (ro carries the lane's 16-byte slot and, with
 // ROT, its rotation in the chunk field, which register index i then flips: chunk i ^ rot)
-template <bool ROT, int CB>
-__device__ __forceinline__ double2 tile_chunk(const char* tile, int ro, int i) {
-  return *reinterpret_cast<const double2*>(tile + (ROT ? (ro ^ (i * CB)) : ro + i * CB));
+template <bool ROT, int CB, class P = double2>
+__device__ __forceinline__ P tile_chunk(const char* tile, int ro, int i) {
+  return *reinterpret_cast<const P*>(tile + (ROT ? (ro ^ (i * CB)) : ro + i * CB));
 }
 
 // One pass of every group of the workgroup over tiles [tile_begin, tile_end).
@@ -195,14 +195,17 @@ __device__ __forceinline__ double2 tile_chunk(const char* tile, int ro, int i) {
 // barrier.  It is what the phase-aligned pass kernels below run: when every group in flight walks its sorted list through the same
 // super-tile at the same time, those reads hit the 4 MB L2 of the XCD (~30 TB/s) instead of the Infinity Cache / HBM (6.5-8 TB/s,
 // profiles/r02_ubench_gather.txt).
-template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROTK = false>
+template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROTK = false, class ST = double>
 __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const Vec<G, R>& xv, Vec<G, R>& g, double& J,
                                            bool active, int64_t& pos, int64_t end, int tile_begin, int tile_end,
                                            const LossDesc& segloss, int lane, int j, int rot = 0) {
   constexpr bool ROT = ROTK && !L2 && tile_rot<G, R>(); // register i holds chunk i ^ rot (see tile_rot)
-  constexpr int ROWB = L2 ? G * R * 8 : tile_row_stride<G, R, ROT>();
-  constexpr int CB = 2 * G * 8;                 // bytes per chunk row of the group
-  const int jrot = j * 16 + (ROT ? rot * CB : 0);
+  static_assert(L2 || sizeof(ST) == 8, "the LDS tile has no float form");
+  using P = typename Pair<ST>::type;            // a lane's chunk as the storage holds it: 16 bytes (double) or 8 (float)
+  constexpr int PB = (int)sizeof(P);
+  constexpr int ROWB = L2 ? G * R * (int)sizeof(ST) : tile_row_stride<G, R, ROT>();
+  constexpr int CB = G * PB;                    // bytes per chunk row of the group
+  const int jrot = j * PB + (ROT ? rot * CB : 0);
   // the whole batch of G observations per step (below) for every model but the uniform QuadLoss one: its two-observation step already
   // keeps eight LDS reads in flight on two interleaved chains (the four-observation step there: C2 15.70 -> 19.05 ms, LABNOTES round 4)
   constexpr bool FOUR = (G == 4 || G == 8) && LOSS != 0;
@@ -213,7 +216,7 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
     for (int i = 0; i < R / 2; ++i) g.v[i] = make_double2(0.0, 0.0);
   }
   const int32_t* __restrict__ idx = a.idx;
-  const double* __restrict__ vals = a.vals;
+  const ST* __restrict__ vals = reinterpret_cast<const ST*>(a.vals); // (float storage: floats behind the double* field)
   // current batch: lane j of the group holds entry pos + j.  Batch loads are UNCONDITIONAL (address clamped
   // into the segment, validity applied when the entry is used) so that the compiler can keep the prefetch of
   // the next batch in flight with a counted s_waitcnt instead of draining the queue at every branch merge.
@@ -315,7 +318,7 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
           bool mine = false;
 #pragma unroll
           for (int u = 0; u < G; ++u) {
-            if constexpr (L2) rp[u] = mem + j * 16 + (int64_t)(ok[u] ? c[u] : c[0]) * ROWB;
+            if constexpr (L2) rp[u] = mem + j * PB + (int64_t)(ok[u] ? c[u] : c[0]) * ROWB;
             else ro[u] = ((ok[u] ? c[u] : c[0]) - (int)lo) * ROWB + jrot;
             mine = (j == u) ? ok[u] : mine;
             p[u] = 0.0;
@@ -325,13 +328,13 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
           // because the scheduler minimises registers in a kernel at its VGPR cap).  Every p[u] still adds its chunks in ascending order.
 #pragma unroll
           for (int i = 0; i < R / 2; ++i) {
-            double2 yv[G];
+            P yv[G];
 #pragma unroll
-            for (int u = 0; u < G; ++u) yv[u] = L2 ? *reinterpret_cast<const double2*>(rp[u] + i * CB) : tile_chunk<ROT, CB>(mem, ro[u], i);
+            for (int u = 0; u < G; ++u) yv[u] = L2 ? *reinterpret_cast<const P*>(rp[u] + i * CB) : tile_chunk<ROT, CB, P>(mem, ro[u], i);
 #pragma unroll
             for (int u = 0; u < G; ++u) {
-              p[u] = fma(xv.v[i].x, yv[u].x, p[u]);
-              p[u] = fma(xv.v[i].y, yv[u].y, p[u]);
+              p[u] = fma(xv.v[i].x, (double)yv[u].x, p[u]);
+              p[u] = fma(xv.v[i].y, (double)yv[u].y, p[u]);
             }
           }
           const bool hi2 = (j & 2) != 0;
@@ -379,13 +382,13 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
             for (int u = 0; u < G; ++u) dv[u] = group_bcast_f64<G>(dL, u, lane);
 #pragma unroll
             for (int i = 0; i < R / 2; ++i) { // chunk-major like the dot products; every component still adds its terms in list order
-              double2 yv[G];
+              P yv[G];
 #pragma unroll
-              for (int u = 0; u < G; ++u) yv[u] = L2 ? *reinterpret_cast<const double2*>(rp[u] + i * CB) : tile_chunk<ROT, CB>(mem, ro[u], i);
+              for (int u = 0; u < G; ++u) yv[u] = L2 ? *reinterpret_cast<const P*>(rp[u] + i * CB) : tile_chunk<ROT, CB, P>(mem, ro[u], i);
 #pragma unroll
               for (int u = 0; u < G; ++u) {
-                g.v[i].x = fma(dv[u], yv[u].x, g.v[i].x);
-                g.v[i].y = fma(dv[u], yv[u].y, g.v[i].y);
+                g.v[i].x = fma(dv[u], (double)yv[u].x, g.v[i].x);
+                g.v[i].y = fma(dv[u], (double)yv[u].y, g.v[i].y);
               }
             }
           }
@@ -403,21 +406,21 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
         const bool ok0 = !done && c0 < (int)hi; // c == INT_MAX past the end of the segment
         const bool ok1 = ok0 && c1 < (int)hi;
         if (ok0) {
-          double2 y0[R / 2], y1[R / 2];
+          P y0[R / 2], y1[R / 2];
           if constexpr (L2) {
             const int c1v = ok1 ? c1 : c0; // a clamped lane re-reads the row of a valid entry
             const char *rp0, *rp1;
             if constexpr (LOSS == 0) {
-              rp0 = sup_base + ((uint32_t)(c0 - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * 16));
-              rp1 = sup_base + ((uint32_t)(c1v - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * 16));
+              rp0 = sup_base + ((uint32_t)(c0 - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * PB));
+              rp1 = sup_base + ((uint32_t)(c1v - (int)lo) * (uint32_t)ROWB + (uint32_t)(j * PB));
             } else { // rank 128 with a loss per column: the 32-bit form costs these kernels SGPR spills
-              rp0 = mem + (int64_t)c0 * ROWB + j * 16;
-              rp1 = mem + (int64_t)c1v * ROWB + j * 16;
+              rp0 = mem + (int64_t)c0 * ROWB + j * PB;
+              rp1 = mem + (int64_t)c1v * ROWB + j * PB;
             }
 #pragma unroll
-            for (int i = 0; i < R / 2; ++i) y0[i] = *reinterpret_cast<const double2*>(rp0 + i * CB);
+            for (int i = 0; i < R / 2; ++i) y0[i] = *reinterpret_cast<const P*>(rp0 + i * CB);
 #pragma unroll
-            for (int i = 0; i < R / 2; ++i) y1[i] = *reinterpret_cast<const double2*>(rp1 + i * CB);
+            for (int i = 0; i < R / 2; ++i) y1[i] = *reinterpret_cast<const P*>(rp1 + i * CB);
           } else {
             const int ro0 = (c0 - (int)lo) * ROWB + jrot, ro1 = ((ok1 ? c1 : c0) - (int)lo) * ROWB + jrot;
 #pragma unroll
@@ -428,13 +431,13 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
           double p0 = 0.0, p1 = 0.0;
 #pragma unroll
           for (int i = 0; i < R / 2; ++i) {
-            p0 = fma(xv.v[i].x, y0[i].x, p0);
-            p0 = fma(xv.v[i].y, y0[i].y, p0);
+            p0 = fma(xv.v[i].x, (double)y0[i].x, p0);
+            p0 = fma(xv.v[i].y, (double)y0[i].y, p0);
           }
 #pragma unroll
           for (int i = 0; i < R / 2; ++i) {
-            p1 = fma(xv.v[i].x, y1[i].x, p1);
-            p1 = fma(xv.v[i].y, y1[i].y, p1);
+            p1 = fma(xv.v[i].x, (double)y1[i].x, p1);
+            p1 = fma(xv.v[i].y, (double)y1[i].y, p1);
           }
           const double keep = odd ? p1 : p0, send = odd ? p0 : p1;
           double dot = keep + dpp_f64<DPP_XOR1>(send); // lane pair sum for observation u0 + odd
@@ -465,13 +468,13 @@ __device__ __forceinline__ void tiled_pass(const TiledArgs& a, char* lds, const 
             const double d0 = group_bcast_f64<2>(dL, 0, lane), d1 = group_bcast_f64<2>(dL, 1, lane);
 #pragma unroll
             for (int i = 0; i < R / 2; ++i) {
-              g.v[i].x = fma(d0, y0[i].x, g.v[i].x);
-              g.v[i].y = fma(d0, y0[i].y, g.v[i].y);
+              g.v[i].x = fma(d0, (double)y0[i].x, g.v[i].x);
+              g.v[i].y = fma(d0, (double)y0[i].y, g.v[i].y);
             }
 #pragma unroll
             for (int i = 0; i < R / 2; ++i) {
-              g.v[i].x = fma(d1, y1[i].x, g.v[i].x);
-              g.v[i].y = fma(d1, y1[i].y, g.v[i].y);
+              g.v[i].x = fma(d1, (double)y1[i].x, g.v[i].x);
+              g.v[i].y = fma(d1, (double)y1[i].y, g.v[i].y);
             }
           }
           nproc += ok1 ? 2 : 1;
@@ -674,15 +677,34 @@ __device__ __forceinline__ int64_t lower_bound_idx(const int32_t* idx, int64_t b
 // (C4 Y half-step 114.1 -> 110.8 ms).  The trial pass stays at what its 98 / 89 VGPRs give, 4 / 5 waves: held to 96 VGPRs and 5 waves the
 // rank-64 one is clean too, but LOSES (113.0 ms; LABNOTES "phase-aligned passes at 4 / 5 waves per SIMD").  Every other instantiation
 // spills at such bounds (rank 128: 20 / 12 B, LOSS != 0: 28-252 B) and keeps its own; no kernel gains scratch or loses a wave.
-template <int G, int R, int LOSS, bool GRAD, bool L2>
+//
+// ST = float (glrm_options.storage = 1; L2 = true only, instantiated in glrm_blocked_f32.hip): a.vals, a.own and a.other hold floats
+// (leading dimension KP floats, the same zero padding), a lane's chunk is one 8-byte float2 load widened at the fma, the gather offset is
+// (row - lo) * KP * 4 + j * 8; part, gsum, trial, jold, alpha, every accumulator and every loss evaluation stay fp64, so every sum adds
+// the terms of the fp64 kernel in its order.  The bound of the float kernels comes from their own registers, and those are NOT half the
+// fp64 ones: the compiler widens a gathered float2 once and keeps the doubles for the dot product and the gradient update, so unbound the
+// rank-64 / rank-32 QuadLoss gradient kernels take 132 / 128 VGPRs and the trial kernels 96 / 88 (fp64: 132 / 128 and 98 / 89).  The
+// gradient pair is built for 4 waves per SIMD like its fp64 twin (128 VGPRs, no scratch); at 5 both spill (148 / 160 B), and forcing the
+// second widening (a register barrier on the floats between dot product and update) spills at 4 already.  The trial kernels take what
+// their registers give, 5 waves.  GLRM_BLOCKED_F32_GRAD_WAVES: the bound of that pair in a variant build (tests/perf/bench_storage_blocked.py
+// measures 1 = unbound, 3 waves, against 4).  profiles/storage_f32_blocked_resusage.txt, DESIGN 4.13.
+#ifndef GLRM_BLOCKED_F32_GRAD_WAVES
+#define GLRM_BLOCKED_F32_GRAD_WAVES 4
+#endif
+template <int G, int R, int LOSS, bool GRAD>
+constexpr int pass_waves_per_simd_f32() { return (LOSS == 0 && R == 8 && (G == 8 || G == 4) && GRAD) ? GLRM_BLOCKED_F32_GRAD_WAVES : 1; }
+
+template <int G, int R, int LOSS, bool GRAD, bool L2, class ST = double>
 constexpr int pass_waves_per_simd() {
   if (!L2) return 4;
+  if (sizeof(ST) == 4) return pass_waves_per_simd_f32<G, R, LOSS, GRAD>();
   if (LOSS == 0 && R == 8 && (G == 8 || G == 4) && GRAD) return 4;
   return 1;
 }
 
-template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROWS = false>
-__global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD, L2>())) tiled_col_pass_kernel(const TiledArgs a) {
+template <int G, int R, int NW, int TILE, int LOSS, bool GRAD, bool L2 = false, bool ROWS = false, class ST = double>
+__global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD, L2, ST>())) tiled_col_pass_kernel(const TiledArgs a) {
+  using P = typename Pair<ST>::type;
   constexpr int KP = G * R, NGW = 64 / G, SPB = NW * NGW, PSTRIDE = KP + 2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -699,13 +721,19 @@ __global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD
   const int ntiles = (int)((a.n_other + TILE - 1) / TILE);
   const int tb = sup * a.tiles_per_sup;
   const int te = tb + a.tiles_per_sup < ntiles ? tb + a.tiles_per_sup : ntiles;
-  const double2* xp = reinterpret_cast<const double2*>(GRAD ? a.own + gseg * KP : a.trial + (have ? seg : 0) * (int64_t)KP);
   // ROWS: the trial rounds of the row view (the row sweep's own passes read padded tiles without rotation: the same bits here)
   constexpr bool ROT = !ROWS && !L2 && LOSS != 0 && tile_rot<G, R>();
   const int rot = ROT ? tile_rot_of(gseg) : 0; // register i <-> chunk i ^ rot (conflict-free tile reads, see tile_rot)
   Vec<G, R> x, g;
+  if constexpr (GRAD && sizeof(ST) == 4) { // the current point as the storage holds it; the trial point below is fp64 in both storages
+    const P* xp = reinterpret_cast<const P*>(reinterpret_cast<const ST*>(a.own) + gseg * KP);
 #pragma unroll
-  for (int i = 0; i < R / 2; ++i) x.v[i] = have ? xp[(i ^ rot) * G + j] : make_double2(0.0, 0.0);
+    for (int i = 0; i < R / 2; ++i) x.v[i] = have ? widen(xp[i * G + j]) : make_double2(0.0, 0.0);
+  } else {
+    const double2* xp = reinterpret_cast<const double2*>(GRAD ? a.own + gseg * KP : a.trial + (have ? seg : 0) * (int64_t)KP);
+#pragma unroll
+    for (int i = 0; i < R / 2; ++i) x.v[i] = have ? xp[(i ^ rot) * G + j] : make_double2(0.0, 0.0);
+  }
   LossDesc segloss = LossDesc{0, 1.0, 0.0, 0.0};
   if constexpr (loss_mode(LOSS) != 2) segloss = load_loss(a.losses, (a.loss_by_segment && have) ? gseg : 0);
   int64_t pos = 0; // first entry of the super-tile: from the start table where the side has one (L2), else the search
@@ -714,7 +742,7 @@ __global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD
     else pos = lower_bound_idx<G>(a.idx, beg, end, (int64_t)tb * TILE);
   }
   double J;
-  tiled_pass<G, R, NW, TILE, LOSS, GRAD, L2, ROT>(a, lds, x, g, J, have, pos, end, tb, te, segloss, lane, j, rot);
+  tiled_pass<G, R, NW, TILE, LOSS, GRAD, L2, ROT, ST>(a, lds, x, g, J, have, pos, end, tb, te, segloss, lane, j, rot);
   if (have) {
     double* p = a.part + ((int64_t)seg * a.nsup + sup) * PSTRIDE;
     if (GRAD) {
@@ -726,8 +754,12 @@ __global__ void __launch_bounds__(NW * 64, (pass_waves_per_simd<G, R, LOSS, GRAD
 }
 
 // After pass 1: reduce the partials in super-tile order, J_old = loss + r(y), first trial point.
-template <int G, int R, bool VR = false>
+// ST = float (the phase-aligned passes of a float handle): a.own holds floats, and the trial point is rounded to the value the storage
+// will hold right after the prox -- before it is written to `trial` and before col_decide evaluates r on it -- so that the search
+// compares objectives of stored factors and an accepted point is stored exactly.  No fixed_alpha branch (refused for f32).
+template <int G, int R, bool VR = false, class ST = double>
 __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
+  using P = typename Pair<ST>::type;
   constexpr int KP = G * R, NGW = 64 / G, PSTRIDE = KP + 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane % G, gi = lane / G;
@@ -753,11 +785,11 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
     if (j == 0 && a.obj) a.obj[gseg] = J;
     return;
   }
-  const double2* yp = reinterpret_cast<const double2*>(a.own + gseg * KP);
+  const P* yp = reinterpret_cast<const P*>(reinterpret_cast<const ST*>(a.own) + gseg * KP);
 #pragma unroll
-  for (int i = 0; i < R / 2; ++i) y.v[i] = yp[i * G + j];
+  for (int i = 0; i < R / 2; ++i) y.v[i] = widen(yp[i * G + j]);
   const RegDesc rd = load_reg(a.regs, a.reg_single ? 0 : seg);
-  if (a.fixed_alpha > 0.0) { // SparseProxGradParams step on this segment, no trial rounds
+  if (sizeof(ST) == 8 && a.fixed_alpha > 0.0) { // SparseProxGradParams step on this segment, no trial rounds
     const double l0 = (double)(a.ptr ? a.ptr[seg + 1] - a.ptr[seg] : a.dense_len) + 1.0;
     const double s0 = a.fixed_alpha / l0;
 #pragma unroll
@@ -784,6 +816,10 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
     yn.v[i].y = fma(-s, g.v[i].y, y.v[i].y);
   }
   reg_prox<G, R, VR>(rd, yn, s, j, a.k);
+  if constexpr (sizeof(ST) == 4) {
+#pragma unroll
+    for (int i = 0; i < R / 2; ++i) yn.v[i] = make_double2(stored<ST>(yn.v[i].x), stored<ST>(yn.v[i].y));
+  }
   double2* gp = reinterpret_cast<double2*>(a.gsum + seg * (int64_t)KP);
   double2* tp = reinterpret_cast<double2*>(a.trial + seg * (int64_t)KP);
 #pragma unroll
@@ -803,9 +839,10 @@ __global__ void __launch_bounds__(256) col_reduce_kernel(const TiledArgs a) {
   }
 }
 
-// After a trial pass: J' = sum of partial losses + r(y'); accept / shrink / give up; next trial point.
-template <int G, int R, bool VR = false>
+// After a trial pass: J' = sum of partial losses + r(y'); accept / shrink / give up; next trial point (ST = float: rounded, see col_reduce).
+template <int G, int R, bool VR = false, class ST = double>
 __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
+  using P = typename Pair<ST>::type;
   constexpr int KP = G * R, NGW = 64 / G, PSTRIDE = KP + 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane % G, gi = lane / G;
@@ -820,7 +857,7 @@ __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
   double Jn = 0.0;
   for (int s = 0; s < a.nsup; ++s) Jn += a.part[((int64_t)seg * a.nsup + s) * PSTRIDE + KP];
   Vec<G, R> y, yn, g;
-  double2* yp = reinterpret_cast<double2*>(a.own + gseg * KP);
+  P* yp = reinterpret_cast<P*>(reinterpret_cast<ST*>(a.own) + gseg * KP);
   double2* tp = reinterpret_cast<double2*>(a.trial + seg * (int64_t)KP);
   const double2* gp = reinterpret_cast<const double2*>(a.gsum + seg * (int64_t)KP);
 #pragma unroll
@@ -832,7 +869,7 @@ __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
   int still = 0, acc = 0;
   if (Jn < Jold) {
 #pragma unroll
-    for (int i = 0; i < R / 2; ++i) yp[i * G + j] = yn.v[i];
+    for (int i = 0; i < R / 2; ++i) store_pair<ST>(&yp[i * G + j], yn.v[i]);
     alpha *= 1.05;
     acc = 1;
     if (j == 0 && a.obj) a.obj[gseg] = Jn;
@@ -846,14 +883,14 @@ __global__ void __launch_bounds__(256) col_decide_kernel(const TiledArgs a) {
       const double s = alpha / l;
 #pragma unroll
       for (int i = 0; i < R / 2; ++i) {
-        y.v[i] = yp[i * G + j];
+        y.v[i] = widen(yp[i * G + j]);
         g.v[i] = gp[i * G + j];
         yn.v[i].x = fma(-s, g.v[i].x, y.v[i].x);
         yn.v[i].y = fma(-s, g.v[i].y, y.v[i].y);
       }
       reg_prox<G, R, VR>(rd, yn, s, j, a.k);
 #pragma unroll
-      for (int i = 0; i < R / 2; ++i) tp[i * G + j] = yn.v[i];
+      for (int i = 0; i < R / 2; ++i) tp[i * G + j] = make_double2(stored<ST>(yn.v[i].x), stored<ST>(yn.v[i].y));
     }
   }
   if (j == 0) {

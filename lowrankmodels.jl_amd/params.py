@@ -46,8 +46,9 @@ class HipProxGradParams(ProxGradParams):
             raise ValueError("mode must be 'fast' or 'reference_order'")
         self.mode = mode
         # SURVEY.md 8(b) fp32 storage (glrm_options.storage, include/glrm_hip_storage.h): "f32" stores A, X and Y as floats and keeps
-        # every sum and the line search in fp64.  Two kernel families have a float form: the gather sweeps (both views) and the cached
-        # row sweep (short rows; GLRM_HIP_CACHED=1 at create forces it, DESIGN.md section 4.13 names the rule without the variable).
+        # every sum and the line search in fp64.  Three kernel families have a float form: the gather sweeps (both views), the cached
+        # row sweep (short rows; GLRM_HIP_CACHED=1 at create forces it, DESIGN.md section 4.13 names the rule without the variable) and
+        # the phase-aligned gather passes (only where GLRM_HIP_BLOCKED asks for them at create).
         # One device, fast mode, scalar losses, scales and element-wise regularizers; the engine refuses everything else (a
         # GLRMError) -- there is no fallback to fp64.
         if storage not in ("f64", "f32"):
