@@ -87,12 +87,17 @@ GLRM_FM double fm_log(double x) {
   return x > 0.0 ? r : (x == 0.0 ? -__builtin_inf() : __builtin_nan(""));
 }
 
-// LogisticLoss (src/losses.jl:298-311) from ONE exponential, in the reference's own structure so that its rounding is reproduced:
-// with z = (2a-1) u and E = exp(-z), w = 1 + E (rounded as in the reference),
+// LogisticLoss (src/losses.jl:298-311) from ONE exponential.  The LOSS keeps the reference's own structure so that its rounding is
+// reproduced: with z = (2a-1) u and E = exp(-z), w = 1 + E (rounded as in the reference),
 //     evaluate = scale * log(1 + exp(-z))        = scale * log(w)            -- exactly 0 once E < 2^-53, Inf once exp overflows
 //     grad     = -(2a-1) scale / (1 + exp(z))    = -(2a-1) scale * E / w     -- exp(z) = 1 / E; for E > 1 as 1 - 1 / w (no Inf * 0)
-// (the line search compares sums of these with a strict `<`: a loss that is "more accurate than the reference" -- log1p(E), or a
+// (the line search compares sums of the losses with a strict `<`: a loss that is "more accurate than the reference" -- log1p(E), or a
 // finite value where the reference overflows -- takes different decisions; found by tests/test_gpu_fuzz.py).
+// The GRADIENT does not reproduce the reference's rounding where its literal formula saturates early: for z in (-37.43, -36.74) the
+// reference's 1 + exp(z) has already rounded to 1 (grad = -(2a-1) scale exactly) and for z in (709.78, 745.14) its exp(z) is already Inf
+// (grad = -+0), while E / w is still the correctly rounded derivative there -- the neighbouring double scale (1 - 2^-53), or a denormal no
+// larger than scale * 2^-1024.  Gradients are only ever summed, never compared, so that is left as it is; everywhere else the two agree to
+// the rounding of their exponentials (tests/test_gpu_loss_pointwise.py: test_logistic_structure asserts exactly this).
 template <bool NEED_GRAD>
 GLRM_FM void fm_logistic(double scale, double aa, double u, double& L, double& dL) {
   const double z = aa * u;

@@ -244,4 +244,171 @@ extern "C" int glrm_test_regvec_prox_eval(const glrm_reg* reg, const double* rve
   if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_regvec_prox_eval: %s", hipGetErrorString(e));
   return GLRM_OK;
 }
+
+// ------------------------------------------------------------------ loss hooks (tests/test_gpu_loss_pointwise.py)
+// The kernels' own device functions on a batch of points: loss_both (csrc/glrm_device.hpp), the primitives of csrc/glrm_fastmath.hpp and
+// obs_loss (csrc/glrm_multi.hpp).  No formula is restated here.
+#include "glrm_multi.hpp"
+
+namespace {
+struct LossHookArgs {
+  const glrm_loss* desc; // n descriptors (nullptr for the primitives that take none)
+  const double* u;
+  const double* a;
+  int64_t n;
+  double* L;  // n
+  double* dL; // n
+};
+
+// One lane per point; neighbouring lanes hold whatever kinds the caller put side by side, so the switch of loss_both runs divergently as it
+// does in the per-observation kernels.  One kernel per instantiation: nothing of one can be shared with another by the compiler.
+template <bool NEED_GRAD, bool TRIG>
+__global__ void __launch_bounds__(64) loss_hook_pointwise(const LossHookArgs h) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= h.n) return;
+  const LossDesc l = load_loss(h.desc, i);
+  double L, dL;
+  loss_both<NEED_GRAD, TRIG>(l, h.u[i], h.a[i], L, dL);
+  h.L[i] = L;
+  h.dL[i] = dL;
+}
+
+// op: 1 fm_exp(u), 2 fm_log_ge1(u), 3 fm_log(u), 4 fm_rcp(u), 5 / 6 fm_logistic<true / false>(desc.scale, a, u) with a = +-1 as it is
+template <int OP>
+__global__ void __launch_bounds__(64) loss_hook_primitive(const LossHookArgs h) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= h.n) return;
+  const double x = h.u[i];
+  double L = 0.0, dL = 0.0;
+  if constexpr (OP == 1) L = fm_exp(x);
+  else if constexpr (OP == 2) L = fm_log_ge1(x);
+  else if constexpr (OP == 3) L = fm_log(x);
+  else if constexpr (OP == 4) L = fm_rcp(x);
+  else fm_logistic<OP == 5>(h.desc[i].scale, h.a[i], x, L, dL);
+  h.L[i] = L;
+  h.dL[i] = dL;
+}
+
+struct ObsHookArgs {
+  const glrm_loss* desc; // n
+  const int32_t* d;      // n: 0 = idle slot, 1 = scalar loss, else the embedding dimension
+  const double* level;   // n: the observation's value (level 1 .. max; the scalar losses' a)
+  const double* u;       // n x P
+  int64_t n;
+  int lg;
+  double* Lg; // n x P: obs_loss<true> as every lane of the slot returns it
+  double* G;  // n x P: cg of lane sub
+  double* Lt; // n x P: obs_loss<false>
+};
+
+// One wave per workgroup, observation i in slot i % (64 / P) of wave i / (64 / P); the slots behind the last observation are idle.  EVERY
+// lane runs the call (obs_loss's contract); only the stores are guarded.
+template <bool GRAD, int KM>
+__global__ void __launch_bounds__(64) loss_hook_obs(const ObsHookArgs h) {
+  const int lane = threadIdx.x, lg = h.lg, P = 1 << lg, SL = 64 >> lg, slot = lane >> lg, sub = lane & (P - 1);
+  const int64_t i = (int64_t)blockIdx.x * SL + slot;
+  const bool valid = i < h.n;
+  const int64_t ic = valid ? i : h.n - 1;
+  const LossDesc l = load_loss(h.desc, ic);
+  const int dd = valid ? h.d[ic] : 0;
+  const double av = h.level[ic];
+  const double u = sub < dd ? h.u[ic * P + sub] : 0.0; // the lanes past the dimension hold 0, as multi_pass leaves them
+  const double u0 = dd > 0 ? h.u[ic * P] : 0.0;
+  double cg = 0.0;
+  const double L = obs_loss<GRAD, true, KM>(l, u, u0, av, dd, sub, lg, lane - sub, nullptr, cg);
+  if (!valid) return;
+  if constexpr (GRAD) {
+    h.Lg[i * P + sub] = L;
+    h.G[i * P + sub] = cg;
+  } else {
+    h.Lt[i * P + sub] = L;
+  }
+}
+
+template <int KM>
+void obs_hook_launch(const ObsHookArgs& h, unsigned grid) {
+  hipLaunchKernelGGL((loss_hook_obs<true, KM>), dim3(grid), dim3(64), 0, 0, h);
+  hipLaunchKernelGGL((loss_hook_obs<false, KM>), dim3(grid), dim3(64), 0, 0, h);
+}
+} // namespace
+
+// op 0: L and dL of loss_both<true, true>, <false, true>, <true, false>, <false, false> at the n points (desc[i], u[i], a[i]); L and dL are
+// 4 x n (host), instantiation major.  op 1 .. 6: one primitive of csrc/glrm_fastmath.hpp (loss_hook_primitive) on u[i]; L and dL are n (dL is
+// 0 except for op 5).  desc may be null for op 1 .. 4, a for op 1 .. 4.
+extern "C" int glrm_test_loss_pointwise(const glrm_loss* desc, const double* u, const double* a, int64_t n, int32_t op, double* L, double* dL) {
+  if (!u || !L || !dL || n <= 0 || n > (1 << 20) || op < 0 || op > 6) return fail(GLRM_ERR_INVALID, "bad argument");
+  const bool need_desc = op == 0 || op >= 5;
+  if (need_desc && (!desc || !a)) return fail(GLRM_ERR_INVALID, "op %d needs descriptors and a", op);
+  const size_t nout = op == 0 ? 4 : 1, N = (size_t)n;
+  DevArena scratch;
+  double* d = nullptr; // [desc: 4 n][u: n][a: n][L: nout n][dL: nout n]
+  if (const int rca = scratch.alloc(&d, (6 + 2 * nout) * N)) return rca;
+  double *du = d + 4 * N, *da = du + N, *dLo = da + N, *ddL = dLo + nout * N;
+  static_assert(sizeof(glrm_loss) == 32, "a descriptor is four doubles wide");
+  hipError_t e = hipMemcpy(du, u, N * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess && need_desc) e = hipMemcpy(d, desc, N * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess && need_desc) e = hipMemcpy(da, a, N * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    LossHookArgs h{reinterpret_cast<const glrm_loss*>(d), du, da, n, dLo, ddL};
+    auto at = [&](size_t v) { LossHookArgs w = h; w.L += v * N; w.dL += v * N; return w; };
+    switch (op) {
+      case 0:
+        hipLaunchKernelGGL((loss_hook_pointwise<true, true>), grid, block, 0, 0, at(0));
+        hipLaunchKernelGGL((loss_hook_pointwise<false, true>), grid, block, 0, 0, at(1));
+        hipLaunchKernelGGL((loss_hook_pointwise<true, false>), grid, block, 0, 0, at(2));
+        hipLaunchKernelGGL((loss_hook_pointwise<false, false>), grid, block, 0, 0, at(3));
+        break;
+      case 1: hipLaunchKernelGGL(loss_hook_primitive<1>, grid, block, 0, 0, h); break;
+      case 2: hipLaunchKernelGGL(loss_hook_primitive<2>, grid, block, 0, 0, h); break;
+      case 3: hipLaunchKernelGGL(loss_hook_primitive<3>, grid, block, 0, 0, h); break;
+      case 4: hipLaunchKernelGGL(loss_hook_primitive<4>, grid, block, 0, 0, h); break;
+      case 5: hipLaunchKernelGGL(loss_hook_primitive<5>, grid, block, 0, 0, h); break;
+      default: hipLaunchKernelGGL(loss_hook_primitive<6>, grid, block, 0, 0, h); break;
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(L, dLo, nout * N * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(dL, ddL, nout * N * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_loss_pointwise: %s", hipGetErrorString(e));
+  return GLRM_OK;
+}
+
+// obs_loss on n observations (desc[i], d[i], level[i], u[i * P .. i * P + d[i])), P = 2^lg lanes per slot, lg in 2 .. 6; observation i sits in
+// slot i % (64 / P) of wave i / (64 / P).  kmask: 0 MULTI_KM_ALL, 1 MULTI_KM_MNL, 2 MULTI_KM_MNL | MULTI_KM_SCALAR, 3 MULTI_KM_ORD (the four
+// glrm_multi.hip instantiates).  Lg, G, Lt: n x P (host): obs_loss<true>'s value and gradient component, obs_loss<false>'s value, per lane.
+extern "C" int glrm_test_obs_loss(const glrm_loss* desc, const int32_t* d, const double* level, const double* u, int64_t n, int32_t lg, int32_t kmask,
+                                  double* Lg, double* G, double* Lt) {
+  if (!desc || !d || !level || !u || !Lg || !G || !Lt || n <= 0 || n > (1 << 20)) return fail(GLRM_ERR_INVALID, "bad argument");
+  if (lg < 2 || lg > 6 || kmask < 0 || kmask > 3) return fail(GLRM_ERR_INVALID, "bad slot width / kind mask (lg %d, mask %d)", lg, kmask);
+  const size_t N = (size_t)n, P = (size_t)1 << lg;
+  for (size_t i = 0; i < N; ++i)
+    if (d[i] < 0 || (size_t)d[i] > P) return fail(GLRM_ERR_INVALID, "observation %zu: dimension %d does not fit a slot of %zu lanes", i, d[i], P);
+  DevArena scratch;
+  double* dev = nullptr; // [desc: 4 n][level: n][u: n P][Lg: n P][G: n P][Lt: n P][d: n int32]
+  if (const int rca = scratch.alloc(&dev, 5 * N + 4 * N * P + (N + 1) / 2)) return rca;
+  double *dlev = dev + 4 * N, *du = dlev + N, *dLg = du + N * P, *dG = dLg + N * P, *dLt = dG + N * P;
+  int32_t* dd = reinterpret_cast<int32_t*>(dLt + N * P);
+  hipError_t e = hipMemcpy(dev, desc, N * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dlev, level, N * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(du, u, N * P * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dd, d, N * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const size_t SL = 64 / P;
+    const unsigned grid = (unsigned)((N + SL - 1) / SL);
+    const ObsHookArgs h{reinterpret_cast<const glrm_loss*>(dev), dd, dlev, du, n, lg, dLg, dG, dLt};
+    if (kmask == 0) obs_hook_launch<MULTI_KM_ALL>(h, grid);
+    else if (kmask == 1) obs_hook_launch<MULTI_KM_MNL>(h, grid);
+    else if (kmask == 2) obs_hook_launch<MULTI_KM_MNL | MULTI_KM_SCALAR>(h, grid);
+    else obs_hook_launch<MULTI_KM_ORD>(h, grid);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(Lg, dLg, N * P * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(G, dG, N * P * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(Lt, dLt, N * P * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(GLRM_ERR_HIP, "glrm_test_obs_loss: %s", hipGetErrorString(e));
+  return GLRM_OK;
+}
 #endif

@@ -44,7 +44,9 @@ def test_the_product_library_carries_no_test_machinery():
     import subprocess
     ensure_built()
     needles = ("LinkEmu", "link_delay_kernel", "link_mark_kernel", "GLRM_HIP_TEST_FAIL_FINALIZE", "GLRM_HIP_RCCL_LIB", "GLRM_HIP_RCCL_ALLOW_SHARED",
-               "GLRM_EXCHANGE_EMULATE_MODE", "GLRM_EXCHANGE_EMULATE_DILATE")
+               "GLRM_EXCHANGE_EMULATE_MODE", "GLRM_EXCHANGE_EMULATE_DILATE",
+               # the pointwise loss hooks (tests/test_gpu_loss_pointwise.py): entry points and kernels
+               "glrm_test_loss_pointwise", "glrm_test_obs_loss", "loss_hook_pointwise", "loss_hook_primitive", "loss_hook_obs")
     for name, want in (("libglrm_hip.so", False), ("libglrm_hip_testing.so", True)):
         path = os.path.join(PKG, name)
         syms = subprocess.run(["nm", "-D", "-C", path], capture_output=True, text=True, check=True).stdout
