@@ -10,7 +10,7 @@ from .convergence import ConvergenceHistory, update_ch
 from .fit import ShardedFit, fit, fit_b, objective, partition
 from .crossval import (cross_validate, cv_by_iter, flatten_observations, get_train_and_test, getfolds, loss_fn,
                              precision_at_k, regularization_path)
-from .initialize import init_kmeanspp_, init_svd_
+from .initialize import init_kmeanspp_, init_nndsvd_, init_svd_
 from .scaling import equilibrate_variance_, prob_scale_
 from .domains import (BoolDomain, CategoricalDomain, CountDomain, Domain, OrdinalDomain, PeriodicDomain, RealDomain, default_domain,
                       error_metric, error_metric_entry, impute, impute_entry, impute_missing)

@@ -169,6 +169,11 @@ REGVEC_SYMBOLS = ("set_regularizers_vec", "multi_set_regularizers_vec")
 #: bound only where the library has it
 TOPK_SYMBOLS = ("xy_select", "xy_select_info", "precision_scan")
 
+#: the NMF initialization extension, include/glrm_hip_nmf.h (init_nndsvd! on the resident lists): outside the boundary, bound only where
+#: the library has it
+NMF_SYMBOLS = ("init_nndsvd",)
+NNDSVD_VARIANTS = {"std": 0, "a": 1, "ar": 2}   # glrm_hip_nmf.h: GLRM_NNDSVD_STD / _A / _AR (ar is refused)
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -269,8 +274,10 @@ class Api:
             "xy_select_info": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
             "precision_scan": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+            "init_nndsvd": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + NMF_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -585,6 +592,28 @@ class Api:
             weights = np.full((k - 1, int(m)), np.nan)
         self._ck(fn(h, _ptr(Y), int(first), _ptr(u) if k > 1 else None, _ptr(centers), _ptr(weights) if k > 1 else None))
         return centers, weights
+
+    # -- NMF initialization extension (include/glrm_hip_nmf.h) -----------------------------
+    def init_nndsvd(self, h, X, Y, scale=True, zeroh=False, variant="std", max_iters=0, svd_max_iter=0, svd_tol=0.0, seed=1):
+        """glrm_hip_init_nndsvd on the handle's resident lists: fills ``X`` (k x m) and ``Y`` (k x n), Fortran-ordered float64.  The lists
+        must not hold a pair twice (the caller's contract; :func:`initialize.init_nndsvd_` checks it).  Returns a dict: the
+        ``singular_values`` of the last round, ``split`` (k x 2: the larger and the smaller of (mp, mn) per component, last round) and
+        ``iterations`` (the subspace iterations of each of the max_iters + 1 rounds)."""
+        fn = self._f.get("init_nndsvd")
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}init_nndsvd: this engine does not have the NMF initialization extension "
+                                             "(include/glrm_hip_nmf.h is implemented by the HIP engine only)")
+        if variant not in NNDSVD_VARIANTS:
+            raise ValueError(f"variant must be one of {sorted(NNDSVD_VARIANTS)}, got {variant!r}")
+        for name, F in (("X", X), ("Y", Y)):
+            if not (isinstance(F, np.ndarray) and F.dtype == np.float64 and F.ndim == 2 and F.flags.f_contiguous):
+                raise ValueError(f"{name} must be a Fortran-ordered float64 k x count array (it is overwritten in place)")
+        k = X.shape[0]
+        sv, split = np.zeros(k), np.zeros((k, 2))
+        iters = np.zeros(max(int(max_iters), 0) + 1, dtype=np.int32)
+        self._ck(fn(h, _ptr(X), _ptr(Y), 1 if scale else 0, 1 if zeroh else 0, NNDSVD_VARIANTS[variant], int(max_iters), int(svd_max_iter),
+                    float(svd_tol), int(seed), _ptr(sv), _ptr(split), _ptr(iters)))
+        return dict(singular_values=sv, split=split, iterations=iters)
 
     # -- top-k extension (include/glrm_hip_topk.h) -------------------------------------------
     def _topk(self, name):

@@ -12,6 +12,8 @@
 //   glrm_blocked_f32.hip fp32 storage: the float instantiations of the phase-aligned passes (glrm_blocked.hpp, glrm_tiled.hpp)
 //   glrm_regvec.hip     regularizers that carry a vector (include/glrm_hip_regvec.h): checks, the handle's tables, the two entry points
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
+//   glrm_nmf.hip        init_nndsvd!: NNDSVD and its soft-impute rounds on the resident lists (include/glrm_hip_nmf.h); shares the subspace
+//                       iteration of glrm_svd.hip through glrm_subspace.hpp
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle keeps what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`, the opposing
