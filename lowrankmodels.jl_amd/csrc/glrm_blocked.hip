@@ -155,12 +155,12 @@ int glrm_setup_blocked(glrm_handle* h) {
   return GLRM_OK;
 }
 
-int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
+int glrm_run_blocked(glrm_handle* h, const glrm_step& step) {
+  const int side = step.side, loss = step.loss;
   TiledArgs a{};
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
-  a.loss_by_segment = loss_by_segment;
-  const bool range = side == GLRM_ROWS && h->rng_e >= 0; // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-  glrm_bind_pass_buffers(a, h, side, range ? h->rng_b : 0);
+  glrm_fill_side(a, h, step);
+  a.loss_by_segment = step.loss_by_segment;
+  glrm_bind_pass_buffers(a, h, side, step.ranged() ? step.row_begin : 0);
   if (side == GLRM_COLS && h->blk_perm_c) { // length-sorted slots; the columns at or above long_from run on the gather sweep (run_sweep, glrm_hip.hip)
     a.segperm = h->blk_perm_c;
     a.npass = h->blk_nshort_c;
@@ -170,37 +170,39 @@ int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, do
       return GLRM_OK;
     }
   }
-  if (range) {
-    glrm_apply_row_range(a, h->rng_b, h->rng_e);
+  if (step.ranged()) {
+    glrm_apply_row_range(a, step);
     if (a.nseg <= 0) return GLRM_OK;
   }
   int rc;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
-  h->sup_order.clear();
-  if (side == GLRM_COLS && h->n_arrival > 0 && !eval_only) {
+  // glrm_hip_step_y_arrival: the order in which the gradient pass walks the super-tiles (launch_blocked_inst); empty without arriving blocks
+  glrm_arrivals* const arr = step.arrivals;
+  std::vector<int> sup_order;
+  if (arr) {
     // a super-tile can run once the LAST (in the host's order) of the blocks it touches is there: sort the super-tiles by that position
     const int64_t rows_per_sup = (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp);
     std::vector<std::pair<int, int>> key((size_t)a.nsup);
     for (int sup = 0; sup < a.nsup; ++sup) {
       const int64_t lo = sup * rows_per_sup, hi = std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other);
       int last = 0;
-      for (int b = 0; b < h->n_arrival; ++b)
-        if (h->arrival[b].begin < hi && h->arrival[b].end > lo && h->arrival[b].event) last = std::max(last, b + 1);
+      for (int b = 0; b < arr->n; ++b)
+        if (arr->blocks[b].begin < hi && arr->blocks[b].end > lo && arr->blocks[b].event) last = std::max(last, b + 1);
       key[sup] = {last, sup};
     }
     std::sort(key.begin(), key.end());
-    for (auto& kv : key) h->sup_order.push_back(kv.second);
+    for (auto& kv : key) sup_order.push_back(kv.second);
   }
   // a float handle (glrm_options.storage = 1) takes the ST = float kernels of glrm_blocked_f32.hip: the same launches over the same buffers
   const bool f32 = h->storage == GLRM_STORAGE_F32;
-  auto pass = [&](bool grad) { return f32 ? glrm_launch_blocked_f32(h, loss, grad, a, side) : launch_blocked_st<double>(h, loss, grad, a, side); };
+  auto pass = [&](bool grad) { return f32 ? glrm_launch_blocked_f32(h, loss, grad, a, side, arr, sup_order) : launch_blocked_st<double>(h, loss, grad, a, side, arr, sup_order); };
   auto small = [&](int stage, const TiledArgs& d) { f32 ? glrm_launch_col_small_f32(h->kp, stage, d, h->stream) : glrm_launch_col_small(h->kp, stage, d, h->stream); };
   if ((rc = pass(true))) return rc;  // gradient + loss partials, super-tile by super-tile
   small(0, a);                       // reduce in super-tile order, J_old, first trial point
   HIPCK(hipGetLastError());
-  if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
+  if (step.eval_only || step.fixed()) return GLRM_OK;
   return glrm_run_rounds(
-      h, a, min_stepsize, glrm_act_lists{},
+      h, a, step.min_stepsize, glrm_act_lists{},
       [&](int, unsigned int, int32_t*) { return pass(false); },  // loss partials at the trial points of the searching segments
       [&](const TiledArgs& d) { small(1, d); });                 // accept / shrink / give up, next trial point
 }

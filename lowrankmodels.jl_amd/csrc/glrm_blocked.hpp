@@ -57,7 +57,7 @@ static int64_t slice_capacity(K kernel, int device, int spb) {
 }
 
 template <int G, int R, int LOSS, bool GRAD, class ST>
-static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
+static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side, glrm_arrivals* arr, const std::vector<int>& sup_order) {
   constexpr int KP = G * R, T = glrm_tile_rows(KP), SPB = BNW * (64 / G);
   auto kernel = tiled_col_pass_kernel<G, R, BNW, T, LOSS, GRAD, true, false, ST>;
   // per handle, view and pass kind: the row passes (LOSS_PER_OBS* instantiations of a heterogeneous model) and the column passes
@@ -76,13 +76,13 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
   const int64_t per = nslices > 0 ? ((nseg + nslices - 1) / nslices + SPB - 1) / SPB * SPB : cap;
   if (!env_int("GLRM_HIP_BLOCKED_SUPPOS", 1)) a.suppos = nullptr;
   // glrm_hip_step_y_arrival: the gradient pass of the column view walks the super-tiles in the order their rows of X arrive, each behind
-  // the events of the blocks it touches (h->sup_order, glrm_run_blocked); the partial sums are per (segment, super-tile) and col_reduce
-  // adds them in super-tile order, so the launch order changes no bit
-  const bool ordered = GRAD && side == GLRM_COLS && h->n_arrival > 0 && (int)h->sup_order.size() == a.nsup;
+  // the events of the blocks it touches (arr and sup_order, from glrm_run_blocked; arr == nullptr: X is complete); the partial sums are
+  // per (segment, super-tile) and col_reduce adds them in super-tile order, so the launch order changes no bit
+  const bool ordered = GRAD && arr;
   const int64_t rows_per_sup = (int64_t)a.tiles_per_sup * T;
   auto launch_sup = [&](int sup) -> int { // one super-tile: behind the events of the blocks it touches (ordered), slice by slice
     if (ordered) {
-      const int rcw = glrm_arrival_wait(h, sup * rows_per_sup, std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other));
+      const int rcw = glrm_arrival_wait(h, *arr, sup * rows_per_sup, std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other));
       if (rcw) return rcw;
     }
     for (int64_t s0 = 0; s0 < nseg; s0 += per) {
@@ -94,7 +94,7 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
     return GLRM_OK;
   };
   std::vector<int> pend;
-  if (ordered) pend = h->sup_order;
+  if (ordered) pend = sup_order;
   else for (int si = 0; si < a.nsup; ++si) pend.push_back(si);
   if (ordered && !h->arrival_static && env_int("GLRM_HIP_ARRIVAL_DYNAMIC", 1)) {
     // TRUE arrival order.  The fixed order above is the order blocks arrive in when every peer keeps pace; behind a lagging peer the
@@ -102,12 +102,12 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
     // super-tile only once the events of ALL its blocks have fired (hipEventQuery), the ready ones in list order, and polls for the
     // rest: the stream never stands in a wait while work is ready.  An event that cannot be queried (or 5 s without any progress) hands
     // the remaining super-tiles -- and every later call on this handle -- to the in-stream waits below.  Which order the super-tiles run in changes no bit.
-    std::vector<char> fired((size_t)h->n_arrival, 0);
+    std::vector<char> fired((size_t)arr->n, 0);
     bool unknown = false;
     auto ready = [&](int sup) {
       const int64_t lo = sup * rows_per_sup, hi = std::min<int64_t>((sup + 1) * rows_per_sup, a.n_other);
-      for (int b = 0; b < h->n_arrival; ++b) {
-        const glrm_arrival& blk = h->arrival[b];
+      for (int b = 0; b < arr->n; ++b) {
+        const glrm_arrival& blk = arr->blocks[b];
         if (fired[b] || !blk.event || blk.end <= lo || blk.begin >= hi) continue;
         const hipError_t q = hipEventQuery((hipEvent_t)blk.event);
         if (q == hipSuccess) { fired[b] = 1; continue; }
@@ -152,12 +152,12 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side) {
 
 
 template <class ST>
-static int launch_blocked_st(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side) {
+static int launch_blocked_st(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side, glrm_arrivals* arr, const std::vector<int>& sup_order) {
   auto by_layout = [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     auto by_loss = [&](auto LOSS) {
       constexpr int L = decltype(LOSS)::value;
-      return grad ? launch_blocked_inst<G, R, L, true, ST>(h, a, side) : launch_blocked_inst<G, R, L, false, ST>(h, a, side);
+      return grad ? launch_blocked_inst<G, R, L, true, ST>(h, a, side, arr, sup_order) : launch_blocked_inst<G, R, L, false, ST>(h, a, side, arr, sup_order);
     };
     return glrm_dispatch<LOSS_QUAD_UNIFORM, LOSS_SEGMENT, LOSS_SEGMENT_NOTRIG, LOSS_PER_OBS_NOTRIG>(loss, by_loss, [&] { return by_loss(glrm_const<LOSS_PER_OBS>{}); });
   };

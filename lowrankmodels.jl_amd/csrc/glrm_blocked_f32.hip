@@ -10,6 +10,6 @@
 
 using namespace glrm;
 
-int glrm_launch_blocked_f32(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side) { return launch_blocked_st<float>(h, loss, grad, a, side); }
+int glrm_launch_blocked_f32(glrm_handle* h, int loss, bool grad, const TiledArgs& a, int side, glrm_arrivals* arr, const std::vector<int>& sup_order) { return launch_blocked_st<float>(h, loss, grad, a, side, arr, sup_order); }
 
 void glrm_launch_col_small_f32(int kp, int stage, const TiledArgs& a, hipStream_t st) { launch_col_small_st<float>(kp, stage, a, st); }

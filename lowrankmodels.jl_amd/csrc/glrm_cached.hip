@@ -277,20 +277,22 @@ void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen) {
   }
 }
 
-// seglist == nullptr: every local row (restricted to the range of glrm_hip_step_x_range, if one is set); otherwise the rows listed
-int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st) {
+// An X half-step (never an evaluation) of the request.  seglist == nullptr: every local row (restricted to the request's row range, if it
+// has one); otherwise the rows listed
+int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, hipStream_t st) {
+  const int loss = step.loss;
   CachedArgs a{};
-  glrm_fill_side(a, h, GLRM_ROWS, min_stepsize, 0);
+  glrm_fill_side(a, h, step);
   a.cap = h->cached_cap;
   a.seg_lo = 0;
   a.seg_hi = h->side[GLRM_ROWS].nseg;
   if (seglist) {
     a.seglist = seglist;
     a.nseg = nlist;
-    if (h->rng_e >= 0) { a.seg_lo = h->rng_b; a.seg_hi = h->rng_e; }
+    if (step.ranged()) { a.seg_lo = step.row_begin; a.seg_hi = step.row_end; }
     if (a.nseg <= 0 || a.seg_hi <= a.seg_lo) return GLRM_OK;
-  } else if (h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    glrm_apply_row_range(a, h->rng_b, h->rng_e);
+  } else if (step.ranged()) {
+    glrm_apply_row_range(a, step);
     if (a.nseg <= 0) return GLRM_OK;
   }
   if (h->storage == GLRM_STORAGE_F32) { // the float instantiations live in a unit of their own

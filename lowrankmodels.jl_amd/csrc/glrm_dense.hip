@@ -158,11 +158,12 @@ static void launch_dense_any(int kp, bool grad, const DenseArgs& a, hipStream_t 
 
 // One half-step on the dense path: pass 1 (residuals, objective, gradient on the matrix cores) -> per-segment
 // reduce + first trial point -> rounds of (trial objective pass, decide) until no segment is still searching.
-int glrm_run_dense(glrm_handle* h, int side, double min_stepsize, int eval_only) {
+int glrm_run_dense(glrm_handle* h, const glrm_step& step) { // (no row range: glrm_hip_step_x_range refuses the dense path)
+  const int side = step.side;
   const glrm_handle::Side& v = h->side[side];
   if (v.nseg <= 0) return GLRM_OK;
   TiledArgs a{};
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
+  glrm_fill_side(a, h, step);
   DenseArgs d{}; // the side as the MFMA kernels read it: what `a` says, plus the packed matrix
   d.nseg = a.nseg; d.xsrc = a.own; d.own_offset = a.own_offset; d.other = a.other;
   d.n_other = h->side[side ^ 1].nglob;
@@ -174,19 +175,19 @@ int glrm_run_dense(glrm_handle* h, int side, double min_stepsize, int eval_only)
   d.nsup = a.nsup;
   d.part = a.part;
   d.active = a.active;
-  const bool gram = h->dense_gram && !eval_only && a.fixed_alpha <= 0.0;
+  const bool gram = h->dense_gram && !step.eval_only && !step.fixed();
   a.jloss = gram ? v.jloss : nullptr;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   if (gram) launch_gram(h->kp, 0, a, d.other, d.n_other, h->gram_part, h->gramH, d.scale, h->stream);
   launch_dense_any(h->kp, true, d, h->stream);
   glrm_launch_col_small(h->kp, 0, a, h->stream);
   HIPCK(hipGetLastError());
-  if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
+  if (step.eval_only || step.fixed()) return GLRM_OK;
   DenseArgs t = d;
   t.xsrc = a.trial; // trial points are stored per local segment
   t.own_offset = 0;
   return glrm_run_rounds(
-      h, a, min_stepsize, glrm_act_lists{},
+      h, a, step.min_stepsize, glrm_act_lists{},
       [&](int, unsigned int, int32_t*) {
         if (gram) launch_gram(h->kp, 1, a, d.other, d.n_other, h->gram_part, h->gramH, d.scale, h->stream);
         else launch_dense_any(h->kp, false, t, h->stream);

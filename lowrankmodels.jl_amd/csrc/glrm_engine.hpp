@@ -16,8 +16,9 @@
 //                       iteration of glrm_svd.hip through glrm_subspace.hpp
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
-// Below: glrm_handle keeps what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`, the opposing
-// side is side ^ 1); glrm_side_family is the one place that says which kernel family runs a side.
+// Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
+// the opposing side is side ^ 1); glrm_step is what ONE half-step is asked to do, built by the entry point and passed down as an argument
+// (the handle holds nothing about a call in flight); glrm_side_family is the one place that says which kernel family runs a side.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -72,8 +73,6 @@ struct glrm_handle {
   bool own_stream = false;
   int64_t m = 0, n = 0;
   int k = 0, kp = 0, G = 4, R = 2;
-  double fixed_alpha = 0.0;           // > 0 while a SparseProxGradParams step (no line search) is being launched
-  int64_t rng_b = 0, rng_e = -1;      // row sub-range of the next X sweep (glrm_hip_step_x_range); rng_e < 0 = all
   int tiled_opt = 0;                  // glrm_options.tiled
   int tG = 4, tR = 2;                 // lane layout of the tiled kernels (kp = tG*tR)
   int tile_rounds = 0;                // LDS-tiled sweeps: line-search rounds over the still-searching segments only (bit0 rows, bit1 columns)
@@ -187,14 +186,9 @@ struct glrm_handle {
   hipStream_t side_stream = nullptr;  // the launches of the minority classes run beside the main launch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int profile = 0;
-  // columns only.  glrm_hip_step_y_arrival: the blocks of X that are still arriving (valid during that call only), which of them the launch
-  // stream has already been made to wait for, and -- phase-aligned column passes -- the order in which the gradient pass walks the super-tiles
-  const glrm_arrival* arrival = nullptr;
-  int n_arrival = 0;
-  std::vector<char> arrival_waited;
+  // columns only, glrm_hip_step_y_arrival (the blocks themselves are the call's: glrm_arrivals below)
   bool arrival_static = false; // true arrival order gave up once (an event that cannot be queried, 5 s without progress): in-stream waits from then on
-  std::vector<int> sup_order;
-  double ms_wait = 0;                 // profile: time the launch stream stood in those waits
+  double ms_wait = 0;                 // profile: time the launch stream stood in the waits for arriving blocks
   int sum_order_opt = 0;              // glrm_options.sum_order (1: reference-order validation sweeps, glrm_reforder.hip)
   // glrm_options.storage.  GLRM_STORAGE_F32: Side::vals / factor / own_factor hold FLOATS behind their double* type (the same
   // element counts); only the float gather sweeps, the float cached row sweep (glrm_cached_f32.hip), the float phase-aligned passes
@@ -211,6 +205,26 @@ struct glrm_handle {
   std::vector<glrm_loss> losses_h;
   struct Ev { hipEvent_t a, b; int slot; }; // slot: the side whose half-step the pair times, 2 = a wait for arriving blocks (ms_wait)
   std::vector<Ev> pending, pool;
+};
+
+// glrm_hip_step_y_arrival: the blocks of X that are still arriving and which of them the launch stream has already been made to wait for.
+// Lives on that entry point's stack, for that call only.
+struct glrm_arrivals {
+  const glrm_arrival* blocks; int n;
+  std::vector<char> waited;
+};
+// What ONE call of run_sweep is asked to do: built by the entry point from its own arguments, const from there down.  `side` is an int that
+// is only ever assigned GLRM_ROWS / GLRM_COLS (a `true` would mean columns: the functions of glrm_hip.hip that build every request refuse a bool).
+struct glrm_step {
+  int side;
+  double min_stepsize = 0.0;
+  bool eval_only = false;               // the loss evaluation of glrm_hip_col_losses / the objective
+  double fixed_alpha = 0.0;             // > 0: the SparseProxGradParams step, no line search
+  int64_t row_begin = 0, row_end = -1;  // glrm_hip_step_x_range: local rows [row_begin, row_end); row_end < 0 = every local row
+  glrm_arrivals* arrivals = nullptr;    // glrm_hip_step_y_arrival; nullptr = X is complete
+  int loss = 0, loss_by_segment = 0;    // the loss variant (LOSS_*), chosen once by run_sweep (loss_variant)
+  bool ranged() const { return side == GLRM_ROWS && row_end >= 0; }
+  bool fixed() const { return fixed_alpha > 0.0 && !eval_only; }
 };
 
 // The kernel family that runs a side's half-step (eval_only: the loss evaluation of glrm_hip_col_losses / the objective).  The ONE statement
@@ -253,7 +267,7 @@ inline int64_t glrm_cached_reg_maxlen(int G) { return (int64_t)13 * (64 / G); }
 // setup: family choice from h->sig and buffers (finalize)
 int glrm_prepare_tiled(glrm_handle* h);
 int glrm_setup_tiled(glrm_handle* h);
-int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only);
+int glrm_run_tiled(glrm_handle* h, const glrm_step& step);
 
 // lane-per-segment LDS-tiled passes (glrm_lane.hip): setup decides lane[] from the whole problem's signature and builds the SELL layouts;
 // run takes the TiledArgs glrm_run_tiled prepared (glrm_tiled.hpp)
@@ -261,19 +275,19 @@ bool glrm_lane_wants(const glrm_handle* h, int side);   // the whole problem's s
 int glrm_setup_lane(glrm_handle* h);
 bool glrm_lane_loss_ok(const glrm_handle* h, int loss);
 bool glrm_lane_few_descriptors(const glrm_handle* h);
-int glrm_run_lane(glrm_handle* h, int side, int loss, const glrm::TiledArgs& a, double min_stepsize, int eval_only);
+int glrm_run_lane(glrm_handle* h, const glrm_step& step, const glrm::TiledArgs& a);
 
 // phase-aligned gather passes (glrm_blocked.hip): setup decides Side::blocked and allocates the pass buffers
 int glrm_setup_blocked(glrm_handle* h);
-int glrm_run_blocked(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only);
+int glrm_run_blocked(glrm_handle* h, const glrm_step& step);
 
-// glrm_hip_step_y_arrival (glrm_hip.hip): make h->stream wait for every block of h->arrival that intersects rows [lo, hi) of X and has
+// glrm_hip_step_y_arrival (glrm_hip.hip): make h->stream wait for every block of `arr` that intersects rows [lo, hi) of X and has
 // not been waited for yet
-int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi);
+int glrm_arrival_wait(glrm_handle* h, glrm_arrivals& arr, int64_t lo, int64_t hi);
 // LDS-tiled / lane column passes under glrm_hip_step_y_arrival (round 6): runs of super-tiles in the order their rows of X are announced --
-// launch(sup_lo, sup_hi) is called once per run, behind the in-stream waits for the blocks the run touches; without arrival blocks: one call
-// over all super-tiles.  Partial sums are per (column, super-tile) and are reduced in super-tile order: which run went first changes no bit.
-int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch);
+// launch(sup_lo, sup_hi) is called once per run, behind the in-stream waits for the blocks the run touches; without arrival blocks (arr ==
+// nullptr): one call over all super-tiles.  Partial sums are per (column, super-tile) and are reduced in super-tile order: which run went first changes no bit.
+int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, glrm_arrivals* arr, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch);
 
 // stable segmented sort of a view by tile index (glrm_tilesort.hip)
 int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, DevArena& owner);
@@ -291,7 +305,7 @@ void glrm_regvec_placeholders(const std::vector<glrm_reg>& in, std::vector<glrm_
 int glrm_regvec_inherit(glrm_handle* child, const glrm_handle* parent);
 void glrm_regvec_drop(glrm_handle* h);
 int glrm_setup_reforder(glrm_handle* h);               // finalize: refuses what the mode does not cover
-int glrm_run_reforder(glrm_handle* h, int side, double min_stepsize, int eval_only);
+int glrm_run_reforder(glrm_handle* h, const glrm_step& step);
 int glrm_reforder_sum(glrm_handle* h, const void* dvec, int64_t n, double* out); // Julia's pairwise sum(::Vector{Float64})
 int glrm_reforder_objective(glrm_handle* h, int include_reg, double* out);       // objective(): ONE accumulator over all observations, then the penalties
 
@@ -307,8 +321,9 @@ int glrm_widen_factor(glrm_handle* h, const void* dev, double* host, int64_t nve
 int glrm_check_narrowable(const char* name, const double* v, int64_t n);             // GLRM_ERR_NONFINITE for a finite value beyond float's range
 void glrm_launch_sweep_f32(int G, int R, int waves, int loss, int side, const glrm::SweepArgs& a, hipStream_t st);
 void glrm_launch_penalty_f32(glrm_handle* h, int side);
-// the float instantiations of the phase-aligned passes and of their reduce / decide kernels (glrm_blocked_f32.hip)
-int glrm_launch_blocked_f32(glrm_handle* h, int loss, bool grad, const glrm::TiledArgs& a, int side);
+// the float instantiations of the phase-aligned passes and of their reduce / decide kernels (glrm_blocked_f32.hip); arr / sup_order: see
+// launch_blocked_inst (glrm_blocked.hpp)
+int glrm_launch_blocked_f32(glrm_handle* h, int loss, bool grad, const glrm::TiledArgs& a, int side, glrm_arrivals* arr, const std::vector<int>& sup_order);
 void glrm_launch_col_small_f32(int kp, int stage, const glrm::TiledArgs& a, hipStream_t st);
 
 // GLRM_PROBLEM_ROWS_FROM_COLS (glrm_transpose.hip): the row view derived on the device from the uploaded column view
@@ -325,14 +340,14 @@ constexpr int GLRM_CACHED_F32_AUTO = 0;
 // GLRM_HIP_BLOCKED (turning it on changes which kernels, and which summation order, existing float handles take)
 constexpr int GLRM_BLOCKED_F32_AUTO = 0;
 void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
-int glrm_run_cached(glrm_handle* h, int loss, double min_stepsize, const int32_t* seglist, int64_t nlist, hipStream_t st);
+int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)
 int glrm_setup_dense(glrm_handle* h, const glrm_problem* p);
-int glrm_run_dense(glrm_handle* h, int side, double min_stepsize, int eval_only);
+int glrm_run_dense(glrm_handle* h, const glrm_step& step);
 
 // general sweeps (glrm_multi.hip)
 int glrm_setup_multi(glrm_handle* h, const glrm_problem* p);
-int glrm_run_multi(glrm_handle* h, int side, double min_stepsize, int eval_only);
+int glrm_run_multi(glrm_handle* h, const glrm_step& step);
 int glrm_run_multi_penalty(glrm_handle* h, int side);
 
 // per-segment reduce (stage = 0) / decide (stage = 1) kernels of glrm_tiled.hpp for a kp-wide factor

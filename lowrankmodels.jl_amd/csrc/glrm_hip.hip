@@ -786,65 +786,80 @@ struct RoctxRange {
   ~RoctxRange() { if (api().pop) api().pop(); }
 };
 
-// One half-step of a side, or with eval_only its loss evaluation.  glrm_side_family names the family; this is the dispatch on it.
-static int run_sweep(glrm_handle* h, int side, double min_stepsize, int eval_only) {
+// The loss variant a side's kernels are instantiated for (LOSS_*): one QuadLoss, one descriptor per segment, or -- the rows of a model
+// with a loss per column -- one per observation; its columns read theirs by segment (*by_segment).  run_sweep launches it,
+// glrm_hip_sum_order describes it.
+static int loss_variant(const glrm_handle* h, int side, int* by_segment) {
+  const bool per_column = !h->loss_quad_uniform && h->n_losses != 1;
+  *by_segment = per_column && side == GLRM_COLS;
+  if (h->loss_quad_uniform) return LOSS_QUAD_UNIFORM;
+  const int loss = per_column && side == GLRM_ROWS ? LOSS_PER_OBS : LOSS_SEGMENT;
+  return h->has_trig ? loss : loss + 2; // LOSS_*_NOTRIG: kernels compiled without the PeriodicLoss case
+}
+
+// An event pair from the pool (or a new one) with `a` recorded on the stream: the caller records `b` behind what it times and appends the
+// pair to h->pending.  slot: glrm_handle::Ev
+static int begin_timing(glrm_handle* h, int slot, glrm_handle::Ev* ev) {
+  if (!h->pool.empty()) { *ev = h->pool.back(); h->pool.pop_back(); }
+  else { HIPCK(hipEventCreate(&ev->a)); HIPCK(hipEventCreate(&ev->b)); }
+  ev->slot = slot;
+  HIPCK(hipEventRecord(ev->a, h->stream));
+  return GLRM_OK;
+}
+
+// One half-step of a side, or with eval_only its loss evaluation, as the request says (the entry points build it; the loss variant is filled
+// in here).  glrm_side_family names the family; this is the dispatch on it.
+static int run_sweep(glrm_handle* h, glrm_step step) {
+  const int side = step.side;
+  const bool eval_only = step.eval_only;
   RoctxRange range(eval_only ? "glrm col_losses" : (side == GLRM_ROWS ? "glrm step_x" : "glrm step_y"));
   GLRM_NEED_FINALIZED(h);
   int rc = ensure_owned(h);
   if (rc) return rc;
   SweepArgs a{};
   glrm_handle::Side& v = h->side[side];
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
+  glrm_fill_side(a, h, step);
   a.storage = h->storage;
   if (a.nseg <= 0) return GLRM_OK;
   if (eval_only) a.trials = nullptr;
   a.seg_lo = 0;
   a.seg_hi = a.nseg;
-  if (side == GLRM_ROWS && h->rng_e >= 0) { // glrm_hip_step_x_range: local rows [rng_b, rng_e)
-    if (h->rng_e - h->rng_b <= 0) return GLRM_OK;
+  if (step.ranged()) { // glrm_hip_step_x_range
+    if (step.row_end - step.row_begin <= 0) return GLRM_OK;
     if (v.seglist) { // several classes: the class launches filter their lists by the range
-      a.seg_lo = h->rng_b; a.seg_hi = h->rng_e;
+      a.seg_lo = step.row_begin; a.seg_hi = step.row_end;
     } else {
-      glrm_apply_row_range(a, h->rng_b, h->rng_e);
+      glrm_apply_row_range(a, step);
       a.seg_hi = a.nseg;
     }
   }
-  int loss;
-  if (h->loss_quad_uniform) { loss = LOSS_QUAD_UNIFORM; a.loss_by_segment = 0; }
-  else if (h->n_losses == 1) { loss = LOSS_SEGMENT; a.loss_by_segment = 0; }
-  else if (side == GLRM_ROWS) { loss = LOSS_PER_OBS; a.loss_by_segment = 0; }
-  else { loss = LOSS_SEGMENT; a.loss_by_segment = 1; }
-  if (!h->has_trig && loss != LOSS_QUAD_UNIFORM) loss += 2; // LOSS_*_NOTRIG: kernels compiled without the PeriodicLoss case
+  step.loss = loss_variant(h, side, &step.loss_by_segment);
+  const int loss = step.loss;
+  a.loss_by_segment = step.loss_by_segment;
   glrm_handle::Ev ev{};
   const bool timed = h->profile && !eval_only;
-  if (timed) {
-    if (!h->pool.empty()) { ev = h->pool.back(); h->pool.pop_back(); }
-    else { HIPCK(hipEventCreate(&ev.a)); HIPCK(hipEventCreate(&ev.b)); }
-    ev.slot = side;
-    HIPCK(hipEventRecord(ev.a, h->stream));
-  }
-  const glrm_family fam = glrm_side_family(h, side, eval_only != 0);
+  if (timed && (rc = begin_timing(h, side, &ev))) return rc;
+  const glrm_family fam = glrm_side_family(h, side, eval_only);
   if (fam == GLRM_FAM_REFERENCE) {
-    rc = glrm_run_reforder(h, side, min_stepsize, eval_only);
+    rc = glrm_run_reforder(h, step);
   } else if (fam == GLRM_FAM_GENERAL) {
-    rc = glrm_run_multi(h, side, min_stepsize, eval_only);
+    rc = glrm_run_multi(h, step);
   } else if (fam == GLRM_FAM_DENSE) {
-    rc = glrm_run_dense(h, side, min_stepsize, eval_only);
+    rc = glrm_run_dense(h, step);
   } else if (fam == GLRM_FAM_TILED || fam == GLRM_FAM_BLOCKED) {
     const bool divert = side == GLRM_COLS && h->blk_nlong_c > 0; // the very long columns: 8-wave gather sweep on the side stream, beside the passes
     if (divert) {
       // the gather sweep reads all of X: behind the sweeps already queued (fork) and, while X is still arriving
       // (glrm_hip_step_y_arrival), behind every block -- without holding up the passes on the main stream
       if ((rc = glrm_fork_side_stream(h))) return rc;
-      for (int b = 0; b < h->n_arrival; ++b)
-        if (h->arrival[b].event) HIPCK(hipStreamWaitEvent(h->side_stream, (hipEvent_t)h->arrival[b].event, 0));
+      for (int b = 0; step.arrivals && b < step.arrivals->n; ++b)
+        if (void* e = step.arrivals->blocks[b].event) HIPCK(hipStreamWaitEvent(h->side_stream, (hipEvent_t)e, 0));
       SweepArgs b = a;
       b.seglist = h->blk_long_c;
       b.nseg = h->blk_nlong_c;
       launch_sweep(h->G, h->R, 8, loss, GLRM_COLS, b, h->side_stream);
     }
-    rc = fam == GLRM_FAM_TILED ? glrm_run_tiled(h, side, loss, a.loss_by_segment, min_stepsize, eval_only)
-                               : glrm_run_blocked(h, side, loss, a.loss_by_segment, min_stepsize, eval_only);
+    rc = fam == GLRM_FAM_TILED ? glrm_run_tiled(h, step) : glrm_run_blocked(h, step);
     if (divert) (void)glrm_join_side_stream(h); // join before anything else (also before reporting an error: later work on the stream stays ordered)
   } else {
     // gather sweeps (and the cached row sweep), class by class -- see build_class_plan
@@ -854,7 +869,7 @@ static int run_sweep(glrm_handle* h, int side, double min_stepsize, int eval_onl
       int cls = 1;
       for (int c = 0; c < 4; ++c) if (ncls[c] > 0) cls = c;
       if (cls == 0 && !eval_only) {
-        if ((rc = glrm_run_cached(h, loss, min_stepsize, nullptr, 0, h->stream))) return rc;
+        if ((rc = glrm_run_cached(h, step, nullptr, 0, h->stream))) return rc;
       } else {
         launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, side, a, h->stream);
       }
@@ -869,7 +884,7 @@ static int run_sweep(glrm_handle* h, int side, double min_stepsize, int eval_onl
         if (ncls[c] <= 0) continue;
         hipStream_t st = c == main_cls ? h->stream : h->side_stream;
         if (c == 0 && !eval_only) {
-          rc_cls = glrm_run_cached(h, loss, min_stepsize, lst + off, ncls[0], st);
+          rc_cls = glrm_run_cached(h, step, lst + off, ncls[0], st);
         } else {
           SweepArgs b = a;
           b.seglist = lst + off;
@@ -894,10 +909,18 @@ static int run_sweep(glrm_handle* h, int side, double min_stepsize, int eval_onl
   return GLRM_OK;
 }
 
+// The requests the entry points make (what they do not name keeps glrm_step's default): a ProxGradParams half-step with its line search,
+// one SparseProxGradParams step of a global step size, the loss evaluation over the column view.
+static glrm_step search_step(int side, double min_stepsize) { glrm_step s{side}; s.min_stepsize = min_stepsize; return s; }
+static glrm_step fixed_step(int side, double alpha) { glrm_step s{side}; s.fixed_alpha = alpha; return s; }
+static glrm_step eval_step() { glrm_step s{GLRM_COLS}; s.eval_only = true; return s; }
+static glrm_step search_step(bool, double) = delete; // `true` would mean columns: a side is GLRM_ROWS / GLRM_COLS (what the deleted bool
+static glrm_step fixed_step(bool, double) = delete;  // overload of glrm_fill_side used to guard; every request is built by these three)
+
 extern "C" int glrm_hip_step_x(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, GLRM_ROWS, min_stepsize, 0);
+  return run_sweep(h, search_step(GLRM_ROWS, min_stepsize));
 }
 
 extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t seg_end, double min_stepsize) {
@@ -906,18 +929,16 @@ extern "C" int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t 
   if (seg_begin < 0 || seg_end > h->side[GLRM_ROWS].nseg || seg_begin > seg_end) return fail(GLRM_ERR_INVALID, "row range out of bounds");
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "step_x_range is not available on the dense path");
   DeviceScope dg(h->device);
-  h->rng_b = seg_begin;
-  h->rng_e = seg_end;
-  const int rc = run_sweep(h, GLRM_ROWS, min_stepsize, 0);
-  h->rng_b = 0;
-  h->rng_e = -1;
-  return rc;
+  glrm_step step = search_step(GLRM_ROWS, min_stepsize);
+  step.row_begin = seg_begin;
+  step.row_end = seg_end;
+  return run_sweep(h, step);
 }
 
 extern "C" int glrm_hip_step_y(glrm_handle* h, double min_stepsize) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, GLRM_COLS, min_stepsize, 0);
+  return run_sweep(h, search_step(GLRM_COLS, min_stepsize));
 }
 
 // the Y half-step runs as passes over super-tiles (LDS-tiled, lane or phase-aligned)
@@ -927,18 +948,16 @@ static bool col_passes(const glrm_handle* h) {
 }
 
 // ---- the Y half-step while X is still arriving (include/glrm_hip.h: glrm_hip_step_y_arrival) ----------------------------------------
-int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi) {
-  for (int b = 0; b < h->n_arrival; ++b) {
-    const glrm_arrival& blk = h->arrival[b];
-    if (h->arrival_waited[b] || blk.end <= lo || blk.begin >= hi) continue;
-    h->arrival_waited[b] = 1;
+int glrm_arrival_wait(glrm_handle* h, glrm_arrivals& arr, int64_t lo, int64_t hi) {
+  for (int b = 0; b < arr.n; ++b) {
+    const glrm_arrival& blk = arr.blocks[b];
+    if (arr.waited[b] || blk.end <= lo || blk.begin >= hi) continue;
+    arr.waited[b] = 1;
     if (!blk.event) continue;
     glrm_handle::Ev ev{};
     if (h->profile) { // what the launch stream spends in front of a block that is not there yet (ms_wait_y)
-      if (!h->pool.empty()) { ev = h->pool.back(); h->pool.pop_back(); }
-      else { HIPCK(hipEventCreate(&ev.a)); HIPCK(hipEventCreate(&ev.b)); }
-      ev.slot = 2;
-      HIPCK(hipEventRecord(ev.a, h->stream));
+      const int rc = begin_timing(h, 2, &ev);
+      if (rc) return rc;
     }
     HIPCK(hipStreamWaitEvent(h->stream, (hipEvent_t)blk.event, 0));
     if (h->profile) {
@@ -949,27 +968,27 @@ int glrm_arrival_wait(glrm_handle* h, int64_t lo, int64_t hi) {
   return GLRM_OK;
 }
 
-int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch) {
-  if (!h->arrival || h->n_arrival <= 0) return launch(0, nsup);
+int glrm_for_sup_runs_in_arrival_order(glrm_handle* h, glrm_arrivals* arr, int nsup, int64_t rows_per_sup, const std::function<int(int, int)>& launch) {
+  if (!arr || arr->n <= 0) return launch(0, nsup);
   if (nsup <= 1) { // one super-tile reads every row: behind ALL announced blocks (before session r6_69 it was launched without any wait --
                    // problems of at most one tile of rows on several shards raced with the exchange: tests/perf/soak_lane_shards.py, seed 5004)
-    const int rc = glrm_arrival_wait(h, 0, h->m);
+    const int rc = glrm_arrival_wait(h, *arr, 0, h->m);
     return rc ? rc : launch(0, nsup);
   }
   // need[s] = the LAST announced block super-tile s touches: the run of super-tiles that become complete with block b is launched behind b
   std::vector<int> need((size_t)nsup, -1);
   for (int s = 0; s < nsup; ++s) {
     const int64_t lo = (int64_t)s * rows_per_sup, hi = std::min<int64_t>(lo + rows_per_sup, h->m);
-    for (int b = 0; b < h->n_arrival; ++b)
-      if (h->arrival[b].begin < hi && h->arrival[b].end > lo && h->arrival[b].begin < h->arrival[b].end) need[s] = b;
+    for (int b = 0; b < arr->n; ++b)
+      if (arr->blocks[b].begin < hi && arr->blocks[b].end > lo && arr->blocks[b].begin < arr->blocks[b].end) need[s] = b;
   }
-  for (int b = -1; b < h->n_arrival; ++b) { // (-1: super-tiles no block touches -- beyond m -- first)
+  for (int b = -1; b < arr->n; ++b) { // (-1: super-tiles no block touches -- beyond m -- first)
     for (int s = 0; s < nsup;) {
       if (need[s] != b) { ++s; continue; }
       int e = s + 1;
       while (e < nsup && need[e] == b) ++e;
       const int64_t lo = (int64_t)s * rows_per_sup, hi = std::min<int64_t>((int64_t)e * rows_per_sup, h->m);
-      int rc = glrm_arrival_wait(h, lo, hi);
+      int rc = glrm_arrival_wait(h, *arr, lo, hi);
       if (!rc) rc = launch(s, e);
       if (rc) return rc;
       s = e;
@@ -999,19 +1018,16 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
   }
   GLRM_NEED_FINALIZED(h);
   DeviceScope dg(h->device);
-  h->arrival = blocks;
-  h->n_arrival = n_blocks;
-  h->arrival_waited.assign((size_t)n_blocks, 0);
+  glrm_arrivals arr{blocks, n_blocks, std::vector<char>((size_t)n_blocks, 0)};
+  glrm_step step = search_step(GLRM_COLS, min_stepsize);
+  step.arrivals = &arr;
   int rc = GLRM_OK;
   // the pass families of the column view can start on a part of X (the phase-aligned passes super-tile by super-tile in true arrival order,
   // the LDS-tiled / lane passes in runs of super-tiles in the announced order: round 6); everything else needs all of it
   const bool by_super_tile = col_passes(h) && env_int("GLRM_HIP_ARRIVAL", 1);
-  if (!by_super_tile) rc = glrm_arrival_wait(h, 0, h->m);
-  if (!rc) rc = run_sweep(h, GLRM_COLS, min_stepsize, 0);
-  if (!rc) rc = glrm_arrival_wait(h, 0, h->m); // (a shard without columns launches nothing: later work on the stream still follows the arrivals)
-  h->arrival = nullptr;
-  h->n_arrival = 0;
-  h->sup_order.clear();
+  if (!by_super_tile) rc = glrm_arrival_wait(h, arr, 0, h->m);
+  if (!rc) rc = run_sweep(h, step);
+  if (!rc) rc = glrm_arrival_wait(h, arr, 0, h->m); // (a shard without columns launches nothing: later work on the stream still follows the arrivals)
   return rc;
 }
 
@@ -1021,10 +1037,7 @@ static int gradstep(glrm_handle* h, int side, double alpha) {
   GLRM_REFUSE_F32(h, "glrm_hip_gradstep_x / glrm_hip_gradstep_y");
   if (!(alpha > 0.0)) return fail(GLRM_ERR_INVALID, "the step size must be positive");
   DeviceScope dg(h->device);
-  h->fixed_alpha = alpha;
-  const int rc = run_sweep(h, side, 0.0, 0);
-  h->fixed_alpha = 0.0;
-  return rc;
+  return run_sweep(h, fixed_step(side, alpha));
 }
 extern "C" int glrm_hip_gradstep_x(glrm_handle* h, double alpha) { return gradstep(h, GLRM_ROWS, alpha); }
 extern "C" int glrm_hip_gradstep_y(glrm_handle* h, double alpha) { return gradstep(h, GLRM_COLS, alpha); }
@@ -1032,7 +1045,7 @@ extern "C" int glrm_hip_gradstep_y(glrm_handle* h, double alpha) { return gradst
 extern "C" int glrm_hip_col_losses(glrm_handle* h) {
   if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
   DeviceScope dg(h->device);
-  return run_sweep(h, GLRM_COLS, 0.0, 1);
+  return run_sweep(h, eval_step());
 }
 
 static int run_penalty(glrm_handle* h, int side) {
@@ -1121,8 +1134,9 @@ extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_or
   o.cached_maxlen = -1;
   o.waves4_from = GLRM_WAVES4_FROM;
   o.waves8_from = GLRM_WAVES8_FROM;
-  // the loss variant run_sweep instantiates: 0 = one QuadLoss, segment = one descriptor per segment, per-observation = rows of a heterogeneous model
-  const bool quad = h->loss_quad_uniform, per_obs = !quad && h->n_losses > 1 && side == GLRM_ROWS;
+  int by_segment; // the loss variant run_sweep instantiates
+  const int loss = loss_variant(h, side, &by_segment);
+  const bool quad = loss == LOSS_QUAD_UNIFORM, per_obs = loss_mode(loss) == LOSS_PER_OBS;
   if (side == GLRM_COLS && col_passes(h)) o.long_from = (int32_t)std::min<int64_t>(h->blk_long_from, INT32_MAX);
   if (fam == GLRM_FAM_REFERENCE) {
     o.family = GLRM_ORDER_REFERENCE; // glrm_reforder.hip: one lane per segment, list order, one accumulator per sum
@@ -1187,7 +1201,7 @@ static int device_objective(glrm_handle* h, int include_reg, double* out) {
     if ((rc = ensure_owned(h))) return rc;
     return glrm_reforder_objective(h, include_reg, out);
   }
-  if ((rc = run_sweep(h, GLRM_COLS, 0.0, 1))) return rc;
+  if ((rc = run_sweep(h, eval_step()))) return rc;
   if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &loss))) return rc;
   if (include_reg) {
     if ((rc = run_penalty(h, GLRM_ROWS))) return rc;
@@ -1229,8 +1243,8 @@ static int build_iteration_graph(glrm_handle* h, const glrm_params* prm) {
   bool ok = true;
   const int64_t lx = h->side[GLRM_ROWS].launches, ly = h->side[GLRM_COLS].launches;
   if (prm->inner_iter_X > 1 || prm->inner_iter_Y > 1) ok = ok && glrm_hip_reset_stepsizes(h, prm->stepsize) == GLRM_OK;
-  for (int64_t in = 0; ok && in < prm->inner_iter_X; ++in) ok = run_sweep(h, GLRM_ROWS, prm->min_stepsize, 0) == GLRM_OK;
-  for (int64_t in = 0; ok && in < prm->inner_iter_Y; ++in) ok = run_sweep(h, GLRM_COLS, prm->min_stepsize, 0) == GLRM_OK;
+  for (int64_t in = 0; ok && in < prm->inner_iter_X; ++in) ok = run_sweep(h, search_step(GLRM_ROWS, prm->min_stepsize)) == GLRM_OK;
+  for (int64_t in = 0; ok && in < prm->inner_iter_Y; ++in) ok = run_sweep(h, search_step(GLRM_COLS, prm->min_stepsize)) == GLRM_OK;
   if (ok) {
     hipLaunchKernelGGL(sum_stage1, dim3(SUM_BLOCKS), dim3(SUM_THREADS), 0, h->stream, (const double*)h->side[GLRM_COLS].obj, h->n, h->partials);
     hipLaunchKernelGGL(sum_stage2, dim3(1), dim3(SUM_THREADS), 0, h->stream, h->partials, h->dscalar);
@@ -1278,9 +1292,9 @@ extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, d
       if (prm->inner_iter_X > 1 || prm->inner_iter_Y > 1)
         if ((rc = glrm_hip_reset_stepsizes(h, prm->stepsize))) return rc; // :112-115
       for (int64_t in = 0; in < prm->inner_iter_X; ++in)
-        if ((rc = run_sweep(h, GLRM_ROWS, prm->min_stepsize, 0))) return rc;    // :117-158
+        if ((rc = run_sweep(h, search_step(GLRM_ROWS, prm->min_stepsize)))) return rc; // :117-158
       for (int64_t in = 0; in < prm->inner_iter_Y; ++in)
-        if ((rc = run_sweep(h, GLRM_COLS, prm->min_stepsize, 0))) return rc;    // :160-203
+        if ((rc = run_sweep(h, search_step(GLRM_COLS, prm->min_stepsize)))) return rc; // :160-203
       if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &obj))) return rc;     // obj = sum(obj_by_col) :205
     }
     const double dt = now_s() - t;
@@ -1315,9 +1329,14 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   DevArena scratch;
   double *bestX = nullptr, *bestY = nullptr;
   if ((rc = scratch.alloc(&bestX, xb / 8)) || (rc = scratch.alloc(&bestY, yb / 8))) return rc;
-  if (hipMemcpyAsync(bestX, h->side[GLRM_ROWS].factor, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(bestY, h->side[GLRM_COLS].factor, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-    return fail(GLRM_ERR_HIP, "device copy failed");
+  // X then Y between the working factors and the best model so far, on the handle's stream
+  auto copy_factors = [&](bool to_best) {
+    double *wx = h->side[GLRM_ROWS].factor, *wy = h->side[GLRM_COLS].factor;
+    const bool ok = hipMemcpyAsync(to_best ? bestX : wx, to_best ? wx : bestX, xb, hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+                    hipMemcpyAsync(to_best ? bestY : wy, to_best ? wy : bestY, yb, hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
+    return ok ? (int)GLRM_OK : fail(GLRM_ERR_HIP, "device copy failed");
+  };
+  if ((rc = copy_factors(true))) return rc;
   double alpha = prm->stepsize;                              // :46
   const double tol = prm->abs_tol * (double)h->side[GLRM_ROWS].nnz;        // :48
   int64_t nrec = 0;
@@ -1327,8 +1346,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   double t = now_s();
   int64_t steps_in_a_row = 0;
   for (int64_t i = 1; i <= prm->max_iter; ++i) {
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, GLRM_ROWS, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
-    for (int64_t in = 0; in < prm->inner_iter; ++in) { h->fixed_alpha = alpha; rc = run_sweep(h, GLRM_COLS, 0.0, 0); h->fixed_alpha = 0.0; if (rc) return rc; }
+    for (int64_t in = 0; in < prm->inner_iter; ++in) if ((rc = run_sweep(h, fixed_step(GLRM_ROWS, alpha)))) return rc;
+    for (int64_t in = 0; in < prm->inner_iter; ++in) if ((rc = run_sweep(h, fixed_step(GLRM_COLS, alpha)))) return rc;
     double obj = 0.0;
     if ((rc = device_objective(h, 1, &obj))) return rc; // :102
     if (obj < objective[nrec - 1]) {                              // :104-110
@@ -1336,18 +1355,14 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
       objective[nrec] = obj;
       seconds[nrec] = seconds[nrec - 1] + dt;
       ++nrec;
-      if (hipMemcpyAsync(bestX, h->side[GLRM_ROWS].factor, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(bestY, h->side[GLRM_COLS].factor, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return fail(GLRM_ERR_HIP, "device copy failed");
+      if ((rc = copy_factors(true))) return rc;
       alpha = alpha * 1.05;
       steps_in_a_row = steps_in_a_row + 1 > 1 ? steps_in_a_row + 1 : 1;
       t = now_s();
     } else {                                                      // :111-117
       const double div = -(double)steps_in_a_row > 1.5 ? -(double)steps_in_a_row : 1.5;
       alpha = alpha / div;
-      if (hipMemcpyAsync(h->side[GLRM_ROWS].factor, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-          hipMemcpyAsync(h->side[GLRM_COLS].factor, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return fail(GLRM_ERR_HIP, "device copy failed");
+      if ((rc = copy_factors(false))) return rc;
       steps_in_a_row = steps_in_a_row - 1 < 0 ? steps_in_a_row - 1 : 0;
     }
     // :119  i>10 && (steps_in_a_row > 3 && ch.objective[end-1] - obj < tol) || alpha <= params.min_stepsize
@@ -1358,9 +1373,7 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   seconds[nrec] = seconds[nrec - 1] + (now_s() - t);
   ++nrec;
   // glrm.X, glrm.Y are the best model found
-  if (hipMemcpyAsync(h->side[GLRM_ROWS].factor, bestX, xb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(h->side[GLRM_COLS].factor, bestY, yb, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-    return fail(GLRM_ERR_HIP, "device copy failed");
+  if ((rc = copy_factors(false))) return rc;
   rc = glrm_hip_get_factors(h, X, Y);
   *n_recorded = nrec;
   return rc;

@@ -218,7 +218,8 @@ int glrm_setup_lane(glrm_handle* h) {
 
 // One half-step (or the evaluation pass of the column view) on the lane-per-segment passes.  `a` comes prepared by glrm_run_tiled: the side's
 // views, factors, pass buffers, slot permutation and -- rows of a sub-range sweep -- everything offset to the range's first row.
-int glrm_run_lane(glrm_handle* h, int side, int loss, const TiledArgs& a_in, double min_stepsize, int eval_only) {
+int glrm_run_lane(glrm_handle* h, const glrm_step& step, const TiledArgs& a_in) {
+  const int side = step.side, loss = step.loss;
   TiledArgs a = a_in;
   hipStream_t st = h->stream;
   LaneArgs la{};
@@ -230,12 +231,10 @@ int glrm_run_lane(glrm_handle* h, int side, int loss, const TiledArgs& a_in, dou
   la.inv = v.lane_inv;
   la.glist = h->lane_glist;
   la.gwaves = 0;
-  (void)min_stepsize;
   // does the SELL layout cover this launch?  It was built on the side's full slot space (slot permutation included); a row sub-range
   // (glrm_hip_step_x_range) is covered when the slots are the rows themselves: its wave blocks run with the lanes outside the range masked
-  const bool range = side == GLRM_ROWS && h->rng_e >= 0;
-  const bool sell_ok = !range || v.perm == nullptr;
-  if (range) la.slot0 = h->rng_b;
+  const bool sell_ok = !step.ranged() || v.perm == nullptr;
+  if (step.ranged()) la.slot0 = step.row_begin;
   const int64_t nslots = a.npass > 0 ? a.npass : a.nseg;
   const int64_t blk_lo = la.slot0 / 64, blk_hi = (la.slot0 + nslots + 63) / 64;
   int rc;
@@ -257,11 +256,11 @@ int glrm_run_lane(glrm_handle* h, int side, int loss, const TiledArgs& a_in, dou
     r.npass = 0;
     return launch_lane_loss<true, 1>(loss, r, csr_args(r), (r.nseg + 63) / 64, st);
   };
-  rc = side == GLRM_ROWS ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), grad); // (rows read Y: complete)
+  rc = side == GLRM_ROWS ? grad(0, a.nsup) : glrm_for_sup_runs_in_arrival_order(h, step.arrivals, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), grad); // (rows read Y: complete)
   if (rc) return rc;
   launch_small(0, a, st);
   HIPCK(hipGetLastError());
-  if (eval_only) return GLRM_OK;
+  if (step.eval_only) return GLRM_OK;
   const TiledArgs full = a;
   const bool gather = env_int("GLRM_HIP_LANE_ROUNDS", 1) != 0 && sell_ok && h->lane_glist && la.bptr && h->side[side].lane_steps > 0 &&
                       full.nseg <= h->lane_gchunks * (int64_t)LANE_CC;
@@ -341,5 +340,5 @@ int glrm_run_lane(glrm_handle* h, int side, int loss, const TiledArgs& a_in, dou
     t.npass = 0;
     return launch_lane_loss<false, 1>(loss, t, csr_args(t), (t.nseg + 63) / 64, st);
   };
-  return glrm_run_rounds(h, full, min_stepsize, lists, trial, [&](const TiledArgs& d) { launch_small(1, d, st); });
+  return glrm_run_rounds(h, full, step.min_stepsize, lists, trial, [&](const TiledArgs& d) { launch_small(1, d, st); });
 }

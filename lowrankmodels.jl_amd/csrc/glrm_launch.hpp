@@ -24,10 +24,12 @@ template <class A, class V> auto set_vecreg(A& a, V v, int) -> decltype(void(a.v
 template <class A, class V> void set_vecreg(A&, V, long) {}
 } // namespace glrm_detail
 
-// The view, factors, step sizes, descriptors and counters of the row (X half-step) or column (Y half-step) side.  What a family does
-// differently (nullable trials, its own mode fields) follows at the call site.
+// The view, factors, step sizes, descriptors and counters of the side the request names (rows: X half-step, columns: Y half-step), and
+// the request's own min_stepsize / eval_only / fixed step.  What a family does differently (nullable trials, its own mode fields, the
+// loss variant) follows at the call site.
 template <class A>
-void glrm_fill_side(A& a, const glrm_handle* h, int side, double min_stepsize, int eval_only) {
+void glrm_fill_side(A& a, const glrm_handle* h, const glrm_step& step) {
+  const int side = step.side;
   const glrm_handle::Side& v = h->side[side];
   a.nseg = v.nseg;
   a.ptr = v.ptr;
@@ -42,20 +44,21 @@ void glrm_fill_side(A& a, const glrm_handle* h, int side, double min_stepsize, i
   a.reg_single = v.n_regs == 1;
   glrm_detail::set_vecreg(a, v.vecreg ? 1 : 0, 0);
   a.k = h->k;
-  a.min_stepsize = min_stepsize;
+  a.min_stepsize = step.min_stepsize;
   a.trials = v.trials;
   a.accepts = v.accepts;
   glrm_detail::set_obj(a, side == GLRM_ROWS ? nullptr : v.obj, 0);
   glrm_detail::set_n_other(a, h->side[side ^ 1].nglob, 0);
-  glrm_detail::set_eval_only(a, eval_only, 0);
-  glrm_detail::set_fixed_alpha(a, eval_only ? 0.0 : h->fixed_alpha, 0);
+  glrm_detail::set_eval_only(a, step.eval_only ? 1 : 0, 0);
+  glrm_detail::set_fixed_alpha(a, step.fixed() ? step.fixed_alpha : 0.0, 0);
 }
-template <class A> void glrm_fill_side(A&, const glrm_handle*, bool, double, int) = delete; // `true` would mean columns.  Guards this function only (it fills kernel arguments); the other `int side` functions convert silently
 
-// glrm_hip_step_x_range: the description restricted to local rows [rng_b, rng_e) (the caller returns when a.nseg <= 0)
+// glrm_hip_step_x_range: the description restricted to the request's local rows [row_begin, row_end) (the caller asks step.ranged() first
+// and returns when a.nseg <= 0)
 template <class A>
-void glrm_apply_row_range(A& a, int64_t rng_b, int64_t rng_e) {
-  a.nseg = rng_e - rng_b;
+void glrm_apply_row_range(A& a, const glrm_step& step) {
+  const int64_t rng_b = step.row_begin;
+  a.nseg = step.row_end - rng_b;
   a.ptr += rng_b; a.alpha += rng_b; a.own_offset += rng_b;
   if (!a.reg_single) a.regs += rng_b;
   if (a.trials) a.trials += rng_b;

@@ -140,23 +140,24 @@ static int run_split_cols(glrm_handle* h, const MultiArgs& a) {
   return GLRM_OK;
 }
 
-int glrm_run_multi(glrm_handle* h, int side, double min_stepsize, int eval_only) {
+int glrm_run_multi(glrm_handle* h, const glrm_step& step) {
+  const int side = step.side;
   MultiArgs a{};
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
+  glrm_fill_side(a, h, step);
   a.ystart = h->ystart;
   a.loss_single = h->n_losses == 1;
   a.kp = h->kp; a.dmax = h->dmax;
   a.lgP = 2;
   while ((1 << a.lgP) < h->k || (1 << a.lgP) < h->dmax) ++a.lgP;
-  a.mode = eval_only ? 1 : (h->fixed_alpha > 0.0 ? 2 : 0);
+  a.mode = step.eval_only ? 1 : (step.fixed() ? 2 : 0);
   if (a.mode != 0) a.trials = a.accepts = nullptr; // the counters belong to the line-search steps
   // the vectors of the side's descriptors (include/glrm_hip_regvec.h), indexed like the descriptors
   a.regvec = h->side[side].regvec;
   a.reglen = h->side[side].reglen;
   a.regvec_single = a.reg_single;
-  if (side == GLRM_ROWS && h->rng_e >= 0) {
-    glrm_apply_row_range(a, h->rng_b, h->rng_e);
-    if (a.regvec && !a.reg_single) { a.regvec += h->rng_b * h->k; a.reglen += h->rng_b; }
+  if (step.ranged()) {
+    glrm_apply_row_range(a, step);
+    if (a.regvec && !a.reg_single) { a.regvec += step.row_begin * h->k; a.reglen += step.row_begin; }
   }
   if (a.nseg <= 0) return GLRM_OK;
   if (side == GLRM_ROWS) {

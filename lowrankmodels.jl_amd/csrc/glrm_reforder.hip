@@ -345,15 +345,17 @@ int glrm_setup_reforder(glrm_handle* h) {
   return GLRM_OK;
 }
 
-int glrm_run_reforder(glrm_handle* h, int side, double min_stepsize, int eval_only) {
-  if (h->fixed_alpha > 0.0 && !eval_only)
+int glrm_run_reforder(glrm_handle* h, const glrm_step& step) {
+  const int side = step.side;
+  const bool eval_only = step.eval_only;
+  if (step.fixed())
     return fail(GLRM_ERR_UNSUPPORTED, "glrm_options.sum_order = 1 (reference order) restates the ProxGradParams half-steps only, not the fixed-step sweeps of SparseProxGradParams");
   if (side == GLRM_ROWS && eval_only) return fail(GLRM_ERR_INVALID, "no evaluation pass over the row view");
   RefArgs a{};
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
+  glrm_fill_side(a, h, step);
   a.n_losses = h->n_losses;
   if (eval_only) a.trials = nullptr;
-  if (side == GLRM_ROWS && h->rng_e >= 0) glrm_apply_row_range(a, h->rng_b, h->rng_e); // glrm_hip_step_x_range
+  if (step.ranged()) glrm_apply_row_range(a, step);
   if (a.nseg <= 0) return GLRM_OK;
   return glrm_dispatch<8, 16, 32, 64>(
       h->kp, [&](auto KP) { return launch_ref<decltype(KP)::value>(side, h->has_trig, a, h->stream); },

@@ -329,25 +329,25 @@ void glrm_launch_col_small(int kp, int stage, const TiledArgs& a, hipStream_t st
 
 // The tiled variants of run_sweep's launch.  Rows: one kernel.  Columns: pass 1 -> reduce -> rounds of
 // (trial pass, decide) until no column is still searching (the count is read back once per round).
-int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, double min_stepsize, int eval_only) {
+int glrm_run_tiled(glrm_handle* h, const glrm_step& step) {
+  const int side = step.side, loss = step.loss;
   TiledArgs a{};
-  glrm_fill_side(a, h, side, min_stepsize, eval_only);
-  a.loss_by_segment = loss_by_segment;
+  glrm_fill_side(a, h, step);
+  a.loss_by_segment = step.loss_by_segment;
   a.descid = side == GLRM_ROWS ? h->rowdescid : nullptr;
   a.udesc = h->udesc;
   a.n_udesc = h->n_udesc;
-  const bool range = side == GLRM_ROWS && h->rng_e >= 0; // glrm_hip_step_x_range
-  if (range) {
-    glrm_apply_row_range(a, h->rng_b, h->rng_e);
+  if (step.ranged()) {
+    glrm_apply_row_range(a, step);
     if (a.nseg <= 0) return GLRM_OK;
   }
   const glrm_act_lists lists = glrm_active_lists(h, side, a.nseg);
-  const bool row_rounds = side == GLRM_ROWS && (h->tile_rounds & 1) && !eval_only && a.fixed_alpha <= 0.0 && h->actlist;
+  const bool row_rounds = side == GLRM_ROWS && (h->tile_rounds & 1) && !step.eval_only && !step.fixed() && h->actlist;
   // lane-per-segment passes (glrm_lane.hpp): the ProxGradParams half-steps and the evaluation pass of the sides that run that family
-  const bool lane_here = h->side[side].lane && glrm_lane_loss_ok(h, loss) && a.fixed_alpha <= 0.0 && (side == GLRM_ROWS ? row_rounds : true);
-  a.segperm = range ? nullptr : h->side[side].perm; // a sub-range sweep keeps the natural order
+  const bool lane_here = h->side[side].lane && glrm_lane_loss_ok(h, loss) && !step.fixed() && (side == GLRM_ROWS ? row_rounds : true);
+  a.segperm = step.ranged() ? nullptr : h->side[side].perm; // a sub-range sweep keeps the natural order
   if (side == GLRM_ROWS && !row_rounds) return launch_tiled(h, loss, 0, a);
-  glrm_bind_pass_buffers(a, h, side, range ? h->rng_b : 0); // (rows: one super-tile, glrm_setup_tiled)
+  glrm_bind_pass_buffers(a, h, side, step.ranged() ? step.row_begin : 0); // (rows: one super-tile, glrm_setup_tiled)
   if (side == GLRM_COLS && h->blk_nlong_c > 0) { // the columns at or above long_from run on the gather sweep beside the passes (run_sweep, glrm_hip.hip)
     a.long_from = h->blk_long_from;
     a.npass = h->blk_nshort_c;
@@ -356,7 +356,7 @@ int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, doub
       return GLRM_OK;
     }
   }
-  if (lane_here) return glrm_run_lane(h, side, loss, a, min_stepsize, eval_only);
+  if (lane_here) return glrm_run_lane(h, step, a);
   int rc;
   HIPCK(hipMemsetAsync(h->nactive, 0, 4, h->stream));
   a.actlist_out = lists.list[0]; // the list the kernels of this stage append to
@@ -364,7 +364,7 @@ int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, doub
     if ((rc = launch_tiled(h, loss, 3, a))) return rc; // gradient pass + first trial; rejected rows are listed
   } else {
     // gradient pass: under glrm_hip_step_y_arrival in runs of super-tiles, each behind the blocks of X it reads (announced order)
-    rc = glrm_for_sup_runs_in_arrival_order(h, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), [&](int s0, int s1) {
+    rc = glrm_for_sup_runs_in_arrival_order(h, step.arrivals, a.nsup, (int64_t)a.tiles_per_sup * glrm_tile_rows(h->kp), [&](int s0, int s1) {
       TiledArgs r = a;
       r.sup0 = s0;
       r.nsup_launch = s1 - s0;
@@ -374,9 +374,9 @@ int glrm_run_tiled(glrm_handle* h, int side, int loss, int loss_by_segment, doub
     glrm_launch_col_small(h->kp, 0, a, h->stream);
   }
   HIPCK(hipGetLastError());
-  if (eval_only || a.fixed_alpha > 0.0) return GLRM_OK;
+  if (step.eval_only || step.fixed()) return GLRM_OK;
   return glrm_run_rounds(
-      h, a, min_stepsize, lists,
+      h, a, step.min_stepsize, lists,
       [&](int, unsigned int nact, int32_t* list) {
         TiledArgs t = a;
         // the trial pass: over the listed segments when they are the minority (a full grid keeps the length / kind order of segperm, which

@@ -223,14 +223,31 @@ def test_row_chunks_give_the_bits_of_the_whole_half_step(monkeypatch):
     assert np.array_equal(parts[0], whole[0]) and np.array_equal(parts[1], whole[1]) and parts[2] == whole[2]
 
 
-def test_reversed_arrival_order_gives_the_bits_of_step_y(monkeypatch):
-    """glrm_hip_step_y_arrival with the blocks announced last to first at rank 64: the super-tiles run from the last one down, each from
-    its own base."""
+def with_a_full_column(pa, j):
+    """pa with column j observing every row (the entries it lacked get the value 0.5)."""
+    I, J, V = np.repeat(np.arange(pa.m), np.diff(pa.rowptr)), pa.colidx.astype(np.int64), pa.rowvals
+    new = np.setdiff1d(np.arange(pa.m), I[J == j])
+    I, J, V = np.concatenate([I, new]), np.concatenate([J, np.full(len(new), j)]), np.concatenate([V, np.full(len(new), 0.5)])
+    o_r, o_c = np.lexsort((J, I)), np.lexsort((I, J))
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(I, minlength=pa.m))]).astype(np.int64)
+    colptr = np.concatenate([[0], np.cumsum(np.bincount(J, minlength=pa.n))]).astype(np.int64)
+    return _capi.ProblemArrays(pa.m, pa.n, pa.k, rowptr, np.ascontiguousarray(J[o_r], dtype=np.int32), np.ascontiguousarray(V[o_r]), colptr,
+                               np.ascontiguousarray(I[o_c], dtype=np.int32), np.ascontiguousarray(V[o_c]), pa.losses, pa.rx, pa.ry)
+
+
+def reversed_arrival(monkeypatch, long_column):
     import torch
     force_blocked(monkeypatch, "1", "3")
     pa, X0, Y0 = c4_recipe(6000, 600, 100, 64)
+    if long_column:
+        pa = with_a_full_column(pa, 17)
     api = _capi.hip_api()
     stream = torch.cuda.current_stream().cuda_stream
+    h = api.create(pa, stream=stream)
+    try:  # does a column leave the passes?  (every column from glrm_sum_order.long_from observations on)
+        assert (np.diff(pa.colptr).max() >= api.sum_order(h, 1).asdict()["long_from"]) == long_column
+    finally:
+        api.destroy(h)
 
     def arrival(h):
         blocks, keep = [], []
@@ -244,3 +261,38 @@ def test_reversed_arrival_order_gives_the_bits_of_step_y(monkeypatch):
     plain = half_steps(api, pa, X0, Y0, lambda h: api.step_x(h, 0.01), lambda h: api.step_y(h, 0.01), stream=stream)
     late = half_steps(api, pa, X0, Y0, lambda h: api.step_x(h, 0.01), arrival, stream=stream)
     assert np.array_equal(late[0], plain[0]) and np.array_equal(late[1], plain[1]) and late[2] == plain[2]
+
+
+def test_reversed_arrival_order_gives_the_bits_of_step_y(monkeypatch):
+    """glrm_hip_step_y_arrival with the blocks announced last to first at rank 64: the super-tiles run from the last one down, each from
+    its own base."""
+    reversed_arrival(monkeypatch, False)
+
+
+def test_reversed_arrival_order_with_a_diverted_long_column(monkeypatch):
+    """The same with one column that observes every row: it leaves the passes for the gather sweep on the side stream (no column of the
+    recipe itself does), which reads all of X and so stands behind every announced block, beside the passes."""
+    reversed_arrival(monkeypatch, True)
+
+
+def test_sparse_solver_with_a_diverted_long_column(monkeypatch):
+    """fit!(::SparseProxGradParams) on the same problem: the fixed-step form of the passes and, beside them, of the gather sweep that
+    takes the long column, against the oracle (1e-5 relative, the bound of the sparse-solver tests of the other families)."""
+    force_blocked(monkeypatch, "1", "3")
+    pa, X0, Y0 = c4_recipe(6000, 600, 100, 64)
+    pa = with_a_full_column(pa, 17)
+    sp = L.SparseProxGradParams(max_iter=12)
+    outs = []
+    for api in (O.oracle_api(), _capi.hip_api()):
+        h = api.create(pa)
+        try:
+            if len(outs) == 1:  # the engine
+                assert api.kernel_stats(h)["tiled"] & BLOCKED == BLOCKED
+                assert np.diff(pa.colptr).max() >= api.sum_order(h, 1).asdict()["long_from"]
+            X, Y = np.array(X0, order="F"), np.array(Y0, order="F")
+            obj, _ = api.fit_sparse(h, sp, X, Y)
+        finally:
+            api.destroy(h)
+        outs.append((np.array(obj), X, Y))
+    assert len(outs[0][0]) == len(outs[1][0]) and cases.rel_err(outs[1][0], outs[0][0]) < 1e-5
+    assert cases.fro_err(outs[1][1], outs[0][1]) < 1e-5 and cases.fro_err(outs[1][2], outs[0][2]) < 1e-5

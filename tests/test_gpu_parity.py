@@ -415,6 +415,48 @@ def test_step_x_range_chunks_equal_full_sweep(mode):
         api.destroy(h)
         res.append((X, Y, st["trials_x"], st["accepts_x"]))
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1]) and res[0][2:] == res[1][2:]
+    if mode == 2:  # rows on the lane-per-segment passes with a slot permutation (lengths more than 25 % apart): the chunks run the CSR form
+        lens = np.diff(pa.rowptr)
+        assert st["tiled"] & 256 and lens.max() * 4 > lens.min() * 5
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_a_request_leaves_nothing_behind_on_the_handle(mode):
+    """A row range, a fixed step, an arrival list and two refused calls are requests of ONE call each: three plain iterations afterwards
+    give the factors and the trial / accept totals of a handle that never saw any of them."""
+    rng = np.random.default_rng(190 + mode)
+    pa, X0, Y0 = random_problem(rng, 700, 150, 32, 0.3, rx=L.NonNegConstraint())
+    api = hip()
+    res = []
+    for used in (False, True):
+        h = api.create(pa, tiled=mode)
+        try:
+            api.set_factors(h, X0, Y0)
+            api.reset_stepsizes(h, 1.0)
+            if used:
+                api.step_x_range(h, 0, 100, 0.01)
+                api.gradstep_x(h, 0.5)
+                api.gradstep_y(h, 0.5)
+                api.set_factors(h, X0, Y0)
+                api.reset_stepsizes(h, 1.0)
+                api.step_y_arrival(h, 0.01, [(0, 350, None), (350, 700, None)])
+                for refused in (lambda: api.step_x_range(h, 5, 3, 0.01), lambda: api.gradstep_x(h, 0.0)):  # argument refusals: nothing is launched
+                    with pytest.raises(_capi.GLRMError) as ei:
+                        refused()
+                    assert ei.value.code == _capi.ERR_INVALID
+                api.set_factors(h, X0, Y0)
+                api.reset_stepsizes(h, 1.0)
+                api.kernel_stats(h, reset=True)
+            for _ in range(3):
+                api.step_x(h, 0.01)
+                api.step_y(h, 0.01)
+            X, Y = np.zeros_like(X0), np.zeros_like(Y0)
+            api.get_factors(h, X, Y)
+            st = api.kernel_stats(h)
+        finally:
+            api.destroy(h)
+        res.append((X, Y, [st[key] for key in ("trials_x", "trials_y", "accepts_x", "accepts_y")]))
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1]) and res[0][2] == res[1][2]
 
 
 def test_set_regularizers_keeps_the_handle_and_matches_a_fresh_one():
