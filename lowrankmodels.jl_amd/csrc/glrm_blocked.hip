@@ -52,7 +52,7 @@ static __global__ void __launch_bounds__(256) suppos_kernel(const int64_t* ptr, 
 static int build_suppos(glrm_handle* h, int side) {
   const glrm_handle::Side& v = h->side[side];
   glrm_handle::PassBuffers& b = h->side[side].pass;
-  const int mode = env_int("GLRM_HIP_BLOCKED_SUPPOS", 1);
+  const int mode = knob(Knob::BLOCKED_SUPPOS);
   const int64_t nseg = v.nseg, nnz = v.nnz, cells = nseg * b.nsup;
   const bool fits = (double)cells * 4.0 * 16.0 <= 12.0 * (double)nnz;
   const bool build = mode != 0 && cells > 0 && (fits || mode >= 2);
@@ -66,7 +66,7 @@ static int build_suppos(glrm_handle* h, int side) {
     HIPCK(hipStreamSynchronize(h->stream));
     if (too_long) return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: a %s holds 2^31 observations or more", side == GLRM_ROWS ? "row" : "column");
   }
-  if (env_int("GLRM_HIP_BLOCKED_TRACE", 0))
+  if (knob(Knob::BLOCKED_TRACE))
     fprintf(stderr, "[glrm blocked] %s view: %d super-tiles x %lld segments, start table %s (%.1f MB, lists %.1f MB)\n", side == GLRM_ROWS ? "row" : "column", b.nsup,
             (long long)nseg, build ? "built" : (mode == 0 ? "off: the passes search" : "over 1/16 of the lists: the passes search"), (double)cells * 4e-6, 12e-6 * (double)nnz);
   return GLRM_OK;
@@ -74,7 +74,7 @@ static int build_suppos(glrm_handle* h, int side) {
 
 int glrm_setup_blocked(glrm_handle* h) {
   for (glrm_handle::Side& v : h->side) v.blocked = 0;
-  int want = env_int("GLRM_HIP_BLOCKED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
+  int want = knob_or(Knob::BLOCKED, h->tiled_opt == 1 ? 0 : -1); // -1 auto, else bit0 rows, bit1 columns (glrm_options.tiled = 1: gather sweeps only)
   const bool f32 = h->storage == GLRM_STORAGE_F32;
   if (f32) {
     // A float handle takes the family only where GLRM_HIP_BLOCKED asks for it (tiled = 1 handles included: the variable outranks the option
@@ -113,7 +113,7 @@ int glrm_setup_blocked(glrm_handle* h) {
     const int64_t nopp = h->side[side ^ 1].nglob;
     const int64_t ntiles = (nopp + T - 1) / T;
     int64_t t = ((int64_t)128 * 1024 * 1024) / ((int64_t)T * h->kp * 8); // ~128 MB of the opposing factor per super-tile
-    t = env_int("GLRM_HIP_BLOCKED_TPS", (int)(t < 1 ? 1 : t));
+    t = knob_or(Knob::BLOCKED_TPS, (int)(t < 1 ? 1 : t));
     // the passes address an observation's vector by a 32-bit byte offset from the first row of its super-tile (tiled_pass, L2 = true)
     if ((double)std::min<int64_t>(t * T, nopp) * h->kp * (f32 ? 4 : 8) >= 4294967296.0) // (the geometry above is the 8-byte one in both storages: one problem, one order)
       return fail(GLRM_ERR_UNSUPPORTED, "phase-aligned passes: GLRM_HIP_BLOCKED_TPS=%lld makes a super-tile of 4 GiB or more of the opposing factor", (long long)t);
@@ -140,8 +140,7 @@ int glrm_setup_blocked(glrm_handle* h) {
     // observations, longest column 1.37e6 against a mean of 9 950; profiles/r05_c4_zipf_*): Y half-step 2 622 ms before, 207 ms with
     // long_from = 16 x mean, 168 / 154 / 151 ms with 8 / 4 / 2 x mean; the uniform recipe (no column reaches 2 x mean) is untouched.
     const int64_t mean_len = h->sig.nnz_cols / (h->n > 0 ? h->n : 1);
-    h->blk_long_from = env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0) > 0 ? env_int("GLRM_HIP_BLOCKED_LONG_FROM", 0)
-                                                                     : std::max<int64_t>(4096, 2 * mean_len);
+    h->blk_long_from = (int64_t)knob_positive(Knob::BLOCKED_LONG_FROM, (double)std::max<int64_t>(4096, 2 * mean_len));
     if (h->side[GLRM_COLS].nseg > 0 && h->blk_long_from > 0) {
       std::vector<int64_t> ptr;
       std::vector<int32_t> shortl, longl;

@@ -52,7 +52,7 @@ static int64_t slice_capacity(K kernel, int device, int spb) {
   // 25 / 33 / 40 / 50 / 60 / 75 / 100 %: 139.7 / 137.0 / 135.6 / 131.0 / 133.0 / 136.9 / 144.4 (profiles/r03_c4_blocked_knobs.txt).
   // With the gradient pass at 4 waves per SIMD (16 384 columns per launch in both passes) 40 / 50 / 60 / 75 %: 116.1 / 110.8 / 117.2 /
   // 119.7 ms (profiles/r13_c4_ab.txt): half stays.  Changes no sum.
-  const int pct = env_int("GLRM_HIP_BLOCKED_FILL", 50);
+  const int pct = knob(Knob::BLOCKED_FILL);
   return std::max<int64_t>(spb, cap * pct / 100 / spb * spb);
 }
 
@@ -68,13 +68,13 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side, glrm_arriv
   const int64_t cap = cap_slot;
   // phase gate in rows of the opposing factor (tiled_pass, L2 = true): read at every pass, so that one handle can be timed under several
   // settings.  Changes no sum.
-  a.gate = std::max(0, env_int("GLRM_HIP_BLOCKED_GATE", sizeof(ST) == 4 ? BLOCKED_GATE_DEFAULT_F32 : BLOCKED_GATE_DEFAULT));
+  a.gate = std::max(0, knob_or(Knob::BLOCKED_GATE, sizeof(ST) == 4 ? BLOCKED_GATE_DEFAULT_F32 : BLOCKED_GATE_DEFAULT));
   const int64_t nseg = a.npass > 0 ? a.npass : a.nseg;
   // equal slices: ceil(nseg / cap) launches per super-tile, all of the same size (a last slice of a few percent of the others is a launch
   // that cannot fill the chip)
   const int64_t nslices = (nseg + cap - 1) / cap;
   const int64_t per = nslices > 0 ? ((nseg + nslices - 1) / nslices + SPB - 1) / SPB * SPB : cap;
-  if (!env_int("GLRM_HIP_BLOCKED_SUPPOS", 1)) a.suppos = nullptr;
+  if (!knob(Knob::BLOCKED_SUPPOS)) a.suppos = nullptr; // (the per-pass drop: same bits)
   // glrm_hip_step_y_arrival: the gradient pass of the column view walks the super-tiles in the order their rows of X arrive, each behind
   // the events of the blocks it touches (arr and sup_order, from glrm_run_blocked; arr == nullptr: X is complete); the partial sums are
   // per (segment, super-tile) and col_reduce adds them in super-tile order, so the launch order changes no bit
@@ -96,7 +96,7 @@ static int launch_blocked_inst(glrm_handle* h, TiledArgs a, int side, glrm_arriv
   std::vector<int> pend;
   if (ordered) pend = sup_order;
   else for (int si = 0; si < a.nsup; ++si) pend.push_back(si);
-  if (ordered && !h->arrival_static && env_int("GLRM_HIP_ARRIVAL_DYNAMIC", 1)) {
+  if (ordered && !h->arrival_static && knob(Knob::ARRIVAL_DYNAMIC)) {
     // TRUE arrival order.  The fixed order above is the order blocks arrive in when every peer keeps pace; behind a lagging peer the
     // in-order stream would stand in front of its block while super-tiles further down the list are ready.  So the host enqueues a
     // super-tile only once the events of ALL its blocks have fired (hipEventQuery), the ready ones in list order, and polls for the

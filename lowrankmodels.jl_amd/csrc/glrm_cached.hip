@@ -227,15 +227,15 @@ int launch_inst(const CachedArgs& a, hipStream_t st) {
 // Does the WHOLE problem run its short rows on the cached sweep (glrm_handle::cached_want)?  Auto (GLRM_HIP_CACHED unset): the rows
 // are not LDS-tiled, the opposing factor is beyond the sizes where the plain gathers already do well (> 32 MB) and the row view
 // holds >= 1e8 observations -- all read from glrm_signature and (m, n, k), never from the shard.  WHICH rows it takes is a
-// function of the row's own length (glrm_cached_maxlen): registers hold up to 13 trips of the lane layout (104 observations at
+// function of the row's own length (glrm_handle::cached_maxlen): registers hold up to 13 trips of the lane layout (104 observations at
 // k = 64, 208 at k <= 32); the LDS variant (GLRM_HIP_CACHED_REGS=0) up to its buffer.  Longer rows run the gather sweep with the
 // waves their length asks for.  A row is therefore always summed in the same order, whatever shard holds it.
-// A float handle (glrm_options.storage = 1): the register variant only (glrm_cached_variant), the same rows, and the auto rule is the
+// A float handle (glrm_options.storage = 1): the register variant only (glrm_handle::cached_variant), the same rows, and the auto rule is the
 // fp64 one on the same (n, kp, nnz_rows) -- the factor counted in 8-byte elements -- so that one problem runs its rows on the same
 // family in both storages.  GLRM_CACHED_F32_AUTO says whether the measurement adopted it.
 int glrm_setup_cached(glrm_handle* h) {
   h->cached_row = h->cached_want = 0;
-  const int want = env_int("GLRM_HIP_CACHED", h->tiled_opt == 1 ? 0 : -1); // -1 auto, 0 off, 1 wherever the rows fit
+  const int want = knob_or(Knob::CACHED, h->tiled_opt == 1 ? 0 : -1); // -1 auto, 0 off, 1 wherever the rows fit
   if (want == 0 || h->side[GLRM_ROWS].tiled || h->sig.nnz_rows <= 0) return GLRM_OK;
   if (!((h->G == 4 || h->G == 8) && h->R == 8)) return GLRM_OK;
   if (want < 0) {
@@ -244,25 +244,20 @@ int glrm_setup_cached(glrm_handle* h) {
     if (opp_bytes <= 32.0 * 1024 * 1024 || (double)h->sig.nnz_rows < 1e8) return GLRM_OK;
   }
   h->cached_want = 1;
-  h->cached_row = glrm_cached_variant(h);
+  // the variant: 2 registers, 1 LDS (GLRM_HIP_CACHED_REGS=0; fp64 only -- the LDS variant has no float form); the waves that share a row of
+  // the register variant: two (GLRM_HIP_CACHED_WAVES = 1 | 4 are experiment switches of the fp64 kernels)
+  const bool f32 = h->storage == GLRM_STORAGE_F32;
+  h->cached_row = h->cached_variant = (f32 || knob(Knob::CACHED_REGS)) ? 2 : 1;
+  h->cached_waves = h->cached_variant != 2 ? 1 : f32 ? 2 : knob(Knob::CACHED_WAVES);
+  // longest row the sweep takes
+  if (h->cached_variant == 2) {
+    h->cached_maxlen = glrm_cached_reg_maxlen(h->G);
+  } else {
+    const int vpi = 64 / (h->kp * 8 / 16);
+    const int64_t budget = want > 0 ? 160 * 1024 : 53 * 1024; // auto: three waves per CU
+    h->cached_maxlen = budget / (h->kp * 8 + 12) / vpi * vpi;
+  }
   return GLRM_OK;
-}
-
-// the variant a handle on the family runs: 2 registers, 1 LDS (GLRM_HIP_CACHED_REGS=0; fp64 only -- the LDS variant has no float form)
-int glrm_cached_variant(const glrm_handle* h) {
-  if (h->storage == GLRM_STORAGE_F32) return 2;
-  return env_int("GLRM_HIP_CACHED_REGS", 1) ? 2 : 1;
-}
-
-// waves that share a row of the register variant: two; GLRM_HIP_CACHED_WAVES = 1 | 4 are experiment switches of the fp64 kernels
-int glrm_cached_waves(const glrm_handle* h) { return h->storage == GLRM_STORAGE_F32 ? 2 : env_int("GLRM_HIP_CACHED_WAVES", 2); }
-
-// longest row the cached sweep takes
-int64_t glrm_cached_maxlen(const glrm_handle* h, int variant) {
-  if (variant == 2) return glrm_cached_reg_maxlen(h->G);
-  const int vpi = 64 / (h->kp * 8 / 16);
-  const int64_t budget = env_int("GLRM_HIP_CACHED", -1) > 0 ? 160 * 1024 : 53 * 1024; // auto: three waves per CU
-  return budget / (h->kp * 8 + 12) / vpi * vpi;
 }
 
 // the launch parameter of the cached kernels for a longest row of `maxlen` observations

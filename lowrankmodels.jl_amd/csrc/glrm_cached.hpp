@@ -502,8 +502,8 @@ int launch_reg_inst(const CachedArgs& a, hipStream_t st, glrm_handle* h) { // a.
   // longest row of the launch (MAXT only adds empty trips).  GLRM_HIP_CACHED_WAVES = 1 | 4 are the experiment switches (fp64 only:
   // the float form exists for two waves).
   constexpr bool F32 = sizeof(ST) == 4;
-  const int waves = F32 ? 2 : env_int("GLRM_HIP_CACHED_WAVES", 2);
-  if (waves == 2 && env_int("GLRM_HIP_CACHED_PERSIST", 1)) { // the persistent form of the two-wave kernel (same bits)
+  const int waves = h->cached_waves; // (what set-up read: the wave count fixes the order of the sums)
+  if (waves == 2 && knob(Knob::CACHED_PERSIST)) { // the persistent form of the two-wave kernel (same bits)
     // resident grid per handle (its device's CU count, its loss variant's occupancy, the fill percentage at its first sweep); the float
     // kernels have an occupancy of their own, hence slots of their own
     const bool small = (a.cap + 1) / 2 <= 4;

@@ -62,6 +62,7 @@ inline int fail(int code, const char* fmt, ...) {
   } while (0)
 
 #include "glrm_devmem.hpp"
+#include "glrm_knobs.hpp"
 
 // which side of the factorization: glrm_handle::side[] and every `int side` argument are indexed by it; the opposing side is side ^ 1
 enum { GLRM_ROWS = 0, GLRM_COLS = 1 }; // rows = row view, X half-step; columns = column view, Y half-step
@@ -113,9 +114,11 @@ struct glrm_handle {
     double *factor = nullptr, *own_factor = nullptr, *obj = nullptr, *own_obj = nullptr;
     // family state
     int tiled = 0;                    // 0 = gather sweep, 1 = LDS-tiled
+    bool grouped = false;             // LDS-tiled rows: the private copy was regrouped by loss kind inside the tile windows (set where the copy is made)
     int blocked = 0;                  // phase-aligned gather passes (glrm_blocked.hip) instead of the one-kernel gather sweep
     // lane-per-segment LDS-tiled passes (glrm_lane.hpp): family flag and the SELL layout of the view
     int lane = 0;
+    bool lane_want = false, lane_compact = false; // glrm_lane_decide: the whole problem admits the family on this side / its stream takes the compact form
     int64_t* lane_bptr = nullptr; int32_t* lane_off = nullptr; double* lane_val = nullptr;
     int64_t lane_nwb = 0, lane_steps = 0; int lane_ntiles = 0;
     uint16_t* lane_off16 = nullptr; int64_t* lane_vptr = nullptr; int32_t* lane_sval = nullptr; // the compact form of the stream (glrm_lane.hpp: LaneArgs::off16 / vptr) of the sides that run it
@@ -164,6 +167,10 @@ struct glrm_handle {
   // rows only: the cached gather row sweep
   int cached_row = 0, cached_cap = 0; // cached gather row sweep (glrm_cached.hip): 0 off, 1 LDS, 2 registers; trips / vectors a row may have
   int cached_want = 0;                // the whole problem runs its short rows on the cached sweep (decided from glrm_signature, never from the shard)
+  // what glrm_setup_cached decided for the whole problem (they hold on a shard whose cached_row fell to 0, too): the variant (2 registers --
+  // always, for float storage -- or 1 LDS), the waves that share a row of the register variant, the longest row the sweep takes
+  int cached_variant = 0, cached_waves = 2;
+  int64_t cached_maxlen = -1;
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]
@@ -248,11 +255,6 @@ inline glrm_family glrm_side_family(const glrm_handle* h, int side, bool eval_on
   do { if (!(h)->finalized) return fail(GLRM_ERR_INVALID, "the handle was created with GLRM_PROBLEM_DEFER_SETUP: call glrm_hip_finalize first"); } while (0)
 inline bool glrm_single_shard(const glrm_handle* h) { return h->side[GLRM_ROWS].begin == 0 && h->side[GLRM_ROWS].end == h->m && h->side[GLRM_COLS].begin == 0 && h->side[GLRM_COLS].end == h->n; }
 
-inline int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-
 namespace glrm { struct TiledArgs; }
 
 
@@ -271,7 +273,7 @@ int glrm_run_tiled(glrm_handle* h, const glrm_step& step);
 
 // lane-per-segment LDS-tiled passes (glrm_lane.hip): setup decides lane[] from the whole problem's signature and builds the SELL layouts;
 // run takes the TiledArgs glrm_run_tiled prepared (glrm_tiled.hpp)
-bool glrm_lane_wants(const glrm_handle* h, int side);   // the whole problem's shape / losses / options admit the family on that side (given that the side runs the LDS tiles)
+void glrm_lane_decide(glrm_handle* h);                 // set-up, once: Side::lane_want / lane_compact from the whole problem's shape / losses / options and the knobs
 int glrm_setup_lane(glrm_handle* h);
 bool glrm_lane_loss_ok(const glrm_handle* h, int loss);
 bool glrm_lane_few_descriptors(const glrm_handle* h);
@@ -331,9 +333,6 @@ int glrm_rows_from_cols(glrm_handle* h);
 
 // cached gather row sweep (glrm_cached.hip)
 int glrm_setup_cached(glrm_handle* h);                 // finalize: cached_want / cached_row from h->sig
-int64_t glrm_cached_maxlen(const glrm_handle* h, int variant); // longest row the cached sweep takes: a function of k and the variant (a cached_row value)
-int glrm_cached_variant(const glrm_handle* h);         // cached_row of a handle on the family: 2 registers (always, for float storage), 1 LDS
-int glrm_cached_waves(const glrm_handle* h);           // waves per row of the register variant
 // float storage, GLRM_HIP_CACHED unset: 1 = the fp64 auto rule applies, 0 = the family stays behind GLRM_HIP_CACHED=1
 constexpr int GLRM_CACHED_F32_AUTO = 0;
 // float storage, GLRM_HIP_BLOCKED unset: 1 = the fp64 auto rule of the phase-aligned passes applies, 0 = the family stays behind
@@ -347,6 +346,7 @@ int glrm_run_dense(glrm_handle* h, const glrm_step& step);
 
 // general sweeps (glrm_multi.hip)
 int glrm_setup_multi(glrm_handle* h, const glrm_problem* p);
+int glrm_setup_multi_split(glrm_handle* h);            // finalize (or the set_regularizers call that moves a handle here): split long columns or not
 int glrm_run_multi(glrm_handle* h, const glrm_step& step);
 int glrm_run_multi_penalty(glrm_handle* h, int side);
 

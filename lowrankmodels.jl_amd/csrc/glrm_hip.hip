@@ -367,7 +367,7 @@ static int build_class_plan(glrm_handle* h, int side) {
   int64_t* ncls = v.ncls;
   const int forced = forced_class(side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col);
   const bool cached = side == GLRM_ROWS && h->cached_row != 0; // only rows have a cached sweep
-  const int64_t cmax = cached ? glrm_cached_maxlen(h, h->cached_row) : -1;
+  const int64_t cmax = cached ? h->cached_maxlen : -1;
   unsigned long long st[6];
   int rc = view_stats(h, side, forced, cmax, st);
   if (rc) return rc;
@@ -507,7 +507,7 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     for (int s = 0; s < 2; ++s) { h->side[s].tiled = h->side[s].blocked = 0; h->side[s].waves = 1; }
     h->cached_row = h->cached_want = 0;
   } else if (h->storage == GLRM_STORAGE_F32) {
-    // float storage: gather sweeps on both views; rows of at most glrm_cached_maxlen observations on the cached row sweep where
+    // float storage: gather sweeps on both views; rows of at most cached_maxlen observations on the cached row sweep where
     // glrm_setup_cached says so, otherwise on the one-wave sweep; the phase-aligned passes where GLRM_HIP_BLOCKED asks for them
     // (glrm_setup_blocked; the other families have no float form)
     for (int s = 0; s < 2; ++s) h->side[s].tiled = h->side[s].blocked = 0;
@@ -517,6 +517,7 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
       if (!h->side[s].blocked && (rc = build_class_plan(h, s))) return rc;
   } else if (h->multi || h->dense) {
     for (int s = 0; s < 2; ++s) h->side[s].waves = opt_waves[s] ? opt_waves[s] : (s == GLRM_ROWS ? 1 : 4);
+    if (h->multi && (rc = glrm_setup_multi_split(h))) return rc;
   } else {
     // a failure from here on leaves re-ordered private views and partial buffers behind: the handle can then only be destroyed
     h->finalize_failed = true;
@@ -715,8 +716,12 @@ int glrm_check_regularizers(const glrm_handle* h, const glrm_reg* rx, int64_t n_
 
 extern "C" int glrm_hip_set_regularizers(glrm_handle* h, const glrm_reg* rx, int64_t n_rx, const glrm_reg* ry, int64_t n_ry) {
   if (const int rc = glrm_check_regularizers(h, rx, n_rx, ry, n_ry)) return rc;
-  if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry)) h->multi = true; // checked above: this handle can run the general sweeps
   DeviceScope dg(h->device);
+  if (!h->multi && any_wrapped(rx, n_rx, ry, n_ry)) { // checked above: this handle can run the general sweeps
+    if (h->finalized && !h->sum_order_opt) // (the part of set-up a handle that arrives late still needs; nothing of the handle has changed yet)
+      if (const int rc = glrm_setup_multi_split(h)) return rc;
+    h->multi = true;
+  }
   glrm_handle::Side &rows = h->side[GLRM_ROWS], &cols = h->side[GLRM_COLS];
   rows.regs_h.assign(rx, rx + n_rx);
   cols.regs_h.assign(ry, ry + n_ry);
@@ -771,7 +776,7 @@ struct RoctxApi {
   int (*push)(const char*) = nullptr;
   int (*pop)() = nullptr;
   RoctxApi() {
-    if (!env_int("GLRM_HIP_ROCTX", 1)) return;
+    if (!knob(Knob::ROCTX)) return;
     void* lib = dlopen("libroctx64.so", RTLD_LAZY | RTLD_LOCAL);
     if (!lib) lib = dlopen("libroctx64.so.4", RTLD_LAZY | RTLD_LOCAL);
     if (!lib) return;
@@ -1024,7 +1029,7 @@ extern "C" int glrm_hip_step_y_arrival(glrm_handle* h, double min_stepsize, cons
   int rc = GLRM_OK;
   // the pass families of the column view can start on a part of X (the phase-aligned passes super-tile by super-tile in true arrival order,
   // the LDS-tiled / lane passes in runs of super-tiles in the announced order: round 6); everything else needs all of it
-  const bool by_super_tile = col_passes(h) && env_int("GLRM_HIP_ARRIVAL", 1);
+  const bool by_super_tile = col_passes(h) && knob(Knob::ARRIVAL);
   if (!by_super_tile) rc = glrm_arrival_wait(h, arr, 0, h->m);
   if (!rc) rc = run_sweep(h, step);
   if (!rc) rc = glrm_arrival_wait(h, arr, 0, h->m); // (a shard without columns launches nothing: later work on the stream still follows the arrivals)
@@ -1153,8 +1158,7 @@ extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_or
     o.rotate = (side == GLRM_COLS && !quad && (h->tG == 4 || h->tG == 8) && h->tR == 8) ? 1 : 0;
     // a private copy in another order: lists the engine tile-sorted, rows regrouped by loss kind inside the tile windows
     const bool sorted_here = side == GLRM_ROWS ? h->sig_local.rows_unordered != 0 : h->sig_local.cols_unordered != 0;
-    const bool grouped = side == GLRM_ROWS && h->n_losses > 1 && h->side[GLRM_ROWS].nnz > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !h->side[GLRM_ROWS].lane; // glrm_tiled.hpp: group_rows_by_kind_kernel (lane rows keep the caller's order)
-    o.private_order = sorted_here ? 1 : grouped ? 2 : 0; // (2: stable grouping by ascending loss kind inside every window -- the oracle restates it)
+    o.private_order = sorted_here ? 1 : h->side[side].grouped ? 2 : 0; // (2: stable grouping by ascending loss kind inside every window, glrm_tiled.hpp: group_rows_by_kind_kernel -- the oracle restates it)
     if (h->side[side].lane) { // lane-per-segment passes (glrm_lane.hpp): two fma chains over the even / odd chunks = the two-lane layout, rotated walk
       o.lanes = 2; o.comps = h->kp / 2;
       o.batch = 2;
@@ -1174,9 +1178,8 @@ extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_or
     const int forced = side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col;
     o.waves = (forced == 1 || forced == 4 || forced == 8) ? forced : 0;
     if (side == GLRM_ROWS && h->cached_want) { // which rows the cached sweep takes is a function of the row's own length
-      const int variant = h->cached_row ? h->cached_row : glrm_cached_variant(h); // 0 on a shard that holds no such row: the variant is still the whole problem's
-      o.cached_maxlen = glrm_cached_maxlen(h, variant);
-      o.cached_waves = variant == 2 ? glrm_cached_waves(h) : 1;
+      o.cached_maxlen = h->cached_maxlen; // (the whole problem's, also on a shard that holds no such row)
+      o.cached_waves = h->cached_waves;
     }
     // four observations per trip with one loss evaluation per lane (sweep_pass: SCATTER): G == 4 and not the uniform QuadLoss kernel;
     // the per-segment variant only on one-wave segments (launch_sweep_loss)
@@ -1226,7 +1229,7 @@ extern "C" int glrm_hip_objective(glrm_handle* h, const double* X, const double*
 // the handle's private stream (the legacy default stream cannot be captured), no per-launch event timing.
 static bool graph_eligible(const glrm_handle* h) {
   return h->own_stream && !h->profile && glrm_side_family(h, GLRM_ROWS, false) == GLRM_FAM_GATHER && glrm_side_family(h, GLRM_COLS, false) == GLRM_FAM_GATHER &&
-         !h->cached_row && env_int("GLRM_HIP_GRAPH", 1) != 0;
+         !h->cached_row && knob(Knob::GRAPH) != 0;
 }
 
 static int build_iteration_graph(glrm_handle* h, const glrm_params* prm) {

@@ -102,20 +102,32 @@ bool glrm_lane_few_descriptors(const glrm_handle* h) {
 }
 
 // what does not depend on the buffers: padded rank, losses, view size -- all of the WHOLE problem
-bool glrm_lane_wants(const glrm_handle* h, int side) {
-  const int want = env_int("GLRM_HIP_LANE", 3); // bit0 rows, bit1 columns
+static bool lane_wants(const glrm_handle* h, int side, int cmode) {
+  const int want = knob(Knob::LANE); // bit0 rows, bit1 columns
   if (!((want >> side) & 1) || h->kp != 32 || h->multi || h->dense || h->sum_order_opt) return false;
   // a loss per column: the row view meets a descriptor per observation -- through one-byte ids, i.e. at most 256 distinct descriptors.
   // Default since session r6_33 (GLRM_HIP_LANE_PER_OBS=0 keeps such rows on the four-lane kernels): with the trial rounds read out of the
   // SELL layout (glrm_run_lane) the C5 recipe's X half-step is 42.5 against 46.6 ms at 1M rows and 194 against 215 ms at its stated size.
   // (Session r6_19/20, rounds on the CSR form: 64.4 against 45.8 ms -- opt-in then.)
-  if (side == GLRM_ROWS && h->n_losses > 1 && (!env_int("GLRM_HIP_UDESC", 1) || !env_int("GLRM_HIP_LANE_PER_OBS", 1) || !glrm_lane_few_descriptors(h))) return false;
+  if (side == GLRM_ROWS && h->n_losses > 1 && (!knob(Knob::UDESC) || !knob(Knob::LANE_PER_OBS) || !glrm_lane_few_descriptors(h))) return false;
   // the SELL copy is 12 B x its padding per observation on top of the lists: a memory policy per view (rows: the copy REPLACES the kind-grouped
   // private row view of such models, and rows pad little; columns pad x 1.5-1.8).  C5 at its stated size: 5e9 observations per view
   // (columns beyond 2e9 observations: the COMPACT form of the stream -- 2-byte offsets, unpadded values, 11.5 instead of 21 B per observation at
   // x 1.76 padding; GLRM_HIP_LANE_COMPACT = 0 never, 1 every side it serves, 2 (default) views beyond 2e9 observations)
-  const int64_t max_nnz = (int64_t)env_int(side == GLRM_ROWS ? "GLRM_HIP_LANE_MAX_NNZ_ROWS_M" : "GLRM_HIP_LANE_MAX_NNZ_M", side == GLRM_ROWS || env_int("GLRM_HIP_LANE_COMPACT", 2) ? 6000 : 2000) * 1000000ll;
+  const int64_t max_nnz = (int64_t)(side == GLRM_ROWS ? knob(Knob::LANE_MAX_NNZ_ROWS_M) : knob_or(Knob::LANE_MAX_NNZ_M, cmode ? 6000 : 2000)) * 1000000ll;
   return (side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols) <= max_nnz;
+}
+
+// Set-up, once, before anything asks (glrm_setup_tiled): does the whole problem admit the family on a side (given that the side runs the LDS
+// tiles), and does the side's stream take the compact form?  Functions of the whole problem (view size, losses, options) and the knobs.
+void glrm_lane_decide(glrm_handle* h) {
+  const int cmode = knob(Knob::LANE_COMPACT);
+  for (int side = 0; side < 2; ++side) {
+    glrm_handle::Side& v = h->side[side];
+    v.lane_want = lane_wants(h, side, cmode);
+    v.lane_compact = !(side == GLRM_ROWS && h->n_losses > 1) && (cmode == 1 || (cmode == 2 && (side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols) > 2000000000ll)) &&
+                     64 * (side == GLRM_ROWS ? h->sig.max_row_len : h->sig.max_col_len) < ((int64_t)1 << 31); // (a wave block's values are counted in 31 bits: LaneArgs::sval)
+  }
 }
 
 // finalize, after glrm_setup_tiled has chosen the LDS tiles and built the slot permutations: decide the family per side and build its SELL layout
@@ -126,7 +138,7 @@ int glrm_setup_lane(glrm_handle* h) {
   hipStream_t st = h->stream;
   for (int side = 0; side < 2; ++side) {
     glrm_handle::Side& v = h->side[side];
-    if (!glrm_lane_wants(h, side)) continue;
+    if (!v.lane_want) continue;
     if (side == GLRM_ROWS ? !(v.tiled && (h->tile_rounds & 1) && h->actlist && v.pass.part) : !v.tiled) continue;
     if (side == GLRM_ROWS && h->n_losses > 1 && !(h->rowdescid && h->n_udesc > 0)) continue;
     v.lane = 1;
@@ -140,10 +152,7 @@ int glrm_setup_lane(glrm_handle* h) {
     if (nwb == 0 || ntiles == 0) continue;
     const int64_t ncell = nwb * ntiles;
     if (ncell > (int64_t)1 << 30) { v.lane = 0; continue; } // (cannot happen at shapes the LDS tiles are chosen for)
-    // the compact form of the stream for this side?  A function of the whole problem (view size, losses, options), like the family itself
-    const int cmode = env_int("GLRM_HIP_LANE_COMPACT", 2);
-    const bool compact = !(side == GLRM_ROWS && h->n_losses > 1) && (cmode == 1 || (cmode == 2 && (side == GLRM_ROWS ? h->sig.nnz_rows : h->sig.nnz_cols) > 2000000000ll)) &&
-                         64 * (side == GLRM_ROWS ? h->sig.max_row_len : h->sig.max_col_len) < ((int64_t)1 << 31); // (a wave block's values are counted in 31 bits: LaneArgs::sval)
+    const bool compact = v.lane_compact; // (a function of the whole problem, like the family itself: glrm_lane_decide)
     int64_t *cnt = nullptr, *scan = nullptr, *vcnt = nullptr;
     char* tmp = nullptr;
     DevArena scratch; // the counts and scans of this side's build
@@ -200,7 +209,7 @@ int glrm_setup_lane(glrm_handle* h) {
       HIPCK(hipGetLastError());
     }
     if (nseg > gseg_max) gseg_max = nseg;
-    if (env_int("GLRM_HIP_LANE_TRACE", 0))
+    if (knob(Knob::LANE_TRACE))
       fprintf(stderr, "[glrm lane] %s view: %lld slots in %lld wave blocks x %d tiles, %lld steps of 64 = %.3f x the %lld observations%s\n", side == GLRM_ROWS ? "row" : "column",
               (long long)nslots, (long long)nwb, ntiles, (long long)steps, (double)steps * 64.0 / (double)std::max<int64_t>(1, v.nnz),
               (long long)v.nnz, compact ? " (compact stream: 2-byte offsets padded, values unpadded)" : "");
@@ -262,12 +271,12 @@ int glrm_run_lane(glrm_handle* h, const glrm_step& step, const TiledArgs& a_in) 
   HIPCK(hipGetLastError());
   if (step.eval_only) return GLRM_OK;
   const TiledArgs full = a;
-  const bool gather = env_int("GLRM_HIP_LANE_ROUNDS", 1) != 0 && sell_ok && h->lane_glist && la.bptr && h->side[side].lane_steps > 0 &&
+  const bool gather = knob(Knob::LANE_ROUNDS) != 0 && sell_ok && h->lane_glist && la.bptr && h->side[side].lane_steps > 0 &&
                       full.nseg <= h->lane_gchunks * (int64_t)LANE_CC;
   // the round's trial pass in whichever form fits the fraction of segments that still searches; `list` holds them (nullptr without lists)
   auto trial = [&](int round, unsigned int nact, int32_t* list) -> int {
     TiledArgs t = full;
-    const int trace = env_int("GLRM_HIP_LANE_TRACE", 0);
+    const int trace = knob(Knob::LANE_TRACE);
     // Three forms of the trial pass, all adding the same terms in the same order (tests/test_gpu_families.py forces each of them on every
     // round).  FORM 0 walks the SELL layout over the full grid (idle segments masked): the cost of a whole pass whatever the fraction that
     // searches -- from 70 % up (sweep at C5's stated size, session r6_50: 55 / 70 / 85 % = 344.5 / 341.6 / 340.5 ms: flat).  FORM 2 reads the layout through gathered waves (glrm_lane.hpp): waves built chunk by chunk of 1 024
@@ -280,20 +289,20 @@ int glrm_run_lane(glrm_handle* h, const glrm_step& step, const TiledArgs& a_in) 
     const int64_t pct = (int64_t)nact * 100 / (full.nseg > 0 ? full.nseg : 1);
     // Tail rounds: a wave per (segment, super-tile) instead of a lane's serial walk through every tile (rows: 1.5-9 ms per round at C5's stated
     // size, eight to ten of them per X half-step) -- below GLRM_HIP_LANE_TAIL / GLRM_HIP_LANE_TAIL_COLS percent of the segments
-    if (list && (int64_t)nact * 100 < full.nseg * (int64_t)(full.nsup == 1 ? env_int("GLRM_HIP_LANE_TAIL", 5) : env_int("GLRM_HIP_LANE_TAIL_COLS", 3))) {
+    if (list && (int64_t)nact * 100 < full.nseg * (int64_t)knob(full.nsup == 1 ? Knob::LANE_TAIL : Knob::LANE_TAIL_COLS)) {
       if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: a wave per segment\n", side == GLRM_ROWS ? "row" : "column", round, nact, (long long)full.nseg);
       return launch_lane_tail(loss, full, list, (int64_t)nact, st);
     }
-    bool packed = list && (int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_GATHER_PACKED", 4);
+    bool packed = list && (int64_t)nact * 100 < full.nseg * knob(Knob::LANE_GATHER_PACKED);
     // (sides with permuted slots: chunk lists over the SLOTS, which were dealt out class by class -- make_segperm)
     const int32_t* gperm = la.inv ? full.segperm : nullptr;
-    const bool chunks_ok = !la.inv || (v.lane_dealt && gperm && env_int("GLRM_HIP_LANE_GATHER_SLOTS", 1));
-    bool use_gather = gather && (chunks_ok || packed) && pct >= env_int("GLRM_HIP_LANE_GATHER_FROM", 0) && pct < env_int("GLRM_HIP_LANE_GATHER_TO", 70);
+    const bool chunks_ok = !la.inv || (v.lane_dealt && gperm && knob(Knob::LANE_GATHER_SLOTS));
+    bool use_gather = gather && (chunks_ok || packed) && pct >= knob(Knob::LANE_GATHER_FROM) && pct < knob(Knob::LANE_GATHER_TO);
     int32_t gwaves = 0;
     if (use_gather) {
       const int off16 = (int)(full.own_offset & 15);
       if (packed) {
-        const int spread = env_int("GLRM_HIP_LANE_GATHER_SPREAD", 32768); // searching segments per step of q: ~2 048 waves before a wave takes more per class
+        const int spread = knob(Knob::LANE_GATHER_SPREAD); // searching segments per step of q: ~2 048 waves before a wave takes more per class
         int q = (int)(((int64_t)nact + spread - 1) / spread);
         q = q < 1 ? 1 : (q > 4 ? 4 : q);
         hipLaunchKernelGGL(lane_compact_list_kernel, dim3(1), dim3(1024), 0, st, list, (int)nact, off16, q, (int)h->lane_gcap, h->lane_glist, h->lane_gtotal);
@@ -324,7 +333,7 @@ int glrm_run_lane(glrm_handle* h, const glrm_step& step, const TiledArgs& a_in) 
       return launch_lane_loss<false, 2>(loss, t, la, (int64_t)gwaves, st);
     }
     // (measured cross-over of the two older forms at about a sixth of the segments, session r6_20)
-    const bool compact = list && ((int64_t)nact * 100 < full.nseg * env_int("GLRM_HIP_LANE_CSR_BELOW", 16) || !sell_ok);
+    const bool compact = list && ((int64_t)nact * 100 < full.nseg * knob(Knob::LANE_CSR_BELOW) || !sell_ok);
     if (trace >= 2) fprintf(stderr, "[glrm lane] %s round %d: %u of %lld segments search: %s\n", side == GLRM_ROWS ? "row" : "column", round, nact, (long long)full.nseg, compact ? "CSR" : "SELL full grid");
     if (compact) {
       // (tried in session r6_45/46 and taken out again: this form over class-aware wave lists -- conflict-free tile reads -- measured the same at

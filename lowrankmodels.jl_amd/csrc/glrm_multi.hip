@@ -54,9 +54,9 @@ int glrm_setup_multi(glrm_handle* h, const glrm_problem* p) {
 
 // A column longer than one chunk (8192 observations; GLRM_HIP_MULTI_CHUNK overrides, 0 = never) is swept by several
 // workgroups.  The chunk is a constant, so the grouping of a column's partial sums depends on its own list only.
-static int setup_split(glrm_handle* h) {
+int glrm_setup_multi_split(glrm_handle* h) {
   if (h->mtrial || h->col_nsplit < 0) return GLRM_OK;
-  const int64_t chunk = env_int("GLRM_HIP_MULTI_CHUNK", 8192);
+  const int64_t chunk = knob(Knob::MULTI_CHUNK);
   // split or not is decided from the longest column of the WHOLE problem (glrm_signature) and the global column count, so that every
   // shard of a sharded fit runs the same kernels
   const int64_t longest = h->sig.max_col_len;
@@ -76,7 +76,7 @@ static int setup_split(glrm_handle* h) {
 // GDC = 8 when no embedding is wider (gradient registers per lane: 8 instead of 32); TRIG: see LOSS_*_NOTRIG in glrm_engine.hpp
 // kind-specialised instantiations (glrm_multi.hpp: MULTI_KM_*) exist for the small-dimension, no-PeriodicLoss variants
 static int kind_class(const glrm_handle* h) { // 0 = all kinds, 1 = MultinomialLoss only, 2 = MultinomialLoss + scalar losses, 3 = ordinal
-  if (!env_int("GLRM_HIP_MULTI_KINDS", 1)) return 0; // (BvSLoss / MultinomialOrdinalLoss: the columns of an ordinal data frame)
+  if (!knob(Knob::MULTI_KINDS)) return 0; // (BvSLoss / MultinomialOrdinalLoss: the columns of an ordinal data frame)
   if (h->multi_kmask == MULTI_KM_MNL) return 1;
   if ((h->multi_kmask & ~(MULTI_KM_MNL | MULTI_KM_SCALAR)) == 0 && (h->multi_kmask & MULTI_KM_MNL)) return 2;
   return h->multi_kmask != 0 && (h->multi_kmask & ~MULTI_KM_ORD) == 0 ? 3 : 0;
@@ -163,7 +163,7 @@ int glrm_run_multi(glrm_handle* h, const glrm_step& step) {
   if (side == GLRM_ROWS) {
     const size_t lds = multi_lds_doubles(true, 1, h->kp, h->dmax, a.lgP) * 8;
     // every embedding dimension <= 8: the opposing block of an observation is held in registers (glrm_multi.hpp: multi_pass, RD)
-    const bool regs = h->dmax <= 8 && env_int("GLRM_HIP_MULTI_REGS", 1);
+    const bool regs = h->dmax <= 8 && knob(Knob::MULTI_REGS);
     const int kc = kind_class(h);
     if (regs) {
       if (h->has_trig) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, true, 8);
@@ -174,9 +174,7 @@ int glrm_run_multi(glrm_handle* h, const glrm_step& step) {
     } else if (h->has_trig) MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, true);
     else MULTI_SWEEP(64, true, 1, GLRM_MAX_EMBEDDING_DIM, false);
   } else {
-    const int rc = setup_split(h); // decides once per handle whether the columns are long enough to split
-    if (rc) return rc;
-    if (h->col_nsplit > 1) return run_split_cols(h, a);
+    if (h->col_nsplit > 1) return run_split_cols(h, a); // (glrm_setup_multi_split decided at set-up whether the columns are long enough to split)
     const size_t lds = multi_lds_doubles(false, 8, h->kp, h->dmax, a.lgP) * 8;
     if (h->dmax <= 8) {
       const int kc = kind_class(h);

@@ -66,8 +66,8 @@ struct Rccl {
   bool ok = false;
   Rccl() {
 #ifdef GLRM_HIP_TESTING // the test build may load a stand-in (tests/stubs/rccl_stub.cpp); the product library only ever opens librccl
-    const char* path = getenv("GLRM_HIP_RCCL_LIB");
-    void* lib = (path && *path) ? dlopen(path, RTLD_LAZY | RTLD_LOCAL) : nullptr;
+    const char* path = knob_path(Knob::RCCL_LIB);
+    void* lib = path ? dlopen(path, RTLD_LAZY | RTLD_LOCAL) : nullptr;
 #else
     void* lib = nullptr;
 #endif
@@ -580,12 +580,12 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     if ((rc = glrm_hip_bind_buffers(mh->sh[s], mh->dX[s], mh->dY[s], mh->dObjCol[s], mh->dObjRow[s]))) return rc;
   }
   mh->exchange = 0;
-  const int want = env_int("GLRM_HIP_EXCHANGE_RCCL", mo->exchange);
+  const int want = knob_or(Knob::EXCHANGE_RCCL, mo->exchange);
   if (want == 1 && n > 1) {
     Rccl& R = Rccl::get();
     // RCCL wants one device per rank (the test build's GLRM_HIP_RCCL_ALLOW_SHARED=1 lifts that for the suite's stand-in library)
 #ifdef GLRM_HIP_TESTING
-    const bool shared_ok = env_int("GLRM_HIP_RCCL_ALLOW_SHARED", 0) != 0;
+    const bool shared_ok = knob(Knob::RCCL_ALLOW_SHARED) != 0;
 #else
     const bool shared_ok = false;
 #endif
@@ -598,7 +598,7 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
   }
   mh->x_chunks = (mo->x_chunks >= 2 && n > 1 && !mh->dense && mh->exchange == 0) ? mo->x_chunks : 1;
   // arrival order: the direct exchange of list problems (the dense path walks A, not X, super-tile by super-tile)
-  mh->arrival = (n > 1 && !mh->dense && mh->exchange == 0 && env_int("GLRM_HIP_MULTI_ARRIVAL", mo->arrival == 2 ? 0 : 1)) ? 1 : 0;
+  mh->arrival = (n > 1 && !mh->dense && mh->exchange == 0 && knob_or(Knob::MULTI_ARRIVAL, mo->arrival == 2 ? 0 : 1)) ? 1 : 0;
   mh->ev_chunk.assign(n, std::vector<std::vector<hipEvent_t>>(n));
   if (mh->arrival)
     for (int s = 0; s < n; ++s) {
@@ -611,8 +611,7 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     }
 #ifdef GLRM_HIP_TESTING
   // link emulation (see the head of this file)
-  const char* eg = getenv("GLRM_EXCHANGE_EMULATE_GBPS");
-  const double gbps = (eg && *eg) ? atof(eg) : 0.0;
+  const double gbps = knob_positive(Knob::EMULATE_GBPS, 0.0);
   if (gbps > 0.0 && n > 1 && mh->exchange == 0) {
     LinkEmu& e = mh->emu;
     int share = 1;
@@ -621,13 +620,13 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
       for (int t = 0; t < n; ++t) c += mh->dev[t] == mh->dev[s];
       share = std::max(share, c);
     }
-    e.dilate = std::max(1, env_int("GLRM_EXCHANGE_EMULATE_DILATE", share));
+    e.dilate = std::max(1, knob_or(Knob::EMULATE_DILATE, share));
     e.gbps = gbps;
     int can = 0;
     if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, mh->dev[0]) != hipSuccess) { (void)hipGetLastError(); can = 0; }
-    e.mode = env_int("GLRM_EXCHANGE_EMULATE_MODE", can ? 1 : 2);
-    if (e.mode != 1 && e.mode != 2) return fail(GLRM_ERR_INVALID, "GLRM_EXCHANGE_EMULATE_MODE must be 1 (stream wait-value) or 2 (delay kernels)");
-    if (e.mode == 1 && !can) return fail(GLRM_ERR_UNSUPPORTED, "GLRM_EXCHANGE_EMULATE_MODE=1: the device does not support hipStreamWaitValue64");
+    e.mode = knob_or(Knob::EMULATE_MODE, can ? 1 : 2);
+    if (e.mode != 1 && e.mode != 2) return fail(GLRM_ERR_INVALID, "link emulator: GLRM_EXCHANGE_EMULATE_MODE must be 1 (stream wait-value) or 2 (delay kernels)");
+    if (e.mode == 1 && !can) return fail(GLRM_ERR_UNSUPPORTED, "link emulator: GLRM_EXCHANGE_EMULATE_MODE=1: the device does not support hipStreamWaitValue64");
     if (e.mode == 1) {
       e.mark.assign(n, nullptr); e.release.assign(n, nullptr); e.ticket.assign(n, 0);
       for (int s = 0; s < n; ++s) {
@@ -650,8 +649,8 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     e.bytes_per_s = gbps * 1e9 / e.dilate; // set last: the hooks are live from here
   }
 #else
-  if (getenv("GLRM_EXCHANGE_EMULATE_GBPS") && *getenv("GLRM_EXCHANGE_EMULATE_GBPS") && atof(getenv("GLRM_EXCHANGE_EMULATE_GBPS")) > 0.0)
-    return fail(GLRM_ERR_UNSUPPORTED, "GLRM_EXCHANGE_EMULATE_GBPS: the link emulator lives in the test build (libglrm_hip_testing.so), not in this library");
+  if (knob_positive(Knob::EMULATE_GBPS, 0.0) > 0.0)
+    return fail(GLRM_ERR_UNSUPPORTED, "link emulator (GLRM_EXCHANGE_EMULATE_GBPS): the link emulator lives in the test build (libglrm_hip_testing.so), not in this library");
 #endif
   return GLRM_OK;
 }

@@ -140,6 +140,8 @@ extern "C" int glrm_hip_set_regularizers_vec(glrm_handle* h, const glrm_reg* rx,
   // all 0 still moves the handle to the general sweeps: how the shards of one problem stay on ONE family when only some hold a vector.
   if (!carries[0] && !carries[1] && !vx && !vy) return glrm_hip_set_regularizers(h, rx, n_rx, ry, n_ry);
   DeviceScope dg(h->device);
+  if (!h->multi && h->finalized && !h->sum_order_opt) // the handle moves to the general sweeps: the part of set-up it still needs (nothing has changed yet)
+    if (const int rc = glrm_setup_multi_split(h)) return rc;
   const int k = h->k;
   std::vector<double> tv[2];
   std::vector<int32_t> tl[2];

@@ -20,8 +20,7 @@ extern "C" int glrm_build_is_testing(void) {
 
 int glrm_test_fail_finalize() {
 #ifdef GLRM_HIP_TESTING
-  const char* v = getenv("GLRM_HIP_TEST_FAIL_FINALIZE");
-  return v && *v && atoi(v) != 0;
+  return knob(Knob::TEST_FAIL_FINALIZE) != 0;
 #else
   return 0;
 #endif

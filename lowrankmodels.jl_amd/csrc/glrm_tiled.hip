@@ -25,7 +25,7 @@ static int make_segperm(glrm_handle* h, int side, int32_t** out, int64_t long_fr
   *out = nullptr;
   const int64_t nseg = h->side[side].nseg;
   if (nshort) *nshort = nseg;
-  if (nseg <= 1 || !env_int("GLRM_HIP_SEGPERM", 1)) return GLRM_OK;
+  if (nseg <= 1 || !knob(Knob::SEGPERM)) return GLRM_OK;
   std::vector<int64_t> ptr;
   int rc = glrm_host_ptr(h, side, ptr);
   if (rc) return rc;
@@ -42,7 +42,7 @@ static int make_segperm(glrm_handle* h, int side, int32_t** out, int64_t long_fr
     const glrm_loss* lt = h->losses_h.data() + h->side[GLRM_COLS].begin;
     std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return lt[x].kind < lt[y].kind; });
   }
-  const bool lane_side = h->side[side].tiled && glrm_lane_wants(h, side) && env_int("GLRM_HIP_LANE_DEAL", 1);
+  const bool lane_side = h->side[side].tiled && h->side[side].lane_want && knob(Knob::LANE_DEAL);
   if (lane_side) {
     // The lane-per-segment passes (glrm_lane.hpp) read their tiles conflict free when the 16 lanes of an LDS cycle hold 16 different
     // classes (global id) & 15 -- true when slot s holds a segment of class s & 15.  In natural order that is given; a sorted list is dealt
@@ -123,7 +123,7 @@ int glrm_setup_tiled(glrm_handle* h) {
   // h->tiled_opt (glrm_options.tiled): 0 auto, 1 gather sweeps only, 2 tiled wherever the index lists are sorted.
   // GLRM_HIP_TILED (tuning): bit0 rows, bit1 columns; overrides the option.
   int want = h->tiled_opt == 1 ? 0 : (h->tiled_opt == 2 ? 3 : -1);
-  want = env_int("GLRM_HIP_TILED", want);
+  want = knob_or(Knob::TILED, want);
   // Auto choice (measured on MI355X, tests/perf/bench_small.py): the tiled sweeps need enough workgroups to fill 256 CUs and
   // enough observations to amortise their per-tile barriers; below ~2e7 observations per view the gather sweeps win (100k x 5k
   // at 1e7 observations: 1.06 vs 1.23 ms per iteration; 300k x 3k at 4.5e7: 4.6 vs 3.1 ms).
@@ -135,11 +135,11 @@ int glrm_setup_tiled(glrm_handle* h) {
   // Lists in arbitrary order (obs tuples pushed in sampling order): the engine's private copy is brought into tile order by a
   // stable segmented sort, so such inputs run the tiled sweeps too.  Only when the auto choice wants the tiled sweeps -- an
   // explicit tiled = 2 keeps its meaning "wherever the lists allow" (GLRM_HIP_TILE_SORT=0 disables, =2 sorts for tiled = 2 as well).
-  const int tsort = env_int("GLRM_HIP_TILE_SORT", 1);
+  const int tsort = knob(Knob::TILE_SORT);
   const bool may_sort = tsort == 2 || (tsort == 1 && want < 0);
   // (a shard whose own lists are already in tile order gets them back unchanged -- the sort is stable -- so the decision may be
   // taken for the whole problem; a list too long for the segmented sort anywhere keeps every shard on the gather sweeps)
-  const int64_t sort_limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0) > 0 ? env_int("GLRM_HIP_TILE_SORT_BATCH", 0) : 1500000000ll;
+  const int64_t sort_limit = (int64_t)knob_positive(Knob::TILE_SORT_BATCH, 1.5e9);
   const bool want_side[2] = {want_row, want_col}, unordered_here[2] = {h->sig_local.rows_unordered != 0, h->sig_local.cols_unordered != 0};
   const int64_t max_len[2] = {h->sig.max_row_len, h->sig.max_col_len};
   for (int s = 0; s < 2; ++s) {
@@ -155,8 +155,10 @@ int glrm_setup_tiled(glrm_handle* h) {
   }
   // (rows on the lane-per-segment passes -- glrm_lane.hpp -- keep the caller's order: every lane evaluates its own observation's loss, so
   // there is no wave-wide formula to align, and the grouped copy would cost 12 B per observation beside the SELL stream)
-  const bool lane_rows = rows.tiled && (env_int("GLRM_HIP_TILE_ROUNDS", 3) & 1) && glrm_lane_wants(h, GLRM_ROWS);
-  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && env_int("GLRM_HIP_GROUP_KINDS", 1) && !lane_rows) {
+  h->tile_rounds = knob(Knob::TILE_ROUNDS); // bit0 rows, bit1 columns (below: the rounds' lists and pass buffers)
+  glrm_lane_decide(h);
+  const bool lane_rows = rows.tiled && (h->tile_rounds & 1) && rows.lane_want;
+  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && knob(Knob::GROUP_KINDS) && !lane_rows) {
     DevArena scratch;
     int32_t* oidx = nullptr;
     double* ovals = nullptr;
@@ -170,8 +172,9 @@ int glrm_setup_tiled(glrm_handle* h) {
     rows.vals = ovals;
     scratch.move_to(h->mem, oidx);
     scratch.move_to(h->mem, ovals);
+    rows.grouped = true;
   }
-  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && env_int("GLRM_HIP_UDESC", 1)) {
+  if (rows.tiled && h->n_losses > 1 && rows.nnz > 0 && knob(Knob::UDESC)) {
     // distinct loss descriptors of the model; with at most 256 of them every entry of the row view carries a one-byte id and the
     // row sweep reads descriptors from an LDS table (TiledArgs::descid)
     std::vector<glrm_loss> uniq;
@@ -210,10 +213,10 @@ int glrm_setup_tiled(glrm_handle* h) {
     // (the lane-per-segment form of the passes holds 512 columns per workgroup and stages its tiles of X at ~3 TB/s with nothing to overlap
     // them: more, shorter super-tiles even the workgroups out -- C2 Y half-step 7.6 -> 7.0 ms at twice the workgroups, session r6_09; the
     // family is a function of the whole problem's signature, so this still is)
-    const bool lane_c = cols.tiled && glrm_lane_wants(h, GLRM_COLS);
+    const bool lane_c = cols.tiled && cols.lane_want;
     const int spb = lane_c ? 512 : 16 * (64 / h->tG);
     const int64_t groups = (h->n + spb - 1) / spb;
-    const int64_t want_wg = env_int("GLRM_HIP_COL_WORKGROUPS", lane_c ? 2048 : 1024);
+    const int64_t want_wg = knob_or(Knob::COL_WORKGROUPS, lane_c ? 2048 : 1024);
     int64_t nsup_target = (want_wg + groups - 1) / groups;
     if (nsup_target < 1) nsup_target = 1;
     int64_t tps = ntiles / nsup_target;
@@ -235,16 +238,16 @@ int glrm_setup_tiled(glrm_handle* h) {
     // longest 879 189): Y half-step 27.5 / 19.0 / 16.2 / 17.1 ms at 1 / 2 / 4 / 8 x mean (profiles/r05_c2_zipf_long_from_sweep.txt): the
     // gather sweep pays 536 B per update where the tiles pay a fraction, so only the head of the distribution is worth diverting.
     const int64_t mean_len = h->sig.nnz_cols / (h->n > 0 ? h->n : 1);
-    h->blk_long_from = env_int("GLRM_HIP_TILED_LONG_FROM", -1) >= 0 ? env_int("GLRM_HIP_TILED_LONG_FROM", 0) : std::max<int64_t>(4096, 4 * mean_len);
+    const int long_from = knob(Knob::TILED_LONG_FROM);
+    h->blk_long_from = long_from >= 0 ? long_from : std::max<int64_t>(4096, 4 * mean_len);
     std::vector<int32_t> longl;
     if ((rc0 = make_segperm(h, GLRM_COLS, &cols.perm, h->blk_long_from, &longl, &h->blk_nshort_c))) return rc0;
     if ((rc0 = glrm_set_long_columns(h, longl))) return rc0;
   }
   if (rows.tiled && (rc0 = make_segperm(h, GLRM_ROWS, &rows.perm))) return rc0;
   // Line-search rounds over the still-searching segments only (glrm_tiled.hpp: TiledArgs::actlist_out).  Columns: the passes after the
-  // first trial; rows: everything after the first trial, which stays fused with the gradient pass in one kernel (GLRM_HIP_TILE_ROUNDS:
-  // bit0 rows, bit1 columns, default 3; 0 = the round-3 forms).  Two lists (the decide kernel reads one and writes the next).
-  h->tile_rounds = env_int("GLRM_HIP_TILE_ROUNDS", 3);
+  // first trial; rows: everything after the first trial, which stays fused with the gradient pass in one kernel (GLRM_HIP_TILE_ROUNDS,
+  // read above into tile_rounds; 0 = the round-3 forms).  Two lists (the decide kernel reads one and writes the next).
   if ((rows.tiled && (h->tile_rounds & 1)) || (cols.tiled && (h->tile_rounds & 2))) {
     const int64_t cap = std::max<int64_t>(1, std::max(rows.tiled ? rows.nseg : 0, cols.tiled ? cols.nseg : 0));
     if ((rc0 = h->mem.alloc(&h->actlist, (size_t)cap * 2))) return rc0;

@@ -41,8 +41,7 @@ struct MinusBase { // segment offsets relative to the batch's first entry
 // caller's, which stay untouched).
 int glrm_tile_sort_view(hipStream_t st, const int64_t* ptr, int64_t nseg, int64_t nnz, int tile, int64_t n_other, int32_t** idx, double** vals, DevArena& owner) {
   if (nnz <= 0 || nseg <= 0) return GLRM_OK;
-  int64_t limit = env_int("GLRM_HIP_TILE_SORT_BATCH", 0);
-  if (limit <= 0) limit = 1500000000ll;
+  const int64_t limit = (int64_t)knob_positive(Knob::TILE_SORT_BATCH, 1.5e9);
   std::vector<int64_t> hp((size_t)nseg + 1);
   HIPCK(hipMemcpyAsync(hp.data(), ptr, ((size_t)nseg + 1) * 8, hipMemcpyDeviceToHost, st));
   HIPCK(hipStreamSynchronize(st));

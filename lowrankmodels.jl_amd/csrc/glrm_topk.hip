@@ -44,8 +44,7 @@ constexpr int TK_LD = TK_TILE + 2;        // doubles per staged component: the 1
 constexpr int TK_BITS = 8;                // digit width
 constexpr int TK_DIGITS = 1 << TK_BITS;
 constexpr int TK_COPIES = 32;             // copies of a digit's counter (one per LDS bank)
-constexpr int TK_GRID = 1024;             // workgroups of a selection pass (4 per CU; 2 are resident)
-constexpr int64_t TK_FINISH = 1ll << 22;  // early finish once the bucket holds at most this many entries
+// (workgroups of a selection pass -- 4 per CU, 2 are resident -- and the bucket size of the early finish: Knob::TOPK_GRID / TOPK_FINISH)
 constexpr int64_t TK_BLOCK_ENTRIES = 1ll << 24; // scan: entries of a block (its byte map)
 constexpr int64_t TK_BLOCK_ROWS = 1ll << 20;    // scan: rows of a block
 static_assert(TK_TILE == 16 * TK_R && TK_THREADS == 256 && TK_THREADS == 16 * TK_KC && TK_LD % 2 == 0 && TK_DIGITS == TK_THREADS && 32 % TK_BITS == 0, "tile layout");
@@ -403,11 +402,11 @@ extern "C" int glrm_hip_xy_select(glrm_handle* h, const double* X, const double*
   const int64_t tiles_m = (m + TK_TILE - 1) / TK_TILE, tiles_n = (n + TK_TILE - 1) / TK_TILE, ntiles = tiles_m * tiles_n;
   // a workgroup's share of the entries must fit its 32-bit counters: at most 2^17 tiles of 2^14 entries
   // (GLRM_HIP_TOPK_GRID: another grid, for the tests that show the result does not depend on it)
-  const int64_t want_grid = std::max(1, env_int("GLRM_HIP_TOPK_GRID", TK_GRID));
+  const int64_t want_grid = std::max(1, knob(Knob::TOPK_GRID));
   const int64_t grid64 = std::min<int64_t>(ntiles, std::max<int64_t>(want_grid, (ntiles + (1ll << 17) - 1) >> 17));
   if (grid64 > 0x7fffffffll) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_xy_select: m x n too large");
   const int grid = (int)grid64;
-  const int64_t finish = (int64_t)env_int("GLRM_HIP_TOPK_FINISH", (int)TK_FINISH);
+  const int64_t finish = knob(Knob::TOPK_FINISH);
 
   DevArena w;
   unsigned long long *slots = nullptr, *totals = nullptr, *woff = nullptr, *keys = nullptr, *sorted = nullptr, *picked = nullptr;

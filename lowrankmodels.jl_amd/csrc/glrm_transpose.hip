@@ -99,9 +99,8 @@ int glrm_rows_from_cols(glrm_handle* h) {
   HIPCK(hipMemsetAsync(rows.ptr, 0, ((size_t)m + 1) * 8, st));
   if (nnz == 0) return GLRM_OK;
   if (m + 1 > (int64_t)INT32_MAX) return fail(GLRM_ERR_UNSUPPORTED, "GLRM_PROBLEM_ROWS_FROM_COLS: %lld rows", (long long)m);
-  const int64_t cap0 = env_int("GLRM_HIP_TRANSPOSE_CHUNK", 1500000000);
-  const int64_t cap = cap0 > 0 && cap0 <= 1500000000 ? cap0 : 1500000000;
-  const bool trace = env_int("GLRM_HIP_TRANSPOSE_TRACE", 0) != 0; // step times on stderr (every step drains the stream)
+  const int64_t cap = std::min<int64_t>((int64_t)knob_positive(Knob::TRANSPOSE_CHUNK, 1.5e9), 1500000000);
+  const bool trace = knob(Knob::TRANSPOSE_TRACE) != 0; // step times on stderr (every step drains the stream)
   double t_last = now_s();
   auto lap = [&](const char* what) {
     if (!trace) return;

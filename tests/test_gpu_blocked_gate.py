@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cases
+import family_env
 import lowrankmodels.jl_amd as L
 import oracle as O
 from lowrankmodels.jl_amd import _capi, synth
@@ -17,10 +18,7 @@ GATES = (None, "0", "1", "37")  # None: the library's default
 
 
 def force_blocked(monkeypatch, tps, fill):
-    monkeypatch.setenv("GLRM_HIP_BLOCKED", "3")
-    monkeypatch.setenv("GLRM_HIP_BLOCKED_TPS", tps)
-    monkeypatch.setenv("GLRM_HIP_BLOCKED_FILL", fill)
-    monkeypatch.setenv("GLRM_HIP_CACHED", "0")
+    family_env.setenv(monkeypatch, family_env.blocked(tps, fill))
 
 
 def run_under_gates(monkeypatch, pa, X0, Y0, params, **create_kw):

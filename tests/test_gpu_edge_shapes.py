@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import family_env
 import oracle as O
 import shapes
 import test_gpu_sum_order as S
@@ -31,8 +32,7 @@ SWITCHES = ("GLRM_HIP_CACHED", "GLRM_HIP_CACHED_PERSIST", "GLRM_HIP_BLOCKED", "G
             "GLRM_HIP_BLOCKED_LONG_FROM", "GLRM_HIP_TILED_LONG_FROM", "GLRM_HIP_COL_WORKGROUPS", "GLRM_HIP_LANE", "GLRM_HIP_LANE_DEAL",
             "GLRM_HIP_LANE_COMPACT", "GLRM_HIP_LANE_ROUNDS", "GLRM_HIP_LANE_GATHER_TO", "GLRM_HIP_LANE_GATHER_PACKED",
             "GLRM_HIP_LANE_GATHER_SPREAD", "GLRM_HIP_LANE_TAIL", "GLRM_HIP_LANE_TAIL_COLS", "GLRM_HIP_LANE_PER_OBS", "GLRM_HIP_GROUP_KINDS")
-GATHER = {"GLRM_HIP_CACHED": "0", "GLRM_HIP_BLOCKED": "0"}
-BLOCKED = {"GLRM_HIP_BLOCKED": "3", "GLRM_HIP_BLOCKED_TPS": "1", "GLRM_HIP_BLOCKED_FILL": "3", "GLRM_HIP_CACHED": "0"}
+GATHER, BLOCKED, FOUR_LANE = family_env.GATHER, family_env.blocked("1", "3"), family_env.FOUR_LANE
 
 
 # ------------------------------------------------------------------------------------------------ per-segment class and report
@@ -266,9 +266,7 @@ def test_cached_rows_at_the_cut(monkeypatch, k, persist):
             i += 1
     segs += [Seg("c0", "col", 0, 0, intent="waves1"), Seg("c1600", "col", 1, 1600, intent="waves4")]
     sh = shapes.build(1800, 1700, k, segs, fill=6, reg="nonneg", seed=k)
-    env = dict(GATHER, GLRM_HIP_CACHED="1")
-    if persist == "0":
-        env["GLRM_HIP_CACHED_PERSIST"] = "0"
+    env = family_env.cached(persist != "0")
 
     def check(o):
         layout(o[0], G, kp // G, family=1, cached_maxlen=cm, cached_waves=2)
@@ -292,9 +290,6 @@ def window_segments(T, m, n, G, sup_rows=None):
              Seg("rwin0", "row", 2, 30, "window", 0, intent="windowed"), Seg("rlast", "row", 3, 1, "last_tile", intent="windowed"),
              Seg("redge", "row", 4, 6, "straddle", T, intent="windowed"), Seg("rdup", "row", 5, 9, "dups", intent="windowed")]
     return segs
-
-
-FOUR_LANE = {"GLRM_HIP_LANE": "0"}
 
 
 @pytest.mark.parametrize("k,sups", [(8, "two"), (16, "cap"), (64, "one"), (64, "default")])
@@ -345,15 +340,8 @@ def test_four_lane_tiles_with_a_loss_per_column(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ lane per segment (k = 32)
 
-LANE_FORMS = {
-    "default": {},
-    "deal off": {"GLRM_HIP_LANE_DEAL": "0"},
-    "compact stream": {"GLRM_HIP_LANE_COMPACT": "1"},
-    "older forms (full grid / CSR)": {"GLRM_HIP_LANE_ROUNDS": "0"},
-    "gathered, chunk lists": {"GLRM_HIP_LANE_GATHER_TO": "101", "GLRM_HIP_LANE_GATHER_PACKED": "0"},
-    "gathered, packed lists": {"GLRM_HIP_LANE_GATHER_TO": "101", "GLRM_HIP_LANE_GATHER_PACKED": "101", "GLRM_HIP_LANE_GATHER_SPREAD": "1000"},
-    "a wave per row": {"GLRM_HIP_LANE_TAIL": "101", "GLRM_HIP_LANE_TAIL_COLS": "101"},
-}
+LANE_FORMS = family_env.lane_forms("default", "deal off", "compact stream", "older forms (full grid / CSR)", "gathered, chunk lists", "gathered, packed lists",
+                                   "a wave per row")
 
 
 def lane_check(o):
@@ -442,7 +430,7 @@ def test_phase_aligned_passes_at_edges(monkeypatch, k, gate):
 
 FAMILY_RANK = {  # family: (environment, create kwargs)
     "gather": (GATHER, {"tiled": 1}),
-    "cached": (dict(GATHER, GLRM_HIP_CACHED="1"), {"tiled": 0}),
+    "cached": (family_env.cached(), {"tiled": 0}),
     "four-lane tiles": (FOUR_LANE, {"tiled": 2}),
     "lane": ({}, {"tiled": 2}),
     "phase-aligned": (BLOCKED, {"tiled": 1}),

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import cases
+import family_env
 import lowrankmodels.jl_amd as L
 import oracle as O
 from lowrankmodels.jl_amd import _capi
@@ -28,10 +29,7 @@ def hip():
 def force_blocked(monkeypatch, tps="1", fill="3"):
     """Phase-aligned passes on both views; one LDS-tile unit per super-tile (many super-tiles: the partial sums per (segment, super-tile)
     and their fixed-order reduction are exercised) and 3 % of the chip's residency per launch slice (many slices per pass)."""
-    monkeypatch.setenv("GLRM_HIP_BLOCKED", "3")
-    monkeypatch.setenv("GLRM_HIP_BLOCKED_TPS", tps)
-    monkeypatch.setenv("GLRM_HIP_BLOCKED_FILL", fill)
-    monkeypatch.setenv("GLRM_HIP_CACHED", "0")
+    family_env.setenv(monkeypatch, family_env.blocked(tps, fill))
 
 
 def against_oracle(pa, X0, Y0, params, want_flags, tol=TOL, **create_kw):
@@ -536,24 +534,13 @@ def test_lane_trial_rounds_give_the_same_bits_in_every_form(monkeypatch, mixed):
     reg = np.array([(1, 0, 0.5)], dtype=_capi.REG_DTYPE)
     pa = _capi.ProblemArrays(m, n, k, rowptr, colidx, rowvals, colptr, rowidx, colvals, losses, reg, reg)
     api = hip()
-    forms = {
-        "default": {},
-        "older forms (full grid / CSR)": {"GLRM_HIP_LANE_ROUNDS": "0"},
-        "gathered, chunk lists": {"GLRM_HIP_LANE_GATHER_TO": "101", "GLRM_HIP_LANE_GATHER_PACKED": "0"},
-        "gathered, packed lists": {"GLRM_HIP_LANE_GATHER_TO": "101", "GLRM_HIP_LANE_GATHER_PACKED": "101", "GLRM_HIP_LANE_GATHER_SPREAD": "1000"},
-        # the COMPACT form of the stream (2-byte offsets padded, values unpadded: what views beyond 2e9 observations run) on every side it
-        # serves -- both views of the QuadLoss model, the column view of the model with a loss per column; its rounds: full grid / CSR
-        "compact stream": {"GLRM_HIP_LANE_COMPACT": "1"},
-        # every round after the first (and a first trial of few rows) on the tail kernel: a wave per (segment, super-tile), no tile
-        "a wave per row": {"GLRM_HIP_LANE_TAIL": "101", "GLRM_HIP_LANE_TAIL_COLS": "101"},
-        "no tail kernel": {"GLRM_HIP_LANE_TAIL": "0", "GLRM_HIP_LANE_TAIL_COLS": "0"},
-    }
+    forms = family_env.lane_forms("default", "older forms (full grid / CSR)", "gathered, chunk lists", "gathered, packed lists", "compact stream", "a wave per row",
+                                  "no tail kernel")
     res = {}
     for name, env in forms.items():
-        for key in ("GLRM_HIP_LANE_ROUNDS", "GLRM_HIP_LANE_GATHER_TO", "GLRM_HIP_LANE_GATHER_PACKED", "GLRM_HIP_LANE_GATHER_SPREAD", "GLRM_HIP_LANE_COMPACT", "GLRM_HIP_LANE_TAIL", "GLRM_HIP_LANE_TAIL_COLS"):
+        for key in family_env.LANE_FORM_KEYS:
             monkeypatch.delenv(key, raising=False)
-        for key, v in env.items():
-            monkeypatch.setenv(key, v)
+        family_env.setenv(monkeypatch, env)
         h = api.create(pa, tiled=2)
         try:
             assert api.kernel_stats(h)["tiled"] & (256 | 512) == (256 | 512)
@@ -631,3 +618,106 @@ def test_arrival_order_with_one_super_tile_waits_for_every_block(monkeypatch, la
             api.destroy(h)
     assert np.array_equal(res[True][0], res[False][0]) and np.array_equal(res[True][1], res[False][1])
     assert res[False][2]["ms_wait_y"] == 0.0 and res[True][2]["ms_wait_y"] > 0.0
+
+
+# ------------------------------------------------------------------------------------------------ read times of the knobs (csrc/glrm_knobs.hpp)
+
+def run_and_report(api, pa, X0, Y0, create_kw, want_bits, after_finalize=None, between=None, stepsize=1.0):
+    """One handle: create (= finalize), then `after_finalize()` (the environment changes under a live handle), three iterations with
+    `between(it)` before each, and everything the handle reports: both sum orders, the statistics, the factors, the objective."""
+    h = api.create(pa, **create_kw)
+    try:
+        if after_finalize:
+            after_finalize()
+        api.set_factors(h, X0, Y0)
+        api.reset_stepsizes(h, stepsize)
+        for it in range(3):
+            if between:
+                between(it)
+            api.step_x(h, 0.01)
+            api.step_y(h, 0.01)
+        orders = [api.sum_order(h, side).asdict() for side in (0, 1)]
+        st = api.kernel_stats(h)
+        assert st["tiled"] & want_bits == want_bits, (st["tiled"], want_bits)
+        X, Y = np.zeros_like(X0), np.zeros_like(Y0)
+        api.get_factors(h, X, Y)
+        obj = api.objective(h, X, Y)
+    finally:
+        api.destroy(h)
+    return orders, st, X, Y, obj
+
+
+def same_run(a, b):
+    (oa, sa, Xa, Ya, fa), (ob, sb, Xb, Yb, fb) = a, b
+    assert oa == ob, (oa, ob)
+    assert np.array_equal(Xa, Xb) and np.array_equal(Ya, Yb) and fa == fb
+    for key in ("tiled", "trials_x", "trials_y", "accepts_x", "accepts_y", "waves_row", "waves_col"):
+        assert sa[key] == sb[key], (key, sa[key], sb[key])
+
+
+def mixed_columns(m, n, k, q):
+    """Quad / Logistic / OrdinalHinge columns in turn (the C5 recipe): a loss descriptor per column."""
+    rowptr, colidx, rowvals, colptr, rowidx, colvals, X0, Y0 = O.synth_cpu(m, n, k, q, value_model=0, loss_mix=1)
+    kinds = [L.QuadLoss().descriptor(), L.LogisticLoss().descriptor(), L.OrdinalHingeLoss(1, 5).descriptor()]
+    losses = np.array([kinds[f % 3] for f in range(n)], dtype=_capi.LOSS_DTYPE)
+    reg = np.array([(1, 0, 1.0)], dtype=_capi.REG_DTYPE)
+    pa = _capi.ProblemArrays(m, n, k, rowptr, colidx, rowvals, colptr, rowidx, colvals, losses, reg, reg)
+    return pa, np.asfortranarray(0.3 * X0), np.asfortranarray(0.3 * Y0)
+
+
+def setup_knob_case(case):
+    """-> problem, start, create kwargs, environment E, the SETUP knobs flipped under the live handle, family bits, a check of the orders"""
+    if case == "heterogeneous LDS-tiled rows":
+        # k = 16: the lane family is out; n = 1 200 columns cross the window boundary at glrm_tile_rows(16) = 1 056; ~20 observations per row
+        pa, X0, Y0 = mixed_columns(1500, 1200, 16, 20)
+        flips = {"GLRM_HIP_GROUP_KINDS": "0", "GLRM_HIP_UDESC": "0", "GLRM_HIP_TILE_ROUNDS": "0"}
+        return pa, X0, Y0, {}, {"GLRM_HIP_TILED": "3"}, flips, 1 | 2, lambda o: o[0]["private_order"] == 2 and o[0]["window"] == 1056
+    if case == "cached register sweep":
+        from test_gpu_cached_chain import problem
+        pa, X0, Y0, lens = problem(1025, 64, long_rows=0)   # every row under glrm_cached_reg_maxlen(8) = 104
+        flips = {"GLRM_HIP_CACHED": "0", "GLRM_HIP_CACHED_WAVES": "1", "GLRM_HIP_CACHED_REGS": "0"}
+        return pa, X0, Y0, {"tiled": 1}, {"GLRM_HIP_CACHED": "1"}, flips, CACHED, lambda o: (o[0]["cached_maxlen"], o[0]["cached_waves"]) == (104, 2)
+    assert case == "lane passes"
+    m, n, k = 400, 600, 32   # the shape of test_arrival_order_with_one_super_tile_waits_for_every_block
+    rowptr, colidx, rowvals, colptr, rowidx, colvals, X0, Y0 = O.synth_cpu(m, n, k, 60, value_model=0)
+    one = np.array([(0, 0, 1.0, 0.0, 0.0)], dtype=_capi.LOSS_DTYPE)
+    reg = np.array([(1, 0, 0.5)], dtype=_capi.REG_DTYPE)
+    pa = _capi.ProblemArrays(m, n, k, rowptr, colidx, rowvals, colptr, rowidx, colvals, one, reg, reg)
+    flips = {"GLRM_HIP_LANE": "0", "GLRM_HIP_LANE_COMPACT": "1", "GLRM_HIP_LANE_PER_OBS": "0"}
+    return pa, np.asfortranarray(0.3 * X0), np.asfortranarray(0.3 * Y0), {"tiled": 2}, {}, flips, 256 | 512, lambda o: all(x["rotate"] == 2 and x["lanes"] == 2 for x in o)
+
+
+@pytest.mark.parametrize("case", ["heterogeneous LDS-tiled rows", "cached register sweep", "lane passes"])
+def test_setup_knobs_are_read_at_setup_and_asked_from_the_handle_afterwards(monkeypatch, case):
+    """A SETUP knob (csrc/glrm_knobs.hpp) decides what set-up builds and which summation order runs; what it decided is kept on the handle.
+    So a handle finalized under environment E, whose SETUP knobs are then set to other legal values, still runs and REPORTS what it built:
+    glrm_sum_order of both sides, kernel_stats, the factors and the objective after three iterations, and the trial / accept counts are those
+    of a handle that lives under E throughout, bit for bit."""
+    pa, X0, Y0, create_kw, env, flips, bits, order_ok = setup_knob_case(case)
+    for key in set(flips) | set(env):
+        monkeypatch.delenv(key, raising=False)
+    family_env.setenv(monkeypatch, env)
+    api = hip()
+    flipped = run_and_report(api, pa, X0, Y0, create_kw, bits, after_finalize=lambda: family_env.setenv(monkeypatch, flips))
+    for key in flips:
+        monkeypatch.delenv(key, raising=False)
+    family_env.setenv(monkeypatch, env)
+    plain = run_and_report(api, pa, X0, Y0, create_kw, bits)
+    assert order_ok(plain[0]), plain[0]
+    assert plain[1]["trials_x"] > 0 and plain[1]["trials_y"] > 0
+    same_run(flipped, plain)
+
+
+def test_a_call_knob_is_still_read_per_call(monkeypatch):
+    """GLRM_HIP_BLOCKED_GATE is a CALL knob: perf tools flip it on one live handle.  Another gate before every iteration -- off, one row,
+    an odd width -- gives the bits of a handle that never saw the variable (the gate changes no sum), on the mixed-loss shape of
+    test_phase_aligned_passes_mixed_losses_sorted_lists."""
+    force_blocked(monkeypatch)
+    monkeypatch.delenv("GLRM_HIP_BLOCKED_GATE", raising=False)
+    pa, X0, Y0 = mixed_columns(2500, 2000, 32, 100)
+    api = hip()
+    bits = BLOCKED_ROWS | BLOCKED_COLS
+    plain = run_and_report(api, pa, X0, Y0, {"tiled": 1}, bits)
+    flipped = run_and_report(api, pa, X0, Y0, {"tiled": 1}, bits, between=lambda it: monkeypatch.setenv("GLRM_HIP_BLOCKED_GATE", ("0", "1", "37")[it]))
+    assert plain[1]["trials_x"] > 0 and plain[1]["trials_y"] > 0
+    same_run(flipped, plain)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cases
+import family_env
 import lowrankmodels.jl_amd as L
 import oracle as O
 from lowrankmodels.jl_amd import _capi
@@ -277,11 +278,11 @@ def test_accounting_rotated_seeds(capsys):
 # ------------------------------------------------------------------------------------------------ every sweep family x {Logistic, OrdinalHinge}
 
 FAMILY_ENV = {
-    "gather": ({"GLRM_HIP_CACHED": "0", "GLRM_HIP_BLOCKED": "0"}, {"tiled": 1}, 0),
+    "gather": (family_env.GATHER, {"tiled": 1}, 0),
     "tiled": ({}, {"tiled": 2}, 3),
-    "blocked": ({"GLRM_HIP_BLOCKED": "3", "GLRM_HIP_BLOCKED_TPS": "1", "GLRM_HIP_BLOCKED_FILL": "3", "GLRM_HIP_CACHED": "0"}, {"tiled": 1}, 48),
-    "cached": ({"GLRM_HIP_CACHED": "1", "GLRM_HIP_BLOCKED": "0"}, {"tiled": 0}, 64),
-    "cached_nopersist": ({"GLRM_HIP_CACHED": "1", "GLRM_HIP_CACHED_PERSIST": "0", "GLRM_HIP_BLOCKED": "0"}, {"tiled": 0}, 64),
+    "blocked": (family_env.blocked("1", "3"), {"tiled": 1}, 48),
+    "cached": (family_env.cached(), {"tiled": 0}, 64),
+    "cached_nopersist": (family_env.cached(persist=False), {"tiled": 0}, 64),
 }
 
 

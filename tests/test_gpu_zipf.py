@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import cases
+import family_env
 import lowrankmodels.jl_amd as L
 import oracle as O
 from lowrankmodels.jl_amd import _capi, synth
@@ -31,7 +32,7 @@ def problem(m=30000, n=3000, k=32, nnz=3_000_000, s=0.8, nonneg=False, seed=5):
 FAMILIES = {  # name: (environment, create kwargs, kernel_stats.tiled bits that must be set)
     "gather": ({"GLRM_HIP_CACHED": "0"}, {"tiled": 1}, 0),
     "tiled": ({}, {"tiled": 2}, 3),
-    "blocked": ({"GLRM_HIP_BLOCKED": "3", "GLRM_HIP_BLOCKED_TPS": "2", "GLRM_HIP_BLOCKED_FILL": "5", "GLRM_HIP_CACHED": "0"}, {}, 16 | 32),
+    "blocked": (family_env.blocked("2", "5"), {}, 16 | 32),
     "cached": ({"GLRM_HIP_CACHED": "1"}, {"tiled": 1}, 64),
     "reference-order": ({}, {"sum_order": 1}, 128),
 }
