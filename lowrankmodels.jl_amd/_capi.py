@@ -174,6 +174,10 @@ TOPK_SYMBOLS = ("xy_select", "xy_select_info", "precision_scan")
 NMF_SYMBOLS = ("init_nndsvd",)
 NNDSVD_VARIANTS = {"std": 0, "a": 1, "ar": 2}   # glrm_hip_nmf.h: GLRM_NNDSVD_STD / _A / _AR (ar is refused)
 
+#: the transform extension, include/glrm_hip_transform.h (inner_iter X half-steps against a fixed Y, fused into one launch where the
+#: register kernel admits the rows): outside the boundary, bound only where the library has it
+TRANSFORM_SYMBOLS = ("solve_x", "solve_x_info")
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -276,8 +280,10 @@ class Api:
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
             "init_nndsvd": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+            "solve_x": (C.c_int, [H, C.c_int64, C.c_double]),
+            "solve_x_info": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + NMF_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -614,6 +620,30 @@ class Api:
         self._ck(fn(h, _ptr(X), _ptr(Y), 1 if scale else 0, 1 if zeroh else 0, NNDSVD_VARIANTS[variant], int(max_iters), int(svd_max_iter),
                     float(svd_tol), int(seed), _ptr(sv), _ptr(split), _ptr(iters)))
         return dict(singular_values=sv, split=split, iterations=iters)
+
+    # -- transform extension (include/glrm_hip_transform.h) ----------------------------------
+    def _transform(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the transform extension "
+                                             "(include/glrm_hip_transform.h is implemented by the HIP engine only)")
+        return fn
+
+    @property
+    def has_transform(self) -> bool:
+        """The library exports the transform extension (the CPU oracle does not: a host loops ``step_x`` there)."""
+        return "solve_x" in self._f
+
+    def solve_x(self, h, inner_iter, min_stepsize):
+        """glrm_hip_solve_x: ``inner_iter`` X half-steps of every local row with Y as it stands; the step sizes are not reset."""
+        self._ck(self._transform("solve_x")(h, int(inner_iter), float(min_stepsize)))
+
+    def solve_x_info(self, h) -> dict:
+        """What the last solve_x on the handle did: ``fused`` (1: rows of at most 104 / 208 observations ran all their steps in one launch
+        of the register kernel), ``fused_rows`` and ``loop_rows`` (rows that ran inner_iter sweep launches)."""
+        fused, fr, lr = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self._transform("solve_x_info")(h, C.byref(fused), C.byref(fr), C.byref(lr)))
+        return dict(fused=fused.value, fused_rows=fr.value, loop_rows=lr.value)
 
     # -- top-k extension (include/glrm_hip_topk.h) -------------------------------------------
     def _topk(self, name):

@@ -224,6 +224,20 @@ int launch_inst(const CachedArgs& a, hipStream_t st) {
 
 } // namespace
 
+// What the family asks of a problem before any size comes into it: `want` (the CACHED knob: -1 auto, 0 off, 1 wherever the rows fit) is
+// not off, the rows are not LDS-tiled, the row view holds an observation, and the lane layout is (4, 8) or (8, 8).
+static bool cached_admits(const glrm_handle* h, int want) {
+  if (want == 0 || h->side[GLRM_ROWS].tiled || h->sig.nnz_rows <= 0) return false;
+  return (h->G == 4 || h->G == 8) && h->R == 8;
+}
+// the variant: 2 registers, 1 LDS (GLRM_HIP_CACHED_REGS=0; fp64 only -- the LDS variant has no float form); the waves that share a row of
+// the register variant: two (GLRM_HIP_CACHED_WAVES = 1 | 4 are experiment switches of the fp64 kernels)
+static void cached_variant_of(const glrm_handle* h, int* variant, int* waves) {
+  const bool f32 = h->storage == GLRM_STORAGE_F32;
+  *variant = (f32 || knob(Knob::CACHED_REGS)) ? 2 : 1;
+  *waves = *variant != 2 ? 1 : f32 ? 2 : knob(Knob::CACHED_WAVES);
+}
+
 // Does the WHOLE problem run its short rows on the cached sweep (glrm_handle::cached_want)?  Auto (GLRM_HIP_CACHED unset): the rows
 // are not LDS-tiled, the opposing factor is beyond the sizes where the plain gathers already do well (> 32 MB) and the row view
 // holds >= 1e8 observations -- all read from glrm_signature and (m, n, k), never from the shard.  WHICH rows it takes is a
@@ -235,20 +249,22 @@ int launch_inst(const CachedArgs& a, hipStream_t st) {
 // family in both storages.  GLRM_CACHED_F32_AUTO says whether the measurement adopted it.
 int glrm_setup_cached(glrm_handle* h) {
   h->cached_row = h->cached_want = 0;
+  // glrm_hip_solve_x (glrm_handle::solve_ok): could the handle run the two-wave register variant here?  The same predicate without what
+  // decides the family of step_x -- glrm_options.tiled = 1 as the knob's default, and the auto rule's sizes below.  (The phase-aligned
+  // passes are set up after this; solve_x asks the handle's family when it is called.)
+  int variant, waves;
+  cached_variant_of(h, &variant, &waves);
+  h->solve_ok = cached_admits(h, knob_or(Knob::CACHED, -1)) && variant == 2 && waves == 2;
   const int want = knob_or(Knob::CACHED, h->tiled_opt == 1 ? 0 : -1); // -1 auto, 0 off, 1 wherever the rows fit
-  if (want == 0 || h->side[GLRM_ROWS].tiled || h->sig.nnz_rows <= 0) return GLRM_OK;
-  if (!((h->G == 4 || h->G == 8) && h->R == 8)) return GLRM_OK;
+  if (!cached_admits(h, want)) return GLRM_OK;
   if (want < 0) {
     if (h->storage == GLRM_STORAGE_F32 && !GLRM_CACHED_F32_AUTO) return GLRM_OK;
     const double opp_bytes = (double)h->n * h->kp * 8;
     if (opp_bytes <= 32.0 * 1024 * 1024 || (double)h->sig.nnz_rows < 1e8) return GLRM_OK;
   }
   h->cached_want = 1;
-  // the variant: 2 registers, 1 LDS (GLRM_HIP_CACHED_REGS=0; fp64 only -- the LDS variant has no float form); the waves that share a row of
-  // the register variant: two (GLRM_HIP_CACHED_WAVES = 1 | 4 are experiment switches of the fp64 kernels)
-  const bool f32 = h->storage == GLRM_STORAGE_F32;
-  h->cached_row = h->cached_variant = (f32 || knob(Knob::CACHED_REGS)) ? 2 : 1;
-  h->cached_waves = h->cached_variant != 2 ? 1 : f32 ? 2 : knob(Knob::CACHED_WAVES);
+  h->cached_row = h->cached_variant = variant;
+  h->cached_waves = waves;
   // longest row the sweep takes
   if (h->cached_variant == 2) {
     h->cached_maxlen = glrm_cached_reg_maxlen(h->G);

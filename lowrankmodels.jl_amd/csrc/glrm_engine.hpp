@@ -14,6 +14,8 @@
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
 //   glrm_nmf.hip        init_nndsvd!: NNDSVD and its soft-impute rounds on the resident lists (include/glrm_hip_nmf.h); shares the subspace
 //                       iteration of glrm_svd.hip through glrm_subspace.hpp
+//   glrm_solve.hip      the fused row solver of glrm_hip_solve_x (include/glrm_hip_transform.h): T X half-steps of a row in one launch of the
+//                       register kernel (glrm_solve.hpp); glrm_solve_f32.hip holds its float instantiations
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
@@ -32,6 +34,7 @@
 #include "../../include/glrm_hip.h"
 #include "../../include/glrm_hip_storage.h"
 #include "../../include/glrm_hip_regvec.h"
+#include "../../include/glrm_hip_transform.h"
 
 // kernel variants by loss model.  The *_NOTRIG variants are compiled without PeriodicLoss (its sin / cos with full range reduction
 // costs ~60 VGPRs of pressure in every kernel that merely CONTAINS the case); models without a PeriodicLoss column use them.
@@ -171,6 +174,17 @@ struct glrm_handle {
   // always, for float storage -- or 1 LDS), the waves that share a row of the register variant, the longest row the sweep takes
   int cached_variant = 0, cached_waves = 2;
   int64_t cached_maxlen = -1;
+  // glrm_hip_solve_x (include/glrm_hip_transform.h; glrm_solve.hpp).  solve_ok: set-up found that the handle COULD run the two-wave register
+  // variant of the cached row sweep on this problem (glrm_setup_cached: its predicate without the auto rule's sizes) -- whether step_x
+  // runs it or not.  A handle whose rows are not on that family gets a class plan of its own at its first solve_x: solve_list = the
+  // local rows class by class (class 0: the rows the register kernel takes), solve_ncls their counts, solve_cap the launch parameter
+  // of class 0 (trips of the lane layout its longest row needs).  solve_fused .. solve_loop_rows: what the last solve_x did (-1: none yet).
+  int solve_ok = 0, solve_cap = 0;
+  bool solve_planned = false;
+  int32_t* solve_list = nullptr;
+  int64_t solve_ncls[4] = {0, 0, 0, 0};
+  int solve_fused = -1;
+  int64_t solve_fused_rows = 0, solve_loop_rows = 0;
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]
@@ -340,6 +354,8 @@ constexpr int GLRM_CACHED_F32_AUTO = 0;
 constexpr int GLRM_BLOCKED_F32_AUTO = 0;
 void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
 int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, hipStream_t st);
+// the fused row solver of glrm_hip_solve_x (glrm_solve.hip): `inner` X half-steps of the listed rows in one launch
+int glrm_run_solve(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, int cap, int inner, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)
 int glrm_setup_dense(glrm_handle* h, const glrm_problem* p);
 int glrm_run_dense(glrm_handle* h, const glrm_step& step);

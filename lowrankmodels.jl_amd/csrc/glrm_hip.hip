@@ -946,6 +946,117 @@ extern "C" int glrm_hip_step_y(glrm_handle* h, double min_stepsize) {
   return run_sweep(h, search_step(GLRM_COLS, min_stepsize));
 }
 
+// ---- glrm_hip_solve_x (include/glrm_hip_transform.h): inner_iter X half-steps with Y as it stands ------------------------------------
+// The class plan of the fused path on a handle whose rows are NOT on the cached family: build_class_plan's, with the rows the two-wave
+// register kernel takes as class 0 -- what a handle of the same problem has under GLRM_HIP_CACHED=1.  Built once, at the first solve_x.
+static int build_solve_plan(glrm_handle* h) {
+  if (h->solve_planned) return GLRM_OK;
+  const glrm_handle::Side& v = h->side[GLRM_ROWS];
+  const int forced = forced_class(h->opts.waves_row);
+  const int64_t cmax = glrm_cached_reg_maxlen(h->G);
+  std::vector<int64_t> ptr;
+  int rc = glrm_host_ptr(h, GLRM_ROWS, ptr);
+  if (rc) return rc;
+  auto cls_of = [&](int64_t s) { const int64_t len = ptr[s + 1] - ptr[s]; return len <= cmax ? 0 : (forced ? forced : glrm_wave_class(len)); };
+  int64_t n[4] = {0, 0, 0, 0}, longest = 0;
+  for (int64_t s = 0; s < v.nseg; ++s) {
+    const int c = cls_of(s);
+    ++n[c];
+    if (c == 0) longest = std::max(longest, ptr[s + 1] - ptr[s]);
+  }
+  std::vector<int32_t> lst((size_t)v.nseg);
+  int64_t pos[4] = {0, n[0], n[0] + n[1], n[0] + n[1] + n[2]};
+  for (int64_t s = 0; s < v.nseg; ++s) lst[(size_t)pos[cls_of(s)]++] = (int32_t)s;
+  if ((rc = glrm_upload_list(h, lst, &h->solve_list))) return rc;
+  if ((rc = glrm_ensure_side_stream(h))) return rc;
+  for (int c = 0; c < 4; ++c) h->solve_ncls[c] = n[c];
+  const int ng = 64 / h->G;
+  h->solve_cap = (int)((longest + ng - 1) / ng); // (glrm_cached_set_cap, register variant)
+  h->solve_planned = true;
+  return GLRM_OK;
+}
+
+// the fused path: class 0 in one launch of the register kernel on the main stream, the longer rows `inner` launches of the gather sweep
+// per class on the side stream (rows are independent: the two run side by side)
+static int solve_fused(glrm_handle* h, int inner, double min_stepsize) {
+  RoctxRange range("glrm solve_x");
+  int rc = ensure_owned(h);
+  if (rc) return rc;
+  glrm_handle::Side& v = h->side[GLRM_ROWS];
+  // the handle's own plan where its rows are on the family (cached_row = 2: two waves, by solve_ok), else the plan built here
+  const bool own = h->cached_row == 2;
+  if (!own && (rc = build_solve_plan(h))) return rc;
+  const int64_t* ncls = own ? v.ncls : h->solve_ncls;
+  const int32_t* lst = own ? v.seglist : h->solve_list;
+  const int cap = own ? h->cached_cap : h->solve_cap;
+  glrm_step step = search_step(GLRM_ROWS, min_stepsize);
+  step.loss = loss_variant(h, GLRM_ROWS, &step.loss_by_segment);
+  glrm_handle::Ev ev{};
+  if (h->profile && (rc = begin_timing(h, GLRM_ROWS, &ev))) return rc;
+  const int64_t nlong = ncls[1] + ncls[2] + ncls[3];
+  if (nlong > 0 && ((rc = glrm_ensure_side_stream(h)) || (rc = glrm_fork_side_stream(h)))) return rc;
+  rc = glrm_run_solve(h, step, lst, ncls[0], cap, inner, h->stream);
+  if (nlong > 0) {
+    SweepArgs a{};
+    glrm_fill_side(a, h, step);
+    a.storage = h->storage;
+    a.seg_lo = 0;
+    a.seg_hi = a.nseg;
+    a.loss_by_segment = step.loss_by_segment;
+    for (int it = 0; it < inner && !rc; ++it) {
+      int64_t off = ncls[0];
+      for (int c = 1; c < 4; off += ncls[c], ++c) {
+        if (ncls[c] <= 0) continue;
+        SweepArgs b = a;
+        b.seglist = lst ? lst + off : nullptr; // (no list: one class holds every local row)
+        b.nseg = ncls[c];
+        launch_sweep(h->G, h->R, glrm_class_waves(c), step.loss, GLRM_ROWS, b, h->side_stream);
+      }
+    }
+    // join also before reporting an error: later work on h->stream must stay ordered after what the side stream already holds
+    const hipError_t e_join = glrm_join_side_stream(h);
+    if (rc) return rc;
+    HIPCK(e_join);
+  }
+  if (rc) return rc;
+  HIPCK(hipGetLastError());
+  if (h->profile) {
+    HIPCK(hipEventRecord(ev.b, h->stream));
+    h->pending.push_back(ev);
+    if (h->pending.size() >= 4096 && (rc = drain_events(h))) return rc;
+  }
+  v.launches += inner;
+  h->solve_fused = 1;
+  h->solve_fused_rows = ncls[0];
+  h->solve_loop_rows = nlong;
+  return GLRM_OK;
+}
+
+extern "C" int glrm_hip_solve_x(glrm_handle* h, int64_t inner_iter, double min_stepsize) {
+  if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
+  if (inner_iter < 1 || inner_iter > INT32_MAX) return fail(GLRM_ERR_INVALID, "inner_iter must be in [1, 2^31 - 1]");
+  GLRM_NEED_FINALIZED(h);
+  DeviceScope dg(h->device);
+  const glrm_handle::Side& v = h->side[GLRM_ROWS];
+  // fused: set-up found the two-wave register kernel admissible (glrm_setup_cached) and the rows run the gather family now
+  if (h->solve_ok && v.nseg > 0 && glrm_side_family(h, GLRM_ROWS, false) == GLRM_FAM_GATHER) return solve_fused(h, (int)inner_iter, min_stepsize);
+  for (int64_t it = 0; it < inner_iter; ++it)
+    if (const int rc = run_sweep(h, search_step(GLRM_ROWS, min_stepsize))) return rc;
+  h->solve_fused = 0;
+  h->solve_fused_rows = 0;
+  h->solve_loop_rows = v.nseg;
+  return GLRM_OK;
+}
+
+extern "C" int glrm_hip_solve_x_info(glrm_handle* h, int32_t* fused, int64_t* fused_rows, int64_t* loop_rows) {
+  if (!h) return fail(GLRM_ERR_INVALID, "NULL handle");
+  if (h->solve_fused < 0) return fail(GLRM_ERR_INVALID, "glrm_hip_solve_x has not run on this handle");
+  if (fused) *fused = h->solve_fused;
+  if (fused_rows) *fused_rows = h->solve_fused_rows;
+  if (loop_rows) *loop_rows = h->solve_loop_rows;
+  return GLRM_OK;
+}
+
 // the Y half-step runs as passes over super-tiles (LDS-tiled, lane or phase-aligned)
 static bool col_passes(const glrm_handle* h) {
   const glrm_family fam = glrm_side_family(h, GLRM_COLS, false);
