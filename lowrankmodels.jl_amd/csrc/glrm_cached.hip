@@ -276,25 +276,24 @@ int glrm_setup_cached(glrm_handle* h) {
   return GLRM_OK;
 }
 
-// the launch parameter of the cached kernels for a longest row of `maxlen` observations
-void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen) {
-  if (h->cached_row == 2) {
-    const int ng = 64 / h->G;
-    h->cached_cap = (int)((maxlen + ng - 1) / ng);
-  } else {
-    const int vpi = 64 / (h->kp * 8 / 16);
-    h->cached_cap = (int)((maxlen + vpi - 1) / vpi * vpi);
-    if (h->cached_cap < vpi) h->cached_cap = vpi;
+// the launch parameter of the cached kernels for a longest row of `maxlen` observations: trips of the lane layout (variant 2, registers),
+// vectors in LDS (variant 1)
+int glrm_cached_cap(int variant, int G, int kp, int64_t maxlen) {
+  if (variant == 2) {
+    const int ng = 64 / G;
+    return (int)((maxlen + ng - 1) / ng);
   }
+  const int vpi = 64 / (kp * 8 / 16);
+  return std::max(vpi, (int)((maxlen + vpi - 1) / vpi * vpi));
 }
 
 // An X half-step (never an evaluation) of the request.  seglist == nullptr: every local row (restricted to the request's row range, if it
-// has one); otherwise the rows listed
-int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, hipStream_t st) {
+// has one); otherwise the rows listed.  cap: glrm_class_plan::cap of the row plan
+int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, int cap, hipStream_t st) {
   const int loss = step.loss;
   CachedArgs a{};
   glrm_fill_side(a, h, step);
-  a.cap = h->cached_cap;
+  a.cap = cap;
   a.seg_lo = 0;
   a.seg_hi = h->side[GLRM_ROWS].nseg;
   if (seglist) {

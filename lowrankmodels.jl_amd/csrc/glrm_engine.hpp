@@ -20,7 +20,8 @@
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
 // the opposing side is side ^ 1); glrm_step is what ONE half-step is asked to do, built by the entry point and passed down as an argument
-// (the handle holds nothing about a call in flight); glrm_side_family is the one place that says which kernel family runs a side.
+// (the handle holds nothing about a call in flight); glrm_side_family is the one place that says which kernel family runs a side;
+// glrm_segment_class is the one rule for the class of a segment on the gather family and glrm_class_plan the plan made from it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,6 +70,17 @@ inline int fail(int code, const char* fmt, ...) {
 
 // which side of the factorization: glrm_handle::side[] and every `int side` argument are indexed by it; the opposing side is side ^ 1
 enum { GLRM_ROWS = 0, GLRM_COLS = 1 }; // rows = row view, X half-step; columns = column view, Y half-step
+
+// The class plan of one view on the gather family (glrm_hip.hip: build_class_plan fills it, glrm_for_each_class launches it).  n counts the
+// local segments per class of glrm_segment_class (0: the rows a cached kernel holds on chip); when more than one class is populated, list
+// holds the local segments class by class (ascending ids inside a class) and each class gets its own launch -- nullptr: one class holds
+// every local segment.  cap is the launch parameter of class 0 (glrm_cached_cap of its longest row).
+struct glrm_class_plan {
+  int32_t* list = nullptr;
+  int64_t n[4] = {0, 0, 0, 0};
+  int cap = 0;
+  bool built = false;
+};
 
 struct glrm_handle {
   int device = 0;
@@ -131,10 +143,9 @@ struct glrm_handle {
     int64_t blocked_cap[2] = {0, 0};  // phase-aligned passes: segments per launch slice, [gradient / trial instantiation]
     // Gather sweeps: the waves that share a segment are a function of the segment's OWN length (1 below 1536 observations, 4 below
     // 98304, else 8; glrm_options.waves_* pins one count for all), so the order of a segment's sums never depends on which shard
-    // holds it.  Class 0 = rows the cached sweep holds on chip.  ncls counts the local segments per class; when more than one class
-    // is populated seglist lists the segments class by class (ascending ids inside a class) and each class gets its own launch.
+    // holds it.  Class 0 = rows the cached sweep holds on chip.  plan: what finalize found on this shard.
     int waves = 1;                    // the class most local segments fall into (reported by glrm_hip_kernel_stats); columns start at 4
-    int32_t* seglist = nullptr; int64_t ncls[4] = {0, 0, 0, 0};
+    glrm_class_plan plan;
     // dense MFMA path (glrm_dense.hip)
     double* A = nullptr; int64_t lda = 0; // packed, zero padded: [nseg_pad][lda]
     int64_t vps = 0;                  // opposing vectors per super-tile
@@ -168,7 +179,7 @@ struct glrm_handle {
   bool dense = false;
   double dense_scale = 1.0;
   // rows only: the cached gather row sweep
-  int cached_row = 0, cached_cap = 0; // cached gather row sweep (glrm_cached.hip): 0 off, 1 LDS, 2 registers; trips / vectors a row may have
+  int cached_row = 0;                 // cached gather row sweep (glrm_cached.hip): 0 off, 1 LDS, 2 registers
   int cached_want = 0;                // the whole problem runs its short rows on the cached sweep (decided from glrm_signature, never from the shard)
   // what glrm_setup_cached decided for the whole problem (they hold on a shard whose cached_row fell to 0, too): the variant (2 registers --
   // always, for float storage -- or 1 LDS), the waves that share a row of the register variant, the longest row the sweep takes
@@ -176,13 +187,10 @@ struct glrm_handle {
   int64_t cached_maxlen = -1;
   // glrm_hip_solve_x (include/glrm_hip_transform.h; glrm_solve.hpp).  solve_ok: set-up found that the handle COULD run the two-wave register
   // variant of the cached row sweep on this problem (glrm_setup_cached: its predicate without the auto rule's sizes) -- whether step_x
-  // runs it or not.  A handle whose rows are not on that family gets a class plan of its own at its first solve_x: solve_list = the
-  // local rows class by class (class 0: the rows the register kernel takes), solve_ncls their counts, solve_cap the launch parameter
-  // of class 0 (trips of the lane layout its longest row needs).  solve_fused .. solve_loop_rows: what the last solve_x did (-1: none yet).
-  int solve_ok = 0, solve_cap = 0;
-  bool solve_planned = false;
-  int32_t* solve_list = nullptr;
-  int64_t solve_ncls[4] = {0, 0, 0, 0};
+  // runs it or not.  A handle whose rows are not on that family gets a row plan of its own at its first solve_x: solve_plan, with the
+  // rows the register kernel takes as class 0.  solve_fused .. solve_loop_rows: what the last solve_x did (-1: none yet).
+  int solve_ok = 0;
+  glrm_class_plan solve_plan;
   int solve_fused = -1;
   int64_t solve_fused_rows = 0, solve_loop_rows = 0;
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
@@ -272,10 +280,20 @@ inline bool glrm_single_shard(const glrm_handle* h) { return h->side[GLRM_ROWS].
 namespace glrm { struct TiledArgs; }
 
 
-// per-segment class of the gather sweeps (see glrm_handle::Side::seglist)
+// per-segment class of the gather sweeps (see glrm_class_plan)
 constexpr int64_t GLRM_WAVES4_FROM = 1536, GLRM_WAVES8_FROM = 98304;
 __host__ __device__ inline int glrm_wave_class(int64_t len) { return len < GLRM_WAVES4_FROM ? 1 : (len < GLRM_WAVES8_FROM ? 2 : 3); }
 constexpr int glrm_class_waves(int cls) { return cls <= 1 ? 1 : (cls == 2 ? 4 : 8); }
+// the class glrm_options.waves_row / waves_col pins for every segment of a side (1 / 4 / 8 waves), 0 for any other value: none
+inline int glrm_forced_class(const glrm_handle* h, int side) {
+  const int waves = side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col;
+  return waves == 1 ? 1 : (waves == 4 ? 2 : (waves == 8 ? 3 : 0));
+}
+// THE class of a segment of `len` observations: 0 where a cached kernel takes it (len <= cached_maxlen; cached_maxlen < 0: no segment),
+// else the pinned class (forced > 0), else the one its own length asks for
+__host__ __device__ inline int glrm_segment_class(int64_t len, int64_t cached_maxlen, int forced) {
+  return (cached_maxlen >= 0 && len <= cached_maxlen) ? 0 : (forced > 0 ? forced : glrm_wave_class(len));
+}
 // rows the register-cached sweep takes: at most 13 trips of the lane layout, 64 / G observations each
 inline int64_t glrm_cached_reg_maxlen(int G) { return (int64_t)13 * (64 / G); }
 
@@ -352,8 +370,8 @@ constexpr int GLRM_CACHED_F32_AUTO = 0;
 // float storage, GLRM_HIP_BLOCKED unset: 1 = the fp64 auto rule of the phase-aligned passes applies, 0 = the family stays behind
 // GLRM_HIP_BLOCKED (turning it on changes which kernels, and which summation order, existing float handles take)
 constexpr int GLRM_BLOCKED_F32_AUTO = 0;
-void glrm_cached_set_cap(glrm_handle* h, int64_t maxlen);
-int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, hipStream_t st);
+int glrm_cached_cap(int variant, int G, int kp, int64_t maxlen); // the launch parameter of a variant's kernels for a longest row of maxlen
+int glrm_run_cached(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, int cap, hipStream_t st);
 // the fused row solver of glrm_hip_solve_x (glrm_solve.hip): `inner` X half-steps of the listed rows in one launch
 int glrm_run_solve(glrm_handle* h, const glrm_step& step, const int32_t* seglist, int64_t nlist, int cap, int inner, hipStream_t st);
 // dense MFMA path (glrm_dense.hip)

@@ -86,11 +86,11 @@ __global__ void seg_stats_kernel(const int64_t* ptr, int64_t nseg, int forced_cl
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
     const int64_t len = ptr[s + 1] - ptr[s];
     mx = (unsigned long long)len > mx ? (unsigned long long)len : mx;
-    if (cache_maxlen >= 0 && len <= cache_maxlen) {
+    const int cls = glrm_segment_class(len, cache_maxlen, forced_cls);
+    if (cls == 0) {
       ++cc;
       mc = (unsigned long long)len > mc ? (unsigned long long)len : mc;
     } else {
-      const int cls = forced_cls > 0 ? forced_cls : glrm_wave_class(len);
       c1 += cls == 1; c2 += cls == 2; c3 += cls == 3;
     }
   }
@@ -355,43 +355,51 @@ static int view_stats(glrm_handle* h, int side, int forced_cls, int64_t cache_ma
   return GLRM_OK;
 }
 
-static int forced_class(int waves_opt) { return waves_opt == 1 ? 1 : (waves_opt == 4 ? 2 : (waves_opt == 8 ? 3 : 0)); }
-
-// The class plan of a view that runs on the gather sweeps (and, for rows, the cached sweep): every segment is swept by the number of
-// waves its OWN length asks for (glrm_wave_class; glrm_options.waves_* pins one count), rows short enough for the cached sweep by that
-// one -- so a segment is summed in the same order whichever shard holds it.  One populated class: one launch over all local segments.
-// Several (skewed lengths: a few very popular columns / very active rows next to many short ones): seglist = the segments class by
-// class, one launch per class, the minority classes on a side stream beside the main launch.
-static int build_class_plan(glrm_handle* h, int side) {
-  glrm_handle::Side& v = h->side[side];
-  int64_t* ncls = v.ncls;
-  const int forced = forced_class(side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col);
-  const bool cached = side == GLRM_ROWS && h->cached_row != 0; // only rows have a cached sweep
-  const int64_t cmax = cached ? h->cached_maxlen : -1;
+// The class plan of a view that runs on the gather sweeps (and, for rows, a cached kernel: cached_maxlen >= 0, `variant` names the cap
+// formula): every segment is swept by the number of waves its OWN length asks for (glrm_segment_class; glrm_options.waves_* pins one
+// count), rows short enough for the cached kernel by that one -- so a segment is summed in the same order whichever shard holds it.  One
+// populated class: one launch over all local segments, no list.  Several (skewed lengths: a few very popular columns / very active rows
+// next to many short ones): the segments class by class, one launch per class (glrm_for_each_class).  Writes the plan and, for a list,
+// creates the side stream: nothing else of the handle.
+static int build_class_plan(glrm_handle* h, int side, int64_t cached_maxlen, int variant, glrm_class_plan* plan) {
+  const glrm_handle::Side& v = h->side[side];
+  const int forced = glrm_forced_class(h, side);
   unsigned long long st[6];
-  int rc = view_stats(h, side, forced, cmax, st);
+  int rc = view_stats(h, side, forced, cached_maxlen, st);
   if (rc) return rc;
-  ncls[0] = (int64_t)st[4]; ncls[1] = (int64_t)st[1]; ncls[2] = (int64_t)st[2]; ncls[3] = (int64_t)st[3];
-  if (cached) {
-    if (ncls[0] == 0) h->cached_row = 0; // this shard holds no row the cached sweep takes
-    else glrm_cached_set_cap(h, (int64_t)st[5]);
+  int64_t* n = plan->n;
+  n[0] = (int64_t)st[4]; n[1] = (int64_t)st[1]; n[2] = (int64_t)st[2]; n[3] = (int64_t)st[3];
+  plan->cap = n[0] > 0 ? glrm_cached_cap(variant, h->G, h->kp, (int64_t)st[5]) : 0;
+  int populated = 0;
+  for (int c = 0; c < 4; ++c) populated += n[c] > 0;
+  if (populated > 1) {
+    std::vector<int64_t> ptr;
+    if ((rc = glrm_host_ptr(h, side, ptr))) return rc;
+    std::vector<int32_t> lst((size_t)v.nseg);
+    int64_t pos[4] = {0, n[0], n[0] + n[1], n[0] + n[1] + n[2]};
+    for (int64_t s = 0; s < v.nseg; ++s) lst[(size_t)pos[glrm_segment_class(ptr[s + 1] - ptr[s], cached_maxlen, forced)]++] = (int32_t)s;
+    if ((rc = glrm_upload_list(h, lst, &plan->list))) return rc;
+    if ((rc = glrm_ensure_side_stream(h))) return rc;
   }
-  int best = 1, populated = 0;
-  for (int c = 0; c < 4; ++c) populated += ncls[c] > 0;
-  for (int c = 2; c < 4; ++c) if (ncls[c] > ncls[best]) best = c;
-  v.waves = forced ? glrm_class_waves(forced) : glrm_class_waves(best);
-  if (populated <= 1) return GLRM_OK;
-  std::vector<int64_t> ptr;
-  if ((rc = glrm_host_ptr(h, side, ptr))) return rc;
-  std::vector<int32_t> lst((size_t)v.nseg);
-  int64_t pos[4] = {0, ncls[0], ncls[0] + ncls[1], ncls[0] + ncls[1] + ncls[2]};
-  for (int64_t s = 0; s < v.nseg; ++s) {
-    const int64_t len = ptr[s + 1] - ptr[s];
-    const int c = (cmax >= 0 && len <= cmax) ? 0 : (forced ? forced : glrm_wave_class(len));
-    lst[(size_t)pos[c]++] = (int32_t)s;
+  plan->built = true;
+  return GLRM_OK;
+}
+
+// finalize: the plans of the sides the gather family runs, and what they say about the handle -- no row for the cached sweep on this shard:
+// cached_row falls to 0; Side::waves: the pinned count, else that of the fullest class by length (ties: the lower)
+static int plan_gather_sides(glrm_handle* h) {
+  for (int s = 0; s < 2; ++s) {
+    glrm_handle::Side& v = h->side[s];
+    if (v.tiled || v.blocked) continue;
+    const bool cached = s == GLRM_ROWS && h->cached_row != 0; // only rows have a cached sweep
+    if (const int rc = build_class_plan(h, s, cached ? h->cached_maxlen : -1, h->cached_row, &v.plan)) return rc;
+    if (cached && v.plan.n[0] == 0) h->cached_row = 0;
+    const int forced = glrm_forced_class(h, s);
+    int best = 1;
+    for (int c = 2; c < 4; ++c) if (v.plan.n[c] > v.plan.n[best]) best = c;
+    v.waves = glrm_class_waves(forced ? forced : best);
   }
-  if ((rc = glrm_upload_list(h, lst, &v.seglist))) return rc;
-  return glrm_ensure_side_stream(h);
+  return GLRM_OK;
 }
 
 static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options* o) {
@@ -513,8 +521,7 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     for (int s = 0; s < 2; ++s) h->side[s].tiled = h->side[s].blocked = 0;
     if ((rc = glrm_setup_cached(h))) return rc;
     if ((rc = glrm_setup_blocked(h))) return rc;
-    for (int s = 0; s < 2; ++s)
-      if (!h->side[s].blocked && (rc = build_class_plan(h, s))) return rc;
+    if ((rc = plan_gather_sides(h))) return rc;
   } else if (h->multi || h->dense) {
     for (int s = 0; s < 2; ++s) h->side[s].waves = opt_waves[s] ? opt_waves[s] : (s == GLRM_ROWS ? 1 : 4);
     if (h->multi && (rc = glrm_setup_multi_split(h))) return rc;
@@ -526,8 +533,7 @@ static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
     if ((rc = glrm_setup_tiled(h))) return rc;
     if ((rc = glrm_setup_cached(h))) return rc;
     if ((rc = glrm_setup_blocked(h))) return rc;
-    for (int s = 0; s < 2; ++s)
-      if (!h->side[s].tiled && !h->side[s].blocked && (rc = build_class_plan(h, s))) return rc;
+    if ((rc = plan_gather_sides(h))) return rc;
     h->finalize_failed = false;
   }
   HIPCK(hipStreamSynchronize(h->stream));
@@ -802,13 +808,39 @@ static int loss_variant(const glrm_handle* h, int side, int* by_segment) {
   return h->has_trig ? loss : loss + 2; // LOSS_*_NOTRIG: kernels compiled without the PeriodicLoss case
 }
 
-// An event pair from the pool (or a new one) with `a` recorded on the stream: the caller records `b` behind what it times and appends the
-// pair to h->pending.  slot: glrm_handle::Ev
+// An event pair from the pool (or a new one) with `a` recorded on the stream; end_timing records `b` behind what the caller timed and
+// queues the pair for glrm_hip_kernel_stats (at 4096 waiting pairs it reads them out itself).  slot: glrm_handle::Ev
 static int begin_timing(glrm_handle* h, int slot, glrm_handle::Ev* ev) {
   if (!h->pool.empty()) { *ev = h->pool.back(); h->pool.pop_back(); }
   else { HIPCK(hipEventCreate(&ev->a)); HIPCK(hipEventCreate(&ev->b)); }
   ev->slot = slot;
   HIPCK(hipEventRecord(ev->a, h->stream));
+  return GLRM_OK;
+}
+static int end_timing(glrm_handle* h, const glrm_handle::Ev& ev) {
+  HIPCK(hipEventRecord(ev.b, h->stream));
+  h->pending.push_back(ev);
+  return h->pending.size() >= 4096 ? drain_events(h) : GLRM_OK;
+}
+
+// launch(class, list, n, stream) for every populated class of a plan.  One class holds every local segment: one call without a list on
+// h->stream.  Several: fork, main_cls on h->stream beside the other classes on the side stream (in class order), join.
+template <typename Launch>
+static int glrm_for_each_class(glrm_handle* h, const glrm_class_plan& p, int main_cls, const Launch& launch) {
+  if (!p.list) {
+    int cls = 1;
+    for (int c = 0; c < 4; ++c) if (p.n[c] > 0) cls = c;
+    return launch(cls, (const int32_t*)nullptr, p.n[cls], h->stream);
+  }
+  int rc = glrm_fork_side_stream(h);
+  if (rc) return rc;
+  int64_t off = 0;
+  for (int c = 0; c < 4 && !rc; off += p.n[c], ++c)
+    if (p.n[c] > 0) rc = launch(c, (const int32_t*)p.list + off, p.n[c], c == main_cls ? h->stream : h->side_stream);
+  // join also before reporting an error: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
+  const hipError_t e_join = glrm_join_side_stream(h);
+  if (rc) return rc;
+  HIPCK(e_join);
   return GLRM_OK;
 }
 
@@ -831,7 +863,7 @@ static int run_sweep(glrm_handle* h, glrm_step step) {
   a.seg_hi = a.nseg;
   if (step.ranged()) { // glrm_hip_step_x_range
     if (step.row_end - step.row_begin <= 0) return GLRM_OK;
-    if (v.seglist) { // several classes: the class launches filter their lists by the range
+    if (v.plan.list) { // several classes: the class launches filter their lists by the range
       a.seg_lo = step.row_begin; a.seg_hi = step.row_end;
     } else {
       glrm_apply_row_range(a, step);
@@ -867,49 +899,21 @@ static int run_sweep(glrm_handle* h, glrm_step step) {
     rc = fam == GLRM_FAM_TILED ? glrm_run_tiled(h, step) : glrm_run_blocked(h, step);
     if (divert) (void)glrm_join_side_stream(h); // join before anything else (also before reporting an error: later work on the stream stays ordered)
   } else {
-    // gather sweeps (and the cached row sweep), class by class -- see build_class_plan
-    const int64_t* ncls = v.ncls;
-    const int32_t* lst = v.seglist;
-    if (!lst) { // one class holds every local segment
-      int cls = 1;
-      for (int c = 0; c < 4; ++c) if (ncls[c] > 0) cls = c;
-      if (cls == 0 && !eval_only) {
-        if ((rc = glrm_run_cached(h, step, nullptr, 0, h->stream))) return rc;
-      } else {
-        launch_sweep(h->G, h->R, cls == 0 ? 1 : glrm_class_waves(cls), loss, side, a, h->stream);
-      }
-    } else {
-      // fork: the minority classes on the side stream, beside the majority class on the main stream; join
-      int main_cls = 0;
-      for (int c = 1; c < 4; ++c) if (ncls[c] > ncls[main_cls]) main_cls = c;
-      if ((rc = glrm_fork_side_stream(h))) return rc;
-      int64_t off = 0;
-      int rc_cls = GLRM_OK;
-      for (int c = 0; c < 4 && !rc_cls; off += ncls[c], ++c) {
-        if (ncls[c] <= 0) continue;
-        hipStream_t st = c == main_cls ? h->stream : h->side_stream;
-        if (c == 0 && !eval_only) {
-          rc_cls = glrm_run_cached(h, step, lst + off, ncls[0], st);
-        } else {
-          SweepArgs b = a;
-          b.seglist = lst + off;
-          b.nseg = ncls[c];
-          launch_sweep(h->G, h->R, c == 0 ? 1 : glrm_class_waves(c), loss, side, b, st);
-        }
-      }
-      // join also before reporting an error: later work on h->stream (and a stream capture) must stay ordered after what the side stream already holds
-      const hipError_t e_join = glrm_join_side_stream(h);
-      if (rc_cls) return rc_cls;
-      HIPCK(e_join);
-    }
+    // gather sweeps (and the cached row sweep), class by class -- see build_class_plan; the fullest class on the main stream (ties: the lower)
+    const glrm_class_plan& p = v.plan;
+    int main_cls = 0;
+    for (int c = 1; c < 4; ++c) if (p.n[c] > p.n[main_cls]) main_cls = c;
+    rc = glrm_for_each_class(h, p, main_cls, [&](int cls, const int32_t* list, int64_t n, hipStream_t st) {
+      if (cls == 0 && !eval_only) return glrm_run_cached(h, step, list, n, p.cap, st);
+      SweepArgs b = a;
+      if (list) { b.seglist = list; b.nseg = n; }
+      launch_sweep(h->G, h->R, glrm_class_waves(cls), loss, side, b, st);
+      return (int)GLRM_OK;
+    });
   }
   if (rc) return rc;
   HIPCK(hipGetLastError());
-  if (timed) {
-    HIPCK(hipEventRecord(ev.b, h->stream));
-    h->pending.push_back(ev);
-    if (h->pending.size() >= 4096) { rc = drain_events(h); if (rc) return rc; }
-  }
+  if (timed && (rc = end_timing(h, ev))) return rc;
   if (!eval_only) v.launches += 1;
   return GLRM_OK;
 }
@@ -947,88 +951,42 @@ extern "C" int glrm_hip_step_y(glrm_handle* h, double min_stepsize) {
 }
 
 // ---- glrm_hip_solve_x (include/glrm_hip_transform.h): inner_iter X half-steps with Y as it stands ------------------------------------
-// The class plan of the fused path on a handle whose rows are NOT on the cached family: build_class_plan's, with the rows the two-wave
-// register kernel takes as class 0 -- what a handle of the same problem has under GLRM_HIP_CACHED=1.  Built once, at the first solve_x.
-static int build_solve_plan(glrm_handle* h) {
-  if (h->solve_planned) return GLRM_OK;
-  const glrm_handle::Side& v = h->side[GLRM_ROWS];
-  const int forced = forced_class(h->opts.waves_row);
-  const int64_t cmax = glrm_cached_reg_maxlen(h->G);
-  std::vector<int64_t> ptr;
-  int rc = glrm_host_ptr(h, GLRM_ROWS, ptr);
-  if (rc) return rc;
-  auto cls_of = [&](int64_t s) { const int64_t len = ptr[s + 1] - ptr[s]; return len <= cmax ? 0 : (forced ? forced : glrm_wave_class(len)); };
-  int64_t n[4] = {0, 0, 0, 0}, longest = 0;
-  for (int64_t s = 0; s < v.nseg; ++s) {
-    const int c = cls_of(s);
-    ++n[c];
-    if (c == 0) longest = std::max(longest, ptr[s + 1] - ptr[s]);
-  }
-  std::vector<int32_t> lst((size_t)v.nseg);
-  int64_t pos[4] = {0, n[0], n[0] + n[1], n[0] + n[1] + n[2]};
-  for (int64_t s = 0; s < v.nseg; ++s) lst[(size_t)pos[cls_of(s)]++] = (int32_t)s;
-  if ((rc = glrm_upload_list(h, lst, &h->solve_list))) return rc;
-  if ((rc = glrm_ensure_side_stream(h))) return rc;
-  for (int c = 0; c < 4; ++c) h->solve_ncls[c] = n[c];
-  const int ng = 64 / h->G;
-  h->solve_cap = (int)((longest + ng - 1) / ng); // (glrm_cached_set_cap, register variant)
-  h->solve_planned = true;
-  return GLRM_OK;
-}
-
 // the fused path: class 0 in one launch of the register kernel on the main stream, the longer rows `inner` launches of the gather sweep
-// per class on the side stream (rows are independent: the two run side by side)
+// per class beside it (rows are independent: the classes run side by side)
 static int solve_fused(glrm_handle* h, int inner, double min_stepsize) {
   RoctxRange range("glrm solve_x");
   int rc = ensure_owned(h);
   if (rc) return rc;
   glrm_handle::Side& v = h->side[GLRM_ROWS];
-  // the handle's own plan where its rows are on the family (cached_row = 2: two waves, by solve_ok), else the plan built here
-  const bool own = h->cached_row == 2;
-  if (!own && (rc = build_solve_plan(h))) return rc;
-  const int64_t* ncls = own ? v.ncls : h->solve_ncls;
-  const int32_t* lst = own ? v.seglist : h->solve_list;
-  const int cap = own ? h->cached_cap : h->solve_cap;
+  // the handle's own plan where its rows are on the family (cached_row = 2: two waves, by solve_ok); else build_class_plan's with the rows the
+  // two-wave register kernel takes as class 0 -- what a handle of the same problem has under GLRM_HIP_CACHED=1 -- built once, here
+  glrm_class_plan& p = h->cached_row == 2 ? v.plan : h->solve_plan;
+  if (!p.built && (rc = build_class_plan(h, GLRM_ROWS, glrm_cached_reg_maxlen(h->G), 2, &p))) return rc;
   glrm_step step = search_step(GLRM_ROWS, min_stepsize);
   step.loss = loss_variant(h, GLRM_ROWS, &step.loss_by_segment);
+  SweepArgs a{};
+  glrm_fill_side(a, h, step);
+  a.storage = h->storage;
+  a.seg_lo = 0;
+  a.seg_hi = a.nseg;
+  a.loss_by_segment = step.loss_by_segment;
   glrm_handle::Ev ev{};
   if (h->profile && (rc = begin_timing(h, GLRM_ROWS, &ev))) return rc;
-  const int64_t nlong = ncls[1] + ncls[2] + ncls[3];
-  if (nlong > 0 && ((rc = glrm_ensure_side_stream(h)) || (rc = glrm_fork_side_stream(h)))) return rc;
-  rc = glrm_run_solve(h, step, lst, ncls[0], cap, inner, h->stream);
-  if (nlong > 0) {
-    SweepArgs a{};
-    glrm_fill_side(a, h, step);
-    a.storage = h->storage;
-    a.seg_lo = 0;
-    a.seg_hi = a.nseg;
-    a.loss_by_segment = step.loss_by_segment;
-    for (int it = 0; it < inner && !rc; ++it) {
-      int64_t off = ncls[0];
-      for (int c = 1; c < 4; off += ncls[c], ++c) {
-        if (ncls[c] <= 0) continue;
-        SweepArgs b = a;
-        b.seglist = lst ? lst + off : nullptr; // (no list: one class holds every local row)
-        b.nseg = ncls[c];
-        launch_sweep(h->G, h->R, glrm_class_waves(c), step.loss, GLRM_ROWS, b, h->side_stream);
-      }
-    }
-    // join also before reporting an error: later work on h->stream must stay ordered after what the side stream already holds
-    const hipError_t e_join = glrm_join_side_stream(h);
-    if (rc) return rc;
-    HIPCK(e_join);
-  }
+  rc = glrm_for_each_class(h, p, 0, [&](int cls, const int32_t* list, int64_t n, hipStream_t st) {
+    if (cls == 0) return glrm_run_solve(h, step, list, n, p.cap, inner, st);
+    SweepArgs b = a;
+    b.seglist = list;
+    b.nseg = n;
+    for (int it = 0; it < inner; ++it) launch_sweep(h->G, h->R, glrm_class_waves(cls), step.loss, GLRM_ROWS, b, st);
+    return (int)GLRM_OK;
+  });
   if (rc) return rc;
   HIPCK(hipGetLastError());
-  if (h->profile) {
-    HIPCK(hipEventRecord(ev.b, h->stream));
-    h->pending.push_back(ev);
-    if (h->pending.size() >= 4096 && (rc = drain_events(h))) return rc;
-  }
+  if (h->profile && (rc = end_timing(h, ev))) return rc;
   v.launches += inner;
   h->solve_fused = 1;
-  h->solve_fused_rows = ncls[0];
-  h->solve_loop_rows = nlong;
+  h->solve_fused_rows = p.n[0];
+  h->solve_loop_rows = p.n[1] + p.n[2] + p.n[3];
   return GLRM_OK;
 }
 
@@ -1076,10 +1034,8 @@ int glrm_arrival_wait(glrm_handle* h, glrm_arrivals& arr, int64_t lo, int64_t hi
       if (rc) return rc;
     }
     HIPCK(hipStreamWaitEvent(h->stream, (hipEvent_t)blk.event, 0));
-    if (h->profile) {
-      HIPCK(hipEventRecord(ev.b, h->stream));
-      h->pending.push_back(ev);
-    }
+    if (h->profile)
+      if (const int rc = end_timing(h, ev)) return rc;
   }
   return GLRM_OK;
 }
@@ -1286,8 +1242,8 @@ extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_or
   } else {
     o.family = GLRM_ORDER_STRIDED;
     o.lanes = h->G; o.comps = h->R;
-    const int forced = side == GLRM_ROWS ? h->opts.waves_row : h->opts.waves_col;
-    o.waves = (forced == 1 || forced == 4 || forced == 8) ? forced : 0;
+    const int forced = glrm_forced_class(h, side);
+    o.waves = forced ? glrm_class_waves(forced) : 0;
     if (side == GLRM_ROWS && h->cached_want) { // which rows the cached sweep takes is a function of the row's own length
       o.cached_maxlen = h->cached_maxlen; // (the whole problem's, also on a shard that holds no such row)
       o.cached_waves = h->cached_waves;

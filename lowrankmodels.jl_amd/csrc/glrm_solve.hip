@@ -1,6 +1,6 @@
 // glrm_solve.hip -- the fused row solver of glrm_hip_solve_x (include/glrm_hip_transform.h, glrm_solve.hpp): the double instantiations of
-// regcached_solve_kernel and the launch both storages go through.  The entry points, the plan of which rows run here and the T-launch
-// loop of the longer rows are glrm_hip.hip's (they share run_sweep's helpers).
+// regcached_solve_kernel and the launch both storages go through.  The entry points and the T launches of the longer rows are
+// glrm_hip.hip's; which rows run here is class 0 of a glrm_class_plan (glrm_engine.hpp), built and launched like run_sweep's.
 #include <hip/hip_runtime.h>
 
 #include "glrm_solve.hpp"

@@ -33,7 +33,7 @@ struct SweepArgs {
   int32_t* trials;       // per local segment accumulators (nullable)
   int32_t* accepts;
   const int32_t* seglist; // nullable: the launch covers the local segments seglist[0..nseg) instead of 0..nseg -- the segments of ONE
-                          // wave class when the shard holds several (glrm_handle::Side::seglist) -- restricted to [seg_lo, seg_hi)
+                          // wave class when the shard holds several (glrm_class_plan::list) -- restricted to [seg_lo, seg_hi)
   int64_t seg_lo, seg_hi; // (glrm_hip_step_x_range on such a shard; otherwise [0, local segments))
   int vecreg;            // 1: a descriptor of this side names a vector regularizer -- the VR = true kernels (csrc/glrm_device.hpp)
   int storage;           // GLRM_STORAGE_*: the type ST behind vals / own / other, i.e. which instantiation the launch takes

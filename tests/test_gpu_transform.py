@@ -54,6 +54,12 @@ def problem(m, k, long_rows=12):
     long_rows = min(long_rows, m // 4)
     if long_rows:
         lens[rng.choice(np.arange(len(pool), m), size=long_rows, replace=False)] = np.linspace(maxlen + 1, 300, long_rows).astype(int)
+    return from_lengths(rng, lens, k)
+
+
+def from_lengths(rng, lens, k):
+    """The problem whose row i holds lens[i] observations (a row longer than N repeats columns).  -> (ProblemArrays, X0, Y0, lens)"""
+    m = len(lens)
     I, J = [], []
     for i, l in enumerate(lens):
         cols = rng.permutation(N)[: min(l, N)]
@@ -70,13 +76,13 @@ def problem(m, k, long_rows=12):
     return g.problem_arrays(), X0, Y0, lens
 
 
-def run(monkeypatch, env, pa, X0, Y0, T, *, solve, stepsize=1.0, min_stepsize=0.01, storage=0, tiled=1, api=None, orders=None):
+def run(monkeypatch, env, pa, X0, Y0, T, *, solve, stepsize=1.0, min_stepsize=0.01, storage=0, tiled=1, api=None, orders=None, waves_row=0):
     """Create under `env`, T X half-steps (one solve_x(T), or T step_x calls), then ONE further step (solve_x(1) / step_x).  -> dict"""
     api = api or hip()
     for key in ENV_KEYS:
         monkeypatch.delenv(key, raising=False)
     family_env.setenv(monkeypatch, env)
-    h = api.create(pa, tiled=tiled, storage=storage) if api is hip() else api.create(pa)
+    h = api.create(pa, tiled=tiled, storage=storage, waves_row=waves_row) if api is hip() else api.create(pa)
     try:
         out = {}
         if orders is not None:
@@ -423,3 +429,66 @@ def test_no_device_memory_leak_over_create_solve_destroy_cycles(monkeypatch):
         levels.append(free_bytes())
     lost = [levels[i] - levels[i + 1] for i in range(2)]
     assert min(lost) < 4 << 20, f"device memory lost per window of 10 cycles (MiB): {[round(x / 2**20, 1) for x in lost]}"
+
+
+# ------------------------------------------------------------------ 10. corners of the class plan and of the class-by-class launcher
+
+@functools.lru_cache(maxsize=None)
+def class_problem(name):
+    """k = 64, built once and shared.  "three-classes": 48 rows the register kernel takes (0 .. 104 observations, both ends present), 12
+    one-wave rows (105 .. 300) and 4 four-wave rows (1536 .. 1700), shuffled so that every class list skips rows.  "all-long": 8 rows of
+    105 .. 300 -- no row for the register kernel."""
+    rng = np.random.default_rng({"three-classes": 64064, "all-long": 64008}[name])
+    if name == "three-classes":
+        short = rng.integers(0, 105, 48)
+        short[:2] = 0, 104
+        lens = np.concatenate([short, np.linspace(105, 300, 12).astype(int), np.linspace(1536, 1700, 4).astype(int)])
+        rng.shuffle(lens)
+    else:
+        lens = np.linspace(105, 300, 8).astype(int)
+    return from_lengths(rng, lens, 64)
+
+
+@pytest.mark.parametrize("T", [2, 5])
+@pytest.mark.parametrize("k", [64, 32])
+def test_solve_x_T_on_a_cached_handle_equals_T_step_x_calls(monkeypatch, k, T):
+    """the handle's own plan (class 0 plus 12 one-wave rows), T > 1: the longer rows take T launches beside the one fused launch"""
+    pa, X0, Y0, lens = problem(600, k)
+    for env in (family_env.cached(), family_env.cached(persist=False)):
+        got = run(monkeypatch, env, pa, X0, Y0, T, solve=True)
+        assert got["tiled"] & CACHED and got["info"] == fused_counts(lens, k) and got["launches"] == T, (got["tiled"], got["info"], got["launches"])
+        same(got, run(monkeypatch, env, pa, X0, Y0, T, solve=False), (env, T))
+
+
+def test_three_classes_in_one_plan(monkeypatch):
+    pa, X0, Y0, lens = class_problem("three-classes")
+    assert (np.sum(lens <= 104), np.sum((lens >= 105) & (lens <= 300)), np.sum((lens >= 1536) & (lens <= 1700))) == (48, 12, 4)
+    got = run(monkeypatch, {}, pa, X0, Y0, 3, solve=True)
+    assert got["tiled"] & CACHED == 0 and got["info"] == dict(fused=1, fused_rows=48, loop_rows=16), (got["tiled"], got["info"])
+    assert got["launches"] == 3 and got["accepts"] > 0
+    ref = run(monkeypatch, family_env.cached(), pa, X0, Y0, 3, solve=False)
+    assert ref["tiled"] & CACHED
+    same(got, ref, "three classes")
+
+
+def test_no_row_for_the_register_kernel(monkeypatch):
+    """every row is long: the fused path runs no fused launch, and the cached handle it is held to fell back to the gather sweep"""
+    pa, X0, Y0, lens = class_problem("all-long")
+    assert lens.min() >= 105 and lens.max() <= 300 and len(lens) == 8
+    got = run(monkeypatch, {}, pa, X0, Y0, 3, solve=True)
+    assert got["info"] == dict(fused=1, fused_rows=0, loop_rows=8), got["info"]
+    assert got["launches"] == 3 and got["accepts"] > 0
+    ref = run(monkeypatch, family_env.cached(), pa, X0, Y0, 3, solve=False)
+    assert ref["tiled"] & CACHED == 0, ref["tiled"]                   # cached_row fell to 0: the shard holds no class-0 row
+    same(got, ref, "no class-0 row")
+
+
+def test_pinned_waves_reach_both_plans(monkeypatch):
+    """waves_row = 4: the twelve longer rows run the four-wave sweep, in the plan solve_x builds and in the cached handle's own"""
+    pa, X0, Y0, lens = problem(600, 64)
+    got = run(monkeypatch, {}, pa, X0, Y0, 2, solve=True, waves_row=4)
+    assert got["tiled"] & CACHED == 0 and got["info"] == fused_counts(lens, 64), (got["tiled"], got["info"])
+    ref = run(monkeypatch, family_env.cached(), pa, X0, Y0, 2, solve=False, waves_row=4)
+    assert ref["tiled"] & CACHED
+    assert got["orders"][0].waves == 4 and ref["orders"][0].waves == 4, (got["orders"][0].waves, ref["orders"][0].waves)
+    same(got, ref, "waves_row = 4")
