@@ -1,6 +1,7 @@
 // glrm_devmem.hpp -- who owns device memory and which device is current (included by glrm_engine.hpp, after fail()).
 //   DeviceScope  every extern "C" entry point that touches the device opens one: the handle's device inside, the caller's again on return
-//   DevArena     owner of device allocations: glrm_handle::mem for everything the handle keeps, a local one for a function's scratch.
+//   DevArena     owner of device allocations: glrm_handle::mem for everything the handle keeps, Shard::mem (glrm_multigpu.hip) for a
+//                shard's replica of a sharded fit, a local one for a function's scratch.
 //                A pointer belongs to exactly one arena from alloc to free; the T* a kernel argument struct is filled from stays raw.
 #pragma once
 

@@ -16,7 +16,7 @@
 //                       iteration of glrm_svd.hip through glrm_subspace.hpp
 //   glrm_solve.hip      the fused row solver of glrm_hip_solve_x (include/glrm_hip_transform.h): T X half-steps of a row in one launch of the
 //                       register kernel (glrm_solve.hpp); glrm_solve_f32.hip holds its float instantiations
-//   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, local scratch)
+//   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, a shard's replica, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
 // the opposing side is side ^ 1); glrm_step is what ONE half-step is asked to do, built by the entry point and passed down as an argument
@@ -26,6 +26,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -279,6 +280,66 @@ inline bool glrm_single_shard(const glrm_handle* h) { return h->side[GLRM_ROWS].
 
 namespace glrm { struct TiledArgs; }
 
+// the two halves of "sum the counts, max the rest" (include/glrm_hip.h: glrm_signature): what a sharding host adds up over its shards, and
+// what glrm_hip_finalize holds the result to
+inline void glrm_signature_add(glrm_signature& whole, const glrm_signature& local) {
+  whole.nnz_rows += local.nnz_rows; whole.nnz_cols += local.nnz_cols;
+  whole.max_row_len = std::max(whole.max_row_len, local.max_row_len); whole.max_col_len = std::max(whole.max_col_len, local.max_col_len);
+  whole.rows_unordered = std::max(whole.rows_unordered, local.rows_unordered); whole.cols_unordered = std::max(whole.cols_unordered, local.cols_unordered);
+}
+inline bool glrm_signature_covers(const glrm_signature& whole, const glrm_signature& local) {
+  return whole.nnz_rows >= local.nnz_rows && whole.nnz_cols >= local.nnz_cols && whole.max_row_len >= local.max_row_len &&
+         whole.max_col_len >= local.max_col_len && whole.rows_unordered >= local.rows_unordered && whole.cols_unordered >= local.cols_unordered;
+}
+
+// structural check of a host array of nseg + 1 segment offsets (name: "rowptr" / "colptr")
+inline int glrm_check_offsets(const char* name, const int64_t* ptr, int64_t nseg) {
+  if (ptr[0] != 0) return fail(GLRM_ERR_INVALID, "%s[0] must be 0", name);
+  for (int64_t s = 0; s < nseg; ++s)
+    if (ptr[s + 1] < ptr[s]) return fail(GLRM_ERR_INVALID, "%s is not monotone at %lld", name, (long long)s);
+  return GLRM_OK;
+}
+
+// ---- the bookkeeping of the ProxGrad outer loop (src/algorithms/proxgrad.jl), shared by glrm_hip_fit and glrm_hip_multi_fit
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// norm(Y) == 0 guard (proxgrad.jl:45-48: the reference would hit an UndefVarError; sparse_proxgrad.jl:41-43: it would re-randomise Y)
+inline bool glrm_all_zero(const double* v, int64_t count) {
+  double norm2 = 0.0;
+  for (int64_t i = 0; i < count; ++i) norm2 += v[i] * v[i];
+  return norm2 == 0.0;
+}
+// Y: k x d, dense
+inline int glrm_check_fit_args(const glrm_params* prm, int64_t cap, const double* Y, int64_t k, int64_t d) {
+  if (prm->max_iter < 0 || cap < prm->max_iter + 1) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+1");
+  if (prm->inner_iter_X < 1 || prm->inner_iter_Y < 1) return fail(GLRM_ERR_INVALID, "inner iteration counts must be >= 1");
+  if (glrm_all_zero(Y, k * d)) return fail(GLRM_ERR_INVALID, "Y is all zeros (the reference cannot start from Y == 0)");
+  return GLRM_OK;
+}
+// ConvergenceHistory (src/convergence.jl:22-26) and the stopping rule of proxgrad.jl:210-213.  start() records the initial objective and
+// starts the clock; record() closes iteration i -- the clock restarts after the entry is written -- and says whether the fit stops.
+struct glrm_trace {
+  double *objective, *seconds;
+  double scaled_abs_tol, rel_tol;      // abs_tol * observations (:72), rel_tol
+  int64_t nrec = 0;
+  double t = 0.0;
+  glrm_trace(double* objective, double* seconds, const glrm_params* prm, int64_t nnz)
+      : objective(objective), seconds(seconds), scaled_abs_tol(prm->abs_tol * (double)nnz), rel_tol(prm->rel_tol) {}
+  void start(double obj0) {                                              // update_ch!(ch, 0, objective(...)) :76
+    objective[0] = obj0;
+    seconds[0] = 0.0;
+    nrec = 1;
+    t = now_s();
+  }
+  bool record(int64_t i, double obj) {
+    const double dt = now_s() - t;
+    objective[nrec] = obj;
+    seconds[nrec] = seconds[nrec - 1] + dt;                              // update_ch!
+    ++nrec;
+    t = now_s();
+    const double dec = objective[nrec - 2] - obj;                        // :210
+    return i > 10 && (dec < scaled_abs_tol || dec / obj < rel_tol);      // :211-213
+  }
+};
 
 // per-segment class of the gather sweeps (see glrm_class_plan)
 constexpr int64_t GLRM_WAVES4_FROM = 1536, GLRM_WAVES8_FROM = 98304;

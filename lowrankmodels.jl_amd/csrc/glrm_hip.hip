@@ -143,9 +143,7 @@ static bool is_classification(int kind) { return kind == GLRM_LOSS_LOGISTIC || k
 static int check_view(const char* name, int64_t nseg, const int64_t* ptr, const int32_t* idx, const double* vals,
                       int64_t bound, const glrm_problem* p, bool by_idx, int64_t seg_offset) {
   if (!ptr) return fail(GLRM_ERR_INVALID, "%s pointer array is NULL", name);
-  if (ptr[0] != 0) return fail(GLRM_ERR_INVALID, "%s[0] must be 0", name);
-  for (int64_t s = 0; s < nseg; ++s)
-    if (ptr[s + 1] < ptr[s]) return fail(GLRM_ERR_INVALID, "%s is not monotone at %lld", name, (long long)s);
+  if (int rc = glrm_check_offsets(name, ptr, nseg)) return rc;
   if (ptr[nseg] > 0 && (!idx || !vals)) return fail(GLRM_ERR_INVALID, "%s index/value arrays are NULL", name);
   for (int64_t s = 0; s < nseg; ++s) {
     for (int64_t t = ptr[s]; t < ptr[s + 1]; ++t) {
@@ -503,9 +501,7 @@ static int create_impl(glrm_handle* h, const glrm_problem* p, const glrm_options
 // Second half of create: kernel families and their buffers, chosen from the signature of the WHOLE problem.
 static int finalize_impl(glrm_handle* h, const glrm_signature* whole) {
   h->sig = whole ? *whole : h->sig_local;
-  if (h->sig.nnz_rows < h->sig_local.nnz_rows || h->sig.nnz_cols < h->sig_local.nnz_cols || h->sig.max_row_len < h->sig_local.max_row_len ||
-      h->sig.max_col_len < h->sig_local.max_col_len || h->sig.rows_unordered < h->sig_local.rows_unordered ||
-      h->sig.cols_unordered < h->sig_local.cols_unordered)
+  if (!glrm_signature_covers(h->sig, h->sig_local))
     return fail(GLRM_ERR_INVALID, "the signature of the whole problem cannot be smaller than this shard's (sum the counts, max the rest)");
   int rc;
   const int opt_waves[2] = {h->opts.waves_row, h->opts.waves_col};
@@ -1259,10 +1255,6 @@ extern "C" int glrm_hip_sum_order(glrm_handle* handle, int32_t side, glrm_sum_or
 
 // ------------------------------------------------------------------ whole-fit API
 
-static double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // loss + rx + ry at the device-resident factors (objective(...), src/evaluate_fit.jl:4-23,91-104)
 static int device_objective(glrm_handle* h, int include_reg, double* out) {
   int rc;
@@ -1334,21 +1326,15 @@ extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, d
                             double* seconds, int64_t cap, int64_t* n_recorded) {
   if (!h || !prm || !X || !Y || !objective || !seconds || !n_recorded) return fail(GLRM_ERR_INVALID, "NULL argument");
   if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit needs a single-shard handle (use the step-level API per shard)");
-  if (prm->max_iter < 0 || cap < prm->max_iter + 1) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+1");
-  if (prm->inner_iter_X < 1 || prm->inner_iter_Y < 1) return fail(GLRM_ERR_INVALID, "inner iteration counts must be >= 1");
-  double ynorm = 0.0; // norm(Y)==0 guard, proxgrad.jl:45-48 (the reference would hit an UndefVarError)
-  for (int64_t i = 0; i < (int64_t)h->k * h->d; ++i) ynorm += Y[i] * Y[i];
-  if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros (the reference cannot start from Y == 0)");
-  DeviceScope dg(h->device);
   int rc;
+  if ((rc = glrm_check_fit_args(prm, cap, Y, h->k, h->d))) return rc;
+  DeviceScope dg(h->device);
   if ((rc = glrm_hip_set_factors(h, X, Y))) return rc;                 // X = glrm.X; Y = glrm.Y (:43)
   if ((rc = glrm_hip_reset_stepsizes(h, prm->stepsize))) return rc;   // :69-70
-  const double scaled_abs_tol = prm->abs_tol * (double)h->side[GLRM_ROWS].nnz;       // :72 (observed_features)
-  int64_t nrec = 0;
-  if ((rc = device_objective(h, 1, &objective[0]))) return rc;        // update_ch!(ch, 0, objective(...)) :76
-  seconds[0] = 0.0;
-  nrec = 1;
-  double t = now_s();
+  glrm_trace trace(objective, seconds, prm, h->side[GLRM_ROWS].nnz);  // :72 (observed_features)
+  double obj0 = 0.0;
+  if ((rc = device_objective(h, 1, &obj0))) return rc;
+  trace.start(obj0);
   const bool use_graph = graph_eligible(h);
   if (use_graph && (rc = build_iteration_graph(h, prm))) return rc;
   for (int64_t i = 1; i <= prm->max_iter; ++i) {                       // :107
@@ -1367,16 +1353,10 @@ extern "C" int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, d
         if ((rc = run_sweep(h, search_step(GLRM_COLS, prm->min_stepsize)))) return rc; // :160-203
       if ((rc = glrm_hip_sum(h, h->side[GLRM_COLS].obj, h->n, &obj))) return rc;     // obj = sum(obj_by_col) :205
     }
-    const double dt = now_s() - t;
-    objective[nrec] = obj;
-    seconds[nrec] = seconds[nrec - 1] + dt;                            // update_ch! (src/convergence.jl:22-26)
-    ++nrec;
-    t = now_s();
-    const double dec = objective[nrec - 2] - obj;                      // :210
-    if (i > 10 && (dec < scaled_abs_tol || dec / obj < prm->rel_tol)) break; // :211-213
+    if (trace.record(i, obj)) break;
   }
   if ((rc = glrm_hip_get_factors(h, X, Y))) return rc;
-  *n_recorded = nrec;
+  *n_recorded = trace.nrec;
   return GLRM_OK;
 }
 
@@ -1389,9 +1369,8 @@ extern "C" int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm
   if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "glrm_hip_fit_sparse needs a single-shard handle");
   if (prm->max_iter < 0 || cap < prm->max_iter + 2) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+2");
   if (prm->inner_iter < 1) return fail(GLRM_ERR_INVALID, "inner_iter must be >= 1");
-  double ynorm = 0.0; // norm(Y)==0 would be re-randomised by the reference (:41-43); not reproducible -> error
-  for (int64_t i = 0; i < (int64_t)h->k * h->d; ++i) ynorm += Y[i] * Y[i];
-  if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros");
+  // norm(Y)==0 would be re-randomised by the reference (:41-43); not reproducible -> error
+  if (glrm_all_zero(Y, (int64_t)h->k * h->d)) return fail(GLRM_ERR_INVALID, "Y is all zeros");
   DeviceScope dg(h->device);
   int rc;
   if ((rc = glrm_hip_set_factors(h, X, Y))) return rc; // working copies X, Y (:33); glrm.X / glrm.Y = best so far

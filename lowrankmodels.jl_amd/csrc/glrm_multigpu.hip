@@ -51,8 +51,6 @@
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // ---- RCCL, resolved at run time ---------------------------------------------------------------------------------------
 struct Rccl {
   typedef void* comm_t;
@@ -144,6 +142,49 @@ struct ShardPool {
   }
 };
 
+// Everything one shard keeps on its device.  Members start null and the vector of shards is built once at its final size, so close()
+// takes a shard in any half-built state.
+struct Link {                       // shard s -> destination t (Shard::to[t]; to[s] stays empty)
+  hipStream_t copy = nullptr;       // copy stream on the source's device
+  hipEvent_t arrived = nullptr;     // the last block pushed over the link has landed
+  std::vector<hipEvent_t> chunk;    // chunk[j]: row chunk j of the source's X block has landed (arrival order only)
+};
+struct Shard {
+  int dev = 0;
+  glrm_handle* h = nullptr;
+  hipStream_t st = nullptr;         // compute stream
+  DevArena mem;                     // the replica below (and the emulator's t0 word)
+  double *X = nullptr, *Y = nullptr, *objCol = nullptr, *objRow = nullptr; // this device's replica
+  hipEvent_t ev_done = nullptr;     // the shard's sweep finished (timing enabled: start of its exchange wait)
+  hipEvent_t ev_ready = nullptr;    // every incoming block has arrived
+  Rccl::comm_t comm = nullptr;
+  double wait_y0 = 0.0;             // ms_wait_y at the start of the fit
+  std::vector<Link> to;
+#ifdef GLRM_HIP_TESTING // link emulator, mode 1: the source's (mark, release) pair of signal words (hipExtMallocWithFlags: not the arena's) and
+  uint64_t *mark = nullptr, *release = nullptr, ticket = 0; // the count of its transfers; mode 2: the time the delay kernel counts from
+  unsigned long long* t0 = nullptr;
+#endif
+  hipError_t select() const { return hipSetDevice(dev); }
+  void close() { // after the shard's handle is gone
+    if (select() != hipSuccess) return;
+    if (comm) (void)Rccl::get().CommDestroy(comm);
+    mem.free_all();
+    for (Link& l : to) {
+      if (l.copy) (void)hipStreamDestroy(l.copy);
+      if (l.arrived) (void)hipEventDestroy(l.arrived);
+      for (hipEvent_t e : l.chunk)
+        if (e) (void)hipEventDestroy(e);
+    }
+#ifdef GLRM_HIP_TESTING
+    if (mark) (void)hipFree(mark);
+    if (release) (void)hipFree(release);
+#endif
+    if (ev_done) (void)hipEventDestroy(ev_done);
+    if (ev_ready) (void)hipEventDestroy(ev_ready);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
 #ifdef GLRM_HIP_TESTING
 // ---- link emulator ----------------------------------------------------------------------------------------------------
 __global__ void link_mark_kernel(unsigned long long* t0) { *t0 = (unsigned long long)wall_clock64(); }
@@ -156,17 +197,13 @@ struct LinkEmu {
   double bytes_per_s = 0.0; // per direction and link, already divided by the dilation; 0 = off
   double gbps = 0.0;
   int dilate = 1, mode = 0; // 1 stream wait-value + host timer, 2 delay kernels
-  // mode 1: one (mark, release) pair of 8-byte signal words per (source, destination) link; tickets count the transfers of a link
-  std::vector<uint64_t*> mark, release;
-  std::vector<uint64_t> ticket;
+  Shard* shards = nullptr;  // mode 1: the words of link `s` are shards[s].mark / release
   struct Job { int link; uint64_t ticket; double seconds; double due; bool started; };
   std::deque<Job> jobs; // per link in ticket order (one copy stream per link keeps them ordered on the device too)
   std::mutex mu;
   std::thread timer;
   std::atomic<bool> quit{false};
-  // mode 2
-  std::vector<unsigned long long*> t0;
-  double wall_hz = 1e8;
+  double wall_hz = 1e8; // mode 2
   void timer_loop() {
     // a transfer may not be released before bytes / rate have passed since its mark; a job that never sees its mark (its stream was
     // torn down) is dropped by destroy, which posts every release value first
@@ -178,9 +215,9 @@ struct LinkEmu {
         const double now = now_s();
         for (auto it = jobs.begin(); it != jobs.end();) {
           busy = true;
-          if (!it->started && __atomic_load_n(mark[it->link], __ATOMIC_ACQUIRE) >= it->ticket) { it->started = true; it->due = now + it->seconds; }
+          if (!it->started && __atomic_load_n(shards[it->link].mark, __ATOMIC_ACQUIRE) >= it->ticket) { it->started = true; it->due = now + it->seconds; }
           if (it->started && now >= it->due) {
-            __atomic_store_n(release[it->link], it->ticket, __ATOMIC_RELEASE);
+            __atomic_store_n(shards[it->link].release, it->ticket, __ATOMIC_RELEASE);
             it = jobs.erase(it);
           } else ++it;
         }
@@ -189,42 +226,41 @@ struct LinkEmu {
       else std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
   }
-  void release_all() { // nothing may be left waiting on the device
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& j : jobs) __atomic_store_n(release[j.link], j.ticket, __ATOMIC_RELEASE);
-    jobs.clear();
+  void stop() { // nothing may be left waiting for a release on the device
+    if (!timer.joinable()) return;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      for (auto& j : jobs) __atomic_store_n(shards[j.link].release, j.ticket, __ATOMIC_RELEASE);
+      jobs.clear();
+    }
+    quit.store(true, std::memory_order_release);
+    timer.join();
   }
 };
 
 #endif // GLRM_HIP_TESTING
 
 struct glrm_multi {
-  int n = 0;
+  const int n;
+  std::vector<Shard> shard;
   ShardPool pool;
   int64_t m = 0, nn = 0, d = 0;
   int k = 0, ld = 0;
-  std::vector<int> dev;
-  std::vector<glrm_handle*> sh;
-  std::vector<hipStream_t> st;                       // compute stream of shard s (device dev[s])
-  std::vector<double*> dX, dY, dObjCol, dObjRow;     // replica of shard s
-  std::vector<std::vector<hipStream_t>> cs;          // cs[s][t]: copy stream on dev[s] for pushes s -> t
-  std::vector<hipEvent_t> ev_done;                   // sweep of shard s finished (timing enabled: start of its exchange wait)
-  std::vector<hipEvent_t> ev_ready;                  // every incoming block of shard s has arrived
-  std::vector<std::vector<hipEvent_t>> ev_arr;       // ev_arr[s][t]: block of s landed on t
-  std::vector<std::vector<std::vector<hipEvent_t>>> ev_chunk; // ev_chunk[s][t][j]: row chunk j of s's X block landed on t
   int arrival = 1;                                   // Y half-step consumes the X chunks in arrival order (glrm_hip_step_y_arrival)
 #ifdef GLRM_HIP_TESTING
   LinkEmu emu;
 #endif
-  std::vector<double> wait_y0;                       // ms_wait_y of every shard at the start of the fit
   std::vector<int64_t> rbs, cbs, ybs;                // shard bounds: rows, columns, vectors of Y
   int exchange = 0;                                  // in use: 0 direct, 1 rccl
-  std::vector<Rccl::comm_t> comms;
   int x_chunks = 1;
   bool dense = false;
   bool profile = false;                              // glrm_options.profile: account the exposed exchange time of every exchange
   double exchange_ms = 0.0;
   int64_t n_rx = 0, n_ry = 0;
+  explicit glrm_multi(int n) : n(n), shard((size_t)n) {
+    for (Shard& s : shard) s.to.resize((size_t)n);
+    pool.start(n);
+  }
 };
 
 namespace {
@@ -264,7 +300,7 @@ int run_all(glrm_multi* mh, const std::function<int(int)>& fn) {
   };
   mh->pool.run(body);
   for (int s = 0; s < n; ++s)
-    if (rc[s]) return fail(rc[s], "shard %d (device %d): %s", s, mh->dev[s], msg[s].c_str());
+    if (rc[s]) return fail(rc[s], "shard %d (device %d): %s", s, mh->shard[s].dev, msg[s].c_str());
   return GLRM_OK;
 }
 
@@ -275,27 +311,27 @@ int run_all(glrm_multi* mh, const std::function<int(int)>& fn) {
   } while (0)
 
 #ifdef GLRM_HIP_TESTING
-// Link emulation around the pushes of source `link` on its link stream c: before / after hooks
-int emu_before(glrm_multi* mh, hipStream_t c, int link) {
+// Link emulation around the pushes of source `src` on its link stream c: before / after hooks
+int emu_before(glrm_multi* mh, hipStream_t c, Shard& src) {
   LinkEmu& e = mh->emu;
   if (e.bytes_per_s <= 0.0) return GLRM_OK;
-  if (e.mode == 1) COMMCK(hipStreamWriteValue64(c, e.mark[link], e.ticket[link] + 1, 0));
-  else hipLaunchKernelGGL(link_mark_kernel, dim3(1), dim3(1), 0, c, e.t0[link]);
+  if (e.mode == 1) COMMCK(hipStreamWriteValue64(c, src.mark, src.ticket + 1, 0));
+  else hipLaunchKernelGGL(link_mark_kernel, dim3(1), dim3(1), 0, c, src.t0);
   return GLRM_OK;
 }
-int emu_after(glrm_multi* mh, hipStream_t c, int link, size_t bytes) {
+int emu_after(glrm_multi* mh, hipStream_t c, Shard& src, size_t bytes) {
   LinkEmu& e = mh->emu;
   if (e.bytes_per_s <= 0.0) return GLRM_OK;
   const double seconds = (double)bytes / e.bytes_per_s;
   if (e.mode == 1) {
-    const uint64_t tk = ++e.ticket[link];
+    const uint64_t tk = ++src.ticket;
     {
       std::lock_guard<std::mutex> lk(e.mu);
-      e.jobs.push_back(LinkEmu::Job{link, tk, seconds, 0.0, false});
+      e.jobs.push_back(LinkEmu::Job{(int)(&src - e.shards), tk, seconds, 0.0, false});
     }
-    COMMCK(hipStreamWaitValue64(c, e.release[link], tk, hipStreamWaitValueGte));
+    COMMCK(hipStreamWaitValue64(c, src.release, tk, hipStreamWaitValueGte));
   } else {
-    hipLaunchKernelGGL(link_delay_kernel, dim3(1), dim3(1), 0, c, e.t0[link], (unsigned long long)(seconds * e.wall_hz));
+    hipLaunchKernelGGL(link_delay_kernel, dim3(1), dim3(1), 0, c, src.t0, (unsigned long long)(seconds * e.wall_hz));
     COMMCK(hipGetLastError());
   }
   return GLRM_OK;
@@ -303,17 +339,24 @@ int emu_after(glrm_multi* mh, hipStream_t c, int link, size_t bytes) {
 
 #endif // GLRM_HIP_TESTING
 
+// `bytes` at element offset `off` of a replica buffer, from s's copy to t's, on stream c of s's device
+int push_range(const Shard& s, const Shard& t, double* Shard::*buf, int64_t off, size_t bytes, hipStream_t c) {
+  if (s.dev == t.dev) COMMCK(hipMemcpyAsync(t.*buf + off, s.*buf + off, bytes, hipMemcpyDeviceToDevice, c));
+  else COMMCK(hipMemcpyPeerAsync(t.*buf + off, t.dev, s.*buf + off, s.dev, bytes, c));
+  return GLRM_OK;
+}
+
 // Shard s owns buf[bounds[s]*unit .. bounds[s+1]*unit) (doubles) restricted to the sub-range [lo_s, hi_s) of its block given by
 // (cj, cn) (fractions j/C of the block for the pipelined X exchange; 0/1 = the whole block).  Phase 1 (push): after the work already
-// queued on st[s], push that range to every destination and record ev_arr[s][t] (and, chunk_events: ev_chunk[s][t][cj]) behind it.
-// Phase 2 (wait): st[t] waits for everything pushed to t so far.
-int exchange_push(glrm_multi* mh, std::vector<double*>& buf, const std::vector<int64_t>& bounds, int64_t unit, int only_dst, int cj,
-                  int cn, bool chunk_events = false) {
+// queued on s's stream, push that range to every destination and record to[t].arrived (and, chunk_events: to[t].chunk[cj]) behind it.
+// Phase 2 (wait): t's stream waits for everything pushed to t so far.
+int exchange_push(glrm_multi* mh, double* Shard::*buf, const std::vector<int64_t>& bounds, int64_t unit, int only_dst, int cj, int cn,
+                  bool chunk_events = false) {
   const int n = mh->n;
   if (n == 1) return GLRM_OK;
-  for (int s = 0; s < n; ++s) {
-    COMMCK(hipSetDevice(mh->dev[s]));
-    COMMCK(hipEventRecord(mh->ev_done[s], mh->st[s]));
+  for (Shard& S : mh->shard) {
+    COMMCK(S.select());
+    COMMCK(hipEventRecord(S.ev_done, S.st));
   }
   if (mh->exchange == 1) { // RCCL: one grouped collective over all communicators (always to every rank; x_chunks is off here)
     Rccl& R = Rccl::get();
@@ -321,13 +364,14 @@ int exchange_push(glrm_multi* mh, std::vector<double*>& buf, const std::vector<i
     for (int s = 1; s < n; ++s) equal = equal && (bounds[s + 1] - bounds[s] == bounds[1] - bounds[0]);
     int rc = R.GroupStart();
     for (int s = 0; s < n && !rc; ++s) {
+      const Shard& S = mh->shard[s];
       if (equal) {
         const size_t cnt = (size_t)((bounds[1] - bounds[0]) * unit);
-        if (cnt) rc = R.AllGather(buf[s] + bounds[s] * unit, buf[s], cnt, NCCL_FLOAT64, mh->comms[s], mh->st[s]);
+        if (cnt) rc = R.AllGather(S.*buf + bounds[s] * unit, S.*buf, cnt, NCCL_FLOAT64, S.comm, S.st);
       } else {
         for (int r = 0; r < n && !rc; ++r) {
           const size_t cnt = (size_t)((bounds[r + 1] - bounds[r]) * unit);
-          if (cnt) rc = R.Broadcast(buf[s] + bounds[r] * unit, buf[s] + bounds[r] * unit, cnt, NCCL_FLOAT64, r, mh->comms[s], mh->st[s]);
+          if (cnt) rc = R.Broadcast(S.*buf + bounds[r] * unit, S.*buf + bounds[r] * unit, cnt, NCCL_FLOAT64, r, S.comm, S.st);
         }
       }
     }
@@ -339,31 +383,31 @@ int exchange_push(glrm_multi* mh, std::vector<double*>& buf, const std::vector<i
   const bool emulate = mh->emu.bytes_per_s > 0.0;
 #endif
   for (int s = 0; s < n; ++s) {
+    Shard& S = mh->shard[s];
     const int64_t blk = bounds[s + 1] - bounds[s];
     const int64_t lo = bounds[s] + blk * cj / cn, hi = bounds[s] + blk * (cj + 1) / cn;
     const size_t bytes = (size_t)((hi - lo) * unit) * 8;
-    COMMCK(hipSetDevice(mh->dev[s]));
+    int rc;
+    COMMCK(S.select());
 #ifdef GLRM_HIP_TESTING
     if (emulate) {
       // ONE stream per source stands for its n - 1 links (they run in parallel and carry equal sizes, so they finish together):
       // mark, the copies, then the wait for bytes / rate since the mark, then the arrival events.  Few streams on purpose: a queue
       // that stands in a wait blocks every stream the runtime maps onto the same hardware queue (GPU_MAX_HW_QUEUES).
-      hipStream_t c = mh->cs[s][(s + 1) % n];
-      COMMCK(hipStreamWaitEvent(c, mh->ev_done[s], 0));
-      int rc = bytes ? emu_before(mh, c, s) : GLRM_OK;
-      if (rc) return rc;
+      hipStream_t c = S.to[(s + 1) % n].copy;
+      COMMCK(hipStreamWaitEvent(c, S.ev_done, 0));
+      if (bytes && (rc = emu_before(mh, c, S))) return rc;
       for (int d = 1; d < n && bytes; ++d) {
         const int t = (s + d) % n;
         if (only_dst >= 0 && t != only_dst) continue;
-        if (mh->dev[s] == mh->dev[t]) COMMCK(hipMemcpyAsync(buf[t] + lo * unit, buf[s] + lo * unit, bytes, hipMemcpyDeviceToDevice, c));
-        else COMMCK(hipMemcpyPeerAsync(buf[t] + lo * unit, mh->dev[t], buf[s] + lo * unit, mh->dev[s], bytes, c));
+        if ((rc = push_range(S, mh->shard[t], buf, lo * unit, bytes, c))) return rc;
       }
-      if (bytes && (rc = emu_after(mh, c, s, bytes))) return rc;
+      if (bytes && (rc = emu_after(mh, c, S, bytes))) return rc;
       for (int d = 1; d < n; ++d) {
         const int t = (s + d) % n;
         if (only_dst >= 0 && t != only_dst) continue;
-        COMMCK(hipEventRecord(mh->ev_arr[s][t], c));
-        if (chunk_events) COMMCK(hipEventRecord(mh->ev_chunk[s][t][cj], c));
+        COMMCK(hipEventRecord(S.to[t].arrived, c));
+        if (chunk_events) COMMCK(hipEventRecord(S.to[t].chunk[cj], c));
       }
       continue;
     }
@@ -371,14 +415,11 @@ int exchange_push(glrm_multi* mh, std::vector<double*>& buf, const std::vector<i
     for (int d = 1; d < n; ++d) { // destinations in ring order from s: no destination is everybody's first
       const int t = (s + d) % n;
       if (only_dst >= 0 && t != only_dst) continue;
-      hipStream_t c = mh->cs[s][t];
-      COMMCK(hipStreamWaitEvent(c, mh->ev_done[s], 0));
-      if (bytes) {
-        if (mh->dev[s] == mh->dev[t]) COMMCK(hipMemcpyAsync(buf[t] + lo * unit, buf[s] + lo * unit, bytes, hipMemcpyDeviceToDevice, c));
-        else COMMCK(hipMemcpyPeerAsync(buf[t] + lo * unit, mh->dev[t], buf[s] + lo * unit, mh->dev[s], bytes, c));
-      }
-      COMMCK(hipEventRecord(mh->ev_arr[s][t], c));
-      if (chunk_events) COMMCK(hipEventRecord(mh->ev_chunk[s][t][cj], c));
+      const Link& l = S.to[t];
+      COMMCK(hipStreamWaitEvent(l.copy, S.ev_done, 0));
+      if (bytes && (rc = push_range(S, mh->shard[t], buf, lo * unit, bytes, l.copy))) return rc;
+      COMMCK(hipEventRecord(l.arrived, l.copy));
+      if (chunk_events) COMMCK(hipEventRecord(l.chunk[cj], l.copy));
     }
   }
   return GLRM_OK;
@@ -389,15 +430,16 @@ int exchange_wait(glrm_multi* mh, int only_dst) {
   if (n == 1 || mh->exchange == 1) return GLRM_OK; // RCCL collectives are ordered on the compute streams themselves
   for (int t = 0; t < n; ++t) {
     if (only_dst >= 0 && t != only_dst) continue;
-    COMMCK(hipSetDevice(mh->dev[t]));
+    const Shard& T = mh->shard[t];
+    COMMCK(T.select());
     for (int s = 0; s < n; ++s)
-      if (s != t) COMMCK(hipStreamWaitEvent(mh->st[t], mh->ev_arr[s][t], 0));
-    COMMCK(hipEventRecord(mh->ev_ready[t], mh->st[t]));
+      if (s != t) COMMCK(hipStreamWaitEvent(T.st, mh->shard[s].to[t].arrived, 0));
+    COMMCK(hipEventRecord(T.ev_ready, T.st));
   }
   return GLRM_OK;
 }
 
-int exchange_all(glrm_multi* mh, std::vector<double*>& buf, const std::vector<int64_t>& bounds, int64_t unit, int only_dst = -1) {
+int exchange_all(glrm_multi* mh, double* Shard::*buf, const std::vector<int64_t>& bounds, int64_t unit, int only_dst = -1) {
   int rc = exchange_push(mh, buf, bounds, unit, only_dst, 0, 1);
   if (rc) return rc;
   return exchange_wait(mh, only_dst);
@@ -407,33 +449,68 @@ int exchange_all(glrm_multi* mh, std::vector<double*>& buf, const std::vector<in
 // last incoming block, max over shards.  Needs every stream drained, so it is only accounted with glrm_options.profile.
 void account_exchange(glrm_multi* mh) {
   if (mh->n == 1 || mh->exchange == 1 || !mh->profile) return;
-  for (int t = 0; t < mh->n; ++t)
-    if (hipSetDevice(mh->dev[t]) != hipSuccess || hipStreamSynchronize(mh->st[t]) != hipSuccess) { (void)hipGetLastError(); return; }
+  for (const Shard& T : mh->shard)
+    if (T.select() != hipSuccess || hipStreamSynchronize(T.st) != hipSuccess) { (void)hipGetLastError(); return; }
   float worst = 0.f;
-  for (int t = 0; t < mh->n; ++t) {
+  for (const Shard& T : mh->shard) {
     float ms = 0.f;
-    if (hipSetDevice(mh->dev[t]) == hipSuccess && hipEventElapsedTime(&ms, mh->ev_done[t], mh->ev_ready[t]) == hipSuccess) worst = std::max(worst, ms);
+    if (T.select() == hipSuccess && hipEventElapsedTime(&ms, T.ev_done, T.ev_ready) == hipSuccess) worst = std::max(worst, ms);
     else (void)hipGetLastError();
   }
   mh->exchange_ms += worst;
 }
 
-int sum_on_shard0(glrm_multi* mh, double* vec, int64_t cnt, double* out) { return glrm_hip_sum(mh->sh[0], vec, cnt, out); }
-
 // loss + rx + ry at the replicated factors (objective(...), src/evaluate_fit.jl:4-23,91-104), fixed-order sums on shard 0
 int multi_objective(glrm_multi* mh, double* out) {
   int rc;
   double loss = 0, px = 0, py = 0;
-  if ((rc = run_all(mh, [&](int s) { return glrm_hip_col_losses(mh->sh[s]); }))) return rc;
-  if ((rc = exchange_all(mh, mh->dObjCol, mh->cbs, 1, 0))) return rc;
-  if ((rc = sum_on_shard0(mh, mh->dObjCol[0], mh->nn, &loss))) return rc;
-  if ((rc = run_all(mh, [&](int s) { return glrm_hip_row_penalties(mh->sh[s]); }))) return rc;
-  if ((rc = exchange_all(mh, mh->dObjRow, mh->rbs, 1, 0))) return rc;
-  if ((rc = sum_on_shard0(mh, mh->dObjRow[0], mh->m, &px))) return rc;
-  if ((rc = run_all(mh, [&](int s) { return glrm_hip_col_penalties(mh->sh[s]); }))) return rc;
-  if ((rc = exchange_all(mh, mh->dObjCol, mh->cbs, 1, 0))) return rc;
-  if ((rc = sum_on_shard0(mh, mh->dObjCol[0], mh->nn, &py))) return rc;
+  const Shard& S0 = mh->shard[0];
+  if ((rc = run_all(mh, [&](int s) { return glrm_hip_col_losses(mh->shard[s].h); }))) return rc;
+  if ((rc = exchange_all(mh, &Shard::objCol, mh->cbs, 1, 0))) return rc;
+  if ((rc = glrm_hip_sum(S0.h, S0.objCol, mh->nn, &loss))) return rc;
+  if ((rc = run_all(mh, [&](int s) { return glrm_hip_row_penalties(mh->shard[s].h); }))) return rc;
+  if ((rc = exchange_all(mh, &Shard::objRow, mh->rbs, 1, 0))) return rc;
+  if ((rc = glrm_hip_sum(S0.h, S0.objRow, mh->m, &px))) return rc;
+  if ((rc = run_all(mh, [&](int s) { return glrm_hip_col_penalties(mh->shard[s].h); }))) return rc;
+  if ((rc = exchange_all(mh, &Shard::objCol, mh->cbs, 1, 0))) return rc;
+  if ((rc = glrm_hip_sum(S0.h, S0.objCol, mh->nn, &py))) return rc;
   *out = loss + (px + py);
+  return GLRM_OK;
+}
+
+// GLRM_PROBLEM_ROWS_FROM_COLS on host arrays.  Omega is a sparse matrix's pattern, handed over as its column view only: every shard needs
+// its rows' lists, so the row view is built here, once, by a counting transpose on the host (columns in order => every row's list
+// ascending), and the shards are cut from both views as usual.  Fills the vectors and *q, which is *p with the row view in place.
+int host_rows_from_cols(const glrm_problem* p, glrm_problem* q, std::vector<int64_t>& rowptr, std::vector<int32_t>& colidx, std::vector<double>& rowvals) {
+  if (p->dense_A || p->rowptr || p->colidx || p->rowvals) return fail(GLRM_ERR_INVALID, "GLRM_PROBLEM_ROWS_FROM_COLS: rowptr / colidx / rowvals must be NULL");
+  if (p->m <= 0 || p->n <= 0 || !p->colptr) return fail(GLRM_ERR_INVALID, "m, n must be positive and colptr given");
+  // the structure of the column view is checked BEFORE anything is counted or written through it (a colptr that does not start
+  // at 0, is not monotone or ends beyond the arrays made the fill loop read and write past the vectors; the single-device path checks first)
+  if (int rc = glrm_check_offsets("colptr", p->colptr, p->n)) return rc;
+  const int64_t nz = p->colptr[p->n]; // >= 0 and >= every other entry from here on
+  if (nz > 0 && (!p->rowidx || !p->colvals)) return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
+  std::vector<int64_t> fill;
+  try {
+    rowptr.assign((size_t)p->m + 1, 0); fill.resize((size_t)p->m);
+    colidx.resize((size_t)nz); rowvals.resize((size_t)nz);
+  } catch (const std::exception&) { // nothing may unwind across the extern "C" boundary
+    return fail(GLRM_ERR_OOM, "out of host memory for the row view of %lld observations", (long long)nz);
+  }
+  for (int64_t t = 0; t < nz; ++t) {
+    if (p->rowidx[t] < 0 || p->rowidx[t] >= p->m) return fail(GLRM_ERR_INVALID, "rowidx holds an index outside [0, m)");
+    rowptr[(size_t)p->rowidx[t] + 1] += 1;
+  }
+  for (int64_t i = 0; i < p->m; ++i) { rowptr[i + 1] += rowptr[i]; fill[i] = rowptr[i]; }
+  for (int64_t f = 0; f < p->n; ++f)
+    for (int64_t t = p->colptr[f]; t < p->colptr[f + 1]; ++t) {
+      const int64_t r = p->rowidx[t], at = fill[r]++;
+      if (at >= rowptr[r + 1]) return fail(GLRM_ERR_INVALID, "the column view changed while it was read"); // (cannot happen on a checked, unchanged view)
+      colidx[at] = (int32_t)f;
+      rowvals[at] = p->colvals[t];
+    }
+  *q = *p;
+  q->flags &= ~GLRM_PROBLEM_ROWS_FROM_COLS;
+  q->rowptr = rowptr.data(); q->colidx = colidx.data(); q->rowvals = rowvals.data();
   return GLRM_OK;
 }
 
@@ -441,55 +518,26 @@ int multi_objective(glrm_multi* mh, double* out) {
 
 extern "C" void glrm_hip_multi_destroy(glrm_multi* mh) {
   if (!mh) return;
-  DeviceScope dg; // the loops below select every shard's device in turn
+  DeviceScope dg; // close() selects every shard's device in turn
 #ifdef GLRM_HIP_TESTING
-  if (mh->emu.timer.joinable()) { // nothing may be left waiting for a release on the device
-    mh->emu.release_all();
-    mh->emu.quit.store(true, std::memory_order_release);
-    mh->emu.timer.join();
-  }
+  mh->emu.stop();
 #endif
-  for (int s = 0; s < (int)mh->sh.size(); ++s) {
-    if (mh->sh[s]) glrm_hip_destroy(mh->sh[s]);
-  }
-  for (int s = 0; s < mh->n && s < (int)mh->dev.size(); ++s) {
-    if (hipSetDevice(mh->dev[s]) != hipSuccess) continue;
-    if (s < (int)mh->comms.size() && mh->comms[s]) (void)Rccl::get().CommDestroy(mh->comms[s]);
-    for (double* p : {s < (int)mh->dX.size() ? mh->dX[s] : nullptr, s < (int)mh->dY.size() ? mh->dY[s] : nullptr,
-                      s < (int)mh->dObjCol.size() ? mh->dObjCol[s] : nullptr, s < (int)mh->dObjRow.size() ? mh->dObjRow[s] : nullptr})
-      if (p) (void)hipFree(p);
-    if (s < (int)mh->cs.size())
-      for (hipStream_t c : mh->cs[s])
-        if (c) (void)hipStreamDestroy(c);
-    if (s < (int)mh->ev_arr.size())
-      for (hipEvent_t e : mh->ev_arr[s])
-        if (e) (void)hipEventDestroy(e);
-    if (s < (int)mh->ev_chunk.size())
-      for (auto& v : mh->ev_chunk[s])
-        for (hipEvent_t e : v)
-          if (e) (void)hipEventDestroy(e);
-#ifdef GLRM_HIP_TESTING
-    if (s < (int)mh->emu.mark.size() && mh->emu.mark[s]) (void)hipFree(mh->emu.mark[s]);
-    if (s < (int)mh->emu.release.size() && mh->emu.release[s]) (void)hipFree(mh->emu.release[s]);
-    if (s < (int)mh->emu.t0.size() && mh->emu.t0[s]) (void)hipFree(mh->emu.t0[s]);
-#endif
-    if (s < (int)mh->ev_done.size() && mh->ev_done[s]) (void)hipEventDestroy(mh->ev_done[s]);
-    if (s < (int)mh->ev_ready.size() && mh->ev_ready[s]) (void)hipEventDestroy(mh->ev_ready[s]);
-    if (s < (int)mh->st.size() && mh->st[s]) (void)hipStreamDestroy(mh->st[s]);
-  }
+  for (Shard& S : mh->shard) // all of them first: each synchronises its stream
+    if (S.h) glrm_hip_destroy(S.h);
+  for (Shard& S : mh->shard) S.close();
   delete mh;
 }
 
 static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_options* o, const glrm_multi_options* mo) {
   const int n = mh->n;
+  std::vector<Shard>& sh = mh->shard;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GLRM_ERR_HIP, "no HIP device is visible (this engine has no CPU fallback)");
-  mh->dev.resize(n);
   bool distinct = true;
   for (int s = 0; s < n; ++s) {
-    mh->dev[s] = mo->device_ids ? mo->device_ids[s] : s;
-    if (mh->dev[s] < 0 || mh->dev[s] >= ndev) return fail(GLRM_ERR_INVALID, "device_ids[%d] = %d out of range (%d devices)", s, mh->dev[s], ndev);
-    for (int t = 0; t < s; ++t) distinct = distinct && mh->dev[t] != mh->dev[s];
+    sh[s].dev = mo->device_ids ? mo->device_ids[s] : s;
+    if (sh[s].dev < 0 || sh[s].dev >= ndev) return fail(GLRM_ERR_INVALID, "device_ids[%d] = %d out of range (%d devices)", s, sh[s].dev, ndev);
+    for (int t = 0; t < s; ++t) distinct = distinct && sh[t].dev != sh[s].dev;
   }
   mh->m = p->m; mh->nn = p->n; mh->k = p->k;
   mh->dense = p->dense_A != nullptr;
@@ -506,28 +554,24 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
   mh->ybs.resize((size_t)n + 1);
   for (int s = 0; s <= n; ++s) mh->ybs[s] = ystart[mh->cbs[s]];
   mh->n_rx = p->n_rx; mh->n_ry = p->n_ry;
-  mh->sh.assign(n, nullptr); mh->st.assign(n, nullptr);
-  mh->dX.assign(n, nullptr); mh->dY.assign(n, nullptr); mh->dObjCol.assign(n, nullptr); mh->dObjRow.assign(n, nullptr);
-  mh->ev_done.assign(n, nullptr); mh->ev_ready.assign(n, nullptr);
-  mh->cs.assign(n, std::vector<hipStream_t>(n, nullptr));
-  mh->ev_arr.assign(n, std::vector<hipEvent_t>(n, nullptr));
   for (int s = 0; s < n; ++s) { // peer access (a no-op for shards that share a device)
-    HIPCK(hipSetDevice(mh->dev[s]));
+    Shard& S = sh[s];
+    HIPCK(S.select());
     for (int t = 0; t < n; ++t) {
-      if (mh->dev[t] == mh->dev[s]) continue;
+      if (sh[t].dev == S.dev) continue;
       int can = 0;
-      if (hipDeviceCanAccessPeer(&can, mh->dev[s], mh->dev[t]) == hipSuccess && can) {
-        const hipError_t e = hipDeviceEnablePeerAccess(mh->dev[t], 0);
+      if (hipDeviceCanAccessPeer(&can, S.dev, sh[t].dev) == hipSuccess && can) {
+        const hipError_t e = hipDeviceEnablePeerAccess(sh[t].dev, 0);
         if (e != hipSuccess) (void)hipGetLastError(); // already enabled is fine; hipMemcpyPeerAsync stages through the host otherwise
       }
     }
-    HIPCK(hipStreamCreateWithFlags(&mh->st[s], hipStreamNonBlocking));
-    HIPCK(hipEventCreate(&mh->ev_done[s]));
-    HIPCK(hipEventCreate(&mh->ev_ready[s]));
+    HIPCK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+    HIPCK(hipEventCreate(&S.ev_done));
+    HIPCK(hipEventCreate(&S.ev_ready));
     for (int t = 0; t < n; ++t) {
       if (t == s) continue;
-      HIPCK(hipStreamCreateWithFlags(&mh->cs[s][t], hipStreamNonBlocking));
-      HIPCK(hipEventCreateWithFlags(&mh->ev_arr[s][t], hipEventDisableTiming));
+      HIPCK(hipStreamCreateWithFlags(&S.to[t].copy, hipStreamNonBlocking));
+      HIPCK(hipEventCreateWithFlags(&S.to[t].arrived, hipEventDisableTiming));
     }
   }
   // shard handles, created concurrently (each uploads its own slices)
@@ -549,35 +593,31 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     if (p->n_ry != 1) { q.ry = p->ry + q.col_begin; q.n_ry = q.col_end - q.col_begin; }
     glrm_options oo{};
     if (o) oo = *o;
-    oo.device_id = mh->dev[s];
-    oo.stream = (void*)mh->st[s];
+    oo.device_id = sh[s].dev;
+    oo.stream = (void*)sh[s].st;
     oo.caller_stream = 1;
     q.flags |= GLRM_PROBLEM_DEFER_SETUP; // the kernel families are chosen below, from the signature of the WHOLE problem
-    return glrm_hip_create(&mh->sh[s], &q, &oo);
+    return glrm_hip_create(&sh[s].h, &q, &oo);
   });
   if (rc) return rc;
   glrm_signature whole{};
-  for (int s = 0; s < n; ++s) {
+  for (Shard& S : sh) {
     glrm_signature l{};
-    if ((rc = glrm_hip_signature(mh->sh[s], &l))) return rc;
-    whole.nnz_rows += l.nnz_rows; whole.nnz_cols += l.nnz_cols;
-    whole.max_row_len = std::max(whole.max_row_len, l.max_row_len); whole.max_col_len = std::max(whole.max_col_len, l.max_col_len);
-    whole.rows_unordered = std::max(whole.rows_unordered, l.rows_unordered); whole.cols_unordered = std::max(whole.cols_unordered, l.cols_unordered);
+    if ((rc = glrm_hip_signature(S.h, &l))) return rc;
+    glrm_signature_add(whole, l);
   }
-  if ((rc = run_all(mh, [&](int s) -> int { return glrm_hip_finalize(mh->sh[s], &whole); }))) return rc;
-  mh->ld = glrm_hip_factor_ld(mh->sh[0]);
-  for (int s = 0; s < n; ++s) {
-    HIPCK(hipSetDevice(mh->dev[s]));
-    const size_t xb = (size_t)mh->ld * mh->m * 8, yb = (size_t)mh->ld * mh->d * 8;
-    HIPCK(hipMalloc((void**)&mh->dX[s], xb));
-    HIPCK(hipMalloc((void**)&mh->dY[s], yb));
-    HIPCK(hipMalloc((void**)&mh->dObjCol[s], (size_t)mh->nn * 8));
-    HIPCK(hipMalloc((void**)&mh->dObjRow[s], (size_t)mh->m * 8));
-    HIPCK(hipMemsetAsync(mh->dX[s], 0, xb, mh->st[s]));
-    HIPCK(hipMemsetAsync(mh->dY[s], 0, yb, mh->st[s]));
-    HIPCK(hipMemsetAsync(mh->dObjCol[s], 0, (size_t)mh->nn * 8, mh->st[s]));
-    HIPCK(hipMemsetAsync(mh->dObjRow[s], 0, (size_t)mh->m * 8, mh->st[s]));
-    if ((rc = glrm_hip_bind_buffers(mh->sh[s], mh->dX[s], mh->dY[s], mh->dObjCol[s], mh->dObjRow[s]))) return rc;
+  if ((rc = run_all(mh, [&](int s) -> int { return glrm_hip_finalize(sh[s].h, &whole); }))) return rc;
+  mh->ld = glrm_hip_factor_ld(sh[0].h);
+  for (Shard& S : sh) { // the replica: bound where the handle's own factors and objective vectors would stand
+    HIPCK(S.select());
+    const size_t xn = (size_t)mh->ld * mh->m, yn = (size_t)mh->ld * mh->d;
+    if ((rc = S.mem.alloc(&S.X, xn)) || (rc = S.mem.alloc(&S.Y, yn)) || (rc = S.mem.alloc(&S.objCol, (size_t)mh->nn)) || (rc = S.mem.alloc(&S.objRow, (size_t)mh->m)))
+      return rc;
+    HIPCK(hipMemsetAsync(S.X, 0, xn * 8, S.st));
+    HIPCK(hipMemsetAsync(S.Y, 0, yn * 8, S.st));
+    HIPCK(hipMemsetAsync(S.objCol, 0, (size_t)mh->nn * 8, S.st));
+    HIPCK(hipMemsetAsync(S.objRow, 0, (size_t)mh->m * 8, S.st));
+    if ((rc = glrm_hip_bind_buffers(S.h, S.X, S.Y, S.objCol, S.objRow))) return rc;
   }
   mh->exchange = 0;
   const int want = knob_or(Knob::EXCHANGE_RCCL, mo->exchange);
@@ -590,8 +630,11 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     const bool shared_ok = false;
 #endif
     if (R.ok && (distinct || shared_ok)) {
-      mh->comms.assign(n, nullptr);
-      const int e = R.CommInitAll(mh->comms.data(), n, mh->dev.data());
+      std::vector<Rccl::comm_t> comms((size_t)n, nullptr);
+      std::vector<int> devs;
+      for (const Shard& S : sh) devs.push_back(S.dev);
+      const int e = R.CommInitAll(comms.data(), n, devs.data());
+      for (int s = 0; s < n; ++s) sh[s].comm = comms[s]; // (whatever a failed call left behind goes with the shard)
       if (e) return fail(GLRM_ERR_COMM, "ncclCommInitAll failed: %s", R.GetErrorString ? R.GetErrorString(e) : "?");
       mh->exchange = 1;
     } // else: direct path (shards sharing a device, or no librccl.so)
@@ -599,14 +642,13 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
   mh->x_chunks = (mo->x_chunks >= 2 && n > 1 && !mh->dense && mh->exchange == 0) ? mo->x_chunks : 1;
   // arrival order: the direct exchange of list problems (the dense path walks A, not X, super-tile by super-tile)
   mh->arrival = (n > 1 && !mh->dense && mh->exchange == 0 && knob_or(Knob::MULTI_ARRIVAL, mo->arrival == 2 ? 0 : 1)) ? 1 : 0;
-  mh->ev_chunk.assign(n, std::vector<std::vector<hipEvent_t>>(n));
   if (mh->arrival)
     for (int s = 0; s < n; ++s) {
-      HIPCK(hipSetDevice(mh->dev[s]));
+      HIPCK(sh[s].select());
       for (int t = 0; t < n; ++t) {
         if (t == s) continue;
-        mh->ev_chunk[s][t].assign((size_t)mh->x_chunks, nullptr);
-        for (int j = 0; j < mh->x_chunks; ++j) HIPCK(hipEventCreateWithFlags(&mh->ev_chunk[s][t][j], hipEventDisableTiming));
+        sh[s].to[t].chunk.assign((size_t)mh->x_chunks, nullptr);
+        for (hipEvent_t& e : sh[s].to[t].chunk) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       }
     }
 #ifdef GLRM_HIP_TESTING
@@ -617,33 +659,32 @@ static int multi_create_impl(glrm_multi* mh, const glrm_problem* p, const glrm_o
     int share = 1;
     for (int s = 0; s < n; ++s) {
       int c = 0;
-      for (int t = 0; t < n; ++t) c += mh->dev[t] == mh->dev[s];
+      for (int t = 0; t < n; ++t) c += sh[t].dev == sh[s].dev;
       share = std::max(share, c);
     }
     e.dilate = std::max(1, knob_or(Knob::EMULATE_DILATE, share));
     e.gbps = gbps;
+    e.shards = sh.data();
     int can = 0;
-    if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, mh->dev[0]) != hipSuccess) { (void)hipGetLastError(); can = 0; }
+    if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, sh[0].dev) != hipSuccess) { (void)hipGetLastError(); can = 0; }
     e.mode = knob_or(Knob::EMULATE_MODE, can ? 1 : 2);
     if (e.mode != 1 && e.mode != 2) return fail(GLRM_ERR_INVALID, "link emulator: GLRM_EXCHANGE_EMULATE_MODE must be 1 (stream wait-value) or 2 (delay kernels)");
     if (e.mode == 1 && !can) return fail(GLRM_ERR_UNSUPPORTED, "link emulator: GLRM_EXCHANGE_EMULATE_MODE=1: the device does not support hipStreamWaitValue64");
     if (e.mode == 1) {
-      e.mark.assign(n, nullptr); e.release.assign(n, nullptr); e.ticket.assign(n, 0);
-      for (int s = 0; s < n; ++s) {
-        HIPCK(hipSetDevice(mh->dev[s]));
-        HIPCK(hipExtMallocWithFlags((void**)&e.mark[s], 8, hipMallocSignalMemory));
-        HIPCK(hipExtMallocWithFlags((void**)&e.release[s], 8, hipMallocSignalMemory));
-        *e.mark[s] = 0; *e.release[s] = 0; // signal memory is host-visible
+      for (Shard& S : sh) {
+        HIPCK(S.select());
+        HIPCK(hipExtMallocWithFlags((void**)&S.mark, 8, hipMallocSignalMemory));
+        HIPCK(hipExtMallocWithFlags((void**)&S.release, 8, hipMallocSignalMemory));
+        *S.mark = 0; *S.release = 0; // signal memory is host-visible
       }
       e.timer = std::thread([mh] { mh->emu.timer_loop(); });
     } else {
-      e.t0.assign(n, nullptr);
       int khz = 0;
-      if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, mh->dev[0]) == hipSuccess && khz > 0) e.wall_hz = khz * 1e3;
+      if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, sh[0].dev) == hipSuccess && khz > 0) e.wall_hz = khz * 1e3;
       else (void)hipGetLastError();
-      for (int s = 0; s < n; ++s) {
-        HIPCK(hipSetDevice(mh->dev[s]));
-        HIPCK(hipMalloc((void**)&e.t0[s], 8));
+      for (Shard& S : sh) {
+        HIPCK(S.select());
+        if ((rc = S.mem.alloc(&S.t0, 1))) return rc;
       }
     }
     e.bytes_per_s = gbps * 1e9 / e.dilate; // set last: the hooks are live from here
@@ -660,44 +701,12 @@ extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, co
   *out = nullptr;
   if (o && o->storage == GLRM_STORAGE_F32) return fail(GLRM_ERR_UNSUPPORTED, "glrm_hip_multi_create is not available with storage = f32 (glrm_options.storage = 1): sharded fits have no f32 form");
   if (o && o->storage != GLRM_STORAGE_F64) return fail(GLRM_ERR_INVALID, "glrm_options.storage must be 0 (f64) or 1 (f32), got %d", o->storage);
+  int rc;
+  glrm_problem q; // *p with the derived row view below (create copies every slice to its device: the vectors go when this returns)
+  std::vector<int64_t> rowptr; std::vector<int32_t> colidx; std::vector<double> rowvals;
   if ((p->flags & GLRM_PROBLEM_ROWS_FROM_COLS) && !(p->flags & GLRM_PROBLEM_DEVICE_ARRAYS)) {
-    // Omega is a sparse matrix's pattern, handed over as its column view only: every shard needs its rows' lists, so the row view is
-    // built here, once, by a counting transpose on the host (columns in order => every row's list ascending), and the shards are cut
-    // from both views as usual
-    if (p->dense_A || p->rowptr || p->colidx || p->rowvals) return fail(GLRM_ERR_INVALID, "GLRM_PROBLEM_ROWS_FROM_COLS: rowptr / colidx / rowvals must be NULL");
-    if (p->m <= 0 || p->n <= 0 || !p->colptr) return fail(GLRM_ERR_INVALID, "m, n must be positive and colptr given");
-    // the structure of the column view is checked BEFORE anything is counted or written through it (a colptr that does not start
-    // at 0, is not monotone or ends beyond the arrays made the fill loop read and write past the vectors; the single-device path checks first)
-    if (p->colptr[0] != 0) return fail(GLRM_ERR_INVALID, "colptr[0] must be 0");
-    for (int64_t f = 0; f < p->n; ++f)
-      if (p->colptr[f + 1] < p->colptr[f]) return fail(GLRM_ERR_INVALID, "colptr is not monotone at %lld", (long long)f);
-    const int64_t nz = p->colptr[p->n]; // >= 0 and >= every other entry from here on
-    if (nz > 0 && (!p->rowidx || !p->colvals)) return fail(GLRM_ERR_INVALID, "index / value arrays are NULL");
-    std::vector<int64_t> rowptr, fill;
-    std::vector<int32_t> colidx;
-    std::vector<double> rowvals;
-    try {
-      rowptr.assign((size_t)p->m + 1, 0); fill.resize((size_t)p->m);
-      colidx.resize((size_t)nz); rowvals.resize((size_t)nz);
-    } catch (const std::exception&) { // nothing may unwind across the extern "C" boundary
-      return fail(GLRM_ERR_OOM, "out of host memory for the row view of %lld observations", (long long)nz);
-    }
-    for (int64_t t = 0; t < nz; ++t) {
-      if (p->rowidx[t] < 0 || p->rowidx[t] >= p->m) return fail(GLRM_ERR_INVALID, "rowidx holds an index outside [0, m)");
-      rowptr[(size_t)p->rowidx[t] + 1] += 1;
-    }
-    for (int64_t i = 0; i < p->m; ++i) { rowptr[i + 1] += rowptr[i]; fill[i] = rowptr[i]; }
-    for (int64_t f = 0; f < p->n; ++f)
-      for (int64_t t = p->colptr[f]; t < p->colptr[f + 1]; ++t) {
-        const int64_t r = p->rowidx[t], at = fill[r]++;
-        if (at >= rowptr[r + 1]) return fail(GLRM_ERR_INVALID, "the column view changed while it was read"); // (cannot happen on a checked, unchanged view)
-        colidx[at] = (int32_t)f;
-        rowvals[at] = p->colvals[t];
-      }
-    glrm_problem q = *p;
-    q.flags &= ~GLRM_PROBLEM_ROWS_FROM_COLS;
-    q.rowptr = rowptr.data(); q.colidx = colidx.data(); q.rowvals = rowvals.data();
-    return glrm_hip_multi_create(out, &q, o, mo); // (create copies every slice to its device: the vectors may go afterwards)
+    if ((rc = host_rows_from_cols(p, &q, rowptr, colidx, rowvals))) return rc;
+    p = &q;
   }
   if (mo->n_shards < 1 || mo->n_shards > 64) return fail(GLRM_ERR_INVALID, "n_shards must be in 1..64");
   if (mo->arrival < 0 || mo->arrival > 2) return fail(GLRM_ERR_INVALID, "glrm_multi_options.arrival must be 0, 1 or 2");
@@ -709,18 +718,11 @@ extern "C" int glrm_hip_multi_create(glrm_multi** out, const glrm_problem* p, co
   if (!p->losses || !(p->n_losses == 1 || p->n_losses == p->n) || !p->rx || !(p->n_rx == 1 || p->n_rx == p->m) || !p->ry ||
       !(p->n_ry == 1 || p->n_ry == p->n))
     return fail(GLRM_ERR_INVALID, "descriptor counts must be 1 or one per column / row");
-  if (!p->dense_A) {
-    if (p->rowptr[0] != 0 || p->colptr[0] != 0) return fail(GLRM_ERR_INVALID, "rowptr[0] / colptr[0] must be 0");
-    for (int64_t s = 0; s < p->m; ++s) if (p->rowptr[s + 1] < p->rowptr[s]) return fail(GLRM_ERR_INVALID, "rowptr is not monotone at %lld", (long long)s);
-    for (int64_t s = 0; s < p->n; ++s) if (p->colptr[s + 1] < p->colptr[s]) return fail(GLRM_ERR_INVALID, "colptr is not monotone at %lld", (long long)s);
-  }
+  if (!p->dense_A && ((rc = glrm_check_offsets("rowptr", p->rowptr, p->m)) || (rc = glrm_check_offsets("colptr", p->colptr, p->n)))) return rc;
   DeviceScope dg;
-  glrm_multi* mh = new (std::nothrow) glrm_multi();
+  glrm_multi* mh = new (std::nothrow) glrm_multi(mo->n_shards);
   if (!mh) return fail(GLRM_ERR_OOM, "out of host memory");
-  mh->n = mo->n_shards;
-  mh->pool.start(mh->n);
-  const int rc = multi_create_impl(mh, p, o, mo);
-  if (rc) {
+  if ((rc = multi_create_impl(mh, p, o, mo))) {
     char keep[sizeof g_err];
     memcpy(keep, g_err, sizeof keep);
     glrm_hip_multi_destroy(mh);
@@ -736,10 +738,11 @@ extern "C" int glrm_hip_multi_set_regularizers(glrm_multi* mh, const glrm_reg* r
   if (n_rx != mh->n_rx || n_ry != mh->n_ry) return fail(GLRM_ERR_INVALID, "regularizer counts must match the create call");
   for (int pass = 0; pass < 2; ++pass) // every shard's slice is checked before any shard is changed: a refusal leaves the model as it was
     for (int s = 0; s < mh->n; ++s) {
+      glrm_handle* h = mh->shard[s].h;
       const glrm_reg* sx = n_rx == 1 ? rx : rx + mh->rbs[s];
       const glrm_reg* sy = n_ry == 1 ? ry : ry + mh->cbs[s];
       const int64_t nx = n_rx == 1 ? 1 : mh->rbs[s + 1] - mh->rbs[s], ny = n_ry == 1 ? 1 : mh->cbs[s + 1] - mh->cbs[s];
-      const int rc = pass == 0 ? glrm_check_regularizers(mh->sh[s], sx, nx, sy, ny) : glrm_hip_set_regularizers(mh->sh[s], sx, nx, sy, ny);
+      const int rc = pass == 0 ? glrm_check_regularizers(h, sx, nx, sy, ny) : glrm_hip_set_regularizers(h, sx, nx, sy, ny);
       if (rc) return rc;
     }
   return GLRM_OK;
@@ -753,11 +756,12 @@ extern "C" int glrm_hip_multi_set_regularizers_vec(glrm_multi* mh, const glrm_re
   if ((vx && (!vx->vec || !vx->len)) || (vy && (!vy->vec || !vy->len))) return fail(GLRM_ERR_INVALID, "glrm_regvec.vec / len are NULL");
   for (int pass = 0; pass < 2; ++pass) // every shard's slice is checked before any shard is changed: a refusal leaves the model as it was
     for (int s = 0; s < mh->n; ++s) {
+      glrm_handle* h = mh->shard[s].h;
       const int64_t ox = n_rx == 1 ? 0 : mh->rbs[s], oy = n_ry == 1 ? 0 : mh->cbs[s];
       const int64_t nx = n_rx == 1 ? 1 : mh->rbs[s + 1] - mh->rbs[s], ny = n_ry == 1 ? 1 : mh->cbs[s + 1] - mh->cbs[s];
       const glrm_regvec sx{vx ? vx->vec + ox * mh->k : nullptr, vx ? vx->len + ox : nullptr}, sy{vy ? vy->vec + oy * mh->k : nullptr, vy ? vy->len + oy : nullptr};
-      const int rc = pass == 0 ? glrm_check_regularizers_vec(mh->sh[s], rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr)
-                               : glrm_hip_set_regularizers_vec(mh->sh[s], rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr);
+      const int rc = pass == 0 ? glrm_check_regularizers_vec(h, rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr)
+                               : glrm_hip_set_regularizers_vec(h, rx + ox, nx, vx ? &sx : nullptr, ry + oy, ny, vy ? &sy : nullptr);
       if (rc) return rc;
     }
   return GLRM_OK;
@@ -775,21 +779,18 @@ extern "C" int glrm_hip_multi_info(glrm_multi* mh, int64_t* row_bounds, int64_t*
 extern "C" int glrm_hip_multi_fit(glrm_multi* mh, const glrm_params* prm, double* X, double* Y, double* objective, double* seconds,
                                   int64_t cap, int64_t* n_recorded) {
   if (!mh || !prm || !X || !Y || !objective || !seconds || !n_recorded) return fail(GLRM_ERR_INVALID, "NULL argument");
-  if (prm->max_iter < 0 || cap < prm->max_iter + 1) return fail(GLRM_ERR_INVALID, "objective/seconds capacity must be >= max_iter+1");
-  if (prm->inner_iter_X < 1 || prm->inner_iter_Y < 1) return fail(GLRM_ERR_INVALID, "inner iteration counts must be >= 1");
-  double ynorm = 0.0; // norm(Y)==0 guard, proxgrad.jl:45-48
-  for (int64_t i = 0; i < (int64_t)mh->k * mh->d; ++i) ynorm += Y[i] * Y[i];
-  if (ynorm == 0.0) return fail(GLRM_ERR_INVALID, "Y is all zeros (the reference cannot start from Y == 0)");
-  DeviceScope dg;
   int rc;
+  if ((rc = glrm_check_fit_args(prm, cap, Y, mh->k, mh->d))) return rc;
+  DeviceScope dg;
+  std::vector<Shard>& sh = mh->shard;
   mh->exchange_ms = 0.0;
   if ((rc = run_all(mh, [&](int s) {                                    // X = glrm.X; Y = glrm.Y (:43), alpharow / alphacol (:69-70)
-         int r = glrm_hip_set_factors(mh->sh[s], X, Y);
-         return r ? r : glrm_hip_reset_stepsizes(mh->sh[s], prm->stepsize);
+         int r = glrm_hip_set_factors(sh[s].h, X, Y);
+         return r ? r : glrm_hip_reset_stepsizes(sh[s].h, prm->stepsize);
        })))
     return rc;
   int64_t nnz_rows = 0;
-  for (int s = 0; s < mh->n; ++s) nnz_rows += mh->sh[s]->side[GLRM_ROWS].nnz;
+  for (const Shard& S : sh) nnz_rows += S.h->side[GLRM_ROWS].nnz;
   // arrival order: what shard t's Y half-step is told about the rows of X -- its own block is there, then chunk 0 of every peer (ring
   // order from t: the order the peers push in), chunk 1 of every peer, ...; the events are re-recorded by every iteration's pushes
   const int n = mh->n, C = mh->x_chunks;
@@ -803,16 +804,14 @@ extern "C" int glrm_hip_multi_fit(glrm_multi* mh, const glrm_params* prm, double
           const int s = (t + n - d) % n; // s pushes to (s + d) % n = t as its d-th destination
           const int64_t blk = mh->rbs[s + 1] - mh->rbs[s];
           const int64_t lo = mh->rbs[s] + blk * j / C, hi = mh->rbs[s] + blk * (j + 1) / C;
-          if (hi > lo) arrv[t].push_back(glrm_arrival{lo, hi, (void*)mh->ev_chunk[s][t][j]});
+          if (hi > lo) arrv[t].push_back(glrm_arrival{lo, hi, (void*)sh[s].to[t].chunk[j]});
         }
     }
-    mh->wait_y0.assign((size_t)n, 0.0);
-    if (mh->profile)
-      for (int s = 0; s < n; ++s) {
-        glrm_kernel_stats ks{};
-        if ((rc = glrm_hip_kernel_stats(mh->sh[s], &ks, 0))) return rc;
-        mh->wait_y0[s] = ks.ms_wait_y;
-      }
+    for (Shard& S : sh) {
+      glrm_kernel_stats ks{};
+      if (mh->profile && (rc = glrm_hip_kernel_stats(S.h, &ks, 0))) return rc;
+      S.wait_y0 = ks.ms_wait_y;
+    }
   }
   // a shard may not overwrite its block of X (Y) while a push of the previous iteration's exchanges still reads it: at the start of an
   // iteration its stream waits for its own outgoing copies (one copy stream per link keeps them in order, so the last event covers all;
@@ -820,73 +819,66 @@ extern "C" int glrm_hip_multi_fit(glrm_multi* mh, const glrm_params* prm, double
   auto wait_outgoing = [&]() -> int {
     if (n == 1 || mh->exchange == 1) return GLRM_OK;
     for (int s = 0; s < n; ++s) {
-      COMMCK(hipSetDevice(mh->dev[s]));
+      COMMCK(sh[s].select());
       for (int t = 0; t < n; ++t)
-        if (t != s) COMMCK(hipStreamWaitEvent(mh->st[s], mh->ev_arr[s][t], 0));
+        if (t != s) COMMCK(hipStreamWaitEvent(sh[s].st, sh[s].to[t].arrived, 0));
     }
     return GLRM_OK;
   };
-  const double scaled_abs_tol = prm->abs_tol * (double)nnz_rows;       // :72
-  if ((rc = multi_objective(mh, &objective[0]))) return rc;           // :76
-  seconds[0] = 0.0;
-  int64_t nrec = 1;
-  double t = now_s();
+  glrm_trace trace(objective, seconds, prm, nnz_rows);                 // :72
+  double obj0 = 0.0;
+  if ((rc = multi_objective(mh, &obj0))) return rc;
+  trace.start(obj0);
   for (int64_t i = 1; i <= prm->max_iter; ++i) {                       // :107
     if (prm->inner_iter_X > 1 || prm->inner_iter_Y > 1)
-      if ((rc = run_all(mh, [&](int s) { return glrm_hip_reset_stepsizes(mh->sh[s], prm->stepsize); }))) return rc; // :112-115
+      if ((rc = run_all(mh, [&](int s) { return glrm_hip_reset_stepsizes(sh[s].h, prm->stepsize); }))) return rc; // :112-115
     if ((rc = wait_outgoing())) return rc;
     for (int64_t in = 0; in + 1 < prm->inner_iter_X; ++in)              // inner sweeps touch own rows only: exchange once
-      if ((rc = run_all(mh, [&](int s) { return glrm_hip_step_x(mh->sh[s], prm->min_stepsize); }))) return rc;
+      if ((rc = run_all(mh, [&](int s) { return glrm_hip_step_x(sh[s].h, prm->min_stepsize); }))) return rc;
     if (C > 1 || arr) { // last inner sweep in row chunks: the push of chunk j overlaps the sweep of chunk j+1
       for (int j = 0; j < C; ++j) {
         if ((rc = run_all(mh, [&](int s) {
-               if (C == 1) return glrm_hip_step_x(mh->sh[s], prm->min_stepsize);
+               if (C == 1) return glrm_hip_step_x(sh[s].h, prm->min_stepsize);
                const int64_t ml = mh->rbs[s + 1] - mh->rbs[s];
-               return glrm_hip_step_x_range(mh->sh[s], ml * j / C, ml * (j + 1) / C, prm->min_stepsize);
+               return glrm_hip_step_x_range(sh[s].h, ml * j / C, ml * (j + 1) / C, prm->min_stepsize);
              })))
           return rc;
-        if ((rc = exchange_push(mh, mh->dX, mh->rbs, mh->ld, -1, j, C, arr))) return rc;
+        if ((rc = exchange_push(mh, &Shard::X, mh->rbs, mh->ld, -1, j, C, arr))) return rc;
       }
       if (!arr) { // the Y half-step needs all of X: wait here (with arrival order it waits block by block, inside step_y_arrival)
         if ((rc = exchange_wait(mh, -1))) return rc;
         account_exchange(mh);
       }
     } else {
-      if ((rc = run_all(mh, [&](int s) { return glrm_hip_step_x(mh->sh[s], prm->min_stepsize); }))) return rc; // :117-158
-      if ((rc = exchange_all(mh, mh->dX, mh->rbs, mh->ld))) return rc;
+      if ((rc = run_all(mh, [&](int s) { return glrm_hip_step_x(sh[s].h, prm->min_stepsize); }))) return rc; // :117-158
+      if ((rc = exchange_all(mh, &Shard::X, mh->rbs, mh->ld))) return rc;
       account_exchange(mh);
     }
     for (int64_t in = 0; in < prm->inner_iter_Y; ++in)                  // :160-203
       if ((rc = run_all(mh, [&](int s) {
-             if (arr && in == 0) return glrm_hip_step_y_arrival(mh->sh[s], prm->min_stepsize, arrv[s].data(), (int32_t)arrv[s].size());
-             return glrm_hip_step_y(mh->sh[s], prm->min_stepsize);
+             if (arr && in == 0) return glrm_hip_step_y_arrival(sh[s].h, prm->min_stepsize, arrv[s].data(), (int32_t)arrv[s].size());
+             return glrm_hip_step_y(sh[s].h, prm->min_stepsize);
            })))
         return rc;
-    if ((rc = exchange_all(mh, mh->dY, mh->ybs, mh->ld))) return rc;
+    if ((rc = exchange_all(mh, &Shard::Y, mh->ybs, mh->ld))) return rc;
     account_exchange(mh);
-    if ((rc = exchange_all(mh, mh->dObjCol, mh->cbs, 1, mh->exchange == 1 ? -1 : 0))) return rc;
+    if ((rc = exchange_all(mh, &Shard::objCol, mh->cbs, 1, mh->exchange == 1 ? -1 : 0))) return rc;
     double obj = 0.0;
-    if ((rc = sum_on_shard0(mh, mh->dObjCol[0], mh->nn, &obj))) return rc; // obj = sum(obj_by_col) :205 (synchronises shard 0)
-    const double dt = now_s() - t;
-    objective[nrec] = obj;
-    seconds[nrec] = seconds[nrec - 1] + dt;                            // update_ch! (src/convergence.jl:22-26)
-    ++nrec;
-    t = now_s();
-    const double dec = objective[nrec - 2] - obj;                      // :210
-    if (i > 10 && (dec < scaled_abs_tol || dec / obj < prm->rel_tol)) break; // :211-213
+    if ((rc = glrm_hip_sum(sh[0].h, sh[0].objCol, mh->nn, &obj))) return rc; // obj = sum(obj_by_col) :205 (synchronises shard 0)
+    if (trace.record(i, obj)) break;
   }
-  for (int s = 0; s < mh->n; ++s)
-    if ((rc = glrm_hip_synchronize(mh->sh[s]))) return rc;
+  for (Shard& S : sh)
+    if ((rc = glrm_hip_synchronize(S.h))) return rc;
   if (arr && mh->profile) { // what the Y half-steps spent in front of blocks of X that had not arrived yet
     double worst = 0.0;
-    for (int s = 0; s < n; ++s) {
+    for (Shard& S : sh) {
       glrm_kernel_stats ks{};
-      if ((rc = glrm_hip_kernel_stats(mh->sh[s], &ks, 0))) return rc;
-      worst = std::max(worst, ks.ms_wait_y - mh->wait_y0[s]);
+      if ((rc = glrm_hip_kernel_stats(S.h, &ks, 0))) return rc;
+      worst = std::max(worst, ks.ms_wait_y - S.wait_y0);
     }
     mh->exchange_ms += worst;
   }
-  if ((rc = glrm_hip_get_factors(mh->sh[0], X, Y))) return rc;
-  *n_recorded = nrec;
+  if ((rc = glrm_hip_get_factors(sh[0].h, X, Y))) return rc;
+  *n_recorded = trace.nrec;
   return GLRM_OK;
 }

@@ -21,8 +21,6 @@
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 __global__ void iota_u32_kernel(uint32_t* p, int64_t n) {
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) p[t] = (uint32_t)t;
 }

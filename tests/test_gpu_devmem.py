@@ -250,6 +250,47 @@ def test_every_extension_call_returns_with_the_count_it_found():
             api.destroy(h)
 
 
+# ------------------------------------------------------------------------------------------------ sharded fits (glrm_hip_multi_*)
+
+@pytest.mark.parametrize("arrival", [1, 2])
+def test_a_sharded_fit_gives_back_what_it_took(arrival):
+    """Three shards on device 0, the X exchange in two chunks; arrival = 1: the Y half-step takes the chunks in arrival order (chunk events),
+    arrival = 2: it waits for the whole exchange."""
+    g, X0, Y0 = list_model()
+    api = engine()
+    with balanced():
+        mh = api.multi_create(g.problem_arrays(), 3, device_ids=[0, 0, 0], x_chunks=2, arrival=arrival)
+        try:
+            assert live() > 0
+            obj, _ = api.multi_fit(mh, L.HipProxGradParams(1.0, max_iter=2), X0.copy(order="F"), Y0.copy(order="F"))
+            assert len(obj) == 3
+            assert api.multi_info(mh, 3)["exchange"] == 0
+        finally:
+            api.multi_destroy(mh)
+
+
+def test_the_replica_of_a_shard_is_counted():
+    """A shard's replica of X, Y and the two objective vectors belongs to the shard's arena: bound to the handle, the four stand where the
+    handle's own four would (ensure_owned, at the first set_factors), so one shard holds exactly what a single-device handle holds."""
+    g, X0, Y0 = list_model()
+    pa = g.problem_arrays()
+    api = engine()
+    before = live()
+    h = api.create(pa)
+    try:
+        api.set_factors(h, X0, Y0)
+        single = live() - before
+    finally:
+        api.destroy(h)
+    assert live() == before
+    mh = api.multi_create(pa, 1, device_ids=[0])
+    try:
+        assert live() - before == single, (live() - before, single)
+    finally:
+        api.multi_destroy(mh)
+    assert live() == before
+
+
 # ------------------------------------------------------------------------------------------------ balance on failing paths
 
 def refused(code, fn, *args, **kw):
@@ -257,6 +298,24 @@ def refused(code, fn, *args, **kw):
         fn(*args, **kw)
     assert e.value.code == code, (e.value.code, e.value.message)
     return e.value.message
+
+
+def test_a_sharded_create_that_fails_before_its_replicas_exist_gives_everything_back(monkeypatch):
+    g, X0, Y0 = list_model()
+    monkeypatch.setenv("GLRM_HIP_TEST_FAIL_FINALIZE", "1")
+    with balanced():
+        msg = refused(_capi.ERR_OOM, engine().multi_create, g.problem_arrays(), 3, device_ids=[0, 0, 0])
+    assert "shard" in msg and "injected" in msg, msg
+
+
+def test_a_sharded_create_that_fails_after_its_replicas_exist_gives_everything_back(monkeypatch):
+    """The emulator's mode is checked last: the replicas, the arrival events and the chunk events have been made by then."""
+    g, X0, Y0 = list_model()
+    monkeypatch.setenv("GLRM_EXCHANGE_EMULATE_GBPS", "1")
+    monkeypatch.setenv("GLRM_EXCHANGE_EMULATE_MODE", "3")
+    with balanced():
+        msg = refused(_capi.ERR_INVALID, engine().multi_create, g.problem_arrays(), 2, device_ids=[0, 0])
+    assert "must be 1" in msg and "or 2" in msg, msg
 
 
 def test_a_set_up_that_fails_half_way_is_given_back_by_destroy(monkeypatch):
@@ -364,6 +423,13 @@ def test_no_entry_point_changes_the_callers_current_device():
         call(api.scale_columns, pa, _capi.SCALE_EQUILIBRATE, device_id=1)
         call(api.fit_sparse, h, L.SparseProxGradParams(0.01, max_iter=2), X0.copy(order="F"), Y0.copy(order="F"))
         call(api.set_regularizers_vec, h, *vector_regs(g, 0.5))
+        mh = call(api.multi_create, pa, 2, device_ids=[1, 0])            # the sharded entry points select every shard's device in turn
+        try:
+            call(api.multi_fit, mh, L.HipProxGradParams(1.0, max_iter=2), X0.copy(order="F"), Y0.copy(order="F"))
+            call(api.multi_set_regularizers, mh, pa.rx, pa.ry)
+            call(api.multi_info, mh, 2)
+        finally:
+            call(api.multi_destroy, mh)
     finally:
         for c in kids:
             api.destroy(c)
