@@ -169,6 +169,11 @@ REGVEC_SYMBOLS = ("set_regularizers_vec", "multi_set_regularizers_vec")
 #: bound only where the library has it
 TOPK_SYMBOLS = ("xy_select", "xy_select_info", "precision_scan")
 
+#: the recommend extension, include/glrm_hip_recommend.h (the kper best columns of every queried row of X'Y, observed ones left out):
+#: outside the boundary, bound only where the library has it
+RECOMMEND_SYMBOLS = ("row_topk", "row_topk_info")
+ROW_TOPK_MAX = 128   # glrm_hip_recommend.h: GLRM_ROW_TOPK_MAX
+
 #: the NMF initialization extension, include/glrm_hip_nmf.h (init_nndsvd! on the resident lists): outside the boundary, bound only where
 #: the library has it
 NMF_SYMBOLS = ("init_nndsvd",)
@@ -278,12 +283,14 @@ class Api:
             "xy_select_info": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
             "precision_scan": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+            "row_topk": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "row_topk_info": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
             "init_nndsvd": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
             "solve_x": (C.c_int, [H, C.c_int64, C.c_double]),
             "solve_x_info": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
+        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -699,6 +706,46 @@ class Api:
             cnt = tp.value + fp.value
             hits = (hr[:cnt].copy(), hc[:cnt].copy(), ht[:cnt].astype(bool))
         return tp.value, fp.value, hits, rows.value
+
+    # -- recommend extension (include/glrm_hip_recommend.h) ----------------------------------
+    def _recommend(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the recommend extension "
+                                             "(include/glrm_hip_recommend.h is implemented by the HIP engine only)")
+        return fn
+
+    def row_topk(self, h, X, Y, rows, kper, exclude=True, col_splits=0, m=None):
+        """glrm_hip_row_topk: the ``kper`` best candidates of every query row, best first.  The candidates of a row are all columns, minus
+        (``exclude``) the columns in the row's resident (train) list; they are ranked by the key of u_ij descending, then by column
+        ascending, under the key of the top-k extension (Julia's isless: NaN greatest, every NaN one value, -0.0 below +0.0), so a NaN
+        score ranks first.  ``X``, ``Y``: k x m and k x n, or both None for the handle's resident factors.  ``rows``: 0-based row indices
+        in any order, repeats allowed, or None for the rows 0 .. m-1 (m is then read from X, or given as ``m`` with resident factors).
+        ``col_splits``: 0 = the engine chooses its column spans, > 0 = that many (the result does not depend on it).  Returns (cols int32 [n_rows, kper], vals float64 [n_rows, kper], count int32 [n_rows]); a row
+        with c < kper candidates holds column -1 and the quiet NaN 0x7FF8000000000000 at the positions t >= c, and count = min(kper, c)."""
+        fn = self._recommend("row_topk")
+        X, Y = self._factor_pair(X, Y)
+        if rows is None:
+            if X is None and m is None:
+                raise ValueError("rows=None (every row) with the resident factors needs m, the number of rows of the handle's problem")
+            n_rows, rptr = (X.shape[1] if m is None else int(m)), None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            n_rows, rptr = len(rows), _ptr(rows)
+        width = max(int(kper), 1)                                    # (kper < 1 is refused by the library; the buffers are never empty)
+        cols = np.full((max(n_rows, 1), width), -1, dtype=np.int32)
+        vals = np.full((max(n_rows, 1), width), np.nan)
+        count = np.zeros(max(n_rows, 1), dtype=np.int32)
+        self._ck(fn(h, _ptr(X), _ptr(Y), rptr, n_rows, int(kper), int(exclude), int(col_splits), _ptr(cols), _ptr(vals), _ptr(count)))
+        return cols[:n_rows], vals[:n_rows], count[:n_rows]
+
+    def row_topk_info(self) -> dict:
+        """Of this thread's last row_topk: ``col_splits`` (the column spans its first block of query rows ran with), ``row_blocks`` and
+        ``candidates_merged`` (the entries of the spans' kept lists the final merge read)."""
+        fn = self._recommend("row_topk_info")
+        s, b, c = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._ck(fn(C.byref(s), C.byref(b), C.byref(c)))
+        return dict(col_splits=s.value, row_blocks=b.value, candidates_merged=c.value)
 
 
 class ProblemArrays:

@@ -12,6 +12,8 @@
 //   glrm_blocked_f32.hip fp32 storage: the float instantiations of the phase-aligned passes (glrm_blocked.hpp, glrm_tiled.hpp)
 //   glrm_regvec.hip     regularizers that carry a vector (include/glrm_hip_regvec.h): checks, the handle's tables, the two entry points
 //   glrm_topk.hip       the rank-th largest entry of X'Y and the ordered scan of precision_at_k (include/glrm_hip_topk.h)
+//   glrm_recommend.hip  the kper best columns of every queried row of X'Y, observed ones left out (include/glrm_hip_recommend.h); shares
+//                       the tile function, the key and the refusals of glrm_topk.hip through glrm_xytile.hpp
 //   glrm_nmf.hip        init_nndsvd!: NNDSVD and its soft-impute rounds on the resident lists (include/glrm_hip_nmf.h); shares the subspace
 //                       iteration of glrm_svd.hip through glrm_subspace.hpp
 //   glrm_solve.hip      the fused row solver of glrm_hip_solve_x (include/glrm_hip_transform.h): T X half-steps of a row in one launch of the
