@@ -183,6 +183,11 @@ NNDSVD_VARIANTS = {"std": 0, "a": 1, "ar": 2}   # glrm_hip_nmf.h: GLRM_NNDSVD_ST
 #: register kernel admits the rows): outside the boundary, bound only where the library has it
 TRANSFORM_SYMBOLS = ("solve_x", "solve_x_info")
 
+#: the impute_at extension, include/glrm_hip_impute_at.h (imputed values and errors at listed entries, whole rows or whole columns, nothing
+#: m x n): outside the boundary, bound only where the library has it
+IMPUTE_AT_SYMBOLS = ("impute_at", "impute_at_info")
+IMPUTE_AT_PAIRS, IMPUTE_AT_ROWS, IMPUTE_AT_COLS = 0, 1, 2   # glrm_hip_impute_at.h: GLRM_IMPUTE_AT_*
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -289,8 +294,12 @@ class Api:
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
             "solve_x": (C.c_int, [H, C.c_int64, C.c_double]),
             "solve_x_info": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+            "impute_at": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+            "impute_at_info": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         }
-        assert tuple(ext) == SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
+        assert tuple(ext) == (SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
+                              + IMPUTE_AT_SYMBOLS)
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -746,6 +755,71 @@ class Api:
         s, b, c = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         self._ck(fn(C.byref(s), C.byref(b), C.byref(c)))
         return dict(col_splits=s.value, row_blocks=b.value, candidates_merged=c.value)
+
+    # -- impute_at extension (include/glrm_hip_impute_at.h) ----------------------------------
+    def _impute_at(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the impute_at extension "
+                                             "(include/glrm_hip_impute_at.h is implemented by the HIP engine only)")
+        return fn
+
+    @property
+    def has_impute_at(self) -> bool:
+        """The library exports the impute_at extension (the CPU oracle does not: a host indexes the full ``impute`` there)."""
+        return "impute_at" in self._f
+
+    def impute_at(self, h, X, Y, domains, m, n, rows=None, cols=None, truth=None, block_entries=0, want_err=True, want_total=True):
+        """glrm_hip_impute_at: the imputed values of listed entries, and with ``truth`` their errors.  ``rows`` and ``cols`` given (equal
+        lengths): the pairs (rows[t], cols[t]), any order, repeats allowed, out of shape (P,).  Only ``rows``: those rows x all ``n``
+        columns, out of shape (len(rows), n).  Only ``cols``: all ``m`` rows x those columns, out of shape (m, len(cols)).  Slabs come
+        back Fortran-ordered, like ``impute``; every value has the bits the entry has in ``impute``'s matrix.  ``X``, ``Y``: k x m and
+        k x d, or both None for the handle's resident factors.  ``domains``: DOMAIN_DTYPE array, one per column.  ``truth``: values of
+        out's shape, or None.  ``block_entries``: 0 = the engine chooses how many entries go through the device at a time, > 0 = that
+        many (the result does not depend on it).  Returns ``out`` without ``truth``, else ``(out, err, total)`` with err of out's shape
+        (None without ``want_err``) and total the sum of err in index order (None without ``want_total``)."""
+        fn = self._impute_at("impute_at")
+        X, Y = self._factor_pair(X, Y)
+        if rows is None and cols is None:
+            raise ValueError("impute_at needs rows, cols or both (every entry of the model is `impute`)")
+        m, n = int(m), int(n)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if cols is not None:
+            cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        if rows is not None and cols is not None:
+            mode, shape = IMPUTE_AT_PAIRS, (len(rows),)
+            if len(rows) != len(cols):
+                raise ValueError(f"pairs need as many rows as cols, got {len(rows)} and {len(cols)}")
+        elif rows is not None:
+            mode, shape = IMPUTE_AT_ROWS, (len(rows), n)
+        else:
+            mode, shape = IMPUTE_AT_COLS, (m, len(cols))
+        total = int(np.prod(shape))
+        if truth is not None:
+            truth = np.asfortranarray(truth, dtype=np.float64)
+            if truth.shape != shape:
+                raise ValueError(f"truth has shape {truth.shape}, the queried entries {shape}")
+        flat = max(total, 1)                                         # (the buffers are never empty)
+        out = np.full(flat, np.nan)
+        err = np.full(flat, np.nan) if truth is not None and want_err else None
+        tot = C.c_double(np.nan)
+        tbuf = None if truth is None else truth if total else np.zeros(1)
+        self._ck(fn(h, _ptr(X), _ptr(Y), _ptr(domains), _ptr(rows) if rows is not None and len(rows) else None, 0 if rows is None else len(rows),
+                    _ptr(cols) if cols is not None and len(cols) else None, 0 if cols is None else len(cols), mode,
+                    _ptr(tbuf), int(block_entries), _ptr(out), _ptr(err), C.byref(tot) if truth is not None and want_total else None))
+        out = out[:total].reshape(shape, order="F")
+        if truth is None:
+            return out
+        return out, (err[:total].reshape(shape, order="F") if err is not None else None), (tot.value if want_total else None)
+
+    def impute_at_info(self) -> dict:
+        """Of this thread's last impute_at: ``blocks`` (the blocks the entries went through the device in), ``entries_fast`` (scalar-loss
+        entries: the coalesced gather kernel) and ``entries_general`` (entries of multi-dimensional columns)."""
+        fn = self._impute_at("impute_at_info")
+        b, f, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(fn(C.byref(b), C.byref(f), C.byref(g)))
+        return dict(blocks=b.value, entries_fast=f.value, entries_general=g.value)
 
 
 class ProblemArrays:

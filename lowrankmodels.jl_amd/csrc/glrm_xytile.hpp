@@ -1,7 +1,8 @@
 // glrm_xytile.hpp -- what the translation units that walk X'Y tile by tile share (glrm_topk.hip: include/glrm_hip_topk.h; glrm_recommend.hip:
 // include/glrm_hip_recommend.h): the tile geometry, THE definition of u_ij on the device (xy_tile), the order-preserving key of a value,
-// the wave-wide list membership test, and the refusals and the factor upload every such entry point starts with.  One definition each:
-// an entry of X'Y has the same bits, and the same place in the order, whichever kernel asks for it.
+// the wave-wide list membership test, and the refusals and the factor upload every such entry point starts with (glrm_impute_at.hip:
+// include/glrm_hip_impute_at.h takes the handle and factor parts of those alone).  One definition each: an entry of X'Y has the same bits,
+// and the same place in the order, whichever kernel asks for it.
 #pragma once
 
 #include <cstring>
@@ -103,21 +104,32 @@ __device__ __forceinline__ bool tk_wave_member(const int32_t* idx, int64_t b, in
   return false;
 }
 
-// the refusals the entries share (nothing is touched)
-inline int tk_check(glrm_handle* h, const double* X, const double* Y, const char* what) {
+// the refusals the entries share (nothing is touched), in three parts: the handle, the model (one vector of Y per column: what an entry
+// point that walks X'Y by column needs, and glrm_hip_impute_at does not), the factors
+inline int xy_check_handle(glrm_handle* h, const char* what) {
   if (!h) return fail(GLRM_ERR_INVALID, "%s: NULL handle", what);
   GLRM_REFUSE_F32(h, what);
   if (h->dense) return fail(GLRM_ERR_UNSUPPORTED, "%s works on the observation lists (create the handle without dense_A)", what);
   if (!glrm_single_shard(h)) return fail(GLRM_ERR_INVALID, "%s needs a single-shard handle", what);
   GLRM_NEED_FINALIZED(h);
+  return GLRM_OK;
+}
+
+inline int xy_check_factors(glrm_handle* h, const double* X, const double* Y, const char* what) {
+  if ((X == nullptr) != (Y == nullptr)) return fail(GLRM_ERR_INVALID, "%s: X and Y must both be given or both be NULL (NULL = the handle's resident factors)", what);
+  if (!X && (!h->side[GLRM_ROWS].factor || !h->side[GLRM_COLS].factor)) return fail(GLRM_ERR_INVALID, "%s: no factors on the device yet (pass X and Y, or fit / glrm_hip_set_factors first)", what);
+  return GLRM_OK;
+}
+
+inline int tk_check(glrm_handle* h, const double* X, const double* Y, const char* what) {
+  const int rc = xy_check_handle(h, what);
+  if (rc) return rc;
   for (size_t j = 0; j < h->losses_h.size(); ++j)
     if (h->losses_h[j].dim > 1)
       return fail(GLRM_ERR_UNSUPPORTED, "%s: column %lld has a multi-dimensional loss (kind %d, dim %d); XY[i,j] with j in 1:n needs one vector "
                   "of Y per data column (d == n)", what, (long long)j, h->losses_h[j].kind, h->losses_h[j].dim);
   if (h->d != h->n) return fail(GLRM_ERR_UNSUPPORTED, "%s: Y has %lld vectors for %lld columns (d != n)", what, (long long)h->d, (long long)h->n);
-  if ((X == nullptr) != (Y == nullptr)) return fail(GLRM_ERR_INVALID, "%s: X and Y must both be given or both be NULL (NULL = the handle's resident factors)", what);
-  if (!X && (!h->side[GLRM_ROWS].factor || !h->side[GLRM_COLS].factor)) return fail(GLRM_ERR_INVALID, "%s: no factors on the device yet (pass X and Y, or fit / glrm_hip_set_factors first)", what);
-  return GLRM_OK;
+  return xy_check_factors(h, X, Y, what);
 }
 
 // after every argument check, inside the entry point's device scope: the factors, uploaded like glrm_hip_impute does it
