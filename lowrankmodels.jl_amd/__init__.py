@@ -15,6 +15,7 @@ from .scaling import equilibrate_variance_, prob_scale_
 from .transform import inverse_transform, transform
 from .recommend import recommend
 from .predict import error_metric_at, impute_at
+from .sample import sample, sample_at, sample_missing, sample_missing_at
 from .domains import (BoolDomain, CategoricalDomain, CountDomain, Domain, OrdinalDomain, PeriodicDomain, RealDomain, default_domain,
                       error_metric, error_metric_entry, impute, impute_entry, impute_missing)
 from .glrm import GLRM, add_offset_, copy_estimate, fix_latent_features_, parameter_estimate, scale_regularizer_, sort_observations

@@ -188,6 +188,11 @@ TRANSFORM_SYMBOLS = ("solve_x", "solve_x_info")
 IMPUTE_AT_SYMBOLS = ("impute_at", "impute_at_info")
 IMPUTE_AT_PAIRS, IMPUTE_AT_ROWS, IMPUTE_AT_COLS = 0, 1, 2   # glrm_hip_impute_at.h: GLRM_IMPUTE_AT_*
 
+#: the sampling extension, include/glrm_hip_sample.h (draws from the fitted model at listed entries, whole rows or whole columns, nothing
+#: m x n): outside the boundary, bound only where the library has it
+SAMPLE_SYMBOLS = ("sample_at", "sample_at_info")
+SAMPLE_NOISE = {"residual": 0, "reference": 1, "given": 2}   # glrm_hip_sample.h: GLRM_SAMPLE_NOISE_*
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -297,9 +302,12 @@ class Api:
             "impute_at": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
             "impute_at_info": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+            "sample_at": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_int32,
+                                    C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "sample_at_info": (C.c_int, [C.POINTER(C.c_int64)] * 5),
         }
         assert tuple(ext) == (SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
-                              + IMPUTE_AT_SYMBOLS)
+                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS)
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -820,6 +828,66 @@ class Api:
         b, f, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._ck(fn(C.byref(b), C.byref(f), C.byref(g)))
         return dict(blocks=b.value, entries_fast=f.value, entries_general=g.value)
+
+
+    # -- sampling extension (include/glrm_hip_sample.h) ----------------------------------------
+    def _sample(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the sampling extension "
+                                             "(include/glrm_hip_sample.h is implemented by the HIP engine only)")
+        return fn
+
+    def sample_at(self, h, X, Y, domains, m, n, rows=None, cols=None, *, seed, noise="residual", noise_sd=None, keep_observed=False,
+                  block_entries=0, want_kept=True, want_noise_sd=True):
+        """glrm_hip_sample_at: a draw from the model at every listed entry; ``rows`` / ``cols`` / the shape of the result as for
+        ``impute_at``.  ``seed``: the 64-bit key of the generator -- a draw is a function of (seed, row, column, X, Y, lists) alone.
+        ``noise``: "residual" (sd_j = sqrt(v_j)), "reference" (1 / sqrt(v_j)) or "given" (``noise_sd``, n values).  ``keep_observed``:
+        an entry whose column is in its row's resident row-view list returns the stored value.  Returns ``(out, kept, noise_sd)``:
+        ``kept`` (bool, out's shape) with ``keep_observed`` and ``want_kept``, else None; ``noise_sd`` (n values, NaN outside the
+        Real x QuadLoss columns) with ``want_noise_sd``, else None."""
+        fn = self._sample("sample_at")
+        X, Y = self._factor_pair(X, Y)
+        if rows is None and cols is None:
+            raise ValueError("sample_at needs rows, cols or both (every entry of the model is `sample`)")
+        m, n = int(m), int(n)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if cols is not None:
+            cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        if rows is not None and cols is not None:
+            mode, shape = IMPUTE_AT_PAIRS, (len(rows),)
+            if len(rows) != len(cols):
+                raise ValueError(f"pairs need as many rows as cols, got {len(rows)} and {len(cols)}")
+        elif rows is not None:
+            mode, shape = IMPUTE_AT_ROWS, (len(rows), n)
+        else:
+            mode, shape = IMPUTE_AT_COLS, (m, len(cols))
+        total = int(np.prod(shape))
+        if noise not in SAMPLE_NOISE:
+            raise ValueError(f"noise must be one of {sorted(SAMPLE_NOISE)}, got {noise!r}")
+        if noise_sd is not None:
+            noise_sd = np.ascontiguousarray(noise_sd, dtype=np.float64).reshape(-1)
+            if len(noise_sd) != n:
+                raise ValueError(f"noise_sd has {len(noise_sd)} values for {n} columns")
+        flat = max(total, 1)                                         # (the buffers are never empty)
+        out = np.full(flat, np.nan)
+        kept = np.zeros(flat, dtype=np.uint8) if keep_observed and want_kept else None
+        sd = np.full(max(n, 1), np.nan) if want_noise_sd else None
+        self._ck(fn(h, _ptr(X), _ptr(Y), _ptr(domains), _ptr(rows) if rows is not None and len(rows) else None, 0 if rows is None else len(rows),
+                    _ptr(cols) if cols is not None and len(cols) else None, 0 if cols is None else len(cols), mode,
+                    int(seed) & 0xFFFFFFFFFFFFFFFF, SAMPLE_NOISE[noise], _ptr(noise_sd), int(bool(keep_observed)), int(block_entries),
+                    _ptr(out), _ptr(kept), _ptr(sd)))
+        return (out[:total].reshape(shape, order="F"), None if kept is None else kept[:total].astype(bool).reshape(shape, order="F"),
+                None if sd is None else sd[:n])
+
+    def sample_at_info(self) -> dict:
+        """Of this thread's last sample_at: ``blocks``, ``entries_fast``, ``entries_general`` (as for impute_at), ``entries_kept``
+        (entries that kept their observed value) and ``variance_columns`` (columns the variance pass computed; 0: it did not run)."""
+        fn = self._sample("sample_at_info")
+        v = [C.c_int64(0) for _ in range(5)]
+        self._ck(fn(*[C.byref(x) for x in v]))
+        return dict(zip(("blocks", "entries_fast", "entries_general", "entries_kept", "variance_columns"), (x.value for x in v)))
 
 
 class ProblemArrays:

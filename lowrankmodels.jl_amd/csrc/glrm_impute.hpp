@@ -37,7 +37,28 @@ __device__ inline double vloss_eval_strided(const LossDesc& l, const double* u, 
     for (int j = 0; j < d; ++j) sumexp += exp(u[j * us] - ua - M);
     return s * (log(sumexp) + M);
   }
+  // the two below: the formulas of vloss_eval (glrm_multi.hpp), for the level walk of glrm_sample.hip; impute_value's generic branch
+  // rejects both kinds before it gets here
+  if (l.kind == GLRM_LOSS_ORDISTIC) { // src/losses.jl:499-505
+    const double ua2 = u[a * us] * u[a * us];
+    double M = -__builtin_inf(), invlik = 0.0;
+    for (int j = 0; j < d; ++j) { const double q = ua2 - u[j * us] * u[j * us]; M = q > M ? q : M; }
+    for (int j = 0; j < d; ++j) invlik += exp((ua2 - u[j * us] * u[j * us]) - M);
+    return s * (M + log(invlik));
+  }
+  if (l.kind == GLRM_LOSS_MULTINOMIAL_ORDINAL) { // :581-590, u already passed through enforce_mnl_ord_rules_strided
+    if (a == 0) return -s * log(1.0 - exp(u[0]));
+    if (a == d) return -s * u[(a - 1) * us];
+    return -s * log(exp(u[(a - 1) * us]) - exp(u[a * us]));
+  }
   return __builtin_nan("");
+}
+
+// enforce_MNLOrdRules! (src/losses.jl:572-578) on a strided u; idempotent
+__device__ inline void enforce_mnl_ord_rules_strided(double* u, int us, int d) {
+  const double TOL = 1e-3;
+  u[0] = u[0] < -TOL ? u[0] : -TOL;
+  for (int j = 1; j < d; ++j) u[j * us] = u[j * us] < u[(j - 1) * us] - TOL ? u[j * us] : u[(j - 1) * us] - TOL;
 }
 
 // impute(D, l, u); *bad is set for pairs the reference rejects
