@@ -300,11 +300,17 @@ int glrm_hip_fit(glrm_handle* h, const glrm_params* prm, double* X, double* Y,
  * step per factor and iteration (no per-row line search), the whole iteration is accepted or reverted on the full
  * objective(glrm, X, Y; sparse=true).  objective[] holds the initial objective, one entry per ACCEPTED iteration and the
  * last value once more (:126-127); cap must be >= max_iter+2.  X, Y return the best model found.
+ * On the handle it leaves: the best model in the resident factors, the column penalties ry_f(y_f) in dObjCol and the row penalties
+ * rx_e(x_e) in dObjRow (its last objective evaluation), the step sizes of the line searches untouched.
  */
 int glrm_hip_fit_sparse(glrm_handle* h, const glrm_sparse_params* prm, double* X, double* Y, double* objective,
                         double* seconds, int64_t cap, int64_t* n_recorded);
 
-/* objective(glrm, X, Y; include_regularization) over observed_examples (src/evaluate_fit.jl:57-81). */
+/* objective(glrm, X, Y; include_regularization) over observed_examples (src/evaluate_fit.jl:57-81).
+ * X and Y are uploaded with glrm_hip_set_factors: they are the resident factors afterwards.  The sums run through the handle's two
+ * objective vectors: with include_reg, dObjCol holds the column penalties ry_f(y_f) and dObjRow the row penalties rx_e(x_e) on return;
+ * without, dObjCol holds the column losses and dObjRow is not written.  A glrm_options.sum_order = 1 handle adds the loss terms in
+ * one accumulator and writes the two penalty vectors only.  The step sizes and the trial / accept counters are not touched. */
 int glrm_hip_objective(glrm_handle* h, const double* X, const double* Y, int include_reg, double* out);
 
 /* ---- step-level API (multi-GPU hosts: one process per GPU, collectives in the host) ---- */
@@ -356,6 +362,8 @@ int glrm_hip_gradstep_y(glrm_handle* h, double alpha);
 /* The X sweep restricted to the shard's local rows [seg_begin, seg_end): lets a multi-GPU host pipeline the
  * all-gather of finished row chunks behind the sweep of the next chunk (rows are independent, :118). */
 int glrm_hip_step_x_range(glrm_handle* h, int64_t seg_begin, int64_t seg_end, double min_stepsize);
+/* The three write the vector named above and nothing else: the factors, the step sizes, the other objective vector and the trial /
+ * accept counters stay (tests/test_gpu_handle_lifetime.py pins this on every kernel family). */
 int glrm_hip_col_losses(glrm_handle* h);
 int glrm_hip_row_penalties(glrm_handle* h);
 int glrm_hip_col_penalties(glrm_handle* h);
@@ -386,17 +394,21 @@ int glrm_hip_subset(glrm_handle* parent, const uint8_t* row_tags, const uint8_t*
  * less than tol * s_1 (tol <= 0: 1e-12; max_iter <= 0: 60).  X and Y are determined up to the sign of each component; X'Y is
  * unique.  The two Omega views must list the same entries without duplicates (the reference works on the expanded MATRIX).
  * `offset` / `scale` of the reference are dead code there (typeof(glrm.rx) == lastentry1 is never true for a Vector) and not
- * reproduced.  singular_values (k) and iters_done may be NULL. */
+ * reproduced.  singular_values (k) and iters_done may be NULL.  Nothing of the handle is written: the resident factors, the step
+ * sizes, the two objective vectors and the counters are what they were. */
 int glrm_hip_init_svd(glrm_handle* h, double* X, double* Y, int32_t max_iter, double tol, uint64_t seed, double* singular_values,
                       int32_t* iters_done);
 /* error_metric(glrm, X, Y, domains; standardize) (src/evaluate_fit.jl:107-153): over observed_examples, the squared error
  * (Real / Ordinal / Count / Periodic domains) or 0-1 misclassification (Bool / Categorical) between A[i,j] and
  * impute(domains[j], losses[j], (X'Y)[i, yidxs[j]]) (src/impute_and_err.jl:37-130); with standardize each column's sum is
  * divided by the mean of A[i,j]^2 over its observed entries (when that is not 0).  domains: n descriptors.  Single-shard
- * list handle.  Domain / loss pairs for which the reference throws (RealDomain + LogisticLoss) return GLRM_ERR_UNSUPPORTED. */
+ * list handle.  Domain / loss pairs for which the reference throws (RealDomain + LogisticLoss) return GLRM_ERR_UNSUPPORTED.
+ * X and Y are uploaded with glrm_hip_set_factors: they are the resident factors afterwards.  The step sizes, dObjCol, dObjRow and
+ * the counters are not touched (the sums run in scratch memory). */
 int glrm_hip_error_metric(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, int32_t standardize, double* out);
 /* impute(domains, losses, X'Y) (src/impute_and_err.jl:149-165, impute(glrm) src/evaluate_fit.jl:156): the full m x n matrix of
- * imputed values, column-major (Ahat[i + j*m]), Bool columns as 1.0 / 0.0. */
+ * imputed values, column-major (Ahat[i + j*m]), Bool columns as 1.0 / 0.0.  On the handle: as glrm_hip_error_metric -- X and Y
+ * become the resident factors, nothing else is touched. */
 int glrm_hip_impute(glrm_handle* h, const double* X, const double* Y, const glrm_domain* domains, double* Ahat);
 /* Fixed-order sum of n device doubles (independent of the number of shards); synchronises. */
 int glrm_hip_sum(glrm_handle* h, const void* dvec, int64_t n, double* out);
