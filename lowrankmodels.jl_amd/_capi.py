@@ -193,6 +193,12 @@ IMPUTE_AT_PAIRS, IMPUTE_AT_ROWS, IMPUTE_AT_COLS = 0, 1, 2   # glrm_hip_impute_at
 SAMPLE_SYMBOLS = ("sample_at", "sample_at_info")
 SAMPLE_NOISE = {"residual": 0, "reference": 1, "given": 2}   # glrm_hip_sample.h: GLRM_SAMPLE_NOISE_*
 
+#: the ALS extension, include/glrm_hip_als.h (the exact half-step of a QuadLoss + QuadReg / ZeroReg model: one Gram matrix and one
+#: rank-k Cholesky per row or column): outside the boundary, bound only where the library has it
+ALS_SYMBOLS = ("als_solve", "als_info")
+ALS_MAX_K = 64                                         # glrm_hip_als.h: GLRM_ALS_MAX_K
+ALS_SOLVED, ALS_KEPT_SHORT, ALS_KEPT_PIVOT = 0, 1, 2   # glrm_hip_als.h: GLRM_ALS_*
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -305,9 +311,11 @@ class Api:
             "sample_at": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_int32,
                                     C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
             "sample_at_info": (C.c_int, [C.POINTER(C.c_int64)] * 5),
+            "als_solve": (C.c_int, [H, C.c_int32]),
+            "als_info": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
         }
         assert tuple(ext) == (SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
-                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS)
+                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS + ALS_SYMBOLS)
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -888,6 +896,37 @@ class Api:
         v = [C.c_int64(0) for _ in range(5)]
         self._ck(fn(*[C.byref(x) for x in v]))
         return dict(zip(("blocks", "entries_fast", "entries_general", "entries_kept", "variance_columns"), (x.value for x in v)))
+
+    # -- ALS extension (include/glrm_hip_als.h) ----------------------------------------------
+    def _als(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the ALS extension "
+                                             "(include/glrm_hip_als.h is implemented by the HIP engine only)")
+        return fn
+
+    @property
+    def has_als(self) -> bool:
+        """The library exports the ALS extension (the CPU oracle does not)."""
+        return "als_solve" in self._f
+
+    def als_solve(self, h, side):
+        """glrm_hip_als_solve: every local row of X (``side`` 0) or column of Y (1) replaced by the exact minimiser of its part of the
+        objective with the opposing factor as it stands (QuadLoss columns, QuadReg / ZeroReg on the solved side).  Asynchronous."""
+        self._ck(self._als("als_solve")(h, int(side)))
+
+    def als_info(self, h, side, nseg=None) -> dict:
+        """What the last als_solve of ``side`` did: ``solved``, ``kept_short`` (penalty scale 0 and fewer than k observations) and
+        ``kept_pivot`` (a pivot failed the rank rule) segments; with ``nseg`` (the local segments of the side) also ``status``, one int8
+        per segment (ALS_SOLVED / ALS_KEPT_SHORT / ALS_KEPT_PIVOT).  Synchronises."""
+        fn = self._als("als_info")
+        n = [C.c_int64(0) for _ in range(3)]
+        status = None if nseg is None else np.full(max(int(nseg), 1), -1, dtype=np.int8)
+        self._ck(fn(h, int(side), C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), _ptr(status)))
+        out = dict(solved=n[0].value, kept_short=n[1].value, kept_pivot=n[2].value)
+        if status is not None:
+            out["status"] = status[: int(nseg)]
+        return out
 
 
 class ProblemArrays:

@@ -18,6 +18,8 @@
 //                       iteration of glrm_svd.hip through glrm_subspace.hpp
 //   glrm_solve.hip      the fused row solver of glrm_hip_solve_x (include/glrm_hip_transform.h): T X half-steps of a row in one launch of the
 //                       register kernel (glrm_solve.hpp); glrm_solve_f32.hip holds its float instantiations
+//   glrm_als.hip        the exact half-step of a quadratic model (include/glrm_hip_als.h): one workgroup per segment accumulates the Gram
+//                       triangle in registers and one wave factorises it in LDS (glrm_als.hpp)
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, a shard's replica, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
@@ -196,6 +198,10 @@ struct glrm_handle {
   glrm_class_plan solve_plan;
   int solve_fused = -1;
   int64_t solve_fused_rows = 0, solve_loop_rows = 0;
+  // glrm_hip_als_solve (include/glrm_hip_als.h; glrm_als.hip), per side, made at the side's first solve: the local segments longest first
+  // (a permutation of its own: Side::perm leaves out the columns diverted to the 8-wave sweep) and the status of every local segment
+  // after the last solve.  solved: glrm_hip_als_info has something to report
+  struct Als { int32_t* order = nullptr; int8_t* status = nullptr; bool solved = false; } als[2];
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]

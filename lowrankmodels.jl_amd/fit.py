@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from .convergence import ConvergenceHistory, update_ch
-from .params import AbstractParams, HipProxGradParams, ProxGradParams, SparseProxGradParams
+from .params import AbstractParams, AlsParams, HipProxGradParams, ProxGradParams, SparseProxGradParams
 
 
 LAST_EXCHANGE_PROBE = None  # the last set-up probe of a ShardedFit in this process (diagnostics; tests)
@@ -134,8 +134,9 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
     if not isinstance(params, AbstractParams):
         raise TypeError("params must be an AbstractParams (ProxGradParams / HipProxGradParams)")
     sparse = isinstance(params, SparseProxGradParams)
+    als = isinstance(params, AlsParams)
     if ch is None:
-        ch = ConvergenceHistory("SparseProxGradGLRM" if sparse else "ProxGradGLRM")
+        ch = ConvergenceHistory("AlsGLRM" if als else "SparseProxGradGLRM" if sparse else "ProxGradGLRM")
     api = engine if engine is not None else _capi.hip_api()
     world = 1
     if group is not None or os.environ.get("WORLD_SIZE", "1") != "1":
@@ -144,6 +145,11 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
             world = dist.get_world_size(group)
     if _storage_opt(params) and (world > 1 or getattr(params, "ngpus", 1) > 1):
         raise ValueError("storage='f32' runs on one device: sharded and multi-GPU fits have no f32 form")
+    if als:  # exact alternating least squares (include/glrm_hip_als.h); Y == 0 is a valid start: the X half-step then solves to the ridge's 0
+        if world > 1:
+            raise ValueError("AlsParams runs on one device: glrm_hip_als_solve needs the whole problem on one handle")
+        from .als import fit_als
+        return fit_als(glrm, params, ch, verbose, api)
     if world > 1:
         if sparse:
             raise NotImplementedError("SparseProxGradParams runs on a single shard (step-level gradstep_x / gradstep_y exist for hosts)")

@@ -75,6 +75,26 @@ class HipProxGradParams(ProxGradParams):
         self.exchange, self.x_chunks = exchange, int(x_chunks)
 
 
+class AlsParams(AbstractParams):
+    """AlsParams(max_iter=100, abs_tol=1e-5, rel_tol=1e-4, device_id=-1): exact alternating least squares for QUADRATIC models
+    (every loss a QuadLoss, every regularizer a QuadReg or ZeroReg): PCA, ridge matrix completion.  An iteration replaces every row
+    of X, then every column of Y, by the closed-form minimiser of its part of the objective (glrm_hip_als_solve,
+    include/glrm_hip_als.h: one Gram matrix and one rank-k Cholesky per row / column), so there is no step size and no line search.  The
+    reference has the row solve only inside streaming_fit! (src/algorithms/quad_streaming.jl:53); in Julia this is
+    ``struct AlsParams <: AbstractParams`` (julia/HipGLRMAls.jl).  The history records the FULL objective (losses and both penalties)
+    after every iteration, which an exact half-step cannot raise; the stopping rule is ProxGradParams' (src/algorithms/proxgrad.jl:210-213).
+    One device, fp64, observation lists; rank at most 64."""
+
+    def __init__(self, max_iter=100, *, abs_tol=0.00001, rel_tol=0.0001, device_id=-1):
+        self.max_iter = int(max_iter)
+        self.abs_tol = float(abs_tol)
+        self.rel_tol = float(rel_tol)
+        self.device_id = int(device_id)
+
+    def __repr__(self):
+        return f"AlsParams(max_iter={self.max_iter}, abs_tol={self.abs_tol}, rel_tol={self.rel_tol}, device_id={self.device_id})"
+
+
 def Params(*args, **kwargs):  # src/fit.jl:5
     return ProxGradParams(*args, **kwargs)
 

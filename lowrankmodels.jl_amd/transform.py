@@ -18,7 +18,7 @@ from . import _capi
 from .convergence import ConvergenceHistory, update_ch
 from .fit import _ensure_handle, _should_stop
 from .glrm import GLRM
-from .params import HipProxGradParams
+from .params import AlsParams, HipProxGradParams
 from .regularizers import Regularizer, _collapse
 
 
@@ -45,7 +45,7 @@ def _objective_buffers(api, params, n, m):
     return (oc, orow), oc.ctypes.data, orow.ctypes.data
 
 
-def transform(glrm, A_new, params=None, *, obs=None, rx=None, X0=None, rng=None, api=None):
+def transform(glrm, A_new, params=None, *, obs=None, rx=None, X0=None, rng=None, api=None, exact=False):
     """Embed the rows of ``A_new`` (m_new x n, the fitted model's columns) into the fitted ``glrm``: minimise over X alone the objective of
     ``GLRM(A_new, glrm.losses, rx, glrm.ry, glrm.k, obs=obs, X=X0, Y=glrm.Y)``.  Returns ``(X_new, ch)``: X_new is k x m_new float64
     (float-representable under ``storage="f32"``), ch the ConvergenceHistory.  ``glrm`` and its Y are not written.
@@ -55,11 +55,18 @@ def transform(glrm, A_new, params=None, *, obs=None, rx=None, X0=None, rng=None,
     ``params``  a HipProxGradParams (``storage="f32"`` is honoured; ``ngpus > 1`` raises): stepsize, max_iter, inner_iter_X, abs_tol,
                 rel_tol and min_stepsize mean what they mean to ``fit!``; inner_iter_Y is not used.
     ``api``     a test hook (an ``_capi.Api``); the product default is the HIP library.
+    ``exact``   True: the fitted model is quadratic (QuadLoss columns; the new rows carry a QuadReg or ZeroReg) and the embedding is ONE
+                glrm_hip_als_solve(h, 0) on the new rows' handle (include/glrm_hip_als.h): every row lands on the exact minimiser, no
+                step size, no iteration.  ``params`` may then also be an AlsParams; only its device_id is used.  ``ch`` holds the full
+                objective at the start and at the end; ``X0`` only matters for the rows the solve keeps (fewer than k observations under
+                ZeroReg, or a rank-deficient system).  A model the engine would refuse is refused before a handle exists.
 
     ``ch.objective[0]`` is the full objective at the start, as ``fit_b`` records it; every later entry is the column losses plus the
     column penalties after the iteration, which is what ``fit!`` records (proxgrad.jl:205).  The stopping rule is proxgrad.jl:210-213 with
     ``abs_tol`` scaled by the new rows' observation count."""
     params = HipProxGradParams() if params is None else params
+    if exact and isinstance(params, AlsParams):
+        params = HipProxGradParams(device_id=params.device_id)
     if not isinstance(params, HipProxGradParams):
         raise TypeError("params must be a HipProxGradParams")
     if getattr(params, "ngpus", 1) > 1:
@@ -71,6 +78,8 @@ def transform(glrm, A_new, params=None, *, obs=None, rx=None, X0=None, rng=None,
     if np.linalg.norm(glrm.Y) == 0:
         raise ValueError("Y is all zeros: the model has not been fitted")
     new = GLRM(A_new, [_copy.copy(l) for l in glrm.losses], rx, [_copy.copy(r) for r in glrm.ry], glrm.k, obs=obs, X=X0, Y=glrm.Y, rng=rng)
+    if exact:
+        return _transform_exact(new, params, api)
     ch = ConvergenceHistory("ProxGradGLRM-transform")
     try:
         h = _ensure_handle(new, api, params, allow_dense=False)[0]
@@ -108,6 +117,30 @@ def transform(glrm, A_new, params=None, *, obs=None, rx=None, X0=None, rng=None,
         api.get_factors(h, X, Y)
     finally:
         new.close()                                                 # (the handle goes before the buffers it was bound to)
+    return X, ch
+
+
+def _transform_exact(new, params, api):
+    """``transform(exact=True)``: one exact X half-step of the new rows' model -> (X_new, ch); closes ``new``'s handle."""
+    from .als import _Objective, check_model
+    ch = ConvergenceHistory("AlsGLRM-transform")
+    try:
+        check_model(new, sides=(0,))
+        h = _ensure_handle(new, api, params, allow_dense=False)[0]
+        X = np.asfortranarray(new.X, dtype=np.float64)
+        Y = np.asfortranarray(new.Y, dtype=np.float64)
+        full = _Objective(api, h, params.device_id, new.m, new.n)
+        try:
+            api.set_factors(h, X, Y)
+            update_ch(ch, 0, full())
+            t = time.time()
+            api.als_solve(h, 0)
+            update_ch(ch, time.time() - t, full())
+            api.get_factors(h, X, Y)
+        finally:
+            full.close()
+    finally:
+        new.close()
     return X, ch
 
 
