@@ -308,6 +308,19 @@ inline int glrm_check_offsets(const char* name, const int64_t* ptr, int64_t nseg
   return GLRM_OK;
 }
 
+// The chunks of a kernel that gives every column gridDim.y = nsplit workgroups of `chunk` entries each and adds their partials in chunk
+// order (the init_svd / init_nndsvd column products, error_metric): base_chunk entries, doubled until the longest column fits gridDim.y.
+// The longest column is the handle's own record: create_impl takes sig_local.max_col_len from the very colptr array side[GLRM_COLS].ptr
+// points to (view_stats; a subset child and a rows-from-cols handle go through create_impl too) and nothing writes that array afterwards
+// (the set-up re-orders idx / vals inside a segment only).  Not h->sig: glrm_hip_finalize accepts a covering signature that may be larger.
+struct glrm_col_chunks { int64_t longest, chunk; int nsplit; };
+inline glrm_col_chunks glrm_chunk_columns(const glrm_handle* h, int64_t base_chunk) {
+  glrm_col_chunks c{h->sig_local.max_col_len, base_chunk, 1};
+  while ((c.longest + c.chunk - 1) / c.chunk > 65535) c.chunk *= 2; // gridDim.y
+  c.nsplit = (int)std::max<int64_t>(1, (c.longest + c.chunk - 1) / c.chunk);
+  return c;
+}
+
 // ---- the bookkeeping of the ProxGrad outer loop (src/algorithms/proxgrad.jl), shared by glrm_hip_fit and glrm_hip_multi_fit
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // norm(Y) == 0 guard (proxgrad.jl:45-48: the reference would hit an UndefVarError; sparse_proxgrad.jl:41-43: it would re-randomise Y)

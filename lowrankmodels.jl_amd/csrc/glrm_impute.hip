@@ -2,7 +2,6 @@
 // src/impute_and_err.jl) on the resident column view.  One thread per entry: d dot products of length k into a per-thread LDS
 // strip, then the domain's imputation rule.  Not a hot path: a single pass per call.
 #include <cmath>
-#include <vector>
 
 #include "glrm_engine.hpp"
 #include "glrm_impute.hpp"
@@ -141,15 +140,9 @@ extern "C" int glrm_hip_error_metric(glrm_handle* h, const double* X, const doub
   double *part = nullptr, *colerr = nullptr;
   int rc = prepare(h, X, Y, domains, a, scratch);
   if (rc) return rc;
-  std::vector<int64_t> cp((size_t)h->n + 1);
-  if (hipMemcpyAsync(cp.data(), h->side[GLRM_COLS].ptr, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess) return fail(GLRM_ERR_HIP, "copy failed");
-  int64_t longest = 0;
-  for (int64_t f = 0; f < h->n; ++f) longest = cp[f + 1] - cp[f] > longest ? cp[f + 1] - cp[f] : longest;
-  a.chunk = 65536;
-  while ((longest + a.chunk - 1) / a.chunk > 65535) a.chunk *= 2; // gridDim.y
-  a.nsplit = (int)((longest + a.chunk - 1) / a.chunk);
-  if (a.nsplit < 1) a.nsplit = 1;
+  const glrm_col_chunks cc = glrm_chunk_columns(h, 65536);
+  a.chunk = cc.chunk;
+  a.nsplit = cc.nsplit;
   if ((rc = scratch.alloc(&part, (size_t)h->n * a.nsplit * 2)) || (rc = scratch.alloc(&colerr, (size_t)h->n))) return rc;
   a.part = part;
   const size_t lds = (size_t)h->dmax * ET * 8;

@@ -3,9 +3,11 @@
 // The reference fills a dense m x n matrix with the observed entries, hands it to NMF.jl's nndsvd and, with max_iters > 0, rewrites
 // every missing entry with <x_i, y_j> and decomposes the dense matrix again.  Here nothing m x n exists.  The matrix of a round is
 //     B_t = P_Omega(s A - X'Y) + X'Y                 (round 0: B_0 = P_Omega(s A))
-// a sparse matrix on the resident lists plus a rank-k term, and the subspace iteration of glrm_svd.hip (glrm_subspace.hpp) needs only
+// a sparse matrix on the resident lists plus a rank-k term, and the subspace iteration (subspace_iterate in glrm_subspace.hpp, the one
+// glrm_svd.hip runs, once per round here) needs only
 //     U <- B_t V  = R V  + X'(Y V)                    row view:    nmf_rows_kernel, T = Y V by nmf_tsmm_kernel
-//     V <- B_t' U = R' U + Y'(X U)                    column view: nmf_cols_kernel, T = X U by nmf_tsmm_kernel
+//     V <- B_t' U = R' U + Y'(X U)                    column view: nmf_cols_kernel (the shared column product of glrm_subspace.hpp over
+//                                                                  NmfArgs), T = X U by nmf_tsmm_kernel
 // with R the residuals r = s_f a - <x_e, y_f>, written once per round and view by nmf_residual_kernel (the hot kernel: one k-vector
 // gathered per observation, like a gradient pass).  The split (positive / negative squared norms of every singular vector in a fixed
 // tree, the mean of B_t for variant `a`, one kernel that writes X and Y) follows include/glrm_hip_nmf.h.  Everything is fp64, no
@@ -135,23 +137,21 @@ __global__ void __launch_bounds__(256) nmf_residual_kernel(const ResidArgs a) {
   }
 }
 
-struct NmfArgs {
-  int64_t nseg;
-  const int64_t* ptr;
-  const int32_t* idx;
-  const double* vals;
+struct NmfArgs;
+__device__ __forceinline__ double nmf_lowrank(const NmfArgs& a, int64_t seg, int c, double s);
+
+// the functor of the column product (glrm_subspace.hpp): one vector per column, the residual or s_f a, the finished sum plus the rank-k term
+struct NmfArgs : ProductArgs {
   const double* resid;  // nullptr in round 0: the value is s_f a
   const glrm_loss* losses;
   int loss_single, use_scale;
-  const double* in;     // rows: V [n][l];  cols: U [m][l]
-  double* out;          // rows: U [m][l];  cols: V [n][l]
-  int l;
-  int nsplit;
-  int64_t chunk;
-  double* partial;      // cols with nsplit > 1: [nseg][nsplit][l]
   const double* F;      // the rank-k term, nullptr in round 0: out[seg, :] += F[:, seg]' T  (F k x nseg, T k x l row-major)
   const double* T;
   int k;
+  struct Col { static constexpr int d = 1; int64_t ys; double sc; };
+  __device__ Col col(int64_t f) const { return {f, !resid && use_scale ? losses[loss_single ? 0 : f].scale : 1.0}; }
+  __device__ double value(const Col& c, int, int64_t t) const { return resid ? resid[t] : c.sc * vals[t]; }
+  __device__ double finish(const Col&, int64_t f, int c, double s) const { return T ? nmf_lowrank(*this, f, c, s) : s; }
 };
 
 // entry c of x_seg' T, the components in ascending order, continued from s
@@ -203,44 +203,9 @@ __global__ void __launch_bounds__(256) nmf_rows_kernel(const NmfArgs a) {
   if (hi) a.out[e * l + lane + 64] = acc1;
 }
 
-// V[f, :] = sum_{(e, v) in Omega^f} v U[e, :]  (+ y_f' T)     workgroup (4 waves) per (column, chunk), as svd_cols_kernel
-__global__ void __launch_bounds__(256) nmf_cols_kernel(const NmfArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t f = blockIdx.x;
-  const int y = blockIdx.y;
-  const int l = a.l;
-  int64_t b = a.ptr[f] + (int64_t)y * a.chunk, e = b + a.chunk;
-  const int64_t e0 = a.ptr[f + 1];
-  b = b < e0 ? b : e0;
-  e = e < e0 ? e : e0;
-  const double sc = !a.resid && a.use_scale ? a.losses[a.loss_single ? 0 : f].scale : 1.0;
-  __shared__ double sh[4][LMAX];
-  double acc0 = 0.0, acc1 = 0.0;
-  for (int64_t t = b + wave; t < e; t += 4) {
-    const double v = a.resid ? a.resid[t] : sc * a.vals[t];
-    const double* ur = a.in + (int64_t)a.idx[t] * l;
-    if (lane < l) acc0 = fma(v, ur[lane], acc0);
-    if (lane + 64 < l) acc1 = fma(v, ur[lane + 64], acc1);
-  }
-  if (lane < l) sh[wave][lane] = acc0;
-  if (lane + 64 < l) sh[wave][lane + 64] = acc1;
-  __syncthreads();
-  for (int c = threadIdx.x; c < l; c += 256) {
-    const double s = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-    if (a.nsplit > 1) a.partial[((size_t)f * a.nsplit + y) * l + c] = s;
-    else a.out[f * l + c] = a.T ? nmf_lowrank(a, f, c, s) : s;
-  }
-}
-
-__global__ void nmf_cols_reduce_kernel(const NmfArgs a) { // chunk partials in chunk order, then the rank-k term
-  const int64_t f = blockIdx.x;
-  const int l = a.l;
-  for (int c = threadIdx.x; c < l; c += blockDim.x) {
-    double s = 0.0;
-    for (int y = 0; y < a.nsplit; ++y) s += a.partial[((size_t)f * a.nsplit + y) * l + c];
-    a.out[f * l + c] = a.T ? nmf_lowrank(a, f, c, s) : s;
-  }
-}
+// V[f, :] = sum_{(e, v) in Omega^f} v U[e, :]  (+ y_f' T): the shared column product under this unit's names
+__global__ void __launch_bounds__(256) nmf_cols_kernel(const NmfArgs a) { cols_product_kernel(a); }
+__global__ void nmf_cols_reduce_kernel(const NmfArgs a) { cols_reduce_kernel(a); }
 
 // partial products F Z of row blocks (F k x nrows column-major, Z nrows x l row-major): thread t owns the entries t, t + 256, ... of the
 // k x l result, as gram_kernel does of its l x l one; the blocks are added in block order by gram_reduce_kernel
@@ -345,20 +310,11 @@ __global__ void nmf_split_kernel(const double* U, int64_t m, const double* V, in
   }
 }
 
-// the row blocks of a tall-skinny reduction: their number and size are functions of nrows only
-void row_blocks(const Work& w, int64_t nrows, int tile, int& nblk, int64_t& rpb) {
-  nblk = (int)std::min<int64_t>(w.nblk_max, (nrows + 255) / 256);
-  if (nblk < 1) nblk = 1;
-  rpb = ((nrows + nblk - 1) / nblk + tile - 1) / tile * tile;
-  nblk = (int)((nrows + rpb - 1) / rpb);
-  if (nblk < 1) nblk = 1;
-}
-
 // T = F Z  (k x l, row-major)
 void tsmm(Work& w, const double* F, const double* Z, int64_t nrows, int k, double* T) {
   int nblk;
   int64_t rpb;
-  row_blocks(w, nrows, NMF_TROWS, nblk, rpb);
+  row_blocks(nrows, NMF_TROWS, nblk, rpb);
   hipLaunchKernelGGL(nmf_tsmm_kernel, dim3(nblk), dim3(256), 0, w.st, F, Z, nrows, k, w.l, rpb, w.gpart);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(16), dim3(256), 0, w.st, (const double*)w.gpart, nblk, k * w.l, T);
 }
@@ -368,7 +324,7 @@ template <bool NORMS>
 int colstat(Work& w, const double* Z, int64_t nrows, int ld, int ncol, double* dtmp, std::vector<double>& out) {
   int nblk;
   int64_t rpb;
-  row_blocks(w, nrows, 2, nblk, rpb);
+  row_blocks(nrows, 2, nblk, rpb);
   const int width = NORMS ? 2 * ncol : ncol;
   hipLaunchKernelGGL(nmf_colstat_kernel<NORMS>, dim3(nblk), dim3(256), 0, w.st, Z, nrows, ld, ncol, rpb, w.gpart);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(16), dim3(256), 0, w.st, (const double*)w.gpart, nblk, width, dtmp);
@@ -405,25 +361,18 @@ extern "C" int glrm_hip_init_nndsvd(glrm_handle* h, double* X, double* Y, int32_
   if (max_iters < 0) return fail(GLRM_ERR_INVALID, "glrm_hip_init_nndsvd: max_iters = %d is negative", max_iters);
   DeviceScope dg(h->device);
   if (!dg.ok) return fail(GLRM_ERR_HIP, "cannot select device %d", h->device);
-  if (svd_max_iter <= 0) svd_max_iter = 60;
-  if (!(svd_tol > 0)) svd_tol = 1e-12;
-  int l = k + 8;
-  if (l > LMAX) l = LMAX;
-  if (l > m) l = (int)m;
-  if (l > n) l = (int)n;
+  const int l = block_width(k, m, n);
   const glrm_handle::Side& rs = h->side[GLRM_ROWS];
   const glrm_handle::Side& cs = h->side[GLRM_COLS];
+  hipStream_t st = h->stream;
   Work w;
-  w.h = h; w.st = h->stream; w.l = l;
-  hipStream_t st = w.st;
   DevArena scratch;
-  double *T = nullptr, *stat = nullptr, *rres = nullptr, *cres = nullptr, *cpart = nullptr;
+  double *T = nullptr, *stat = nullptr, *rres = nullptr, *cres = nullptr, *dX = nullptr, *dY = nullptr;
   SplitCoef* dcoef = nullptr;
   int rc;
-  if ((rc = scratch.alloc(&w.V, (size_t)n * l)) || (rc = scratch.alloc(&w.U, (size_t)m * l)) || (rc = scratch.alloc(&w.gpart, (size_t)w.nblk_max * std::max(l * l, 2 * k))) || // Gram, F Z (k l) and the 2 k norms per block
-      (rc = scratch.alloc(&w.G, (size_t)l * l)) || (rc = scratch.alloc(&w.M, (size_t)l * l)) || (rc = scratch.alloc(&T, (size_t)k * l)) ||
-      (rc = scratch.alloc(&stat, (size_t)2 * LMAX)) || (rc = scratch.alloc(&dcoef, (size_t)k)) || (rc = scratch.alloc(&w.dX, (size_t)m * k)) ||
-      (rc = scratch.alloc(&w.dY, (size_t)n * k)))
+  if ((rc = alloc_work(w, scratch, st, l, m, n, (size_t)std::max(l * l, 2 * k))) || // Gram, F Z (k l) and the 2 k norms per block
+      (rc = scratch.alloc(&T, (size_t)k * l)) || (rc = scratch.alloc(&stat, (size_t)2 * LMAX)) || (rc = scratch.alloc(&dcoef, (size_t)k)) ||
+      (rc = scratch.alloc(&dX, (size_t)m * k)) || (rc = scratch.alloc(&dY, (size_t)n * k)))
     return rc;
   if (max_iters > 0) {
     char what[256];
@@ -434,39 +383,26 @@ extern "C" int glrm_hip_init_nndsvd(glrm_handle* h, double* X, double* Y, int32_
   NmfArgs ra{}, ca{};
   ra.nseg = m; ra.ptr = rs.ptr; ra.idx = rs.idx; ra.vals = rs.vals;
   ra.losses = h->losses; ra.loss_single = h->n_losses == 1 ? 1 : 0; ra.use_scale = scale ? 1 : 0;
-  ra.in = w.V; ra.out = w.U; ra.l = l; ra.nsplit = 1; ra.k = k;
+  ra.in = w.V; ra.out = w.U; ra.l = l; ra.nsplit = 1; ra.dmax = 1; ra.k = k;
   ca = ra;
   ca.nseg = n; ca.ptr = cs.ptr; ca.idx = cs.idx; ca.vals = cs.vals; ca.in = w.U; ca.out = w.V;
-  { // long columns: several workgroups per column, partials added in chunk order
-    std::vector<int64_t> cp((size_t)n + 1);
-    HIPCK(hipMemcpyAsync(cp.data(), cs.ptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    int64_t longest = 0;
-    for (int64_t f = 0; f < n; ++f) longest = std::max(longest, cp[f + 1] - cp[f]);
-    ca.chunk = 16384;
-    while ((longest + ca.chunk - 1) / ca.chunk > 65535) ca.chunk *= 2; // gridDim.y
-    ca.nsplit = (int)std::max<int64_t>(1, (longest + ca.chunk - 1) / ca.chunk);
-    if (ca.nsplit > 1) {
-      if ((rc = scratch.alloc(&cpart, (size_t)n * ca.nsplit * l))) return rc;
-      ca.partial = cpart;
-    } else ca.chunk = longest > 0 ? longest : 1;
-  }
+  if ((rc = chunk_product(h, scratch, ca))) return rc;
   ResidArgs rr{}, cr{};
   rr.nseg = m; rr.ptr = rs.ptr; rr.idx = rs.idx; rr.vals = rs.vals; rr.losses = h->losses; rr.loss_single = ra.loss_single; rr.use_scale = ra.use_scale;
-  rr.cols = 0; rr.chunk = 0; rr.Fseg = w.dX; rr.Fopp = w.dY; rr.k = k; rr.resid = rres;
+  rr.cols = 0; rr.chunk = 0; rr.Fseg = dX; rr.Fopp = dY; rr.k = k; rr.resid = rres;
   cr = rr;
-  cr.nseg = n; cr.ptr = cs.ptr; cr.idx = cs.idx; cr.vals = cs.vals; cr.cols = 1; cr.chunk = ca.chunk; cr.Fseg = w.dY; cr.Fopp = w.dX; cr.resid = cres;
+  cr.nseg = n; cr.ptr = cs.ptr; cr.idx = cs.idx; cr.vals = cs.vals; cr.cols = 1; cr.chunk = ca.chunk; cr.Fseg = dY; cr.Fopp = dX; cr.resid = cres;
   const bool vec2 = k % 2 == 0;
   auto BV = [&]() { // U = B_t V
-    if (ra.T) tsmm(w, w.dY, w.V, n, k, T);
+    if (ra.T) tsmm(w, dY, w.V, n, k, T);
     hipLaunchKernelGGL(nmf_rows_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, ra);
   };
   auto BtU = [&]() { // V = B_t' U
-    if (ca.T) tsmm(w, w.dX, w.U, m, k, T);
+    if (ca.T) tsmm(w, dX, w.U, m, k, T);
     hipLaunchKernelGGL(nmf_cols_kernel, dim3((unsigned)n, (unsigned)ca.nsplit), dim3(256), 0, st, ca);
     if (ca.nsplit > 1) hipLaunchKernelGGL(nmf_cols_reduce_kernel, dim3((unsigned)n), dim3(256), 0, st, ca);
   };
-  std::vector<double> ritz, E, nu, nv, x1, y1, larger((size_t)k), smaller((size_t)k);
+  std::vector<double> ritz, nu, nv, x1, y1, larger((size_t)k), smaller((size_t)k);
   std::vector<SplitCoef> coef((size_t)k);
   for (int round = 0; round <= max_iters; ++round) {
     if (round > 0) { // the residuals against the factors of the round before, once per view
@@ -478,8 +414,8 @@ extern "C" int glrm_hip_init_nndsvd(glrm_handle* h, double* X, double* Y, int32_
         hipLaunchKernelGGL(nmf_residual_kernel<false>, dim3((unsigned)n, (unsigned)ca.nsplit), dim3(256), 0, st, cr);
       }
       HIPCK(hipGetLastError());
-      ra.resid = rres; ra.F = w.dX; ra.T = T;
-      ca.resid = cres; ca.F = w.dY; ca.T = T;
+      ra.resid = rres; ra.F = dX; ra.T = T;
+      ca.resid = cres; ca.F = dY; ca.T = T;
     }
     double v0 = 0.0;
     if (variant == GLRM_NNDSVD_A) { // mean(B_t) = (sum over Omega of the sparse part + (X 1)'(Y 1)) / (m n), before X and Y are replaced
@@ -491,36 +427,16 @@ extern "C" int glrm_hip_init_nndsvd(glrm_handle* h, double* X, double* Y, int32_
       HIPCK(hipMemcpyAsync(&total, stat, 8, hipMemcpyDeviceToHost, st));
       HIPCK(hipStreamSynchronize(st));
       if (round > 0) {
-        if ((rc = colstat<false>(w, w.dX, m, k, k, stat, x1)) || (rc = colstat<false>(w, w.dY, n, k, k, stat, y1))) return rc;
+        if ((rc = colstat<false>(w, dX, m, k, k, stat, x1)) || (rc = colstat<false>(w, dY, n, k, k, stat, y1))) return rc;
         double dot = 0.0;
         for (int c = 0; c < k; ++c) dot = std::fma(x1[c], y1[c], dot);
         total += dot;
       }
       v0 = total / ((double)m * (double)n);
     }
-    // the subspace iteration of glrm_hip_init_svd
-    hipLaunchKernelGGL(randn_kernel, dim3(1024), dim3(256), 0, st, w.V, n * l, seed);
-    if ((rc = orthonormalize(w, w.V, n))) return rc;
-    std::vector<double> prev;
     int it = 0;
-    for (it = 1; it <= svd_max_iter; ++it) {
-      BV();
-      if ((rc = orthonormalize(w, w.U, m))) return rc;
-      BtU();
-      HIPCK(hipGetLastError());
-      if ((rc = orthonormalize(w, w.V, n, &ritz, &E))) return rc; // eigenvalues of (B'U)'(B'U) = squared singular values
-      bool done = !prev.empty();
-      for (int c = 0; c < k && done; ++c) {
-        const double s = std::sqrt(std::max(ritz[c], 0.0)), sp = std::sqrt(std::max(prev[c], 0.0)), s0 = std::sqrt(std::max(ritz[0], 0.0));
-        if (std::fabs(s - sp) > svd_tol * (s0 > 0 ? s0 : 1.0)) done = false;
-      }
-      prev = ritz;
-      if (done) break;
-    }
-    if (it > svd_max_iter) it = svd_max_iter;
+    if ((rc = subspace_iterate(w, m, n, k, svd_max_iter, svd_tol, seed, BV, BtU, ritz, it))) return rc;
     if (iters_done) iters_done[round] = it;
-    // V = orth(B'U) = right singular vectors (columns by descending value); left ones = U E
-    if ((rc = rightmul(w, w.U, m, E))) return rc;
     // the split
     if ((rc = colstat<true>(w, w.U, m, l, k, stat, nu)) || (rc = colstat<true>(w, w.V, n, l, k, stat, nv))) return rc;
     for (int c = 0; c < k; ++c) {
@@ -537,12 +453,12 @@ extern "C" int glrm_hip_init_nndsvd(glrm_handle* h, double* X, double* Y, int32_
     }
     HIPCK(hipMemcpyAsync(dcoef, coef.data(), (size_t)k * sizeof(SplitCoef), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(nmf_split_kernel, dim3(1024), dim3(256), 0, st, (const double*)w.U, m, (const double*)w.V, n, l, k, (const SplitCoef*)dcoef, v0,
-                       zeroh ? 1 : 0, w.dX, w.dY);
+                       zeroh ? 1 : 0, dX, dY);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(st)); // coef is reused by the next round
   }
-  HIPCK(hipMemcpyAsync(X, w.dX, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(Y, w.dY, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(X, dX, (size_t)m * k * 8, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(Y, dY, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
   HIPCK(hipStreamSynchronize(st));
   if (singular_values) for (int c = 0; c < k; ++c) singular_values[c] = std::sqrt(std::max(ritz[c], 0.0));
   if (split) for (int c = 0; c < k; ++c) { split[2 * c] = larger[c]; split[2 * c + 1] = smaller[c]; }

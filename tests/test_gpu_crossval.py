@@ -76,6 +76,36 @@ def test_subset_child_outlives_parent_and_keeps_kernel_family():
         api.destroy(hc)
 
 
+def test_error_metric_of_a_subset_child_has_the_bits_of_a_fresh_handle():
+    """error_metric takes the longest column from the handle's own record.  The parent's longest column spans two 65536-entry chunks and
+    is not in the child, whose longest spans one chunk plus 17 entries: a child that carried its parent's length, or a fresh handle that
+    measured wrong, would chunk differently or lose entries.  Inexact factors, so the sums depend on their order."""
+    chunk = 65536
+    m, lens = 2 * chunk, [2 * chunk, chunk + 17, 300, 0]
+    rng = np.random.default_rng(17)
+    A = rng.standard_normal((m, len(lens)))
+    I = np.concatenate([np.sort(rng.choice(m, n_f, replace=False)) for n_f in lens])
+    g = L.GLRM(A, L.QuadLoss(), L.ZeroReg(), L.ZeroReg(), 2, obs=(I, np.repeat(np.arange(len(lens)), lens)))
+    X, Y, doms = np.asfortranarray(rng.standard_normal((2, m))), np.asfortranarray(rng.standard_normal((2, len(lens)))), pack_domains([L.RealDomain()] * len(lens))
+    sp = crossval._Split(g)
+    keep = (sp.J != 0).astype(np.uint8)
+    fresh = L.GLRM(A, L.QuadLoss(), L.ZeroReg(), L.ZeroReg(), 2, obs=(sp.I[keep == 1], sp.J[keep == 1]))
+    assert np.diff(fresh.problem_arrays().colptr).tolist() == [0] + lens[1:]
+    api = hip()
+    h = api.create(g.problem_arrays())
+    try:
+        hc = api.subset(h, keep, keep[sp.perm], 1, False)
+    finally:
+        api.destroy(h)
+    hf = api.create(fresh.problem_arrays())
+    try:
+        assert api.error_metric(hc, X, Y, doms, False) == api.error_metric(hf, X, Y, doms, False)
+        assert api.signature(hc).max_col_len == api.signature(hf).max_col_len == chunk + 17
+    finally:
+        api.destroy(hc)
+        api.destroy(hf)
+
+
 def test_subset_rejects_dense_parent():
     rng = np.random.default_rng(4)
     A = rng.standard_normal((64, 48))
