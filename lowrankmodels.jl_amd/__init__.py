@@ -22,7 +22,7 @@ from .glrm import GLRM, add_offset_, copy_estimate, fix_latent_features_, parame
 from .losses import (BvSLoss, HingeLoss, HuberLoss, L1Loss, LogisticLoss, Loss, MultinomialLoss, MultinomialOrdinalLoss,
                      OrdinalHingeLoss, OrdisticLoss, OvALoss, PeriodicLoss, PoissonLoss, QuadLoss, QuantileLoss,
                      WeightedHingeLoss, embedding_dim, evaluate, get_yidxs, grad)
-from .params import AbstractParams, AlsParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams
+from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams
 from .regularizers import (KSparseConstraint, MNLOrdinalReg, NonNegConstraint, NonNegOneReg, OneReg, OneSparseConstraint, OrdinalReg,
                            QuadConstraint, QuadReg, Regularizer, SimplexConstraint, UnitOneSparseConstraint, ZeroReg, lastentry1,
                            lastentry_unpenalized, prox,

@@ -199,6 +199,12 @@ ALS_SYMBOLS = ("als_solve", "als_info")
 ALS_MAX_K = 64                                         # glrm_hip_als.h: GLRM_ALS_MAX_K
 ALS_SOLVED, ALS_KEPT_SHORT, ALS_KEPT_PIVOT = 0, 1, 2   # glrm_hip_als.h: GLRM_ALS_*
 
+#: the coordinate-descent extension, include/glrm_hip_cd.h (cyclic coordinate-descent sweeps on every row or column of a QuadLoss model
+#: with ZeroReg / QuadReg / OneReg / NonNegConstraint on the solved side): outside the boundary, bound only where the library has it
+CD_SYMBOLS = ("cd_solve", "cd_info")
+CD_MAX_K, CD_MAX_SWEEPS = 64, 256                      # glrm_hip_cd.h: GLRM_CD_MAX_K, GLRM_CD_MAX_SWEEPS
+CD_CONVERGED, CD_SKIPPED = 1, 2                        # glrm_hip_cd.h: GLRM_CD_* status bits
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -313,9 +319,11 @@ class Api:
             "sample_at_info": (C.c_int, [C.POINTER(C.c_int64)] * 5),
             "als_solve": (C.c_int, [H, C.c_int32]),
             "als_info": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
+            "cd_solve": (C.c_int, [H, C.c_int32, C.c_int32]),
+            "cd_info": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
         }
         assert tuple(ext) == (SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
-                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS + ALS_SYMBOLS)
+                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS + ALS_SYMBOLS + CD_SYMBOLS)
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -926,6 +934,40 @@ class Api:
         out = dict(solved=n[0].value, kept_short=n[1].value, kept_pivot=n[2].value)
         if status is not None:
             out["status"] = status[: int(nseg)]
+        return out
+
+    # -- coordinate-descent extension (include/glrm_hip_cd.h) ---------------------------------
+    def _cd(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the coordinate-descent extension "
+                                             "(include/glrm_hip_cd.h is implemented by the HIP engine only)")
+        return fn
+
+    @property
+    def has_cd(self) -> bool:
+        """The library exports the coordinate-descent extension (the CPU oracle does not)."""
+        return "cd_solve" in self._f
+
+    def cd_solve(self, h, side, sweeps):
+        """glrm_hip_cd_solve: at most ``sweeps`` cyclic coordinate-descent sweeps on every local row of X (``side`` 0) or column of Y (1)
+        with the opposing factor as it stands (QuadLoss columns; ZeroReg, QuadReg, OneReg or NonNegConstraint on the solved side).
+        Asynchronous."""
+        self._ck(self._cd("cd_solve")(h, int(side), int(sweeps)))
+
+    def cd_info(self, h, side, nseg=None) -> dict:
+        """What the last cd_solve of ``side`` did: the segments that stopped because a whole sweep changed no bit (``converged``), those
+        with a coordinate that failed the denominator rule (``skipped``) and the sweeps run summed over the segments (``sweeps_total``);
+        with ``nseg`` (the local segments of the side) also ``status`` (int8 bits CD_CONVERGED / CD_SKIPPED) and ``sweeps_run`` (int32)
+        per segment.  Synchronises."""
+        fn = self._cd("cd_info")
+        n = [C.c_int64(0) for _ in range(3)]
+        status = None if nseg is None else np.full(max(int(nseg), 1), -1, dtype=np.int8)
+        run = None if nseg is None else np.full(max(int(nseg), 1), -1, dtype=np.int32)
+        self._ck(fn(h, int(side), C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), _ptr(status), _ptr(run)))
+        out = dict(converged=n[0].value, skipped=n[1].value, sweeps_total=n[2].value)
+        if status is not None:
+            out["status"], out["sweeps_run"] = status[: int(nseg)], run[: int(nseg)]
         return out
 
 

@@ -9,6 +9,7 @@
 //              Every entry has one accumulator that walks t ascending, so the chunk, the block shape and the lane count change no bit.
 //   factorise  the triangle is written packed into LDS (over the stage) and wave 0 -- lane i = row i -- runs the left-looking Cholesky
 //              and the two substitutions; values cross lanes by LDS (L) and by shuffles (the pivots, z_c, x_c).
+// The first two stages are als_gram below, which cd_solve_kernel (glrm_cd.hpp) calls too.
 // Blocks: KP = 64 -> 136 triangle + 16 right-hand-side blocks on 192 lanes; KP = 32 -> 36 + 8 on 64; KP = 16 -> 10 + 4; KP = 8 -> 3 + 2.
 #pragma once
 
@@ -46,26 +47,16 @@ __device__ __forceinline__ void als_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// The stage and the accumulation above, for the segment [lo, lo + len) of the solved side's view: on return (after a workgroup barrier)
+// the packed lower triangle of G stands at lds[als_tri(r, c)] and b at lds[KP * (KP + 1) / 2 + r].  Called by every lane of the workgroup;
+// als_solve_kernel and cd_solve_kernel (glrm_cd.hpp) share it, so the two solvers see the same G and b bit for bit.
 template <int KP>
-__global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_kernel(const AlsArgs a) {
+__device__ __forceinline__ void als_gram(const AlsArgs& a, const int64_t lo, const int64_t len, const double wseg, double* const lds, double* const wl) {
   constexpr int T = als_threads(KP), LD = als_ld(KP), NB = KP / ALS_B, NTRI = NB * (NB + 1) / 2, NBLK = NTRI + NB;
   constexpr int P = KP / 2;                                  // 16-byte pieces per vector
   constexpr int NIT = (ALS_CHUNK * P + T - 1) / T;           // pieces per lane and chunk
-  constexpr int STAGE = ALS_CHUNK * LD, TRI = KP * (KP + 1) / 2 + KP;
   static_assert(NBLK <= T && ALS_CHUNK <= T && KP <= 64 && KP % ALS_B == 0, "one block per lane, one row per lane of wave 0");
-  __shared__ __attribute__((aligned(16))) double lds[(STAGE > TRI ? STAGE : TRI)];
-  __shared__ double wl[ALS_CHUNK];
-
-  const int tid = threadIdx.x, k = a.k;
-  const int64_t seg = a.order[blockIdx.x];
-  const int64_t lo = a.ptr[seg], len = a.ptr[seg + 1] - lo;
-  const glrm_reg reg = a.regs[a.reg_single ? 0 : seg];
-  const double gamma = reg.kind == GLRM_REG_QUAD ? reg.scale : 0.0;
-  if (gamma == 0.0 && len < k) {                             // the short rule (workgroup-uniform)
-    if (tid == 0) a.status[seg] = GLRM_ALS_KEPT_SHORT;
-    return;
-  }
-  const double wseg = a.side == GLRM_COLS ? a.losses[a.loss_single ? 0 : seg].scale : 0.0;
+  const int tid = threadIdx.x;
 
   // this lane's block: rows ALS_B * br .., columns ALS_B * bc .. (bc == NB: the right-hand side)
   int br = 0, bc = 0;
@@ -156,6 +147,29 @@ __global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_
     }
   }
   __syncthreads();
+}
+
+// doubles of LDS a kernel over als_gram needs: the stage, or the packed triangle and the right-hand side written over it
+constexpr int als_lds_doubles(int KP) { return ALS_CHUNK * als_ld(KP) > KP * (KP + 1) / 2 + KP ? ALS_CHUNK * als_ld(KP) : KP * (KP + 1) / 2 + KP; }
+
+template <int KP>
+__global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_kernel(const AlsArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[als_lds_doubles(KP)];
+  __shared__ double wl[ALS_CHUNK];
+
+  const int tid = threadIdx.x, k = a.k;
+  const int64_t seg = a.order[blockIdx.x];
+  const int64_t lo = a.ptr[seg], len = a.ptr[seg + 1] - lo;
+  const glrm_reg reg = a.regs[a.reg_single ? 0 : seg];
+  const double gamma = reg.kind == GLRM_REG_QUAD ? reg.scale : 0.0;
+  if (gamma == 0.0 && len < k) {                             // the short rule (workgroup-uniform)
+    if (tid == 0) a.status[seg] = GLRM_ALS_KEPT_SHORT;
+    return;
+  }
+  const double wseg = a.side == GLRM_COLS ? a.losses[a.loss_single ? 0 : seg].scale : 0.0;
+  als_gram<KP>(a, lo, len, wseg, lds, wl);
+  double* const tri = lds;
+  double* const rhs = lds + KP * (KP + 1) / 2;
   if (tid >= 64) return;
 
   // wave 0: lane i = row i of the leading k x k system

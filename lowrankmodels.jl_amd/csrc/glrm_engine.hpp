@@ -20,6 +20,8 @@
 //                       register kernel (glrm_solve.hpp); glrm_solve_f32.hip holds its float instantiations
 //   glrm_als.hip        the exact half-step of a quadratic model (include/glrm_hip_als.h): one workgroup per segment accumulates the Gram
 //                       triangle in registers and one wave factorises it in LDS (glrm_als.hpp)
+//   glrm_cd.hip         coordinate-descent sweeps for ZeroReg / QuadReg / OneReg / NonNegConstraint under QuadLoss (include/glrm_hip_cd.h):
+//                       the Gram stage of glrm_als.hpp, then one wave sweeps the coordinates with x and the residual in registers (glrm_cd.hpp)
 //   glrm_devmem.hpp     DeviceScope (the one device guard) and DevArena (the one owner of device memory: glrm_handle::mem, a shard's replica, local scratch)
 // The launch layer the run functions of every family go through (side description, rounds driver, dispatch) is glrm_launch.hpp.
 // Below: glrm_handle describes a model -- what exists once per view in side[GLRM_ROWS] / side[GLRM_COLS] (host functions take `int side`,
@@ -202,6 +204,9 @@ struct glrm_handle {
   // (a permutation of its own: Side::perm leaves out the columns diverted to the 8-wave sweep) and the status of every local segment
   // after the last solve.  solved: glrm_hip_als_info has something to report
   struct Als { int32_t* order = nullptr; int8_t* status = nullptr; bool solved = false; } als[2];
+  // glrm_hip_cd_solve (include/glrm_hip_cd.h; glrm_cd.hip), per side, made at the side's first solve: the same longest-first order, and
+  // the status bits and the sweeps run of every local segment after the last solve
+  struct Cd { int32_t* order = nullptr; int8_t* status = nullptr; int32_t* sweeps_run = nullptr; bool solved = false; } cd[2];
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from .convergence import ConvergenceHistory, update_ch
-from .params import AbstractParams, AlsParams, HipProxGradParams, ProxGradParams, SparseProxGradParams
+from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, ProxGradParams, SparseProxGradParams
 
 
 LAST_EXCHANGE_PROBE = None  # the last set-up probe of a ShardedFit in this process (diagnostics; tests)
@@ -135,8 +135,9 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
         raise TypeError("params must be an AbstractParams (ProxGradParams / HipProxGradParams)")
     sparse = isinstance(params, SparseProxGradParams)
     als = isinstance(params, AlsParams)
+    cd = isinstance(params, CdParams)
     if ch is None:
-        ch = ConvergenceHistory("AlsGLRM" if als else "SparseProxGradGLRM" if sparse else "ProxGradGLRM")
+        ch = ConvergenceHistory("AlsGLRM" if als else "CdGLRM" if cd else "SparseProxGradGLRM" if sparse else "ProxGradGLRM")
     api = engine if engine is not None else _capi.hip_api()
     world = 1
     if group is not None or os.environ.get("WORLD_SIZE", "1") != "1":
@@ -150,6 +151,11 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
             raise ValueError("AlsParams runs on one device: glrm_hip_als_solve needs the whole problem on one handle")
         from .als import fit_als
         return fit_als(glrm, params, ch, verbose, api)
+    if cd:  # alternating coordinate descent (include/glrm_hip_cd.h)
+        if world > 1:
+            raise ValueError("CdParams runs on one device: glrm_hip_cd_solve needs the whole problem on one handle")
+        from .cd import fit_cd
+        return fit_cd(glrm, params, ch, verbose, api)
     if world > 1:
         if sparse:
             raise NotImplementedError("SparseProxGradParams runs on a single shard (step-level gradstep_x / gradstep_y exist for hosts)")

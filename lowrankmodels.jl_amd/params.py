@@ -95,6 +95,29 @@ class AlsParams(AbstractParams):
         return f"AlsParams(max_iter={self.max_iter}, abs_tol={self.abs_tol}, rel_tol={self.rel_tol}, device_id={self.device_id})"
 
 
+class CdParams(AbstractParams):
+    """CdParams(max_iter=100, sweeps=4, abs_tol=1e-5, rel_tol=1e-4, device_id=-1): alternating cyclic coordinate descent for QuadLoss
+    models whose regularizers are ZeroReg, QuadReg, OneReg or NonNegConstraint: non-negative matrix factorisation, the lasso, and
+    everything AlsParams takes.  An iteration runs at most ``sweeps`` sweeps over the coordinates of every row of X, then of every column
+    of Y (glrm_hip_cd_solve, include/glrm_hip_cd.h: one Gram matrix per row / column, then every coordinate set to the exact minimiser
+    of the row's part of the objective with the others held), so there is no step size and no line search.  The reference has no such
+    solver; in Julia this is ``struct CdParams <: AbstractParams`` (julia/HipGLRMCd.jl).  ``sweeps = 4`` is a starting default, not a tuned
+    one: a sweep costs about k^2 multiply-adds where the Gram matrix costs L k^2 / 2.  The history records the FULL objective (losses
+    and both penalties) after every iteration, which a sweep cannot raise; the stopping rule is ProxGradParams'
+    (src/algorithms/proxgrad.jl:210-213).  One device, fp64, observation lists; rank at most 64."""
+
+    def __init__(self, max_iter=100, *, sweeps=4, abs_tol=0.00001, rel_tol=0.0001, device_id=-1):
+        self.max_iter = int(max_iter)
+        self.sweeps = int(sweeps)
+        self.abs_tol = float(abs_tol)
+        self.rel_tol = float(rel_tol)
+        self.device_id = int(device_id)
+
+    def __repr__(self):
+        return (f"CdParams(max_iter={self.max_iter}, sweeps={self.sweeps}, abs_tol={self.abs_tol}, rel_tol={self.rel_tol}, "
+                f"device_id={self.device_id})")
+
+
 def Params(*args, **kwargs):  # src/fit.jl:5
     return ProxGradParams(*args, **kwargs)
 
