@@ -2,7 +2,7 @@
  * glrm_hip_als.h -- the ALS extension of libglrm_hip.so: the EXACT half-step of a quadratic model.  glrm_hip_als_solve replaces every
  * local row of X (or every local column of Y) by the closed-form minimiser of its part of the objective with the opposing factor as it
  * stands -- the row solve inside the reference's streaming_fit! (src/algorithms/quad_streaming.jl:53), for every segment at once.
- * streaming_fit! itself (rows strictly one after another) is not reproduced.
+ * streaming_fit! itself is glrm_hip_stream_rows (include/glrm_hip_stream.h), which runs this solve row after row.
  *
  * An extension header like glrm_hip_transform.h: include/glrm_hip.h, GLRM_HIP_ABI_VERSION and every struct layout are unchanged, and
  * the CPU oracle has no counterpart.  A host that never calls it is unaffected: no existing entry point, option, default, kernel choice

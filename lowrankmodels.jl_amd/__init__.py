@@ -16,13 +16,14 @@ from .transform import inverse_transform, transform
 from .recommend import recommend
 from .predict import error_metric_at, impute_at
 from .sample import sample, sample_at, sample_missing, sample_missing_at
+from .stream import keep_rows, streaming_fit, streaming_impute, streaming_impute_at
 from .domains import (BoolDomain, CategoricalDomain, CountDomain, Domain, OrdinalDomain, PeriodicDomain, RealDomain, default_domain,
                       error_metric, error_metric_entry, impute, impute_entry, impute_missing)
 from .glrm import GLRM, add_offset_, copy_estimate, fix_latent_features_, parameter_estimate, scale_regularizer_, sort_observations
 from .losses import (BvSLoss, HingeLoss, HuberLoss, L1Loss, LogisticLoss, Loss, MultinomialLoss, MultinomialOrdinalLoss,
                      OrdinalHingeLoss, OrdisticLoss, OvALoss, PeriodicLoss, PoissonLoss, QuadLoss, QuantileLoss,
                      WeightedHingeLoss, embedding_dim, evaluate, get_yidxs, grad)
-from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams
+from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, Params, ProxGradParams, SparseProxGradParams, StreamingParams
 from .regularizers import (KSparseConstraint, MNLOrdinalReg, NonNegConstraint, NonNegOneReg, OneReg, OneSparseConstraint, OrdinalReg,
                            QuadConstraint, QuadReg, Regularizer, SimplexConstraint, UnitOneSparseConstraint, ZeroReg, lastentry1,
                            lastentry_unpenalized, prox,

@@ -205,6 +205,11 @@ CD_SYMBOLS = ("cd_solve", "cd_info")
 CD_MAX_K, CD_MAX_SWEEPS = 64, 256                      # glrm_hip_cd.h: GLRM_CD_MAX_K, GLRM_CD_MAX_SWEEPS
 CD_CONVERGED, CD_SKIPPED = 1, 2                        # glrm_hip_cd.h: GLRM_CD_* status bits
 
+#: the streaming extension, include/glrm_hip_stream.h (the reference's one-pass streaming_fit! on the device: rows run level by level, the
+#: decay of Y is applied when a column is read): outside the boundary, bound only where the library has it
+STREAM_SYMBOLS = ("stream_plan", "stream_rows", "stream_info")
+STREAM_MAX_K = 64                                      # glrm_hip_stream.h: GLRM_STREAM_MAX_K
+
 
 #: Bumped whenever a loss / regularizer object is created or modified or a model's descriptor list changes: lets a model reuse
 #: its packed descriptors (and its engine handle) without re-reading a million Python objects per fit! call.
@@ -321,9 +326,13 @@ class Api:
             "als_info": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
             "cd_solve": (C.c_int, [H, C.c_int32, C.c_int32]),
             "cd_info": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+            "stream_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+                            + [C.POINTER(C.c_int64)] * 4),
+            "stream_rows": (C.c_int, [H, C.c_int64, C.c_double, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "stream_info": (C.c_int, [H] + [C.POINTER(C.c_int64)] * 6 + [C.POINTER(C.c_double), C.c_void_p]),
         }
         assert tuple(ext) == (SCALE_SYMBOLS + INIT_SYMBOLS + STORAGE_SYMBOLS + REGVEC_SYMBOLS + TOPK_SYMBOLS + RECOMMEND_SYMBOLS + NMF_SYMBOLS + TRANSFORM_SYMBOLS
-                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS + ALS_SYMBOLS + CD_SYMBOLS)
+                              + IMPUTE_AT_SYMBOLS + SAMPLE_SYMBOLS + ALS_SYMBOLS + CD_SYMBOLS + STREAM_SYMBOLS)
         for name, (res, args) in ext.items():
             fn = getattr(lib, prefix + name, None)
             if fn is not None:
@@ -968,6 +977,71 @@ class Api:
         out = dict(converged=n[0].value, skipped=n[1].value, sweeps_total=n[2].value)
         if status is not None:
             out["status"], out["sweeps_run"] = status[: int(nseg)], run[: int(nseg)]
+        return out
+
+    # -- streaming extension (include/glrm_hip_stream.h) ---------------------------------------
+    def _stream(self, name):
+        fn = self._f.get(name)
+        if fn is None:
+            raise GLRMError(ERR_UNSUPPORTED, f"{self.prefix}{name}: this engine does not have the streaming extension "
+                                             "(include/glrm_hip_stream.h is implemented by the HIP engine only)")
+        return fn
+
+    @property
+    def has_stream(self) -> bool:
+        """The library exports the streaming extension (the CPU oracle does not)."""
+        return "stream_rows" in self._f
+
+    @staticmethod
+    def _queries(qptr, qcol):
+        if (qptr is None) != (qcol is None):
+            raise GLRMError(ERR_INVALID, "qptr and qcol go together (both, or neither)")
+        if qptr is None:
+            return None, None
+        return np.ascontiguousarray(qptr, dtype=np.int64), np.ascontiguousarray(qcol, dtype=np.int32)
+
+    def stream_plan(self, m, n, first, rowptr, colidx, qptr=None, qcol=None, sequential=False) -> dict:
+        """glrm_hip_stream_plan (pure host code): the level of every row first .. m-1 of a CSR row view and the plan's figures ->
+        dict(level, nlevels, nlaunches, max_width, dup_rows)."""
+        fn = self._stream("stream_plan")
+        rowptr, colidx = np.ascontiguousarray(rowptr, dtype=np.int64), np.ascontiguousarray(colidx, dtype=np.int32)
+        if len(rowptr) != int(m) + 1 or len(colidx) < int(rowptr[-1]):
+            raise GLRMError(ERR_INVALID, "stream_plan: rowptr holds m + 1 offsets and colidx rowptr[m] columns")
+        qptr, qcol = self._queries(qptr, qcol)
+        if qptr is not None and (len(qptr) != int(m) + 1 or len(qcol) < int(qptr[-1])):
+            raise GLRMError(ERR_INVALID, "stream_plan: qptr holds m + 1 offsets and qcol qptr[m] columns")
+        level = np.zeros(max(int(m) - int(first), 1), dtype=np.int64)
+        v = [C.c_int64(0) for _ in range(4)]
+        self._ck(fn(int(m), int(n), int(first), _ptr(rowptr), _ptr(colidx), _ptr(qptr), _ptr(qcol), 1 if sequential else 0, _ptr(level),
+                    *[C.byref(x) for x in v]))
+        return dict(level=level[: max(int(m) - int(first), 0)], nlevels=v[0].value, nlaunches=v[1].value, max_width=v[2].value, dup_rows=v[3].value)
+
+    def stream_rows(self, h, m, first, stepsize, interval, sequential=False, qptr=None, qcol=None, want_objective=True):
+        """glrm_hip_stream_rows: rows ``first`` .. m-1 of the handle streamed once over the resident X and Y (``m``: the handle's rows).
+        ``qptr`` / ``qcol``: the queries of every row (m + 1 offsets, columns).  Synchronises -> (objective per streamed row or None,
+        query results or None)."""
+        fn = self._stream("stream_rows")
+        qptr, qcol = self._queries(qptr, qcol)
+        if qptr is not None and (len(qptr) != int(m) + 1 or len(qcol) < int(qptr[-1])):
+            raise GLRMError(ERR_INVALID, "stream_rows: qptr holds m + 1 offsets and qcol qptr[m] columns")
+        rows = max(int(m) - int(first), 0)
+        obj = np.full(max(rows, 1), np.nan) if want_objective else None
+        qout = None if qptr is None else np.full(max(int(qptr[-1]), 1), np.nan)
+        self._ck(fn(h, int(first), float(stepsize), int(interval), 1 if sequential else 0, _ptr(qptr), _ptr(qcol), _ptr(qout), _ptr(obj)))
+        return (None if obj is None else obj[:rows]), (None if qout is None else qout[: int(qptr[-1])])
+
+    def stream_info(self, h, rows=None) -> dict:
+        """What the last stream_rows did: ``solved`` / ``kept_short`` / ``kept_pivot`` rows, the plan's ``nlevels`` / ``nlaunches`` /
+        ``max_width`` and ``plan_ms``; with ``rows`` (the rows streamed) also ``status``, one int8 per streamed row (ALS_*)."""
+        fn = self._stream("stream_info")
+        v = [C.c_int64(0) for _ in range(6)]
+        ms = C.c_double(0.0)
+        status = None if rows is None else np.full(max(int(rows), 1), -1, dtype=np.int8)
+        self._ck(fn(h, *[C.byref(x) for x in v], C.byref(ms), _ptr(status)))
+        out = dict(zip(("solved", "kept_short", "kept_pivot", "nlevels", "nlaunches", "max_width"), (x.value for x in v)))
+        out["plan_ms"] = ms.value
+        if status is not None:
+            out["status"] = status[: int(rows)]
         return out
 
 

@@ -5,8 +5,9 @@
                             regularizers (include/glrm_hip_regvec.h), the top-k extension (include/glrm_hip_topk.h), the recommend extension
                             (include/glrm_hip_recommend.h), the NMF initialization extension (include/glrm_hip_nmf.h), the transform
                             extension (include/glrm_hip_transform.h), the impute_at extension (include/glrm_hip_impute_at.h), the
-                            sampling extension (include/glrm_hip_sample.h), the ALS extension (include/glrm_hip_als.h) and the
-                            coordinate-descent extension (include/glrm_hip_cd.h) -- the PRODUCT
+                            sampling extension (include/glrm_hip_sample.h), the ALS extension (include/glrm_hip_als.h), the
+                            coordinate-descent extension (include/glrm_hip_cd.h) and the streaming extension
+                            (include/glrm_hip_stream.h) -- the PRODUCT
                             library: no test hook, no link emulator in it
     libglrm_hip_testing.so  the same objects, with csrc/glrm_testhooks.hip and csrc/glrm_multigpu.hip rebuilt under -DGLRM_HIP_TESTING: the
                             environment-driven test hooks (injected set-up failure, RCCL stand-in, link emulator) live only here; loaded by name
@@ -26,8 +27,8 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 TARGETS = {
-    "libglrm_hip.so": (["glrm_hip.hip", "glrm_tiled.hip", "glrm_dense.hip", "glrm_multi.hip", "glrm_subset.hip", "glrm_svd.hip", "glrm_impute.hip", "glrm_tilesort.hip", "glrm_multigpu.hip", "glrm_blocked.hip", "glrm_cached.hip", "glrm_reforder.hip", "glrm_transpose.hip", "glrm_testhooks.hip", "glrm_lane.hip", "glrm_scale.hip", "glrm_kmeanspp.hip", "glrm_storage.hip", "glrm_cached_f32.hip", "glrm_blocked_f32.hip", "glrm_regvec.hip", "glrm_topk.hip", "glrm_recommend.hip", "glrm_nmf.hip", "glrm_solve.hip", "glrm_solve_f32.hip", "glrm_impute_at.hip", "glrm_sample.hip", "glrm_als.hip", "glrm_cd.hip"],
-                       ["glrm_device.hpp", "glrm_fastmath.hpp", "glrm_tiled.hpp", "glrm_dense.hpp", "glrm_multi.hpp", "glrm_impute.hpp", "glrm_engine.hpp", "glrm_knobs.hpp", "glrm_devmem.hpp", "glrm_launch.hpp", "glrm_sweep.hpp", "glrm_lane.hpp", "glrm_refreg.hpp", "glrm_blockreg.hpp", "glrm_cached.hpp", "glrm_solve.hpp", "glrm_blocked.hpp", "glrm_subspace.hpp", "glrm_xytile.hpp", "glrm_entries.hpp", "glrm_als.hpp", "glrm_cd.hpp", "../../include/glrm_hip.h", "../../include/glrm_hip_scale.h", "../../include/glrm_hip_init.h", "../../include/glrm_hip_storage.h", "../../include/glrm_hip_regvec.h", "../../include/glrm_hip_topk.h", "../../include/glrm_hip_recommend.h", "../../include/glrm_hip_nmf.h", "../../include/glrm_hip_transform.h", "../../include/glrm_hip_impute_at.h", "../../include/glrm_hip_sample.h", "../../include/glrm_hip_als.h", "../../include/glrm_hip_cd.h"]),
+    "libglrm_hip.so": (["glrm_hip.hip", "glrm_tiled.hip", "glrm_dense.hip", "glrm_multi.hip", "glrm_subset.hip", "glrm_svd.hip", "glrm_impute.hip", "glrm_tilesort.hip", "glrm_multigpu.hip", "glrm_blocked.hip", "glrm_cached.hip", "glrm_reforder.hip", "glrm_transpose.hip", "glrm_testhooks.hip", "glrm_lane.hip", "glrm_scale.hip", "glrm_kmeanspp.hip", "glrm_storage.hip", "glrm_cached_f32.hip", "glrm_blocked_f32.hip", "glrm_regvec.hip", "glrm_topk.hip", "glrm_recommend.hip", "glrm_nmf.hip", "glrm_solve.hip", "glrm_solve_f32.hip", "glrm_impute_at.hip", "glrm_sample.hip", "glrm_als.hip", "glrm_cd.hip", "glrm_stream.hip"],
+                       ["glrm_device.hpp", "glrm_fastmath.hpp", "glrm_tiled.hpp", "glrm_dense.hpp", "glrm_multi.hpp", "glrm_impute.hpp", "glrm_engine.hpp", "glrm_knobs.hpp", "glrm_devmem.hpp", "glrm_launch.hpp", "glrm_sweep.hpp", "glrm_lane.hpp", "glrm_refreg.hpp", "glrm_blockreg.hpp", "glrm_cached.hpp", "glrm_solve.hpp", "glrm_blocked.hpp", "glrm_subspace.hpp", "glrm_xytile.hpp", "glrm_entries.hpp", "glrm_als.hpp", "glrm_cd.hpp", "glrm_stream.hpp", "../../include/glrm_hip.h", "../../include/glrm_hip_scale.h", "../../include/glrm_hip_init.h", "../../include/glrm_hip_storage.h", "../../include/glrm_hip_regvec.h", "../../include/glrm_hip_topk.h", "../../include/glrm_hip_recommend.h", "../../include/glrm_hip_nmf.h", "../../include/glrm_hip_transform.h", "../../include/glrm_hip_impute_at.h", "../../include/glrm_hip_sample.h", "../../include/glrm_hip_als.h", "../../include/glrm_hip_cd.h", "../../include/glrm_hip_stream.h"]),
     "libglrm_synth.so": (["glrm_synth.hip"], ["../../include/glrm_synth.h"]),
 }
 

@@ -8,7 +8,7 @@
 //              code.  Per observation a lane reads 2 x ALS_B doubles from LDS for ALS_B^2 multiply-adds; u = w * v is formed in registers.
 //              Every entry has one accumulator that walks t ascending, so the chunk, the block shape and the lane count change no bit.
 //   factorise  the triangle is written packed into LDS (over the stage) and wave 0 -- lane i = row i -- runs the left-looking Cholesky
-//              and the two substitutions; values cross lanes by LDS (L) and by shuffles (the pivots, z_c, x_c).
+//              and the two substitutions (als_factor_solve); values cross lanes by LDS (L) and by shuffles (the pivots, z_c, x_c).
 // The first two stages are als_gram below, which cd_solve_kernel (glrm_cd.hpp) calls too.
 // Blocks: KP = 64 -> 136 triangle + 16 right-hand-side blocks on 192 lanes; KP = 32 -> 36 + 8 on 64; KP = 16 -> 10 + 4; KP = 8 -> 3 + 2.
 #pragma once
@@ -152,28 +152,11 @@ __device__ __forceinline__ void als_gram(const AlsArgs& a, const int64_t lo, con
 // doubles of LDS a kernel over als_gram needs: the stage, or the packed triangle and the right-hand side written over it
 constexpr int als_lds_doubles(int KP) { return ALS_CHUNK * als_ld(KP) > KP * (KP + 1) / 2 + KP ? ALS_CHUNK * als_ld(KP) : KP * (KP + 1) / 2 + KP; }
 
-template <int KP>
-__global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_kernel(const AlsArgs a) {
-  __shared__ __attribute__((aligned(16))) double lds[als_lds_doubles(KP)];
-  __shared__ double wl[ALS_CHUNK];
-
-  const int tid = threadIdx.x, k = a.k;
-  const int64_t seg = a.order[blockIdx.x];
-  const int64_t lo = a.ptr[seg], len = a.ptr[seg + 1] - lo;
-  const glrm_reg reg = a.regs[a.reg_single ? 0 : seg];
-  const double gamma = reg.kind == GLRM_REG_QUAD ? reg.scale : 0.0;
-  if (gamma == 0.0 && len < k) {                             // the short rule (workgroup-uniform)
-    if (tid == 0) a.status[seg] = GLRM_ALS_KEPT_SHORT;
-    return;
-  }
-  const double wseg = a.side == GLRM_COLS ? a.losses[a.loss_single ? 0 : seg].scale : 0.0;
-  als_gram<KP>(a, lo, len, wseg, lds, wl);
-  double* const tri = lds;
-  double* const rhs = lds + KP * (KP + 1) / 2;
-  if (tid >= 64) return;
-
-  // wave 0: lane i = row i of the leading k x k system
-  const int i = tid;
+// Wave 0 of a workgroup after als_gram, lane i = row i of the leading k x k system: the diagonal M_aa = G_aa + gamma, the pivot tolerance,
+// the left-looking Cholesky and the two substitutions of include/glrm_hip_als.h.  Returns GLRM_ALS_SOLVED with x_i in `x` of lane i < k, or
+// GLRM_ALS_KEPT_PIVOT (wave-uniform).  als_solve_kernel and stream_kernel (glrm_stream.hpp) both call it: one statement of the solve.
+__device__ __forceinline__ int als_factor_solve(double* const tri, const double* const rhs, const int k, const double gamma, double& x) {
+  const int i = threadIdx.x;
   const bool row = i < k;
   if (row) tri[als_tri(i, i)] = tri[als_tri(i, i)] + gamma;
   als_wave_sync();
@@ -194,10 +177,7 @@ __global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_
       }
     }
     const double sj = __shfl(s, j, 64);
-    if (!(sj > tol)) {                                       // the pivot rule (wave-uniform); the point keeps every bit
-      if (i == 0) a.status[seg] = GLRM_ALS_KEPT_PIVOT;
-      return;
-    }
+    if (!(sj > tol)) return GLRM_ALS_KEPT_PIVOT;             // the pivot rule (wave-uniform); the point keeps every bit
     const double d = sqrt(sj);
     if (row && i >= j) tri[als_tri(i, j)] = i == j ? d : s / d;
     als_wave_sync();
@@ -221,8 +201,33 @@ __global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_
       s = s - prod;
     }
   }
-  if (row) a.own[seg * KP + i] = s;
-  if (i == 0) a.status[seg] = GLRM_ALS_SOLVED;
+  x = s;
+  return GLRM_ALS_SOLVED;
+}
+
+template <int KP>
+__global__ void __launch_bounds__(als_threads(KP), als_min_waves(KP)) als_solve_kernel(const AlsArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[als_lds_doubles(KP)];
+  __shared__ double wl[ALS_CHUNK];
+
+  const int tid = threadIdx.x, k = a.k;
+  const int64_t seg = a.order[blockIdx.x];
+  const int64_t lo = a.ptr[seg], len = a.ptr[seg + 1] - lo;
+  const glrm_reg reg = a.regs[a.reg_single ? 0 : seg];
+  const double gamma = reg.kind == GLRM_REG_QUAD ? reg.scale : 0.0;
+  if (gamma == 0.0 && len < k) {                             // the short rule (workgroup-uniform)
+    if (tid == 0) a.status[seg] = GLRM_ALS_KEPT_SHORT;
+    return;
+  }
+  const double wseg = a.side == GLRM_COLS ? a.losses[a.loss_single ? 0 : seg].scale : 0.0;
+  als_gram<KP>(a, lo, len, wseg, lds, wl);
+  if (tid >= 64) return;
+
+  // wave 0: lane i = row i of the leading k x k system
+  double x = 0.0;
+  const int st = als_factor_solve(lds, lds + KP * (KP + 1) / 2, k, gamma, x);
+  if (st == GLRM_ALS_SOLVED && tid < k) a.own[seg * KP + tid] = x;
+  if (tid == 0) a.status[seg] = (int8_t)st;
 }
 
 } // namespace glrm

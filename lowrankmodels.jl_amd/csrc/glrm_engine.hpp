@@ -207,6 +207,16 @@ struct glrm_handle {
   // glrm_hip_cd_solve (include/glrm_hip_cd.h; glrm_cd.hip), per side, made at the side's first solve: the same longest-first order, and
   // the status bits and the sweeps run of every local segment after the last solve
   struct Cd { int32_t* order = nullptr; int8_t* status = nullptr; int32_t* sweeps_run = nullptr; bool solved = false; } cd[2];
+  // glrm_hip_stream_rows (include/glrm_hip_stream.h; glrm_stream.hip): the divisions every column has received (n counts, made at the first
+  // call and zeroed by every call), and what the last call did -- the status of every streamed row and the figures of its plan.
+  // ran: glrm_hip_stream_info has something to report
+  struct Stream {
+    int64_t* epoch = nullptr;
+    std::vector<int8_t> status;
+    int64_t rows = 0, nlevels = 0, nlaunches = 0, max_width = 0;
+    double plan_ms = 0.0;
+    bool ran = false;
+  } stream_state;
   // glrm_options.quad_gram: trials from the quadratic form (glrm_dense.hpp: dense_gram_*)
   bool dense_gram = false;
   double *gramH = nullptr, *gram_part = nullptr; // [kp*kp], [GRAM_BLOCKS][kp*kp]

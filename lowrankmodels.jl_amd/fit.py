@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from .convergence import ConvergenceHistory, update_ch
-from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, ProxGradParams, SparseProxGradParams
+from .params import AbstractParams, AlsParams, CdParams, HipProxGradParams, ProxGradParams, SparseProxGradParams, StreamingParams
 
 
 LAST_EXCHANGE_PROBE = None  # the last set-up probe of a ShardedFit in this process (diagnostics; tests)
@@ -133,6 +133,8 @@ def fit_b(glrm, params=None, *, ch=None, verbose=True, engine=None, group=None, 
         params = SparseProxGradParams() if _issparse(glrm.A) else HipProxGradParams()
     if not isinstance(params, AbstractParams):
         raise TypeError("params must be an AbstractParams (ProxGradParams / HipProxGradParams)")
+    if isinstance(params, StreamingParams):  # as in the reference: streaming_fit! is a function of its own, fit! has no method for it
+        raise TypeError("fit has no method for StreamingParams: call streaming_fit(glrm, params)")
     sparse = isinstance(params, SparseProxGradParams)
     als = isinstance(params, AlsParams)
     cd = isinstance(params, CdParams)

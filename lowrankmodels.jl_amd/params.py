@@ -118,6 +118,27 @@ class CdParams(AbstractParams):
                 f"device_id={self.device_id})")
 
 
+class StreamingParams(AbstractParams):
+    """StreamingParams(T0=1000; stepsize=1/T0, Y_update_interval=10) (src/algorithms/quad_streaming.jl:7-19): the first ``T0`` rows
+    initialise Y (init_svd! of keep_rows), every later row is visited once -- solved against Y as it stands, then Y takes one gradient
+    step of ``stepsize`` on the row's columns, and every ``Y_update_interval`` rows all of Y is divided by
+    1 + 2 stepsize Y_update_interval ry.scale.  ``streaming_fit`` / ``streaming_impute`` / ``streaming_impute_at`` take it
+    (glrm_hip_stream_rows, include/glrm_hip_stream.h); as in the reference there is no ``fit!`` method for it.  ``sequential=True`` runs
+    the rows strictly one after another instead of level by level (the same bits; for measurements).  One device, fp64, observation
+    lists, QuadLoss of scale 1, QuadReg / ZeroReg on both sides; rank at most 64."""
+
+    def __init__(self, T0=1000, *, stepsize=None, Y_update_interval=10, device_id=-1, sequential=False):
+        self.T0 = int(T0)
+        self.stepsize = float(1 / self.T0 if stepsize is None else stepsize)
+        self.Y_update_interval = int(Y_update_interval)
+        self.device_id = int(device_id)
+        self.sequential = bool(sequential)
+
+    def __repr__(self):
+        return (f"StreamingParams(T0={self.T0}, stepsize={self.stepsize}, Y_update_interval={self.Y_update_interval}, "
+                f"device_id={self.device_id}, sequential={self.sequential})")
+
+
 def Params(*args, **kwargs):  # src/fit.jl:5
     return ProxGradParams(*args, **kwargs)
 
